@@ -9,9 +9,16 @@ and the per-rank partials [sum w, sum w*u] are all-reduced once per iteration.
 
 Inputs (pose + reference window) are precomputed on the host and passed as kernel arguments; the warm start u*
 stays resident in HBM and evolves from step to step.  Nothing under oracle/ is touched except for the
-`cpu_baseline` leg (rank 0, N=1), which times the CPU restatement of the reference loop on the host.
+`cpu_baseline` leg (rank 0, N=1, --full only), which times the CPU restatement of the reference loop on the host.
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+A plain run sets up, warms up, times the steps and prints the result line (`value`, `ms_per_step`, `config`).  Everything
+else -- the per-kernel event pass and roofline, the live PMC traffic, the device-copy ceiling, end-to-end latency, the
+closed-loop leg, C3 / C4, the reference-default operating points and the CPU baselines -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (u*, and the costs and normalised weights of its samples) as
+DIR/<name>.npy; the inputs and the warm start before the warm-up are the same from run to run.
+
+  python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR]
+  python bench.py --gpus 1 --full       (the whole measurement set)
   python bench.py --gpus N ...          (no launcher: the parent starts the N ranks itself, before anything touches a GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -95,11 +102,14 @@ def script_inputs(amd, w, n):
 
 
 def host_cores():
-    """CPUs this process may run on (the GPU boxes give a one-GPU job a share of a 256-CPU host)."""
+    """CPUs this process may run on (the GPU boxes give a one-GPU job a share of a 256-CPU host): the affinity mask, capped
+    by OMP_NUM_THREADS where the environment sets one (the share a job may use can be smaller than the mask)."""
     try:
-        return len(os.sched_getaffinity(0))
+        n = len(os.sched_getaffinity(0))
     except AttributeError:
-        return os.cpu_count() or 1
+        n = os.cpu_count() or 1
+    cap = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(cap))) if cap.isdigit() and int(cap) > 0 else n
 
 
 def cpu_baseline(w, budget_s=12.0, by_value=False):
@@ -215,7 +225,7 @@ def live_pmc_traffic(workload_name, timeout_s=60):
     for counter in ("WRITE_SIZE", "FETCH_SIZE"):
         d = tempfile.mkdtemp(prefix="ccv_pmc_", dir="/tmp")
         cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-               "--workload", workload_name, "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-kernel-events",
+               "--workload", workload_name, "--steps", "40", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-kernel-events",
                "--no-closed-loop-leg", "--no-other-workloads", "--no-defaults-leg", "--no-live-traffic"]
         try:
             res = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True, timeout=timeout_s)
@@ -379,6 +389,21 @@ def defaults_leg(amd, device, with_cpu=True):
     return out
 
 
+DUMP_MAX_ELEMENTS = 1 << 21   # per array (16 MiB of float64): larger read-backs are dumped as a fixed, seeded sample
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float64.  An array of more than DUMP_MAX_ELEMENTS values is reduced to the
+    same seeded choice of flat indices (sorted) in every run, so two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment, 127.0.0.1 rendezvous), let rank 0 print the JSON line on the inherited
@@ -434,21 +459,30 @@ def main():
                     help="N > 1: how the partial vectors meet -- p2p: written straight into the peers' HBM by the update "
                          "kernel (one node); rccl: one all-reduce per iteration; auto: p2p when it can be set up and "
                          "reproduces the all-reduce result, else rccl")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole measurement set besides the headline: kernel event pass and roofline, live PMC traffic, "
+                         "device-copy ceiling, end-to-end latency, closed-loop leg, C3 / C4, reference defaults, CPU baselines "
+                         "(the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64): u_star "
+                         "(H-1 x u_dim), costs and weights (normalised) of the samples (rank 0's shard), trace (--closed-loop)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-closed-loop-leg", action="store_true", help="skip the device-resident closed-loop figure of the default line")
+    ap.add_argument("--no-closed-loop-leg", action="store_true", help="skip the device-resident closed-loop figure of the --full line")
     ap.add_argument("--no-state-store", action="store_true", help="skip the KxH x,y buffer (not the headline)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not record per-kernel hipEvents in the timed region")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the pass of per-kernel hipEvents after the timed region")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed PMC profile instead of two rocprofv3 --pmc child runs of this launch")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the C3 / C4 legs of the default line")
+    ap.add_argument("--no-other-workloads", action="store_true", help="skip the C3 / C4 legs of the --full line")
     ap.add_argument("--no-defaults-leg", action="store_true", help="skip the reference-default operating points (K = 1 000 / 10 000, H = 15)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
-    # roofline.traffic, measured for THIS run (the headline launch only; before anything here touches the GPU)
+    # roofline.traffic, measured for THIS run (--full, the headline launch only; before anything here touches the GPU)
     live_traffic, live_detail = None, "not the headline launch"
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_live_traffic and not args.closed_loop
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_live_traffic and not args.closed_loop
             and args.workload in ("C2", "C3", "C4") and args.samples_per_gpu is None and args.dt is None and args.path is None
             and not args.no_state_store and not os.environ.get("CCV_MPPI_KERNEL")):
         live_traffic, live_detail = live_pmc_traffic(args.workload)
@@ -607,10 +641,12 @@ def main():
 
     # Set-up, not part of the warm-up count: for the first several hundred launches of a process the host side of a
     # launch is several times slower on some boxes (runtime pools growing, host and device clocks ramping; measured with
-    # tools/host_cost.py: 120 us/call for the first ~600 calls, 12 us afterwards).  Run until half a second has passed.
-    # (N > 1: every step is a collective, so all ranks must run the same number -- fixed count, no clock)
-    t_prime, n_prime = time.perf_counter(), 0
-    while (n_prime < 4096) if world > 1 else (time.perf_counter() - t_prime < 0.5 or n_prime < 1024):
+    # tools/host_cost.py: 120 us/call for the first ~600 calls, 12 us afterwards).  A fixed count, not a clock (0.6 s at C2):
+    # the warm start the set-up leaves -- and so the warm-up, the timed steps and what --dump-outputs writes -- depends on the
+    # arguments alone.  (N > 1: every step is a collective, so all ranks must run the same number anyway.)
+    n_prime_total = 4096 if world > 1 else 16384
+    n_prime = 0
+    while n_prime < n_prime_total:
         for _ in range(128):
             step(n_prime)
             n_prime += 1
@@ -630,10 +666,17 @@ def main():
         step(args.warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
-    # Kernel durations: a separate pass right after the timed region (same inputs, same warm start), hipEvents attached
-    # to the rollout kernel's dispatch and to the end of the launch sequence of EVERY launch, on `stream` -- at least 256
-    # launches whatever --steps is (recording inside the timed region would cost ~8 us/step of launch serialisation).
-    n_event_pass = 0 if args.no_kernel_events else max(256, min(args.steps, 2048))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives after its last step: u* (the deferred update is completed by the read),
+        # and the costs and normalised weights of this rank's samples
+        outputs = {"u_star": ctl.get_nominal(), "costs": ctl.read_costs(), "weights": ctl.read_weights()}
+        if args.closed_loop:
+            outputs["trace"] = ctl.resident_read_trace()
+        dump_outputs(args.dump_outputs, outputs)
+    # Kernel durations (--full): a separate pass right after the timed region (same inputs, same warm start), hipEvents
+    # attached to the rollout kernel's dispatch and to the end of the launch sequence of EVERY launch, on `stream` -- at
+    # least 256 launches whatever --steps is (recording inside the timed region would cost ~8 us/step of launch serialisation).
+    n_event_pass = 0 if (args.no_kernel_events or not args.full) else max(256, min(args.steps, 2048))
     roll_us = iter_us = 0.0
     n_ev = 0
     if n_event_pass:
@@ -654,19 +697,6 @@ def main():
         elapsed = float(t.item())
 
     if rank == 0:
-        B, B_roll = algorithmic_bytes(p.horizon, p.udim)
-        roll_avg_s = roll_us / max(n_ev, 1) * 1e-6
-        iter_avg_s = iter_us / max(n_ev, 1) * 1e-6
-        achieved = B_roll * k_local / roll_avg_s / 1e9 if roll_avg_s > 0 else None
-        # the committed PMC pass is of the workload's own launch (its K, its kernel): no figure for any other launch
-        pmc_applies = world == 1 and k_local == w.params.num_samples and args.dt is None and not args.no_state_store
-        traffic = latest_pmc_traffic(args.workload) if pmc_applies else None
-        traffic_source = ("rocprofv3 --pmc pass of the same workload and kernel, committed under profiles/ (not measured by this run%s)"
-                          % ("" if args.no_live_traffic else ": " + str(live_detail))) if traffic else None
-        if pmc_applies and live_traffic:
-            traffic = live_traffic
-            traffic_source = {"measured": "by this run: two child runs of this command under rocprofv3 --pmc, before the timed region",
-                              **live_detail}
         out = {
             # BASELINE.json's metric string; `value` is its first component, `ms_per_step` the second (ms per MPPI iteration)
             "metric": "trajectory rollouts/s (K\u00d7iters/s) + ms/MPPI-iteration, diff-drive T=50" if args.workload == "C2"
@@ -692,28 +722,42 @@ def main():
                        "state_store": not args.no_state_store,
                        **({"closed_loop": "device-resident: plant + get_CurrentIndex + calc_RefPath on the device, "
                                           "%d path poses" % len(cl_px)} if args.closed_loop else {})},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
-                         # `frac` divides the CONTRACT's algorithmic bytes (fp64 controls written and re-read)
-                         # by the kernel time; the kernel really moves `traffic` bytes (it stores the fp32 normals and
-                         # re-derives the controls), i.e. measured_traffic_frac of the 8 TB/s -- what limits it is VALU issue
-                         # (profiles/*_pmc_summary.txt: SQ_ACTIVE_INST_VALU), not HBM
-                         "measured_traffic_frac": (traffic / roll_avg_s / 1e9 / HBM_PEAK_GBS) if (traffic and roll_avg_s > 0) else None,
-                         "traffic_source": traffic_source,
-                         "limiter": "valu-issue (contract bound: hbm)",
-                         "kernel": rollout_kernel_name(p.model, k_local, local_rank) if args.dt is None else
-                                   rollout_kernel_name(p.model, k_local, local_rank) + " (its full-range sin/cos instantiation beyond the small-turn gate)",
-                         "kernel_avg_us": 1e6 * roll_avg_s,
-                         "kernel_launches_averaged": int(n_ev),
-                         "algorithmic_bytes_per_launch": B_roll * k_local,
-                         "iteration_avg_us": 1e6 * iter_avg_s,
-                         "iteration_algorithmic_bytes": B * k_local,
-                         "iteration_achieved": (B * k_local / iter_avg_s / 1e9) if iter_avg_s > 0 else None,
-                         "iteration_frac": (B * k_local / iter_avg_s / 1e9 / HBM_PEAK_GBS) if iter_avg_s > 0 else None},
         }
+        if args.full:
+            B, B_roll = algorithmic_bytes(p.horizon, p.udim)
+            roll_avg_s = roll_us / max(n_ev, 1) * 1e-6
+            iter_avg_s = iter_us / max(n_ev, 1) * 1e-6
+            achieved = B_roll * k_local / roll_avg_s / 1e9 if roll_avg_s > 0 else None
+            # the committed PMC pass is of the workload's own launch (its K, its kernel): no figure for any other launch
+            pmc_applies = world == 1 and k_local == w.params.num_samples and args.dt is None and not args.no_state_store
+            traffic = latest_pmc_traffic(args.workload) if pmc_applies else None
+            traffic_source = ("rocprofv3 --pmc pass of the same workload and kernel, committed under profiles/ (not measured by this run%s)"
+                              % ("" if args.no_live_traffic else ": " + str(live_detail))) if traffic else None
+            if pmc_applies and live_traffic:
+                traffic = live_traffic
+                traffic_source = {"measured": "by this run: two child runs of this command under rocprofv3 --pmc, before the timed region",
+                                  **live_detail}
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
+                               # `frac` divides the CONTRACT's algorithmic bytes (fp64 controls written and re-read)
+                               # by the kernel time; the kernel really moves `traffic` bytes (it stores the fp32 normals and
+                               # re-derives the controls), i.e. measured_traffic_frac of the 8 TB/s -- what limits it is VALU issue
+                               # (profiles/*_pmc_summary.txt: SQ_ACTIVE_INST_VALU), not HBM
+                               "measured_traffic_frac": (traffic / roll_avg_s / 1e9 / HBM_PEAK_GBS) if (traffic and roll_avg_s > 0) else None,
+                               "traffic_source": traffic_source,
+                               "limiter": "valu-issue (contract bound: hbm)",
+                               "kernel": rollout_kernel_name(p.model, k_local, local_rank) if args.dt is None else
+                                         rollout_kernel_name(p.model, k_local, local_rank) + " (its full-range sin/cos instantiation beyond the small-turn gate)",
+                               "kernel_avg_us": 1e6 * roll_avg_s,
+                               "kernel_launches_averaged": int(n_ev),
+                               "algorithmic_bytes_per_launch": B_roll * k_local,
+                               "iteration_avg_us": 1e6 * iter_avg_s,
+                               "iteration_algorithmic_bytes": B * k_local,
+                               "iteration_achieved": (B * k_local / iter_avg_s / 1e9) if iter_avg_s > 0 else None,
+                               "iteration_frac": (B * k_local / iter_avg_s / 1e9 / HBM_PEAK_GBS) if iter_avg_s > 0 else None}
         headline = (world == 1 and not args.closed_loop and args.workload == "C2" and args.samples_per_gpu is None
                     and args.dt is None and args.path is None and not args.no_state_store)
-        if world == 1:
+        if args.full and world == 1:
             out["roofline"]["device_copy_gbs"] = device_copy_gbs(torch)
             if not args.closed_loop:
                 # SURVEY.md 8(d), end to end through the blocking C-ABI call: host window in, u* out (PCIe and the host
@@ -762,16 +806,16 @@ def main():
             d = np.hypot(cl_px[None, :] - tr[:, 0:1], cl_py[None, :] - tr[:, 1:2]).min(axis=1)
             out["closed_loop"] = {"ticks": int(len(tr)), "distance_travelled_m": float(np.hypot(np.diff(tr[:, 0]), np.diff(tr[:, 1])).sum()),
                                   "path_error_rms_m": float(np.sqrt(np.mean(d * d))), "path_error_max_m": float(d.max())}
-        if world == 1 and not args.closed_loop and args.workload == "C2" and not args.no_closed_loop_leg:
+        if args.full and world == 1 and not args.closed_loop and args.workload == "C2" and not args.no_closed_loop_leg:
             out["closed_loop"] = closed_loop_leg(amd, torch, ctl, w, seed)
-        if headline and not args.no_other_workloads:
+        if args.full and headline and not args.no_other_workloads:
             # BASELINE configs[2] and configs[3], measured like the headline (their own handles; C2's is released first)
             ctl.close()
             out["other_workloads"] = {"C3": measure_workload(amd, torch, configs, "C3", 100, 10, stream, local_rank),
                                       "C4": measure_workload(amd, torch, configs, "C4", 60, 10, stream, local_rank)}
-        if headline and not args.no_defaults_leg:
+        if args.full and headline and not args.no_defaults_leg:
             out["defaults"] = defaults_leg(amd, local_rank, with_cpu=not args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w)
             out["cpu_baseline_reference_shaped"] = cpu_baseline(w, budget_s=10.0, by_value=True)
             out["cpu_baseline_all_cores"] = cpu_baseline_threads(w, max(1, host_cores()))

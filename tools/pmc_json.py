@@ -33,6 +33,6 @@ for w in ("C2", "C3", "C4"):
                        "'FETCH_SIZE reports exactly 1/2'; calibrated for this code's 8-byte-per-lane pattern with tools/microbench/hbm_calib.hip): doubled",
          "hbm_bytes_per_launch": int((wr + 2 * fe) * 1024), "algorithmic_bytes_per_launch": ALG[w],
          "command": "tools/profile_r03.sh %s: rocprofv3 --pmc WRITE_SIZE (and, in its own run, --pmc FETCH_SIZE) --output-format csv -- python3 bench.py "
-                    "--workload %s --steps 40 --warmup 5 --no-cpu-baseline --no-other-workloads --no-defaults-leg --no-kernel-events --no-closed-loop-leg" % (tag, w)}
+                    "--full --workload %s --steps 40 --warmup 5 --no-cpu-baseline --no-other-workloads --no-defaults-leg --no-kernel-events --no-closed-loop-leg" % (tag, w)}
     json.dump(d, open(os.path.join(out_dir, "%s_pmc.json" % w), "w"), indent=1)
     print(w, d["hbm_bytes_per_launch"], "vs algorithmic", ALG[w], "ratio %.3f" % (d["hbm_bytes_per_launch"] / ALG[w]))

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for so in sorted(glob.glob(os.path.join(ROOT, "_abl", "lib_*.so"))):
     name = os.path.basename(so)[4:-3]
     env = dict(os.environ, CCV_MPPI_LIB=so)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + sys.argv[1:], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + sys.argv[1:], env=env,
                        capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:
