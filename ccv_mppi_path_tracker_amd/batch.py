@@ -1,0 +1,127 @@
+"""B independent MPPI problems in one launch: the batch handle of the C ABI (ccv_mppi_batch_*, include/ccv_mppi.h).
+
+Every array carries the instance as its first axis.  Instance b computes what an MPPIController with the same parameters
+computes for the same inputs and warm start; all compute happens in libccv_mppi_hip.so.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .controller import MPPIError, make_config
+from .configs import MPPIParams
+
+
+class BatchController:
+    """`batch` controllers with one shared configuration (K = num_samples per instance) on one device."""
+
+    def __init__(self, params: MPPIParams, batch, device=0, num_samples=None, no_state_store=False):
+        self.lib = capi.load()
+        self.params = params
+        self.B = int(batch)
+        self.K = int(num_samples if num_samples is not None else params.num_samples)
+        self.H = params.horizon
+        self.udim = params.udim
+        self.nstate = params.nstate
+        self._h = capi._H()
+        cfg = make_config(params, device, 0, False, no_state_store, self.K)
+        rc = self.lib.ccv_mppi_batch_create(C.byref(cfg), self.B, C.byref(self._h))
+        if rc != capi.OK:
+            self._h = capi._H()
+            raise MPPIError(rc, "ccv_mppi_batch_create failed (bad arguments, or no usable MI355X/HIP device) -- there is no CPU fallback")
+
+    # ---- plumbing ----
+    def _check(self, rc):
+        if rc != capi.OK:
+            msg = self.lib.ccv_mppi_batch_last_error(self._h)
+            raise MPPIError(rc, msg.decode() if msg else "")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self.lib.ccv_mppi_batch_destroy(self._h)
+            self._h = capi._H()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, stream_ptr):
+        self._check(self.lib.ccv_mppi_batch_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    def synchronize(self):
+        self._check(self.lib.ccv_mppi_batch_synchronize(self._h))
+
+    def last_kernel(self):
+        """capi.BATCH_KERNEL_* of the last iteration (| BATCH_KERNEL_WIDE for the wide-turn form), -1 before the first."""
+        return self.lib.ccv_mppi_batch_last_kernel(self._h)
+
+    # ---- warm starts [B][H-1][u_dim] ----
+    def set_nominal(self, u):
+        u = capi.as_f64(u, (self.B, self.H - 1, self.udim))
+        self._check(self.lib.ccv_mppi_batch_set_nominal(self._h, capi.dptr(u)))
+
+    def get_nominal(self):
+        u = np.empty((self.B, self.H - 1, self.udim))
+        self._check(self.lib.ccv_mppi_batch_get_nominal(self._h, capi.dptr(u)))
+        return u
+
+    # ---- whole iteration of every instance ----
+    def _inputs(self, x0, dt, x_ref, y_ref, yaw_ref0, seed):
+        x0 = np.asarray(x0, dtype=np.float64)
+        if x0.ndim != 2 or x0.shape[0] != self.B or x0.shape[1] > 5:
+            raise ValueError("x0: expected shape (%d, <= 5), got %s" % (self.B, x0.shape))
+        x = np.zeros((self.B, 5))
+        x[:, :x0.shape[1]] = x0
+        d = capi.as_f64(np.broadcast_to(np.asarray(dt, dtype=np.float64), (self.B,)))
+        xr, yr = capi.as_f64(x_ref, (self.B, self.H)), capi.as_f64(y_ref, (self.B, self.H))
+        yw = capi.as_f64(np.broadcast_to(np.asarray(yaw_ref0, dtype=np.float64), (self.B,)))
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, dtype=np.uint64), (self.B,)))
+        return x, d, xr, yr, yw, sd
+
+    def iterate(self, x0, dt, x_ref, y_ref, yaw_ref0, seed, iteration, want_stats=True):
+        """x0 [B][nstate], dt / yaw_ref0 / seed [B] (or one value for all), x_ref / y_ref [B][H] -> u* [B][H-1][u_dim]
+        (and a list of B capi.Stats)."""
+        x, d, xr, yr, yw, sd = self._inputs(x0, dt, x_ref, y_ref, yaw_ref0, seed)
+        u = np.empty((self.B, self.H - 1, self.udim))
+        st = (capi.Stats * self.B)()
+        self._check(self.lib.ccv_mppi_batch_iterate(self._h, capi.dptr(x), capi.dptr(d), capi.dptr(xr), capi.dptr(yr),
+                                                    capi.dptr(yw), sd.ctypes.data_as(C.POINTER(C.c_uint64)), int(iteration),
+                                                    capi.dptr(u), st if want_stats else None))
+        return (u, list(st)) if want_stats else u
+
+    def iterate_enqueue(self, x0, dt, x_ref, y_ref, yaw_ref0, seed, iteration):
+        x, d, xr, yr, yw, sd = self._inputs(x0, dt, x_ref, y_ref, yaw_ref0, seed)
+        self._check(self.lib.ccv_mppi_batch_iterate_enqueue(self._h, capi.dptr(x), capi.dptr(d), capi.dptr(xr), capi.dptr(yr),
+                                                            capi.dptr(yw), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                            int(iteration)))
+
+    # ---- per-instance read-back of the last iteration ----
+    def read_costs(self, instance, first=0, count=None):
+        count = self.K - first if count is None else count
+        out = np.empty(count)
+        self._check(self.lib.ccv_mppi_batch_read_costs(self._h, int(instance), int(first), int(count), capi.dptr(out)))
+        return out
+
+    def read_weights(self, instance, first=0, count=None):
+        count = self.K - first if count is None else count
+        out = np.empty(count)
+        self._check(self.lib.ccv_mppi_batch_read_weights(self._h, int(instance), int(first), int(count), capi.dptr(out)))
+        return out
+
+    def read_candidates(self, instance, first=0, count=None, stride=1):
+        count = self.K if count is None else count
+        out = np.empty((count, self.H, 2))
+        self._check(self.lib.ccv_mppi_batch_read_candidates(self._h, int(instance), int(first), int(count), int(stride),
+                                                            capi.dptr(out)))
+        return out
+
+    # ---- measurement ----
+    def timing_enable(self, on=True, every=1):
+        self._check(self.lib.ccv_mppi_batch_timing_enable(self._h, (max(1, int(every)) if on else 0)))
+
+    def timing_read(self, reset=True):
+        a, b, n = C.c_double(), C.c_double(), C.c_int64()
+        self._check(self.lib.ccv_mppi_batch_timing_read(self._h, C.byref(a), C.byref(b), C.byref(n), 1 if reset else 0))
+        return a.value, b.value, n.value

@@ -681,6 +681,13 @@ int exchange_check(ccv_mppi_handle* h) {
     }
     return CCV_MPPI_OK;
 }
+
+// the four-wave kernel's wave priorities: (rank + level[role] + b) mod 4 with the roles' levels per model -- noise / dynamics /
+// distance / store (r4_rotate_priority, mppi_rollout_pc.h: where the numbers are)
+int r4_prio_levels(int model) {
+    auto levels = [](int noise, int dynamics, int distance, int store) { return 16 + (noise | dynamics << 2 | distance << 4 | store << 6); };
+    return model == CCV_MPPI_DIFF_DRIVE ? levels(3, 2, 1, 0) : model == CCV_MPPI_STEERING_DIFF_DRIVE ? levels(2, 3, 1, 0) : levels(0, 1, 2, 3);
+}
 }  // namespace
 
 extern "C" {
@@ -746,12 +753,8 @@ int ccv_mppi_create(const ccv_mppi_config* cfg, ccv_mppi_handle** out) {
     }
     // wave priorities (pc_rotate_priority): measured -4 us on the three-wave kernel (C2), -3 % on the two-wave one (C4), and
     // with four levels -5 us on the four-wave kernel (43.4 -> 38.3 us at C2)
-    // four-wave kernel: (rank + level[role] + b) mod 4 with the roles' levels per model -- noise / dynamics / distance / store
-    // (r4_rotate_priority, mppi_rollout_pc.h: where the numbers are)
-    auto levels = [](int noise, int dynamics, int distance, int store) { return 16 + (noise | dynamics << 2 | distance << 4 | store << 6); };
-    const int kR4PrioLevels = h->cfg.model == CCV_MPPI_DIFF_DRIVE ? levels(3, 2, 1, 0)
-                              : h->cfg.model == CCV_MPPI_STEERING_DIFF_DRIVE ? levels(2, 3, 1, 0) : levels(0, 1, 2, 3);
-    h->prio_rotate = h->coop == 3 ? kR4PrioLevels : h->coop ? 1 : 0;
+    // four-wave kernel: the roles' levels per model (r4_prio_levels)
+    h->prio_rotate = h->coop == 3 ? r4_prio_levels(h->cfg.model) : h->coop ? 1 : 0;
     if (const char* pv = std::getenv("CCV_MPPI_PRIO")) {   // 0: off; 2 .. 5: the formula schedules; 16 + digits: a level table
         const int v = std::atoi(pv);
         h->prio_rotate = v == 0 ? 0 : (((v >= 2 && v <= 5) || (v >= 16 && v < 16 + 256)) && h->coop == 3) ? v : h->prio_rotate;
@@ -1519,6 +1522,476 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
         h->t_n = 0;
     }
     return CCV_MPPI_OK;
+}
+
+}  // extern "C"
+
+// ---- batch handles: B independent problems in one launch (ccv_mppi_batch_*) -------------------------------------------
+// One configuration, B instances on one sample axis of B * Kpad columns (Kpad = K rounded up to 64; mppi_kernels.h,
+// batch_view): the buffers, the stream, the mailbox and the timing of a ccv_mppi_handle whose K is the instance's and whose
+// pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
+// one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
+struct ccv_mppi_batch {
+    ccv_mppi_handle h;
+    int B = 0, kpad = 0, rec_doubles = 0;
+    double* d_rec = nullptr;                        // [B][rec_doubles]: BatchHead + window a[H], b[H], c[H] per instance
+    static constexpr int kRecSlots = 4;             // pinned staging of the records, in rotation: a slot is refilled only
+    double* h_rec[kRecSlots] = {nullptr, nullptr, nullptr, nullptr};   // after the copy that read it has run
+    hipEvent_t rec_ev[kRecSlots] = {nullptr, nullptr, nullptr, nullptr};
+    bool rec_used[kRecSlots] = {false, false, false, false};
+    int rec_next = 0;
+    int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
+    bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
+    bool have_result = false;
+};
+
+namespace {
+
+int batch_fail(ccv_mppi_batch* b, int code, const char* what) { return fail(b ? &b->h : nullptr, code, what); }
+
+int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
+                     const double* yaw_ref0, const uint64_t* seed) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!x0 || !dt || !x_ref || !y_ref || !yaw_ref0 || !seed) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    for (int b = 0; b < bh->B; ++b)
+        if (!(dt[b] == dt[b])) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "dt is NaN");
+    return CCV_MPPI_OK;
+}
+
+// records -> device, rollout of all instances, per-instance update.  The kernel family is the single handle's rule applied to
+// the batch's total number of workgroups (chosen at create); the plain kernel for the whole batch when one instance's
+// headings can leave the fast sin / cos's range, the wide-turn instantiation when one instance needs it.
+int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
+                  const double* yaw_ref0, const uint64_t* seed, uint64_t iter) {
+    ccv_mppi_handle* h = &bh->h;
+    const int B = bh->B, H = h->H, nx = h->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+    const int slot = bh->rec_next;
+    bh->rec_next = (slot + 1) % ccv_mppi_batch::kRecSlots;
+    if (bh->rec_used[slot]) HIP_TRY(h, hipEventSynchronize(bh->rec_ev[slot]));
+    double* rec = bh->h_rec[slot];
+    std::memset(rec, 0, (size_t)B * bh->rec_doubles * sizeof(double));
+    RolloutArgs A;
+    fill_args(h, A, x0, dt[0], yaw_ref0[0], seed[0], iter);
+    int trig = h->coop ? kTrigSafe : kTrigUnsafe;
+    for (int b = 0; b < B; ++b) {
+        const double* xb = x0 + (size_t)5 * b;
+        BatchHead* hd = reinterpret_cast<BatchHead*>(rec + (size_t)b * bh->rec_doubles);
+        for (int i = 0; i < nx; ++i) hd->x0[i] = xb[i];
+        hd->yaw_ref0 = yaw_ref0[b];
+        hd->dt = dt[b];
+        hd->inv_dt = 1.0 / dt[b];
+        hd->seed_lo = (uint32_t)seed[b];
+        hd->seed_hi = (uint32_t)(seed[b] >> 32);
+        hd->K = b * bh->kpad + h->K;
+        hd->k_offset = -b * bh->kpad;
+        hd->nominal = h->d_nominal + (size_t)b * h->R;
+        // the window coefficients, as fill_window() forms them
+        double* win = rec + (size_t)b * bh->rec_doubles + kBatchHeadDoubles;
+        const double* xr = x_ref + (size_t)b * H;
+        const double* yr = y_ref + (size_t)b * H;
+        for (int j = 0; j < H; ++j) {
+            const double xl = xr[j] - hd->x0[0], yl = yr[j] - hd->x0[1];
+            win[j] = -2.0 * xl;
+            win[H + j] = -2.0 * yl;
+            win[2 * H + j] = xl * xl + yl * yl;
+        }
+        if (trig != kTrigUnsafe) {
+            for (int i = 0; i < 5; ++i) A.x0[i] = hd->x0[i];
+            A.dt = dt[b];
+            const int t = fast_trig_safe(h, A, MODE_FUSED);
+            if (t == kTrigUnsafe || t == kTrigWide) trig = t;
+        }
+    }
+    HIP_TRY(h, hipMemcpyAsync(bh->d_rec, rec, (size_t)B * bh->rec_doubles * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipEventRecord(bh->rec_ev[slot], h->stream));
+    bh->rec_used[slot] = true;
+
+    const bool plain = trig == kTrigUnsafe;
+    A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
+    A.nparts = B * h->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
+    A.fuse_update = plain ? 0 : 1;
+    A.store_u = 1;
+    A.store_xy = (h->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) ? 0 : 1;
+    A.do_cost = 1;
+    size_t tslot = 0;
+    const bool timed = h->timing && (h->timing_count++ % h->timing_every) == 0;
+    if (timed) {
+        if (int rc = timing_begin(h, tslot)) return rc;
+    }
+    static const Window kNoWindow{};   // (the windows are in the records)
+    const LaunchAt at{h->stream, timed && !plain ? h->ev[tslot] : nullptr, timed && !plain ? h->ev[tslot + 1] : nullptr};
+    if (plain) {
+        if (timed) HIP_TRY(h, hipEventRecord(h->ev[tslot], h->stream));
+        launch_rollout_plain_batch(h->cfg.model, B, at, A, kNoWindow);
+        if (timed) HIP_TRY(h, hipEventRecord(h->ev[tslot + 1], h->stream));
+        bh->last_kernel = CCV_MPPI_BATCH_KERNEL_PLAIN;
+    } else if (h->solo) {
+        launch_rollout_solo_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
+        bh->last_kernel = CCV_MPPI_BATCH_KERNEL_ONE_WAVE;
+    } else {
+        launch_rollout_r4_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
+        bh->last_kernel = CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
+    }
+    if (trig == kTrigWide) bh->last_kernel |= CCV_MPPI_BATCH_KERNEL_WIDE;
+    HIP_TRY(h, hipGetLastError());
+    int nparts = h->nblocks;
+    if (plain) {   // the plain kernel stores w and the controls: the single handle's unfused reduction, instance by instance
+        UpdateArgs U;
+        U.u = h->d_u;
+        U.w = h->d_w;
+        U.cost = h->d_cost;
+        U.partial = h->d_partial;
+        U.statpart = h->d_statpart;
+        U.K = h->K;
+        U.pitch = h->pitch;
+        U.R = h->R;
+        U.nchunks = h->nchunks;
+        hipLaunchKernelGGL(k_update_partials_batch, dim3(h->nchunks, h->R + 1, B), dim3(kBlock), 0, h->stream, U, bh->kpad);
+        nparts = h->nchunks;
+    }
+    FinalizeArgs F;
+    F.partial = h->d_partial;
+    F.statpart = h->d_statpart;
+    F.nominal = h->d_nominal;
+    F.vec = h->d_vec;
+    F.stats = h->d_stats;
+    F.R = h->R;
+    F.nchunks = nparts;
+    F.normalise = 1;
+    F.mail = nullptr;
+    F.mail_seq = 0;
+    // The mailbox up to the largest one a single handle posts; beyond, one copy and a stream synchronisation are faster
+    // (diff drive K = 1 000, H = 15, blocking us, mailbox vs copy, one box: B = 1 45 vs 51, B = 64 107 vs 66, B = 256 220 vs
+    // 118; the mailbox_blocking_us / copy_blocking_us columns of profiles/batch_bench.json repeat the comparison)
+    const bool mail_fits = (size_t)B * (h->R + 4) <= (size_t)(CCV_MPPI_MAX_HORIZON - 1) * CCV_MPPI_MAX_UDIM + 4;
+    if (h->want_mail && h->use_mail && (mail_fits || bh->mail_any_size)) {
+        if (++h->mail_seq == 0) h->mail_seq = 1;
+        F.mail = h->d_mail;
+        F.mail_seq = h->mail_seq;
+        h->mail_pending = true;
+    }
+    h->want_mail = false;
+    hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(h->R), B), dim3(kBlock), 0, h->stream, F, plain ? 0 : 1);
+    HIP_TRY(h, hipGetLastError());
+    if (timed) HIP_TRY(h, hipEventRecord(h->ev[tslot + 2], h->stream));
+    if (h->throttle && ++h->enqueued % ccv_mppi_handle::kThrottleEvery == 0) {
+        const int ts = (int)((h->enqueued / ccv_mppi_handle::kThrottleEvery) % ccv_mppi_handle::kThrottleSlots);
+        if (h->throttle_used[ts]) HIP_TRY(h, hipEventSynchronize(h->throttle_ev[ts]));
+        HIP_TRY(h, hipEventRecord(h->throttle_ev[ts], h->stream));
+        h->throttle_used[ts] = true;
+    }
+    bh->have_result = true;
+    return CCV_MPPI_OK;
+}
+
+// u* [B][R] and the statistics of every instance: from the mailbox the update kernel posted into, or copied
+int batch_fetch(ccv_mppi_batch* bh, double* u_opt_out, ccv_mppi_stats* stats) {
+    ccv_mppi_handle* h = &bh->h;
+    const size_t B = (size_t)bh->B, R = (size_t)h->R;
+    double* v = h->h_pin;   // [B][R + 4]
+    if (h->mail_pending) {
+        h->mail_pending = false;
+        if (int rc = wait_mail(h, B * (R + 4))) return rc;
+        for (size_t i = 0; i < B * (R + 4); ++i) {
+            const unsigned long long hi = h->h_mail[2 * i], lo = h->h_mail[2 * i + 1];
+            const unsigned long long bits = (hi & 0xFFFFFFFF00000000ull) | (lo >> 32);
+            std::memcpy(&v[i], &bits, sizeof(double));
+        }
+    } else {
+        double* u = v + B * (R + 4);
+        double* st = u + B * R;
+        HIP_TRY(h, hipMemcpyAsync(u, h->d_nominal, B * R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(st, h->d_stats, B * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t b = 0; b < B; ++b) {
+            std::memcpy(v + b * (R + 4), u + b * R, R * sizeof(double));
+            std::memcpy(v + b * (R + 4) + R, st + b * 4, 4 * sizeof(double));
+        }
+    }
+    if (stats && h->timing) {
+        if (int rc = timing_collect(h)) return rc;
+    }
+    for (size_t b = 0; b < B; ++b) {
+        const double* vb = v + b * (R + 4);
+        int nonfinite = 0;
+        for (size_t i = 0; i < R; ++i) {
+            if (!std::isfinite(vb[i])) nonfinite = 1;
+            if (u_opt_out) u_opt_out[b * R + i] = vb[i];
+        }
+        if (stats) {
+            ccv_mppi_stats& s = stats[b];
+            std::memset(&s, 0, sizeof(s));
+            s.sum_w = vb[R + 0];
+            s.min_cost = vb[R + 1];
+            s.max_cost = vb[R + 2];
+            s.n_zero_weight = (int64_t)vb[R + 3];
+            s.nonfinite = nonfinite;
+            if (h->timing) {
+                s.device_us = h->last_iter_us;
+                s.rollout_us = h->last_roll_us;
+            }
+        }
+    }
+    return CCV_MPPI_OK;
+}
+
+int batch_check_read(ccv_mppi_batch* bh, int32_t instance, const void* out) {
+    if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
+    if (instance < 0 || instance >= bh->B) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
+    if (!bh->have_result) return batch_fail(bh, CCV_MPPI_ERR_STATE, "no iteration yet");
+    return CCV_MPPI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ccv_mppi_batch_create(const ccv_mppi_config* cfg, int32_t batch, ccv_mppi_batch** out) {
+    // every argument is checked before a device is looked at
+    if (!cfg || !out) return CCV_MPPI_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (cfg->abi_version != CCV_MPPI_ABI_VERSION) return CCV_MPPI_ERR_INVALID_ARG;
+    if (cfg->model < CCV_MPPI_DIFF_DRIVE || cfg->model > CCV_MPPI_FULL_BODY) return CCV_MPPI_ERR_INVALID_ARG;
+    if (cfg->num_samples < 1 || cfg->horizon < 3 || cfg->horizon > CCV_MPPI_MAX_HORIZON) return CCV_MPPI_ERR_INVALID_ARG;
+    if (cfg->sample_offset != 0) return CCV_MPPI_ERR_INVALID_ARG;
+    if (cfg->flags & CCV_MPPI_FLAG_MIN_SHIFT) return CCV_MPPI_ERR_INVALID_ARG;
+    if (batch < 1) return CCV_MPPI_ERR_INVALID_ARG;
+    const int kpad = round_up(cfg->num_samples, 64);
+    if ((int64_t)batch * kpad > (int64_t)CCV_MPPI_BATCH_MAX_SAMPLES) return CCV_MPPI_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CCV_MPPI_ERR_NO_DEVICE;
+    if (cfg->device < 0 || cfg->device >= ndev) return CCV_MPPI_ERR_NO_DEVICE;
+    ccv_mppi_batch* bh = new (std::nothrow) ccv_mppi_batch();
+    if (!bh) return CCV_MPPI_ERR_ALLOC;
+    const DeviceGuard guard(cfg->device);
+    ccv_mppi_handle* h = &bh->h;
+    h->cfg = *cfg;
+    h->udim = udim_of(cfg->model);
+    h->K = cfg->num_samples;
+    h->H = cfg->horizon;
+    h->R = (h->H - 1) * h->udim;
+    h->pitch = batch * kpad;
+    h->nchunks = (h->K + kChunk - 1) / kChunk;
+    h->nblocks = kpad / kPcSamples;   // workgroups per instance
+    bh->B = batch;
+    bh->kpad = kpad;
+    bh->rec_doubles = batch_record_doubles(h->H);
+    int cus = 256;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    }
+    h->cu_count = cus;
+    // the single handle's selection (ccv_mppi_create) on the batch's workgroups: the four-wave kernel up to five per CU (full
+    // body: one), the one-wave kernel beyond -- also where a single full-body handle would take the two-wave kernel, which has
+    // no batched form.  CCV_MPPI_KERNEL=v1 selects the plain kernel; its other values are ignored here.
+    const char* kenv = getenv("CCV_MPPI_KERNEL");
+    const bool v1 = kenv && std::strcmp(kenv, "v1") == 0;
+    const int64_t total = (int64_t)batch * h->nblocks;
+    const bool fb = cfg->model == CCV_MPPI_FULL_BODY;
+    h->solo = !v1 && total > (int64_t)(fb ? 1 : 5) * cus;
+    h->coop = v1 ? 0 : (fb && h->solo) ? 1 : 3;
+    h->prio_rotate = h->coop == 3 ? r4_prio_levels(cfg->model) : h->coop ? 1 : 0;
+    h->prune = (h->coop && h->H > 16) ? 1 : 0;
+
+    auto bail = [&](int code, const char* what, hipError_t e) {
+        fail(h, code, what, e);
+        std::fprintf(stderr, "ccv_mppi_batch_create: %s\n", h->err.c_str());
+        ccv_mppi_batch_destroy(bh);
+        return code;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(cfg->device)) != hipSuccess) return bail(CCV_MPPI_ERR_NO_DEVICE, "hipSetDevice", e);
+    if ((e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(CCV_MPPI_ERR_HIP, "hipStreamCreate", e);
+    h->stream = h->own_stream;
+    const size_t P = (size_t)h->pitch, B = (size_t)batch;
+    const size_t nparts_max = B * (size_t)(h->nblocks > h->nchunks ? h->nblocks : h->nchunks);
+    struct Piece { void** p; size_t bytes; } pieces[] = {
+        {(void**)&h->d_z, (size_t)h->R * P * sizeof(float)},
+        {(void**)&h->d_xs, (size_t)h->H * P * sizeof(double)},
+        {(void**)&h->d_ys, (size_t)h->H * P * sizeof(double)},
+        {(void**)&h->d_u, (size_t)h->R * P * sizeof(double)},
+        {(void**)&h->d_cost, P * sizeof(double)},
+        {(void**)&h->d_w, P * sizeof(double)},
+        {(void**)&h->d_partial, (size_t)(h->R + 1) * nparts_max * sizeof(double)},
+    };
+    constexpr size_t kPieceAlign = (size_t)2 << 20;
+    size_t arena_bytes = 0;
+    for (const Piece& pc : pieces) arena_bytes += (pc.bytes + kPieceAlign - 1) / kPieceAlign * kPieceAlign;
+    if ((e = hipMalloc(&h->d_arena, arena_bytes)) != hipSuccess) return bail(CCV_MPPI_ERR_ALLOC, "hipMalloc", e);
+    if ((e = hipMemset(h->d_arena, 0, arena_bytes)) != hipSuccess) return bail(CCV_MPPI_ERR_HIP, "hipMemset", e);
+    {
+        size_t at = 0;
+        for (const Piece& pc : pieces) {
+            *pc.p = static_cast<char*>(h->d_arena) + at;
+            at += (pc.bytes + kPieceAlign - 1) / kPieceAlign * kPieceAlign;
+        }
+    }
+    const size_t pad = (size_t)(CCV_MPPI_MAX_HORIZON + 8) * CCV_MPPI_MAX_UDIM;
+    struct { double** p; size_t n; } allocs[] = {
+        {&h->d_nominal, B * h->R + pad},
+        {&h->d_nom_used, pad},
+        {&h->d_statpart, nparts_max * 3},
+        {&h->d_vec, B * (h->R + 1)},
+        {&h->d_stats, B * 4},
+        {&bh->d_rec, B * bh->rec_doubles},
+    };
+    for (auto& a : allocs) {
+        if ((e = hipMalloc(a.p, a.n * sizeof(double))) != hipSuccess) return bail(CCV_MPPI_ERR_ALLOC, "hipMalloc", e);
+        if ((e = hipMemset(*a.p, 0, a.n * sizeof(double))) != hipSuccess) return bail(CCV_MPPI_ERR_HIP, "hipMemset", e);
+    }
+    if (const char* tv = std::getenv("CCV_MPPI_THROTTLE")) h->throttle = std::strcmp(tv, "0") != 0;
+    for (hipEvent_t& te : h->throttle_ev)
+        if ((e = hipEventCreateWithFlags(&te, hipEventDisableTiming)) != hipSuccess) return bail(CCV_MPPI_ERR_HIP, "hipEventCreate", e);
+    for (int s = 0; s < ccv_mppi_batch::kRecSlots; ++s) {
+        if ((e = hipEventCreateWithFlags(&bh->rec_ev[s], hipEventDisableTiming)) != hipSuccess) return bail(CCV_MPPI_ERR_HIP, "hipEventCreate", e);
+        if ((e = hipHostMalloc(&bh->h_rec[s], B * bh->rec_doubles * sizeof(double), hipHostMallocDefault)) != hipSuccess)
+            return bail(CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e);
+    }
+    h->pin_doubles = B * ((size_t)h->R + 4) * 2;   // (the mailbox's values, or the two copies of the fall-back path)
+    if ((e = hipHostMalloc(&h->h_pin, h->pin_doubles * sizeof(double), hipHostMallocDefault)) != hipSuccess)
+        return bail(CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e);
+    {
+        const size_t mail_bytes = B * ((size_t)h->R + 4) * 2 * sizeof(unsigned long long);
+        if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->h_mail), mail_bytes, hipHostMallocMapped)) != hipSuccess)
+            return bail(CCV_MPPI_ERR_ALLOC, "hipHostMalloc(mailbox)", e);
+        std::memset(h->h_mail, 0, mail_bytes);
+        if ((e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_mail), h->h_mail, 0)) != hipSuccess)
+            return bail(CCV_MPPI_ERR_HIP, "hipHostGetDevicePointer(mailbox)", e);
+        if (const char* mv = std::getenv("CCV_MPPI_MAILBOX")) h->use_mail = std::strcmp(mv, "0") != 0;
+        if (const char* mv = std::getenv("CCV_MPPI_BATCH_MAIL")) bh->mail_any_size = std::strcmp(mv, "1") == 0;
+    }
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return bail(CCV_MPPI_ERR_HIP, "hipDeviceSynchronize", e);
+    *out = bh;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    const DeviceGuard guard(h->cfg.device);
+    (void)hipSetDevice(h->cfg.device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->own_stream && h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
+    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->throttle_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (int s = 0; s < ccv_mppi_batch::kRecSlots; ++s) {
+        if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
+        if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
+    }
+    void* bufs[] = {h->d_arena, h->d_nominal, h->d_nom_used, h->d_statpart, h->d_vec, h->d_stats, h->d_scratch, bh->d_rec};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (h->h_pin) (void)hipHostFree(h->h_pin);
+    if (h->h_mail) (void)hipHostFree(h->h_mail);
+    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    delete bh;
+    return CCV_MPPI_OK;
+}
+
+const char* ccv_mppi_batch_last_error(const ccv_mppi_batch* bh) { return bh ? bh->h.err.c_str() : "null handle"; }
+
+int ccv_mppi_batch_size(const ccv_mppi_batch* bh) { return bh ? bh->B : CCV_MPPI_ERR_INVALID_ARG; }
+
+int ccv_mppi_batch_last_kernel(const ccv_mppi_batch* bh) { return bh ? bh->last_kernel : CCV_MPPI_ERR_INVALID_ARG; }
+
+int ccv_mppi_batch_set_stream(ccv_mppi_batch* bh, void* hip_stream) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
+    for (bool& u : h->throttle_used) u = false;   // marks recorded on the old stream are complete (synchronised above)
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_synchronize(ccv_mppi_batch* bh) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    HIP_TRY(&bh->h, hipStreamSynchronize(bh->h.stream));
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_set_nominal(ccv_mppi_batch* bh, const double* u) {
+    if (!bh || !u) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    HIP_TRY(h, hipMemcpyAsync(h->d_nominal, u, (size_t)bh->B * h->R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
+    if (!bh || !u) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    HIP_TRY(h, hipMemcpyAsync(u, h->d_nominal, (size_t)bh->B * h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_iterate(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
+                           const double* yaw_ref0, const uint64_t* seed, uint64_t iter, double* u_opt_out, ccv_mppi_stats* stats) {
+    int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
+    if (rc) return rc;
+    bh->h.want_mail = !(stats && bh->h.timing);   // (a timed call synchronises for its events anyway)
+    rc = batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
+    bh->h.want_mail = false;
+    if (rc) return rc;
+    return batch_fetch(bh, u_opt_out, stats);
+}
+
+int ccv_mppi_batch_iterate_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref,
+                                   const double* y_ref, const double* yaw_ref0, const uint64_t* seed, uint64_t iter) {
+    int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
+    if (rc) return rc;
+    return batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
+}
+
+int ccv_mppi_batch_read_costs(ccv_mppi_batch* bh, int32_t instance, int32_t first, int32_t count, double* out) {
+    if (int rc = batch_check_read(bh, instance, out)) return rc;
+    ccv_mppi_handle* h = &bh->h;
+    if (first < 0 || count < 0 || (int64_t)first + count > h->K) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
+    const size_t col = (size_t)instance * bh->kpad + first;
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_cost + col, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_read_weights(ccv_mppi_batch* bh, int32_t instance, int32_t first, int32_t count, double* out) {
+    if (int rc = batch_check_read(bh, instance, out)) return rc;
+    ccv_mppi_handle* h = &bh->h;
+    if (first < 0 || count < 0 || (int64_t)first + count > h->K) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
+    if (count == 0) return CCV_MPPI_OK;
+    if (int rc = ensure_scratch(h, (size_t)count * sizeof(double))) return rc;
+    hipLaunchKernelGGL(k_normalise_weights, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream,
+                       h->d_w + (size_t)instance * bh->kpad, h->d_stats + (size_t)instance * 4, first, count, h->d_scratch);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_scratch, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_read_candidates(ccv_mppi_batch* bh, int32_t instance, int32_t first, int32_t count, int32_t stride,
+                                   double* xy_out) {
+    if (int rc = batch_check_read(bh, instance, xy_out)) return rc;
+    ccv_mppi_handle* h = &bh->h;
+    if (first < 0 || count < 0 || stride < 1) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "first < 0, count < 0 or stride < 1");
+    if (h->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) return batch_fail(bh, CCV_MPPI_ERR_STATE, "state buffer disabled (NO_STATE_STORE)");
+    if (count == 0) return CCV_MPPI_OK;
+    if ((int64_t)first + (int64_t)(count - 1) * stride >= h->K) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "candidate range exceeds num_samples");
+    const size_t n = (size_t)count * h->H * 2;
+    if (int rc = ensure_scratch(h, n * sizeof(double))) return rc;
+    hipLaunchKernelGGL(k_gather_xy, dim3((count * h->H + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->d_xs, h->d_ys,
+                       h->pitch, h->H, instance * bh->kpad + first, count, stride, h->d_scratch);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(xy_out, h->d_scratch, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_timing_enable(ccv_mppi_batch* bh, int32_t on) {
+    return bh ? ccv_mppi_timing_enable(&bh->h, on) : CCV_MPPI_ERR_INVALID_ARG;
+}
+
+int ccv_mppi_batch_timing_read(ccv_mppi_batch* bh, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset) {
+    return bh ? ccv_mppi_timing_read(&bh->h, rollout_us_sum, iter_us_sum, n_iters, reset) : CCV_MPPI_ERR_INVALID_ARG;
 }
 
 }  // extern "C"

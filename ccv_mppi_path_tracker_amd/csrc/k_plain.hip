@@ -22,6 +22,14 @@ void launch_rollout_plain(int model, bool philox, bool lds_window, const LaunchA
     else launch_plain_model<CCV_MPPI_FULL_BODY>(philox, lds_window, at, A, W);
 }
 
+// batch handles: grid (workgroups per instance, instances)
+void launch_rollout_plain_batch(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
+    const dim3 grid((unsigned)((A.K + kBlock - 1) / kBlock), (unsigned)batch), block(kBlock);
+    if (model == CCV_MPPI_DIFF_DRIVE) launch_at(k_rollout_cost<CCV_MPPI_DIFF_DRIVE, SRC_PHILOX, true, true>, grid, block, at, A, W);
+    else if (model == CCV_MPPI_STEERING_DIFF_DRIVE) launch_at(k_rollout_cost<CCV_MPPI_STEERING_DIFF_DRIVE, SRC_PHILOX, true, true>, grid, block, at, A, W);
+    else launch_at(k_rollout_cost<CCV_MPPI_FULL_BODY, SRC_PHILOX, true, true>, grid, block, at, A, W);
+}
+
 void launch_sample(int model, hipStream_t stream, const RolloutArgs& A) {
     const int R = (A.H - 1) * udim_of(model);
     const dim3 grid((unsigned)((A.K + kBlock - 1) / kBlock), (unsigned)((R + 3) / 4)), block(kBlock);

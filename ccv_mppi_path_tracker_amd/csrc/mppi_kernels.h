@@ -73,6 +73,22 @@ struct ResidentFrame {
     double x_ref[kMaxH], y_ref[kMaxH];
 };
 
+// Batch handles (ccv_mppi_batch_*): B independent problems of K samples each share one configuration and lie on ONE sample
+// axis of B * Kpad columns (Kpad = K rounded up to 64) in the layout above, so no workgroup of 64 samples straddles two
+// instances.  What differs per instance travels in a record in device memory, one per instance, batch_record_doubles(H)
+// doubles apart: a BatchHead (two 64-byte lines), then the window coefficients a[H], b[H], c[H].  A batched rollout is
+// launched with RolloutArgs::frame pointing at record 0 and takes its instance's record in batch_view() below.
+struct BatchHead {
+    double x0[5];
+    double yaw_ref0;
+    double dt, inv_dt;
+    uint32_t seed_lo, seed_hi;
+    int32_t K, k_offset;        // b * Kpad + K and -b * Kpad (see batch_view)
+    const double* nominal;      // the instance's warm start
+};
+constexpr int kBatchHeadDoubles = 16;
+__host__ __device__ constexpr int batch_record_doubles(int H) { return kBatchHeadDoubles + ((3 * H + 7) & ~7); }
+
 struct RolloutArgs {
     double x0[5];
     double dt;
@@ -133,12 +149,52 @@ __device__ __forceinline__ RolloutArgs with_resident_pose(const RolloutArgs& Ak)
     return A;
 }
 
+// Instance `inst` of a batched launch as a single handle of its own: pose, dt, 1 / dt, yaw_ref0, the noise key and its slice
+// of the warm start from its record, the window from the record too (stage_window<true>, r4_stage_issue<..., true>).  The
+// sample index stays the global column k = inst * Kpad + local k: K and k_offset are shifted by inst * Kpad instead (the
+// host writes them into the record), so that `k < K` masks the lanes past the instance's own K and k_offset + k is the
+// LOCAL index, the counter word of noise_spec.h.  The partials stay [(R+1)][nparts] with nparts = B * the instance's
+// workgroups: column blockIdx.x, each instance's columns contiguous (k_finalize_batch).  Workgroup 0 of the launch
+// (instance 0) writes nominal_used; the batch has no read-back of the controls that would need the other instances'.
+__device__ __forceinline__ RolloutArgs batch_view(const RolloutArgs& Ak, const int inst) {
+    RolloutArgs A = Ak;
+    const double* rec = reinterpret_cast<const double*>(Ak.frame) + (size_t)inst * batch_record_doubles(Ak.H);
+    // (read through the constant address space, like the kernel arguments: the compiler may load a field again where it is
+    //  used instead of holding it in registers from entry to exit -- held, they pushed the four-wave kernel into more spills)
+    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
+    const auto& hd = *(ConstHead)(const void*)rec;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) A.x0[i] = hd.x0[i];
+    A.yaw_ref0 = hd.yaw_ref0;
+    A.dt = hd.dt;
+    A.inv_dt = hd.inv_dt;
+    A.seed_lo = hd.seed_lo;
+    A.seed_hi = hd.seed_hi;
+    A.frame = reinterpret_cast<const ResidentFrame*>(rec);
+    A.K = hd.K;
+    A.k_offset = hd.k_offset;
+    A.nominal = hd.nominal;
+    return A;
+}
+// the kernel arguments of a workgroup of 64 samples: batched (instance = workgroup / workgroups per instance) or not
+template <int MODEL, bool BATCH>
+__device__ __forceinline__ RolloutArgs rollout_view(const RolloutArgs& Ak) {
+    if constexpr (BATCH) return batch_view(Ak, (int)blockIdx.x / ((Ak.K + 63) >> 6));
+    else return with_resident_pose(Ak);
+}
+
 // window coefficients -> LDS, padded to a multiple of 4 points with c = +inf (never the minimum)
-template <class SH>
+template <bool BATCH = false, class SH>
 __device__ __forceinline__ void stage_window(const RolloutArgs& A, const Window& Wk, SH& sh, int nthreads,
                                              const int tid = threadIdx.x) {   // (tid: 0 .. nthreads-1 over the staging threads)
     const int H = A.H, H4 = (H + 3) & ~3;
-    if (A.frame) {
+    if constexpr (BATCH) {   // (batch_view: the instance's record)
+        const double* win = reinterpret_cast<const double*>(A.frame) + kBatchHeadDoubles;
+        for (int j = tid; j < H4; j += nthreads) {
+            sh.ab[j] = j < H ? make_double2(win[j], win[H + j]) : make_double2(0.0, 0.0);
+            sh.c[j] = j < H ? win[2 * H + j] : INFINITY;
+        }
+    } else if (A.frame) {
         const Window& W = A.frame->W;
         for (int j = tid; j < H4; j += nthreads) {
             sh.ab[j] = j < H ? make_double2(W.a[j], W.b[j]) : make_double2(0.0, 0.0);
@@ -213,20 +269,30 @@ __device__ __forceinline__ void window_min(const double (&px)[kTU], const double
     }
 }
 
-template <int MODEL, int SRC, bool LDSWIN>
-__global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs A, const Window W) {
+// BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view)
+template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false>
+__global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
+    static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
     constexpr int UD = udim_of(MODEL);
     __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
     __shared__ double s_c[LDSWIN ? kMaxH : 1];
+    const RolloutArgs A = BATCH ? batch_view(Ak, (int)blockIdx.y) : Ak;
     const int H = A.H;
-    if constexpr (LDSWIN) {
+    if constexpr (BATCH) {
+        const double* win = reinterpret_cast<const double*>(A.frame) + kBatchHeadDoubles;
+        for (int j = threadIdx.x; j < H; j += kBlock) {
+            s_ab[j] = make_double2(win[j], win[H + j]);
+            s_c[j] = win[2 * H + j];
+        }
+        __syncthreads();
+    } else if constexpr (LDSWIN) {
         for (int j = threadIdx.x; j < H; j += kBlock) {
             s_ab[j] = make_double2(W.a[j], W.b[j]);
             s_c[j] = W.c[j];
         }
         __syncthreads();
     }
-    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const int k = blockIdx.x * kBlock + threadIdx.x + (BATCH ? (int)blockIdx.y * ((Ak.K + 63) & ~63) : 0);
     const bool live = k < A.K;
     const int kk = live ? k : A.K - 1;
     const size_t pitch = (size_t)A.pitch;

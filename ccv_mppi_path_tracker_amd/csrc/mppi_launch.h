@@ -1,5 +1,5 @@
 // Launchers of the rollout kernel families.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip,
-// k_r4_fb.hip, k_pc_fb.hip, k_solo.hip, k_solo_fb.hip, k_plain.hip): hipcc spends over a minute on all instantiations in one file, the
+// k_r4_fb.hip, k_pc_fb.hip, k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip: batch forms): hipcc spends over a minute on all instantiations in one file, the
 // units compile side by side (build.py).  ccv_mppi_capi.hip -- the C ABI -- selects the family and calls these.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +24,11 @@ void launch_rollout_solo(int model, bool wide, const LaunchAt& at, const Rollout
 // the plain one-sample-per-lane kernel: philox = device noise (fused iteration) or controls read from the buffer
 void launch_rollout_plain(int model, bool philox, bool lds_window, const LaunchAt& at, const RolloutArgs& A, const Window& W);
 void launch_sample(int model, hipStream_t stream, const RolloutArgs& A);
+// batch handles (the fused iteration of `batch` instances of A.K samples each; A.frame = their records, batch_view): the
+// four-wave kernel, the one-wave kernel and the plain kernel (unbounded headings)
+void launch_rollout_r4_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+void launch_rollout_solo_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+void launch_rollout_plain_batch(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
 
 template <class KERNEL>
 inline void launch_at(KERNEL kernel, const dim3 grid, const dim3 block, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
@@ -31,5 +36,6 @@ inline void launch_at(KERNEL kernel, const dim3 grid, const dim3 block, const La
     else hipLaunchKernelGGL(kernel, grid, block, 0, at.stream, A, W);
 }
 inline dim3 blocks_of_64(const RolloutArgs& A) { return dim3((unsigned)((A.K + 63) / 64)); }
+inline dim3 blocks_of_64(const RolloutArgs& A, const int batch) { return dim3((unsigned)batch * (unsigned)((A.K + 63) / 64)); }
 
 }  // namespace ccv

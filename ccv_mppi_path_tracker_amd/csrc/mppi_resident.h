@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kAdvanceThreads) void k_advance(const AdvanceArgs A
 // and runs the prologue with it.
 __global__ __launch_bounds__(kBlock) void k_finalize_advance(const FinalizeArgs F, const AdvanceArgs A) {
     if ((int)blockIdx.x < finalize_blocks(F.R)) {
-        finalize_rows(F);
+        finalize_rows(F, (size_t)F.nchunks);
         return;
     }
     __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];

@@ -145,14 +145,19 @@ struct R4Staged {
     double nv[kPerThread];
     double S;
 };
-template <int MODEL, int NT>
+template <int MODEL, int NT, bool BATCH = false>
 __device__ __forceinline__ void r4_stage_issue(const RolloutArgs& A, const Window& Wk, const int tid, R4Staged<MODEL, NT>& L) {
     static_assert(NT >= kMaxH + 4, "one window point per thread");
     const int H = A.H, R = (H - 1) * udim_of(MODEL);
     L.wa = L.wb = 0.0;
     L.wc = INFINITY;
     if (tid < H) {
-        if (A.frame) {   // (a wave-uniform choice: the resident loop's window, or the copy in the kernel arguments)
+        if constexpr (BATCH) {   // (batch_view: the instance's record)
+            const double* win = reinterpret_cast<const double*>(A.frame) + kBatchHeadDoubles;
+            L.wa = win[tid];
+            L.wb = win[H + tid];
+            L.wc = win[2 * H + tid];
+        } else if (A.frame) {   // (a wave-uniform choice: the resident loop's window, or the copy in the kernel arguments)
             const Window& W = A.frame->W;
             L.wa = W.a[tid];
             L.wb = W.b[tid];
@@ -227,17 +232,20 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // at a 256 cap; alone on its SIMD a wave may have 512 -- i.e. one workgroup per CU: the kernel for K up to one block of 64
 // samples per CU, where the reference's own operating point lies (K = 10 000: 157 blocks on 256 CUs; in the two-wave kernel every
 // wave was alone on its SIMD there too, and its producer made the 40 normals of a block itself).
-template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false>
+// BATCH (fused iteration): workgroup blockIdx.x serves instance blockIdx.x / (its workgroups per instance) of a batch handle
+// (batch_view, mppi_kernels.h); everything else is the single handle's code
+template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
     constexpr int UD = udim_of(MODEL);
     static_assert(!WIDE || (MODEL == CCV_MPPI_DIFF_DRIVE && MODE == MODE_FUSED), "the wide-turn form exists for the fused diff-drive iteration");
     static_assert(!TAIL || MODE == MODE_FUSED, "the stage-wise modes carry the masked producer anyway");
+    static_assert(!BATCH || MODE == MODE_FUSED, "batch handles run the fused iteration only");
     __shared__ R4Shared<MODEL> sh;
     static_assert(offsetof(R4Shared<MODEL>, zs) + sizeof(sh.zs) >= kR4Waves * kR4RB<MODEL> * (kPcSamples + 2) * sizeof(double), "epilogue buffers");
     touch_rollout_args();
-    const RolloutArgs A = with_resident_pose(Ak);
+    const RolloutArgs A = rollout_view<MODEL, BATCH>(Ak);
     // The prologue runs in all sixteen waves of a CU at once and SIMD arbitration is oldest first: the workgroup dispatched last
     // to a CU was through it 1.5 us after the first (stamps: staging barrier passed at 1.4 / 1.7 / 2.0 / 3.0 us by dispatch
     // rank) and carried that lag to the end of the kernel, which ends with the slowest.  Until the loops' rotation takes over,
@@ -263,7 +271,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     bool bad_nominal = false;
     if constexpr (MODE == MODE_FUSED) {
         R4Staged<MODEL, kR4Waves * 64> staged;
-        r4_stage_issue<MODEL>(A, Wk, (int)threadIdx.x, staged);
+        r4_stage_issue<MODEL, kR4Waves * 64, BATCH>(A, Wk, (int)threadIdx.x, staged);
         if (nfull > 0) {
             constexpr int NCALL = kTU * UD / 4;
             const R4Lane L = r4_lane(A);

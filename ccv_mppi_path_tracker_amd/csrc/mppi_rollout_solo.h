@@ -24,16 +24,17 @@ struct SoloShared {
     alignas(32) double nom[(kMaxH + 8) * udim_of(MODEL)];  // warm start u*
 };
 
-template <int MODEL, int MODE, bool WIDE = false>   // WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4)
+// WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h)
+template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false>
 __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArgs Ak, const Window Wk) {
     static_assert(MODE == MODE_FUSED, "the stage-wise modes use k_rollout_pc");
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     __shared__ SoloShared<MODEL> sh;
     static_assert(sizeof(sh.p) >= kUpdRB * (kPcSamples + 2) * sizeof(double), "epilogue buffer");
-    const RolloutArgs A = with_resident_pose(Ak);
+    const RolloutArgs A = rollout_view<MODEL, BATCH>(Ak);
     const int H = A.H;
     const int lane = threadIdx.x;
-    stage_window(A, Wk, sh, kPcSamples);
+    stage_window<BATCH>(A, Wk, sh, kPcSamples);
     // two-instruction clamps (clampd_fast, mppi_kernels.h): the host has checked sigma and the bounds, this wave the warm start;
     // a NaN anywhere takes every block through the compare-and-select instantiation
     const bool fast_clamp = A.fast_clamp && __builtin_amdgcn_ballot_w64(pc_stage_nominal<MODEL>(A, sh, kPcSamples)) == 0ull;

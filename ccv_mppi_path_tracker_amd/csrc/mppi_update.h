@@ -40,7 +40,7 @@ struct UpdateArgs {
 
 // grid (nchunks, R+1).  Row n < R: sum_k w_k*u[n][k] over this chunk; row R: sum_k w_k (+ cost stats).
 // Fixed reduction order => bitwise reproducible (no atomics).
-__global__ __launch_bounds__(kBlock) void k_update_partials(const UpdateArgs A) {
+__device__ __forceinline__ void update_partials(const UpdateArgs& A) {
     __shared__ double red[4][4];
     const int row = blockIdx.y;
     const int chunk = blockIdx.x;
@@ -100,6 +100,19 @@ __global__ __launch_bounds__(kBlock) void k_update_partials(const UpdateArgs A) 
             A.statpart[chunk * 3 + 2] = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
         }
     }
+}
+__global__ __launch_bounds__(kBlock) void k_update_partials(const UpdateArgs A) { update_partials(A); }
+// Batch handles (the plain kernel's iteration): grid (nchunks, R+1, B).  Instance blockIdx.z owns the columns
+// [z * kpad, z * kpad + K) of the shared rows and a block of partials [(R+1)][nchunks] and statistics [nchunks][3] of its own:
+// the single handle's reduction, instance by instance.
+__global__ __launch_bounds__(kBlock) void k_update_partials_batch(UpdateArgs A, const int kpad) {
+    const size_t b = blockIdx.z;
+    A.u += b * kpad;
+    A.w += b * kpad;
+    A.cost += b * kpad;
+    A.partial += b * (size_t)(A.R + 1) * A.nchunks;
+    A.statpart += b * (size_t)A.nchunks * 3;
+    update_partials(A);
 }
 
 struct FinalizeArgs {
@@ -188,7 +201,8 @@ __device__ __forceinline__ void finalize_cost_stats(const FinalizeArgs& A, const
 }
 constexpr int finalize_blocks(int R) { return (R + 2 + kBlock / 64 - 1) / (kBlock / 64); }   // waves: R rows, sum w, statistics
 
-__device__ __forceinline__ void finalize_rows(const FinalizeArgs& A) {
+// (stride: the row pitch of the partials, nchunks but for a batch handle's fused partials)
+__device__ __forceinline__ void finalize_rows(const FinalizeArgs& A, const size_t stride) {
     const int lane = threadIdx.x & 63;
     // rows 0..R-1: one wave each; wave R: sum w; wave R + 1: the cost statistics
     const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -199,7 +213,7 @@ __device__ __forceinline__ void finalize_rows(const FinalizeArgs& A) {
     const int nrow = n < A.R ? n : A.R;
     // S = sum w and this wave's row are fetched together
     double s, v;
-    lane_partial_sum2(A.partial + (size_t)A.R * A.nchunks, A.partial + (size_t)nrow * A.nchunks, A.nchunks, lane, s, v);
+    lane_partial_sum2(A.partial + (size_t)A.R * stride, A.partial + (size_t)nrow * stride, A.nchunks, lane, s, v);
     s = wave_sum(s);
     v = wave_sum(v);
     if (n < A.R && lane == 0) {
@@ -216,7 +230,22 @@ __device__ __forceinline__ void finalize_rows(const FinalizeArgs& A) {
         if (A.mail) mail_post(A, A.R, s);
     }
 }
-__global__ __launch_bounds__(kBlock) void k_finalize(const FinalizeArgs A) { finalize_rows(A); }
+__global__ __launch_bounds__(kBlock) void k_finalize(const FinalizeArgs A) { finalize_rows(A, (size_t)A.nchunks); }
+// Batch handles: grid (finalize_blocks(R), B); instance blockIdx.y reduces its own nchunks columns of the partials in the
+// single handle's order (the same bits) into its slices of u* [B][R], vec [B][R+1], stats [B][4] and mailbox slots [B][R+4] --
+// every packet under the launch's one sequence number.  Partials: `fused` -- the rollout kernels' [(R+1)][B * nchunks],
+// instance b in columns b * nchunks ...; otherwise k_update_partials_batch's [B][(R+1)][nchunks].  Statistics [B][nchunks][3].
+__global__ __launch_bounds__(kBlock) void k_finalize_batch(FinalizeArgs A, const int fused) {
+    const size_t b = blockIdx.y;
+    const size_t stride = fused ? (size_t)gridDim.y * A.nchunks : (size_t)A.nchunks;
+    A.partial += fused ? b * A.nchunks : b * (size_t)(A.R + 1) * A.nchunks;
+    A.statpart += b * (size_t)A.nchunks * 3;
+    A.nominal += b * A.R;
+    A.vec += b * (size_t)(A.R + 1);
+    A.stats += b * 4;
+    if (A.mail) A.mail += 2 * b * (size_t)(A.R + 4);
+    finalize_rows(A, stride);
+}
 
 // ---- K sharded over the GPUs of one node without a collective library call ---------------------------
 // The exchanged message is 1 + (H-1)*u_dim doubles (<= 3.2 KB): far below the size at which a ring all-reduce pays, and a

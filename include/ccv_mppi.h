@@ -227,6 +227,58 @@ int ccv_mppi_timing_enable(ccv_mppi_handle* h, int32_t on);
 int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters,
                          int32_t reset);
 
+/* ---- batch handles: B independent problems in one launch -------------------------------------------------------- */
+/* B controllers that share one configuration (model, K = num_samples per instance, H, sigma, lambda, bounds, weights, flags)
+ * and differ in pose, dt, reference window, warm start and noise seed: one call runs all of them with one rollout launch and
+ * one update launch -- what a process that serves N robots, or sweeps N scenarios, would otherwise spend N handles and N
+ * blocking round trips on.  Instance b computes what a single handle with the same configuration computes for the same
+ * (x0[b], dt[b], x_ref[b], y_ref[b], yaw_ref0[b], seed[b], iter) from the same warm start: its noise is that of noise_spec.h
+ * with key seed[b] and the local sample index 0 .. K-1; no input of one instance changes any output bit of another.
+ * The bits equal the single handle's where both run the same kernel family, which the single handle's selection rule, applied
+ * to the batch's B * ceil(K / 64) workgroups of 64 samples, decides (four-wave kernel up to five workgroups per CU, full body
+ * one; the one-wave kernel beyond, also where a single full-body handle would run the two-wave kernel).  One instance whose
+ * headings can leave the range of the kernels' fast sin / cos sends the whole batch through the plain kernel, one diff-drive
+ * instance with |w|max dt > pi/4 through the wide-turn instantiation: the results then agree with the single handle's to
+ * rounding.  CCV_MPPI_KERNEL=v1 selects the plain kernel; the environment's other kernel overrides do not apply to batches.
+ * Conventions as above: int status, one batch handle per caller thread, the caller's current device is restored. */
+#define CCV_MPPI_BATCH_MAX_SAMPLES (1 << 29) /* B * ceil(K / 64) * 64: the kernels index the sample axis with 32-bit byte offsets */
+/* ccv_mppi_batch_last_kernel(): the rollout kernel of the last call (FOUR_WAVE / ONE_WAVE / PLAIN, | WIDE: wide-turn form) */
+#define CCV_MPPI_BATCH_KERNEL_PLAIN 0
+#define CCV_MPPI_BATCH_KERNEL_ONE_WAVE 1
+#define CCV_MPPI_BATCH_KERNEL_FOUR_WAVE 4
+#define CCV_MPPI_BATCH_KERNEL_WIDE 16
+
+typedef struct ccv_mppi_batch ccv_mppi_batch;
+
+/* batch >= 1; cfg->sample_offset must be 0; CCV_MPPI_FLAG_MIN_SHIFT is refused (CCV_MPPI_ERR_INVALID_ARG: the stabilised
+ * weights are not built for batches); batch * ceil(K / 64) * 64 <= CCV_MPPI_BATCH_MAX_SAMPLES.  Arguments are checked before
+ * any device is touched; without a device: CCV_MPPI_ERR_NO_DEVICE. */
+int ccv_mppi_batch_create(const ccv_mppi_config* cfg, int32_t batch, ccv_mppi_batch** out);
+int ccv_mppi_batch_destroy(ccv_mppi_batch* b);
+int ccv_mppi_batch_set_stream(ccv_mppi_batch* b, void* hip_stream);
+int ccv_mppi_batch_synchronize(ccv_mppi_batch* b);
+const char* ccv_mppi_batch_last_error(const ccv_mppi_batch* b);
+int ccv_mppi_batch_size(const ccv_mppi_batch* b);
+int ccv_mppi_batch_last_kernel(const ccv_mppi_batch* b);
+/* warm starts, layout [B][(H-1)][u_dim] */
+int ccv_mppi_batch_set_nominal(ccv_mppi_batch* b, const double* u);
+int ccv_mppi_batch_get_nominal(ccv_mppi_batch* b, double* u);
+/* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
+ * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
+int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
+                           const double* yaw_ref0, const uint64_t* seed, uint64_t iter, double* u_opt_out, ccv_mppi_stats* stats);
+/* the same work without a host synchronisation; u* stays resident as the next call's warm start (ccv_mppi_batch_get_nominal) */
+int ccv_mppi_batch_iterate_enqueue(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
+                                   const double* yaw_ref0, const uint64_t* seed, uint64_t iter);
+/* per-instance read-backs of the last iteration, as ccv_mppi_read_costs / _read_weights / _read_candidates */
+int ccv_mppi_batch_read_costs(ccv_mppi_batch* b, int32_t instance, int32_t first, int32_t count, double* out);
+int ccv_mppi_batch_read_weights(ccv_mppi_batch* b, int32_t instance, int32_t first, int32_t count, double* out);
+int ccv_mppi_batch_read_candidates(ccv_mppi_batch* b, int32_t instance, int32_t first, int32_t count, int32_t stride,
+                                   double* xy_out);
+/* as ccv_mppi_timing_enable / _read: the rollout kernel of the whole batch and the whole launch sequence */
+int ccv_mppi_batch_timing_enable(ccv_mppi_batch* b, int32_t on);
+int ccv_mppi_batch_timing_read(ccv_mppi_batch* b, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset);
+
 #ifdef __cplusplus
 }
 #endif
