@@ -12,6 +12,13 @@ from .controller import MPPIError, make_config
 from .configs import MPPIParams
 
 
+def _is_1d(a):
+    try:
+        return np.asarray(a, dtype=np.float64).ndim == 1
+    except (TypeError, ValueError):
+        return False
+
+
 class BatchController:
     """`batch` controllers with one shared configuration (K = num_samples per instance) on one device."""
 
@@ -116,6 +123,60 @@ class BatchController:
         self._check(self.lib.ccv_mppi_batch_read_candidates(self._h, int(instance), int(first), int(count), int(stride),
                                                             capi.dptr(out)))
         return out
+
+    # ---- device-resident closed loop of every instance (ccv_mppi_batch_resident_*) ----
+    def resident_set_paths(self, paths, resolution=None):
+        """paths: B (path_x, path_y) pairs, or one pair for every instance; resolution: one value or [B] (default: the
+        parameters' resolution)."""
+        if len(paths) == 2 and _is_1d(paths[0]) and _is_1d(paths[1]):
+            paths = [paths] * self.B
+        if len(paths) != self.B:
+            raise ValueError("paths: expected %d (path_x, path_y) pairs, got %d" % (self.B, len(paths)))
+        xs, ys = [], []
+        for b, (px, py) in enumerate(paths):
+            px, py = np.asarray(px, dtype=np.float64), np.asarray(py, dtype=np.float64)
+            if px.ndim != 1 or px.shape != py.shape or px.size < 1:
+                raise ValueError("path %d: path_x and path_y must be non-empty 1-D arrays of one length" % b)
+            xs.append(px)
+            ys.append(py)
+        n = np.ascontiguousarray([len(px) for px in xs], dtype=np.int32)
+        res = self.params.resolution if resolution is None else resolution
+        res = capi.as_f64(np.broadcast_to(np.asarray(res, dtype=np.float64), (self.B,)))
+        px, py = capi.as_f64(np.concatenate(xs)), capi.as_f64(np.concatenate(ys))
+        self._check(self.lib.ccv_mppi_batch_resident_set_paths(self._h, capi.dptr(px), capi.dptr(py),
+                                                               n.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(res)))
+
+    def resident_set_poses(self, states, seeds):
+        """states [B][nstate] (x, y, yaw[, roll, pitch]); seeds [B] (or one value): every instance's noise key."""
+        st = np.asarray(states, dtype=np.float64)
+        if st.ndim != 2 or st.shape[0] != self.B or not 3 <= st.shape[1] <= 5:
+            raise ValueError("states: expected shape (%d, 3..5), got %s" % (self.B, st.shape))
+        x = np.zeros((self.B, 5))
+        x[:, :st.shape[1]] = st
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (self.B,)))
+        self._check(self.lib.ccv_mppi_batch_resident_set_poses(self._h, capi.dptr(x), sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def resident_step_enqueue(self, dt, iteration, advance=True):
+        """One tick of every instance, no host data: (advance) pose += plant(u*[b][0]) -> window -> MPPI iteration."""
+        self._check(self.lib.ccv_mppi_batch_resident_step_enqueue(self._h, float(dt), int(iteration), 1 if advance else 0))
+
+    def resident_read(self):
+        """(states [B][nstate], current_index [B], x_ref [B][H], y_ref [B][H], yaw_ref0 [B], steps); synchronises."""
+        st = np.zeros((self.B, 5))
+        idx = np.zeros(self.B, dtype=np.int32)
+        xr, yr, yaw0 = np.zeros((self.B, self.H)), np.zeros((self.B, self.H)), np.zeros(self.B)
+        steps = C.c_int64()
+        self._check(self.lib.ccv_mppi_batch_resident_read(self._h, capi.dptr(st), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          capi.dptr(xr), capi.dptr(yr), capi.dptr(yaw0), C.byref(steps)))
+        return st[:, :self.nstate].copy(), idx, xr, yr, yaw0, steps.value
+
+    def resident_read_trace(self, instance, max_rows=None):
+        """Instance `instance`'s poses of the last ticks, oldest first: rows (x, y, yaw, roll, pitch, current_index)."""
+        max_rows = capi.BATCH_TRACE_ROWS if max_rows is None else int(max_rows)
+        rows = np.zeros((max(max_rows, 0), 6))
+        n = C.c_int32()
+        self._check(self.lib.ccv_mppi_batch_resident_read_trace(self._h, int(instance), max_rows, capi.dptr(rows), C.byref(n)))
+        return rows[:n.value].copy()
 
     # ---- measurement ----
     def timing_enable(self, on=True, every=1):

@@ -25,6 +25,7 @@ DIFF_DRIVE, STEERING_DIFF_DRIVE, FULL_BODY = 0, 1, 2
 FLAG_ROLL_OFF, FLAG_STEER_OFF, FLAG_MIN_SHIFT, FLAG_NO_STATE_STORE = 0x1, 0x2, 0x4, 0x8
 BATCH_MAX_SAMPLES = 1 << 29
 BATCH_KERNEL_PLAIN, BATCH_KERNEL_ONE_WAVE, BATCH_KERNEL_FOUR_WAVE, BATCH_KERNEL_WIDE = 0, 1, 4, 16
+BATCH_TRACE_ROWS = 1024
 
 
 class Config(C.Structure):
@@ -110,6 +111,11 @@ SIGNATURES = {
     "ccv_mppi_batch_read_candidates": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "ccv_mppi_batch_timing_enable": (C.c_int, [_H, C.c_int32]),
     "ccv_mppi_batch_timing_read": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int64), C.c_int32]),
+    "ccv_mppi_batch_resident_set_paths": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int32), _dp]),
+    "ccv_mppi_batch_resident_set_poses": (C.c_int, [_H, _dp, C.POINTER(C.c_uint64)]),
+    "ccv_mppi_batch_resident_step_enqueue": (C.c_int, [_H, C.c_double, C.c_uint64, C.c_int32]),
+    "ccv_mppi_batch_resident_read": (C.c_int, [_H, _dp, C.POINTER(C.c_int32), _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "ccv_mppi_batch_resident_read_trace": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int32)]),
     # include/ccv_mppi_host.h
     "ccv_mppi_calc_ref_path": (C.c_int, [_dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_double, C.c_int32, _dp, _dp, _dp]),

@@ -1543,6 +1543,20 @@ struct ccv_mppi_batch {
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
     bool have_result = false;
+    // device-resident closed loop of every instance (ccv_mppi_batch_resident_*, mppi_resident.h): the update of a resident
+    // tick is launched together with the next tick's prologue (k_finalize_advance_batch); anything else that needs u*, the
+    // statistics or the stream first gets a plain k_finalize_batch (batch_flush)
+    bool fin_pending = false;
+    FinalizeArgs fin_args{};
+    ResidentFrame* d_rframe = nullptr;      // [B]
+    BatchInstance* d_inst = nullptr;        // [B]
+    double* d_rpath = nullptr;              // [2][n_total]
+    double* d_rtrace = nullptr;             // [B][CCV_MPPI_BATCH_TRACE_ROWS][6]
+    int64_t n_total = 0;
+    std::vector<BatchInstance> inst;        // host copy of d_inst
+    std::vector<double> res_angle_abs;      // [B][3]: bounds on |yaw|, |roll|, |pitch| of every resident pose
+    bool have_paths = false, have_poses = false;
+    int64_t res_steps = 0;                  // resident ticks since the poses were set (every instance's step count)
 };
 
 namespace {
@@ -1555,6 +1569,18 @@ int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, con
     if (!x0 || !dt || !x_ref || !y_ref || !yaw_ref0 || !seed) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
     for (int b = 0; b < bh->B; ++b)
         if (!(dt[b] == dt[b])) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "dt is NaN");
+    return CCV_MPPI_OK;
+}
+
+int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, int trig, bool defer);
+
+// a deferred resident update (batch_launch) is launched now, as the plain k_finalize_batch of the fused partials
+int batch_flush(ccv_mppi_batch* bh) {
+    if (!bh->fin_pending) return CCV_MPPI_OK;
+    ccv_mppi_handle* h = &bh->h;
+    hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(h->R), bh->B), dim3(kBlock), 0, h->stream, bh->fin_args, 1);
+    bh->fin_pending = false;
+    HIP_TRY(h, hipGetLastError());
     return CCV_MPPI_OK;
 }
 
@@ -1605,7 +1631,14 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
     HIP_TRY(h, hipMemcpyAsync(bh->d_rec, rec, (size_t)B * bh->rec_doubles * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipEventRecord(bh->rec_ev[slot], h->stream));
     bh->rec_used[slot] = true;
+    return batch_launch(bh, A, trig, false);
+}
 
+// the rollout of every instance from the records in d_rec, then the per-instance update; `defer` (resident ticks): the update
+// of the fused kernels waits in bh->fin_args for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
+int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
+    ccv_mppi_handle* h = &bh->h;
+    const int B = bh->B;
     const bool plain = trig == kTrigUnsafe;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * h->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -1671,8 +1704,13 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
         h->mail_pending = true;
     }
     h->want_mail = false;
-    hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(h->R), B), dim3(kBlock), 0, h->stream, F, plain ? 0 : 1);
-    HIP_TRY(h, hipGetLastError());
+    if (defer && !plain && !timed && !F.mail) {
+        bh->fin_args = F;
+        bh->fin_pending = true;
+    } else {
+        hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(h->R), B), dim3(kBlock), 0, h->stream, F, plain ? 0 : 1);
+        HIP_TRY(h, hipGetLastError());
+    }
     if (timed) HIP_TRY(h, hipEventRecord(h->ev[tslot + 2], h->stream));
     if (h->throttle && ++h->enqueued % ccv_mppi_handle::kThrottleEvery == 0) {
         const int ts = (int)((h->enqueued / ccv_mppi_handle::kThrottleEvery) % ccv_mppi_handle::kThrottleSlots);
@@ -1739,7 +1777,7 @@ int batch_check_read(ccv_mppi_batch* bh, int32_t instance, const void* out) {
     if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
     if (instance < 0 || instance >= bh->B) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
     if (!bh->have_result) return batch_fail(bh, CCV_MPPI_ERR_STATE, "no iteration yet");
-    return CCV_MPPI_OK;
+    return batch_flush(bh);
 }
 }  // namespace
 
@@ -1870,6 +1908,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     ccv_mppi_handle* h = &bh->h;
     const DeviceGuard guard(h->cfg.device);
     (void)hipSetDevice(h->cfg.device);
+    if (h->stream) (void)batch_flush(bh);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream && h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -1879,7 +1918,8 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
-    void* bufs[] = {h->d_arena, h->d_nominal, h->d_nom_used, h->d_statpart, h->d_vec, h->d_stats, h->d_scratch, bh->d_rec};
+    void* bufs[] = {h->d_arena, h->d_nominal, h->d_nom_used, h->d_statpart, h->d_vec, h->d_stats, h->d_scratch, bh->d_rec,
+                    bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -1898,6 +1938,7 @@ int ccv_mppi_batch_last_kernel(const ccv_mppi_batch* bh) { return bh ? bh->last_
 int ccv_mppi_batch_set_stream(ccv_mppi_batch* bh, void* hip_stream) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     ccv_mppi_handle* h = &bh->h;
+    if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
     for (bool& u : h->throttle_used) u = false;   // marks recorded on the old stream are complete (synchronised above)
@@ -1906,6 +1947,7 @@ int ccv_mppi_batch_set_stream(ccv_mppi_batch* bh, void* hip_stream) {
 
 int ccv_mppi_batch_synchronize(ccv_mppi_batch* bh) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(&bh->h, hipStreamSynchronize(bh->h.stream));
     return CCV_MPPI_OK;
 }
@@ -1913,14 +1955,23 @@ int ccv_mppi_batch_synchronize(ccv_mppi_batch* bh) {
 int ccv_mppi_batch_set_nominal(ccv_mppi_batch* bh, const double* u) {
     if (!bh || !u) return CCV_MPPI_ERR_INVALID_ARG;
     ccv_mppi_handle* h = &bh->h;
+    if (int rc = batch_flush(bh)) return rc;   // (a deferred resident update must not land on top of it)
     HIP_TRY(h, hipMemcpyAsync(h->d_nominal, u, (size_t)bh->B * h->R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    // (the resident plant integrates u*[b][0]: its angle bounds must cover what the caller put there; NaN sticks)
+    for (int d = 0; d < CCV_MPPI_MAX_UDIM; ++d) h->nom_absmax[d] = 0.0;
+    for (size_t n = 0; n < (size_t)bh->B * h->R; ++n) {
+        const int d = (int)(n % (size_t)h->udim);
+        const double a = std::fabs(u[n]), m = h->nom_absmax[d];
+        if (a != a || (m == m && a > m)) h->nom_absmax[d] = a;
+    }
     return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
     if (!bh || !u) return CCV_MPPI_ERR_INVALID_ARG;
     ccv_mppi_handle* h = &bh->h;
+    if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(h, hipMemcpyAsync(u, h->d_nominal, (size_t)bh->B * h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return CCV_MPPI_OK;
@@ -1930,6 +1981,7 @@ int ccv_mppi_batch_iterate(ccv_mppi_batch* bh, const double* x0, const double* d
                            const double* yaw_ref0, const uint64_t* seed, uint64_t iter, double* u_opt_out, ccv_mppi_stats* stats) {
     int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
     if (rc) return rc;
+    if ((rc = batch_flush(bh))) return rc;   // (the rollout reads u*)
     bh->h.want_mail = !(stats && bh->h.timing);   // (a timed call synchronises for its events anyway)
     rc = batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
     bh->h.want_mail = false;
@@ -1941,6 +1993,7 @@ int ccv_mppi_batch_iterate_enqueue(ccv_mppi_batch* bh, const double* x0, const d
                                    const double* y_ref, const double* yaw_ref0, const uint64_t* seed, uint64_t iter) {
     int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
     if (rc) return rc;
+    if ((rc = batch_flush(bh))) return rc;   // (the rollout reads u*)
     return batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
 }
 
@@ -1992,6 +2045,211 @@ int ccv_mppi_batch_timing_enable(ccv_mppi_batch* bh, int32_t on) {
 
 int ccv_mppi_batch_timing_read(ccv_mppi_batch* bh, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset) {
     return bh ? ccv_mppi_timing_read(&bh->h, rollout_us_sum, iter_us_sum, n_iters, reset) : CCV_MPPI_ERR_INVALID_ARG;
+}
+
+// ---- batch handles: device-resident closed loop of every instance (mppi_resident.h) ---------------------------------
+
+int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* bh, const double* path_x, const double* path_y, const int32_t* n_path,
+                                      const double* resolution) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    if (!path_x || !path_y || !n_path || !resolution) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    const int B = bh->B;
+    std::vector<BatchInstance> inst((size_t)B);
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n_path[b] < 1 || !(resolution[b] > 0.0))
+            return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "paths: an empty path or a resolution <= 0");
+        inst[b] = BatchInstance{};
+        inst[b].path_off = total;
+        inst[b].n_path = n_path[b];
+        inst[b].resolution = resolution[b];
+        if (bh->inst.size() == (size_t)B) {   // (the noise keys of ccv_mppi_batch_resident_set_poses stay)
+            inst[b].seed_lo = bh->inst[b].seed_lo;
+            inst[b].seed_hi = bh->inst[b].seed_hi;
+        }
+        total += n_path[b];
+    }
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a queued prologue may still read the old paths)
+    if (total > bh->n_total || !bh->d_rpath) {
+        if (bh->d_rpath) HIP_TRY(h, hipFree(bh->d_rpath));
+        bh->d_rpath = nullptr;
+        bh->have_paths = false;
+        HIP_TRY(h, hipMalloc(&bh->d_rpath, (size_t)2 * total * sizeof(double)));
+    }
+    bh->n_total = total;   // (the y half starts at n_total; a shorter set reuses the array, a longer one reallocates it)
+    HIP_TRY(h, hipMemcpy(bh->d_rpath, path_x, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(bh->d_rpath + total, path_y, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
+    if (!bh->d_rframe) {
+        const size_t trace_bytes = (size_t)B * CCV_MPPI_BATCH_TRACE_ROWS * 6 * sizeof(double);
+        HIP_TRY(h, hipMalloc(&bh->d_rframe, (size_t)B * sizeof(ResidentFrame)));
+        HIP_TRY(h, hipMemset(bh->d_rframe, 0, (size_t)B * sizeof(ResidentFrame)));
+        HIP_TRY(h, hipMalloc(&bh->d_inst, (size_t)B * sizeof(BatchInstance)));
+        HIP_TRY(h, hipMalloc(&bh->d_rtrace, trace_bytes));
+        HIP_TRY(h, hipMemset(bh->d_rtrace, 0, trace_bytes));
+    }
+    HIP_TRY(h, hipMemcpy(bh->d_inst, inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    bh->inst.swap(inst);
+    bh->have_paths = true;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, const uint64_t* seed) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    if (!state || !seed) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->have_paths) return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths first");
+    const int B = bh->B, nx = h->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+    // pose and step counter: the head of every instance's frame (as ccv_mppi_resident_set_pose)
+    struct Head { double x0[5]; double yaw_ref0; int32_t index, steps; };
+    static_assert(offsetof(ResidentFrame, W) == sizeof(Head), "frame head layout");
+    std::vector<Head> heads((size_t)B);
+    std::vector<double> angles((size_t)B * 3);
+    for (int b = 0; b < B; ++b) {
+        heads[b] = Head{};
+        for (int i = 0; i < nx; ++i) heads[b].x0[i] = state[(size_t)b * 5 + i];
+        for (int i = 0; i < 3; ++i) angles[(size_t)b * 3 + i] = std::fabs(heads[b].x0[2 + i]);
+        bh->inst[b].seed_lo = (uint32_t)seed[b];
+        bh->inst[b].seed_hi = (uint32_t)(seed[b] >> 32);
+    }
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy2D(bh->d_rframe, sizeof(ResidentFrame), heads.data(), sizeof(Head), sizeof(Head), (size_t)B,
+                           hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    bh->res_angle_abs.swap(angles);
+    bh->res_steps = 0;
+    bh->have_poses = true;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t iter, int32_t advance) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    const ccv_mppi_config& c = h->cfg;
+    const int B = bh->B;
+    // every check that can refuse the step comes before anything is launched: no pose moves on a refusal
+    if (!(dt >= 0.0) || !std::isfinite(dt)) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: dt must be finite and not negative");
+    if (!bh->have_paths || !bh->have_poses)
+        return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
+    for (int b = 0; b < B; ++b) {
+        const double stride = c.v_ref * dt / bh->inst[b].resolution;
+        if (!std::isfinite(stride) || stride < 0.0 || stride * h->H > 2.0e9)
+            return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: v_ref * dt / resolution is not a usable window stride");
+    }
+    // the angle bounds of resident_step(), instance by instance; the batch's kernel rule (ccv_mppi_batch_create) with no
+    // plain kernel: the wide-turn instantiation when one instance needs it, a refusal where the plain kernel would be needed
+    auto lim = [&](int d) {
+        const double a = std::fmax(std::fabs(c.u_min[d]), std::fabs(c.u_max[d]));
+        const double m = std::fmax(h->inj_absmax[d], h->nom_absmax[d]);
+        return (m == m) ? std::fmax(a, m) : m;   // NaN sticks
+    };
+    std::vector<double> nb(bh->res_angle_abs);
+    int trig = h->coop ? kTrigSafe : kTrigUnsafe;
+    RolloutArgs A;
+    const double zero[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    fill_args(h, A, zero, dt, 0.0, 0, iter);   // (the instance's pose, window and key: its record, batch_view)
+    for (int b = 0; b < B && trig != kTrigUnsafe; ++b) {
+        double* n3 = nb.data() + (size_t)b * 3;
+        if (advance) {
+            auto step = [&](double bound, int d) {
+                const double after = bound + lim(d) * dt;
+                return after <= kAngleRebase ? after : (after == after ? kAngleRebase : after);   // (beyond it the plant re-bases)
+            };
+            n3[0] = step(n3[0], 1);
+            if (c.model == CCV_MPPI_FULL_BODY) {
+                n3[1] = step(n3[1], 3);
+                n3[2] = step(n3[2], 4);
+            }
+        }
+        for (int i = 0; i < 3; ++i) A.x0[2 + i] = n3[i];
+        // the prologue itself takes sin / cos of the OLD heading (+ the steering command)
+        const double heading_bound = bh->res_angle_abs[(size_t)b * 3] + (c.model == CCV_MPPI_DIFF_DRIVE ? 0.0 : lim(2));
+        const int t = fast_trig_safe(h, A, MODE_FUSED);
+        if (t == kTrigUnsafe || !(heading_bound <= kFastTrigLimit)) trig = kTrigUnsafe;
+        else if (t == kTrigWide) trig = kTrigWide;
+    }
+    if (trig == kTrigUnsafe)
+        return batch_fail(bh, CCV_MPPI_ERR_STATE, "the resident loop needs the cooperative kernels and bounded pose angles / commands");
+    BatchAdvanceArgs G;
+    G.frames = bh->d_rframe;
+    G.rec = bh->d_rec;
+    G.inst = bh->d_inst;
+    G.path = bh->d_rpath;
+    G.nominal = h->d_nominal;
+    G.trace = bh->d_rtrace;
+    G.n_total = bh->n_total;
+    G.dt = dt;
+    G.inv_dt = 1.0 / dt;
+    G.v_ref = c.v_ref;
+    G.H = h->H;
+    G.R = h->R;
+    G.K = h->K;
+    G.kpad = bh->kpad;
+    G.model = c.model;
+    G.advance = advance ? 1 : 0;
+    G.trace_cap = CCV_MPPI_BATCH_TRACE_ROWS;
+    if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
+        hipLaunchKernelGGL(k_finalize_advance_batch, dim3(finalize_blocks(bh->fin_args.R) + 1, B), dim3(kBlock), 0, h->stream,
+                           bh->fin_args, G);
+        bh->fin_pending = false;
+    } else {
+        hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, h->stream, G);
+    }
+    HIP_TRY(h, hipGetLastError());
+    bh->res_steps += 1;
+    bh->res_angle_abs.swap(nb);
+    // the rollout reads every instance's record (batch_view): pose, window, dt, noise key, warm start
+    A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
+    return batch_launch(bh, A, trig, true);
+}
+
+int ccv_mppi_batch_resident_read(ccv_mppi_batch* bh, double* state, int32_t* current_index, double* x_ref, double* y_ref,
+                                 double* yaw_ref0, int64_t* steps) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    if (!bh->have_paths || !bh->have_poses)
+        return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
+    const int B = bh->B, H = h->H, nx = h->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+    std::vector<ResidentFrame> F((size_t)B);
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(F.data(), bh->d_rframe, (size_t)B * sizeof(ResidentFrame), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) {
+        if (state) {
+            for (int i = 0; i < 5; ++i) state[(size_t)b * 5 + i] = i < nx ? F[b].x0[i] : 0.0;
+        }
+        if (current_index) current_index[b] = F[b].index;
+        if (x_ref) std::memcpy(x_ref + (size_t)b * H, F[b].x_ref, (size_t)H * sizeof(double));
+        if (y_ref) std::memcpy(y_ref + (size_t)b * H, F[b].y_ref, (size_t)H * sizeof(double));
+        if (yaw_ref0) yaw_ref0[b] = F[b].yaw_ref0;
+    }
+    if (steps) *steps = bh->res_steps;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* bh, int32_t instance, int32_t max_rows, double* rows, int32_t* n_rows) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    if (!rows || !n_rows || max_rows < 0) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "rows / n_rows null or max_rows < 0");
+    if (instance < 0 || instance >= bh->B) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
+    if (!bh->have_paths || !bh->have_poses)
+        return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    // the last min(steps, capacity, max_rows) ticks, oldest first
+    const int64_t cap = CCV_MPPI_BATCH_TRACE_ROWS;
+    const int64_t have = bh->res_steps < cap ? bh->res_steps : cap;
+    const int64_t n = have < max_rows ? have : max_rows;
+    std::vector<double> ring((size_t)cap * 6);
+    HIP_TRY(h, hipMemcpy(ring.data(), bh->d_rtrace + (size_t)instance * cap * 6, ring.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t step = bh->res_steps - n + i;
+        std::memcpy(rows + i * 6, ring.data() + (step % cap) * 6, 6 * sizeof(double));
+    }
+    *n_rows = (int32_t)n;
+    return CCV_MPPI_OK;
 }
 
 }  // extern "C"

@@ -31,9 +31,11 @@ struct AdvanceArgs {
 
 constexpr int kAdvanceThreads = 1024;   // one workgroup; a path of a few thousand poses is one or two batches of loads per thread
 
-// NT threads of one workgroup; cmd: the command u*[0][0 .. u_dim) (read only when A.advance)
-template <int NT>
-__device__ __forceinline__ void advance_body(const AdvanceArgs& A, const double* cmd) {
+// NT threads of one workgroup; cmd: the command u*[0][0 .. u_dim) (read only when A.advance).  BATCH: the window
+// coefficients go into the instance's batch record `rec` (BatchHead + a[H], b[H], c[H]) instead of A.frame->W, and the pose
+// and yaw_ref0 into its head as well -- what batch_enqueue() writes on the host for the same pose and window.
+template <int NT, bool BATCH = false>
+__device__ __forceinline__ void advance_body(const AdvanceArgs& A, const double* cmd, double* rec = nullptr) {
     __shared__ double s_d[NT / 64];
     __shared__ int s_i[NT / 64];
     __shared__ int s_start;
@@ -113,14 +115,31 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& A, const double*
         F.x_ref[i] = xr;
         F.y_ref[i] = yr;
         const double xl = xr - x, yl = yr - y;
-        F.W.a[i] = -2.0 * xl;
-        F.W.b[i] = -2.0 * yl;
-        F.W.c[i] = xl * xl + yl * yl;
+        if constexpr (BATCH) {
+            double* win = rec + kBatchHeadDoubles;
+            win[i] = -2.0 * xl;
+            win[A.H + i] = -2.0 * yl;
+            win[2 * A.H + i] = xl * xl + yl * yl;
+        } else {
+            F.W.a[i] = -2.0 * xl;
+            F.W.b[i] = -2.0 * yl;
+            F.W.c[i] = xl * xl + yl * yl;
+        }
     }
     if (threadIdx.x == 0) {
         const int i1 = (int)(start + 1 * stride), i0 = (int)(start + 0 * stride);
         const int s1 = i1 < A.n_path ? i1 : A.n_path - 1, s0 = i0 < A.n_path ? i0 : A.n_path - 1;
-        F.yaw_ref0 = atan2(A.path_y[s1] - A.path_y[s0], A.path_x[s1] - A.path_x[s0]);
+        const double yaw_ref0 = atan2(A.path_y[s1] - A.path_y[s0], A.path_x[s1] - A.path_x[s0]);
+        F.yaw_ref0 = yaw_ref0;
+        if constexpr (BATCH) {
+            BatchHead* hd = reinterpret_cast<BatchHead*>(rec);
+            hd->x0[0] = x;
+            hd->x0[1] = y;
+            hd->x0[2] = yaw;
+            hd->x0[3] = roll;
+            hd->x0[4] = pitch;
+            hd->yaw_ref0 = yaw_ref0;
+        }
         F.x0[0] = x;
         F.x0[1] = y;
         F.x0[2] = yaw;
@@ -165,6 +184,102 @@ __global__ __launch_bounds__(kBlock) void k_finalize_advance(const FinalizeArgs 
     }
     __syncthreads();
     advance_body<kBlock>(A, cmd);
+}
+
+// ---- batch handles (ccv_mppi_batch_resident_*): the same prologue for B instances, one workgroup each ---------------------
+// Instance b has a path of its own (a slice of one array of all paths), a ResidentFrame of its own (pose, index, window,
+// step count; its W is not used) and a trace ring of its own.  The prologue writes the instance's batch record -- the block
+// batch_enqueue() fills on the host and the batched rollout reads (BatchHead + window) -- so that a batched resident tick
+// needs no host data.
+struct BatchInstance {
+    int64_t path_off;    // first pose of the instance's path in BatchAdvanceArgs::path
+    int32_t n_path, pad;
+    double resolution;
+    uint32_t seed_lo, seed_hi;   // the instance's noise key (ccv_mppi_batch_resident_set_poses)
+};
+
+struct BatchAdvanceArgs {
+    ResidentFrame* frames;          // [B]
+    double* rec;                    // [B][batch_record_doubles(H)]
+    const BatchInstance* inst;      // [B]
+    const double* path;             // [2][n_total]: every instance's x, back to back, then every instance's y
+    double* nominal;                // u* [B][R]
+    double* trace;                  // [B][trace_cap][6]
+    int64_t n_total;
+    double dt, inv_dt, v_ref;       // (inv_dt: 1 / dt, correctly rounded on the host, as batch_enqueue writes it)
+    int32_t H, R, K, kpad, model, advance, trace_cap;
+};
+
+constexpr int kBatchAdvanceThreads = kBlock;   // (the lexicographic reduction is exact: any width gives the same index)
+
+// instance b's view of the batch: its AdvanceArgs, and the fields of its record that do not depend on the pose
+__device__ __forceinline__ AdvanceArgs batch_advance_view(const BatchAdvanceArgs& G, const int b, double*& rec) {
+    const BatchInstance in = G.inst[b];
+    AdvanceArgs A;
+    A.frame = G.frames + b;
+    A.path_x = G.path + in.path_off;
+    A.path_y = G.path + G.n_total + in.path_off;
+    A.nominal = G.nominal + (size_t)b * G.R;
+    A.trace = G.trace + (size_t)b * G.trace_cap * 6;
+    A.dt = G.dt;
+    A.v_ref = G.v_ref;
+    A.resolution = in.resolution;
+    A.n_path = in.n_path;
+    A.H = G.H;
+    A.model = G.model;
+    A.advance = G.advance;
+    A.trace_cap = G.trace_cap;
+    rec = G.rec + (size_t)b * batch_record_doubles(G.H);
+    if (threadIdx.x == 0) {
+        BatchHead* hd = reinterpret_cast<BatchHead*>(rec);
+        hd->dt = G.dt;
+        hd->inv_dt = G.inv_dt;
+        hd->seed_lo = in.seed_lo;
+        hd->seed_hi = in.seed_hi;
+        hd->K = b * G.kpad + G.K;
+        hd->k_offset = -b * G.kpad;
+        hd->nominal = G.nominal + (size_t)b * G.R;
+    }
+    return A;
+}
+
+// grid B: instance blockIdx.x, its command read from u*[b][0]
+__global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch(const BatchAdvanceArgs G) {
+    double* rec;
+    const AdvanceArgs A = batch_advance_view(G, (int)blockIdx.x, rec);
+    advance_body<kBatchAdvanceThreads, true>(A, A.nominal, rec);
+}
+
+// The batched k_finalize_advance: grid (finalize_blocks(R) + 1, B).  Blocks x < finalize_blocks(R) are k_finalize_batch
+// (fused partials) for instance y; block x = finalize_blocks(R) forms instance y's command from the instance's own partial
+// columns in k_finalize_batch's order (the bits its waves write into u*[y][0]) and runs the instance's prologue with it.
+__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs G) {
+    const size_t b = blockIdx.y;
+    const size_t stride = (size_t)gridDim.y * F.nchunks;
+    F.partial += b * F.nchunks;
+    if ((int)blockIdx.x < finalize_blocks(F.R)) {
+        F.statpart += b * (size_t)F.nchunks * 3;
+        F.nominal += b * F.R;
+        F.vec += b * (size_t)(F.R + 1);
+        F.stats += b * 4;
+        finalize_rows(F, stride);   // (no mailbox: a deferred update is never a blocking call's)
+        return;
+    }
+    __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
+    if (G.advance) {
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(G.model);
+        for (int d = wv; d < ud; d += kBlock / 64) {
+            double s, v;
+            lane_partial_sum2(F.partial + (size_t)F.R * stride, F.partial + (size_t)d * stride, F.nchunks, lane, s, v);
+            s = wave_sum(s);
+            v = wave_sum(v);
+            if (lane == 0) cmd[d] = v / s;
+        }
+    }
+    __syncthreads();
+    double* rec;
+    const AdvanceArgs A = batch_advance_view(G, (int)b, rec);
+    advance_body<kBlock, true>(A, cmd, rec);
 }
 
 }  // namespace ccv

@@ -279,6 +279,37 @@ int ccv_mppi_batch_read_candidates(ccv_mppi_batch* b, int32_t instance, int32_t 
 int ccv_mppi_batch_timing_enable(ccv_mppi_batch* b, int32_t on);
 int ccv_mppi_batch_timing_read(ccv_mppi_batch* b, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset);
 
+/* ---- batch handles: device-resident closed loop of every instance ---------------------------------------------------- */
+/* The device-resident closed loop above for all B instances of a batch handle at once: every instance has a path, a pose, a
+ * noise key, a step counter and a trace of its own in HBM, and one step runs every instance's prologue (plant, index,
+ * window) and writes the instance's record -- what ccv_mppi_batch_iterate copies from the host -- on the device.  A tick
+ * costs two launches however large B is (the update of a tick is launched together with the prologue of the next one) and
+ * no host data.  Instance b's index, window, pose and u* are bit-identical to ccv_mppi_calc_ref_path() +
+ * ccv_mppi_plant_step() on the host driving ccv_mppi_batch_iterate; yaw_ref[0] comes from the device atan2 (as above).
+ * Kernel selection is the batch's (ccv_mppi_batch_create), without the plain kernel: a step that would need it
+ * (CCV_MPPI_KERNEL=v1, pose angles or commands of some instance that can leave the fast sin / cos's range) is refused with
+ * CCV_MPPI_ERR_STATE, a bad dt, or a window stride v_ref * dt / resolution[b] that is not usable, with
+ * CCV_MPPI_ERR_INVALID_ARG -- in both cases before any pose moves.  Every other call on the batch handle (warm starts,
+ * ccv_mppi_batch_iterate*, the read-backs, synchronisation, streams, new paths or poses, destroy) first launches a pending
+ * update, so resident steps and host-record iterations may be mixed: each sees the other's u*.  The noise key of instance b
+ * is seed[b] of _set_poses; a step passes the iteration number only, and dt is one for all instances. */
+#define CCV_MPPI_BATCH_TRACE_ROWS 1024 /* rows of every instance's trace ring: 48 KB per instance */
+/* B paths back to back: instance b's n_path[b] >= 1 poses start at sum(n_path[0..b)); resolution [B] > 0 */
+int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* b, const double* path_x, const double* path_y, const int32_t* n_path,
+                                      const double* resolution);
+/* state [B][5] (x, y, yaw[, roll, pitch]), seed [B] (the noise key of every later step; the step passes iter);
+ * restarts every instance's step counter and trace.  After _set_paths. */
+int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* b, const double* state, const uint64_t* seed);
+/* one tick of every instance, one dt for all; no host data, no synchronisation */
+int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* b, double dt, uint64_t iter, int32_t advance);
+/* synchronises; any pointer may be NULL: state [B][5], index [B], x_ref / y_ref [B][H] (the last step's windows),
+ * yaw_ref0 [B], steps (shared: the steps since _set_poses) */
+int ccv_mppi_batch_resident_read(ccv_mppi_batch* b, double* state, int32_t* current_index, double* x_ref, double* y_ref,
+                                 double* yaw_ref0, int64_t* steps);
+/* one instance's last rows, oldest first, (x, y, yaw, roll, pitch, index); at most max_rows and at most
+ * CCV_MPPI_BATCH_TRACE_ROWS */
+int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int32_t max_rows, double* rows, int32_t* n_rows);
+
 #ifdef __cplusplus
 }
 #endif
