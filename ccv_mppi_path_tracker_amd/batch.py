@@ -1,9 +1,10 @@
 """B independent MPPI problems in one launch: the batch handle of the C ABI (ccv_mppi_batch_*, include/ccv_mppi.h).
 
-Every array carries the instance as its first axis.  Instance b computes what an MPPIController with the same parameters
+Every array carries the instance as its first axis.  Instance b computes what an MPPIController with instance b's parameters
 computes for the same inputs and warm start; all compute happens in libccv_mppi_hip.so.
 """
 import ctypes as C
+from dataclasses import replace
 
 import numpy as np
 
@@ -19,23 +20,50 @@ def _is_1d(a):
         return False
 
 
-class BatchController:
-    """`batch` controllers with one shared configuration (K = num_samples per instance) on one device."""
+# the fields every instance of a batch shares (they fix the layout and the kernels); the rest may differ per instance
+SHARED_FIELDS = ("model", "horizon", "roll_off", "steer_off", "num_samples")
 
-    def __init__(self, params: MPPIParams, batch, device=0, num_samples=None, no_state_store=False):
+
+def check_shared(seq, first=None):
+    """ValueError unless every MPPIParams of `seq` agrees with `first` (default: seq[0]) in SHARED_FIELDS."""
+    first = seq[0] if first is None else first
+    for b, p in enumerate(seq):
+        for f in SHARED_FIELDS:
+            if getattr(p, f) != getattr(first, f):
+                raise ValueError("params[%d].%s = %r differs from the batch's %r (shared by every instance)"
+                                 % (b, f, getattr(p, f), getattr(first, f)))
+
+
+class BatchController:
+    """`batch` controllers on one device: one MPPIParams shared by all, or a sequence of `batch` MPPIParams that agree in
+    SHARED_FIELDS (per-instance sigma, lambda, v_ref, bounds and weights; K = num_samples per instance)."""
+
+    def __init__(self, params, batch, device=0, num_samples=None, no_state_store=False):
+        seq = None
+        if not isinstance(params, MPPIParams):
+            seq = list(params)
+            if len(seq) != int(batch):
+                raise ValueError("params: expected one MPPIParams or %d, got %d" % (int(batch), len(seq)))
+            check_shared(seq)
+            params = seq[0]
         self.lib = capi.load()
         self.params = params
+        self.params_list = [params] * int(batch)
         self.B = int(batch)
         self.K = int(num_samples if num_samples is not None else params.num_samples)
         self.H = params.horizon
         self.udim = params.udim
         self.nstate = params.nstate
+        self.device = int(device)
+        self.no_state_store = bool(no_state_store)
         self._h = capi._H()
         cfg = make_config(params, device, 0, False, no_state_store, self.K)
         rc = self.lib.ccv_mppi_batch_create(C.byref(cfg), self.B, C.byref(self._h))
         if rc != capi.OK:
             self._h = capi._H()
             raise MPPIError(rc, "ccv_mppi_batch_create failed (bad arguments, or no usable MI355X/HIP device) -- there is no CPU fallback")
+        if seq is not None:
+            self.set_params(seq)
 
     # ---- plumbing ----
     def _check(self, rc):
@@ -63,6 +91,36 @@ class BatchController:
     def last_kernel(self):
         """capi.BATCH_KERNEL_* of the last iteration (| BATCH_KERNEL_WIDE for the wide-turn form), -1 before the first."""
         return self.lib.ccv_mppi_batch_last_kernel(self._h)
+
+    # ---- per-instance parameters (ccv_mppi_batch_set_params) ----
+    def set_params(self, seq):
+        """seq: B MPPIParams (instance b's sigma, lambda, v_ref, bounds, weights, resolution), or None: every instance back to
+        the creation parameters and the shared kernels.  Disagreeing SHARED_FIELDS raise ValueError before the library is
+        called.  Flushes a pending resident update; warm starts, paths and poses stay."""
+        if seq is None:
+            self._check(self.lib.ccv_mppi_batch_set_params(self._h, None))
+            self.params_list = [self.params] * self.B
+            return
+        seq = list(seq)
+        if len(seq) != self.B:
+            raise ValueError("params: expected %d MPPIParams, got %d" % (self.B, len(seq)))
+        check_shared(seq, self.params)
+        cfgs = (capi.Config * self.B)(*[make_config(p, self.device, 0, False, self.no_state_store, self.K) for p in seq])
+        self._check(self.lib.ccv_mppi_batch_set_params(self._h, cfgs))
+        self.params_list = seq
+
+    def get_params(self):
+        """The B effective MPPIParams, as the library holds them (dt and resolution: the host side's)."""
+        cfgs = (capi.Config * self.B)()
+        self._check(self.lib.ccv_mppi_batch_get_params(self._h, cfgs))
+        out = []
+        for p, c in zip(self.params_list, cfgs):
+            ud = p.udim
+            out.append(replace(p, control_noise=c.control_noise, lam=c.lam, v_ref=c.v_ref,
+                               u_min=tuple(c.u_min[:ud]), u_max=tuple(c.u_max[:ud]), path_weight=c.path_weight,
+                               v_weight=c.v_weight, zmp_weight=c.zmp_weight, roll_v_weight=c.roll_v_weight,
+                               back_weight=c.back_weight, yaw_weight=c.yaw_weight))
+        return out
 
     # ---- warm starts [B][H-1][u_dim] ----
     def set_nominal(self, u):
@@ -126,8 +184,8 @@ class BatchController:
 
     # ---- device-resident closed loop of every instance (ccv_mppi_batch_resident_*) ----
     def resident_set_paths(self, paths, resolution=None):
-        """paths: B (path_x, path_y) pairs, or one pair for every instance; resolution: one value or [B] (default: the
-        parameters' resolution)."""
+        """paths: B (path_x, path_y) pairs, or one pair for every instance; resolution: one value or [B] (default: each
+        instance's parameters' resolution)."""
         if len(paths) == 2 and _is_1d(paths[0]) and _is_1d(paths[1]):
             paths = [paths] * self.B
         if len(paths) != self.B:
@@ -140,7 +198,10 @@ class BatchController:
             xs.append(px)
             ys.append(py)
         n = np.ascontiguousarray([len(px) for px in xs], dtype=np.int32)
-        res = self.params.resolution if resolution is None else resolution
+        if resolution is None:
+            plist = getattr(self, "params_list", None) or [self.params] * self.B
+            resolution = [p.resolution for p in plist]
+        res = resolution
         res = capi.as_f64(np.broadcast_to(np.asarray(res, dtype=np.float64), (self.B,)))
         px, py = capi.as_f64(np.concatenate(xs)), capi.as_f64(np.concatenate(ys))
         self._check(self.lib.ccv_mppi_batch_resident_set_paths(self._h, capi.dptr(px), capi.dptr(py),

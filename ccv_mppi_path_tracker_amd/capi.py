@@ -25,6 +25,7 @@ DIFF_DRIVE, STEERING_DIFF_DRIVE, FULL_BODY = 0, 1, 2
 FLAG_ROLL_OFF, FLAG_STEER_OFF, FLAG_MIN_SHIFT, FLAG_NO_STATE_STORE = 0x1, 0x2, 0x4, 0x8
 BATCH_MAX_SAMPLES = 1 << 29
 BATCH_KERNEL_PLAIN, BATCH_KERNEL_ONE_WAVE, BATCH_KERNEL_FOUR_WAVE, BATCH_KERNEL_WIDE = 0, 1, 4, 16
+BATCH_KERNEL_VARIED = 32
 BATCH_TRACE_ROWS = 1024
 
 
@@ -103,6 +104,8 @@ SIGNATURES = {
     "ccv_mppi_batch_last_kernel": (C.c_int, [_H]),
     "ccv_mppi_batch_set_nominal": (C.c_int, [_H, _dp]),
     "ccv_mppi_batch_get_nominal": (C.c_int, [_H, _dp]),
+    "ccv_mppi_batch_set_params": (C.c_int, [_H, C.POINTER(Config)]),
+    "ccv_mppi_batch_get_params": (C.c_int, [_H, C.POINTER(Config)]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),

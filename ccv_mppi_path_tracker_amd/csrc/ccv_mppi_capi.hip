@@ -171,14 +171,9 @@ int ensure_scratch(ccv_mppi_handle* h, size_t bytes) {
     return CCV_MPPI_OK;
 }
 
-void fill_args(const ccv_mppi_handle* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed,
-               uint64_t iter) {
-    const ccv_mppi_config& c = h->cfg;
-    std::memset(&A, 0, sizeof(A));
-    const int nx = c.model == CCV_MPPI_FULL_BODY ? 5 : 3;
-    for (int i = 0; i < nx; ++i) A.x0[i] = x0[i];
-    A.dt = dt;
-    A.yaw_ref0 = yaw_ref0;
+// the controller parameters of configuration c (sigma, lambda, v_ref, bounds, clamp form, weights) into A: fill_args(), and
+// every row of a batch's parameter table (batch_params_of)
+void fill_params(const ccv_mppi_config& c, const bool fast_clamp_allowed, RolloutArgs& A) {
     A.sigma = c.control_noise;
     A.lambda = c.lambda;
     A.v_ref = c.v_ref;
@@ -191,7 +186,7 @@ void fill_args(const ccv_mppi_handle* h, RolloutArgs& A, const double* x0, doubl
     A.fast_clamp = std::isfinite(c.control_noise) ? 1 : 0;
     for (int d = 0; d < udim_of(c.model); ++d)
         if (!(c.u_min[d] <= c.u_max[d])) A.fast_clamp = 0;
-    if (!h->fast_clamp_allowed) A.fast_clamp = 0;   // (CCV_MPPI_FAST_CLAMP=0: tests, experiments)
+    if (!fast_clamp_allowed) A.fast_clamp = 0;   // (CCV_MPPI_FAST_CLAMP=0: tests, experiments)
     const bool roll_off = (c.flags & CCV_MPPI_FLAG_ROLL_OFF) != 0;
     A.w_path = c.path_weight;
     A.w_v = c.v_weight;
@@ -199,6 +194,17 @@ void fill_args(const ccv_mppi_handle* h, RolloutArgs& A, const double* x0, doubl
     A.w_rollv = roll_off ? 0.0 : c.roll_v_weight;
     A.w_back = c.back_weight;
     A.w_yaw = c.yaw_weight;
+}
+
+void fill_args(const ccv_mppi_handle* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed,
+               uint64_t iter) {
+    const ccv_mppi_config& c = h->cfg;
+    std::memset(&A, 0, sizeof(A));
+    const int nx = c.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+    for (int i = 0; i < nx; ++i) A.x0[i] = x0[i];
+    A.dt = dt;
+    A.yaw_ref0 = yaw_ref0;
+    fill_params(c, h->fast_clamp_allowed, A);
     // fb.h:212-216, fb:86-91
     const double upper_body_height = 0.8075, upper_body_width = 0.208, mass = 60.0;
     const double base2CoM = upper_body_height / 2;
@@ -325,11 +331,12 @@ int materialize_controls(ccv_mppi_handle* h) {
 // every heading inside the range but a turn per step beyond pi/4 -- the instantiation that evaluates sin / cos of every
 // heading in full (as the steering model's does) instead of advancing them by the step's turn.
 enum : int { kTrigUnsafe = 0, kTrigSafe = 1, kTrigWide = 2 };
-int fast_trig_safe(const ccv_mppi_handle* h, const RolloutArgs& A, int mode) {
+// (c: the configuration whose clamp bounds apply -- h->cfg, or an instance's of a batch with per-instance parameters)
+int fast_trig_safe(const ccv_mppi_handle* h, const ccv_mppi_config& c, const RolloutArgs& A, int mode) {
     const int ud = h->udim;
     double umax[CCV_MPPI_MAX_UDIM];
     for (int d = 0; d < ud; ++d) {
-        umax[d] = mode == MODE_FUSED ? std::fmax(std::fabs(h->cfg.u_min[d]), std::fabs(h->cfg.u_max[d])) : h->inj_absmax[d];
+        umax[d] = mode == MODE_FUSED ? std::fmax(std::fabs(c.u_min[d]), std::fabs(c.u_max[d])) : h->inj_absmax[d];
     }
     const double steps = (double)(h->H - 1) * std::fabs(A.dt);
     double bound = std::fabs(A.x0[2]) + steps * umax[1];
@@ -355,6 +362,7 @@ int fast_trig_safe(const ccv_mppi_handle* h, const RolloutArgs& A, int mode) {
     if (!(bound <= kFastTrigLimit)) return kTrigUnsafe;   // (also for NaN)
     return wide ? kTrigWide : kTrigSafe;
 }
+int fast_trig_safe(const ccv_mppi_handle* h, const RolloutArgs& A, int mode) { return fast_trig_safe(h, h->cfg, A, mode); }
 
 int launch_rollout(ccv_mppi_handle* h, const RolloutArgs& A_in, const Window& W, int mode) {
     RolloutArgs A = A_in;
@@ -1557,11 +1565,19 @@ struct ccv_mppi_batch {
     std::vector<double> res_angle_abs;      // [B][3]: bounds on |yaw|, |roll|, |pitch| of every resident pose
     bool have_paths = false, have_poses = false;
     int64_t res_steps = 0;                  // resident ticks since the poses were set (every instance's step count)
+    // per-instance parameters (ccv_mppi_batch_set_params): the VARIED kernels read instance b's row of d_params through the
+    // pointer in its record's head; without them (varied = false) every instance has h.cfg and the shared kernels run
+    bool varied = false;
+    std::vector<ccv_mppi_config> cfgs;      // [B] the instances' configurations while varied
+    BatchParams* d_params = nullptr;        // [B], allocated at the first _set_params, freed at destroy
 };
 
 namespace {
 
 int batch_fail(ccv_mppi_batch* b, int code, const char* what) { return fail(b ? &b->h : nullptr, code, what); }
+
+// instance b's configuration: its own under per-instance parameters, the creation configuration otherwise
+const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->h.cfg; }
 
 int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
                      const double* yaw_ref0, const uint64_t* seed) {
@@ -1611,6 +1627,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
         hd->K = b * bh->kpad + h->K;
         hd->k_offset = -b * bh->kpad;
         hd->nominal = h->d_nominal + (size_t)b * h->R;
+        if (bh->varied) hd->params = bh->d_params + b;
         // the window coefficients, as fill_window() forms them
         double* win = rec + (size_t)b * bh->rec_doubles + kBatchHeadDoubles;
         const double* xr = x_ref + (size_t)b * H;
@@ -1624,7 +1641,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
         if (trig != kTrigUnsafe) {
             for (int i = 0; i < 5; ++i) A.x0[i] = hd->x0[i];
             A.dt = dt[b];
-            const int t = fast_trig_safe(h, A, MODE_FUSED);
+            const int t = fast_trig_safe(h, batch_cfg(bh, b), A, MODE_FUSED);   // (the instance's own bounds)
             if (t == kTrigUnsafe || t == kTrigWide) trig = t;
         }
     }
@@ -1653,19 +1670,24 @@ int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool 
     }
     static const Window kNoWindow{};   // (the windows are in the records)
     const LaunchAt at{h->stream, timed && !plain ? h->ev[tslot] : nullptr, timed && !plain ? h->ev[tslot + 1] : nullptr};
+    // (varied: the same families with per-instance parameters, k_batch_varied.hip)
     if (plain) {
         if (timed) HIP_TRY(h, hipEventRecord(h->ev[tslot], h->stream));
-        launch_rollout_plain_batch(h->cfg.model, B, at, A, kNoWindow);
+        if (bh->varied) launch_rollout_plain_batch_varied(h->cfg.model, B, at, A, kNoWindow);
+        else launch_rollout_plain_batch(h->cfg.model, B, at, A, kNoWindow);
         if (timed) HIP_TRY(h, hipEventRecord(h->ev[tslot + 1], h->stream));
         bh->last_kernel = CCV_MPPI_BATCH_KERNEL_PLAIN;
     } else if (h->solo) {
-        launch_rollout_solo_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
+        if (bh->varied) launch_rollout_solo_batch_varied(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
+        else launch_rollout_solo_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
         bh->last_kernel = CCV_MPPI_BATCH_KERNEL_ONE_WAVE;
     } else {
-        launch_rollout_r4_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
+        if (bh->varied) launch_rollout_r4_batch_varied(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
+        else launch_rollout_r4_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
         bh->last_kernel = CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
     }
     if (trig == kTrigWide) bh->last_kernel |= CCV_MPPI_BATCH_KERNEL_WIDE;
+    if (bh->varied) bh->last_kernel |= CCV_MPPI_BATCH_KERNEL_VARIED;
     HIP_TRY(h, hipGetLastError());
     int nparts = h->nblocks;
     if (plain) {   // the plain kernel stores w and the controls: the single handle's unfused reduction, instance by instance
@@ -1919,7 +1941,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
     void* bufs[] = {h->d_arena, h->d_nominal, h->d_nom_used, h->d_statpart, h->d_vec, h->d_stats, h->d_scratch, bh->d_rec,
-                    bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace};
+                    bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace, bh->d_params};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -1974,6 +1996,74 @@ int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(h, hipMemcpyAsync(u, h->d_nominal, (size_t)bh->B * h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CCV_MPPI_OK;
+}
+
+// ---- per-instance parameters ------------------------------------------------------------------------------------------
+
+int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    ccv_mppi_handle* h = &bh->h;
+    const int B = bh->B;
+    if (!cfgs) {   // back to the creation configuration and the shared kernels
+        if (int rc = batch_flush(bh)) return rc;
+        bh->varied = false;
+        bh->cfgs.clear();
+        return CCV_MPPI_OK;
+    }
+    // the fields that fix the layout, the kernel family and the compile-time shape stay the creation configuration's; every
+    // check comes before anything changes
+    const ccv_mppi_config& c0 = h->cfg;
+    for (int b = 0; b < B; ++b) {
+        const ccv_mppi_config& c = cfgs[b];
+        const char* field = c.abi_version != c0.abi_version       ? "abi_version"
+                            : c.model != c0.model                 ? "model"
+                            : c.num_samples != c0.num_samples     ? "num_samples"
+                            : c.horizon != c0.horizon             ? "horizon"
+                            : c.sample_offset != c0.sample_offset ? "sample_offset"
+                            : c.device != c0.device               ? "device"
+                            : c.flags != c0.flags                 ? "flags"
+                                                                  : nullptr;
+        if (field) {
+            char msg[128];
+            std::snprintf(msg, sizeof(msg), "set_params: instance %d: %s differs from the creation configuration", b, field);
+            return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, msg);
+        }
+    }
+    std::vector<BatchParams> rows((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        RolloutArgs A;
+        std::memset(&A, 0, sizeof(A));
+        fill_params(cfgs[b], h->fast_clamp_allowed, A);   // (per instance: the clamp form of its own sigma and bounds)
+        BatchParams& P = rows[(size_t)b];
+        std::memset(&P, 0, sizeof(P));
+        P.sigma = A.sigma;
+        P.lambda = A.lambda;
+        P.v_ref = A.v_ref;
+        for (int d = 0; d < 5; ++d) {
+            P.umin[d] = A.umin[d];
+            P.umax[d] = A.umax[d];
+        }
+        P.w_path = A.w_path;
+        P.w_v = A.w_v;
+        P.w_zmp = A.w_zmp;
+        P.w_rollv = A.w_rollv;
+        P.w_back = A.w_back;
+        P.w_yaw = A.w_yaw;
+        P.fast_clamp = A.fast_clamp;
+    }
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a queued rollout or prologue may still read the old table)
+    if (!bh->d_params) HIP_TRY(h, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
+    HIP_TRY(h, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
+    bh->cfgs.assign(cfgs, cfgs + B);
+    bh->varied = true;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_get_params(ccv_mppi_batch* bh, ccv_mppi_config* out) {
+    if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
+    for (int b = 0; b < bh->B; ++b) out[b] = batch_cfg(bh, b);
     return CCV_MPPI_OK;
 }
 
@@ -2134,14 +2224,15 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     if (!bh->have_paths || !bh->have_poses)
         return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
     for (int b = 0; b < B; ++b) {
-        const double stride = c.v_ref * dt / bh->inst[b].resolution;
+        const double stride = batch_cfg(bh, b).v_ref * dt / bh->inst[b].resolution;   // (the instance's own v_ref)
         if (!std::isfinite(stride) || stride < 0.0 || stride * h->H > 2.0e9)
             return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: v_ref * dt / resolution is not a usable window stride");
     }
     // the angle bounds of resident_step(), instance by instance; the batch's kernel rule (ccv_mppi_batch_create) with no
     // plain kernel: the wide-turn instantiation when one instance needs it, a refusal where the plain kernel would be needed
-    auto lim = [&](int d) {
-        const double a = std::fmax(std::fabs(c.u_min[d]), std::fabs(c.u_max[d]));
+    auto lim = [&](int b, int d) {   // (the instance's own bounds)
+        const ccv_mppi_config& cb = batch_cfg(bh, b);
+        const double a = std::fmax(std::fabs(cb.u_min[d]), std::fabs(cb.u_max[d]));
         const double m = std::fmax(h->inj_absmax[d], h->nom_absmax[d]);
         return (m == m) ? std::fmax(a, m) : m;   // NaN sticks
     };
@@ -2154,7 +2245,7 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
         double* n3 = nb.data() + (size_t)b * 3;
         if (advance) {
             auto step = [&](double bound, int d) {
-                const double after = bound + lim(d) * dt;
+                const double after = bound + lim(b, d) * dt;
                 return after <= kAngleRebase ? after : (after == after ? kAngleRebase : after);   // (beyond it the plant re-bases)
             };
             n3[0] = step(n3[0], 1);
@@ -2165,8 +2256,8 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
         }
         for (int i = 0; i < 3; ++i) A.x0[2 + i] = n3[i];
         // the prologue itself takes sin / cos of the OLD heading (+ the steering command)
-        const double heading_bound = bh->res_angle_abs[(size_t)b * 3] + (c.model == CCV_MPPI_DIFF_DRIVE ? 0.0 : lim(2));
-        const int t = fast_trig_safe(h, A, MODE_FUSED);
+        const double heading_bound = bh->res_angle_abs[(size_t)b * 3] + (c.model == CCV_MPPI_DIFF_DRIVE ? 0.0 : lim(b, 2));
+        const int t = fast_trig_safe(h, batch_cfg(bh, b), A, MODE_FUSED);
         if (t == kTrigUnsafe || !(heading_bound <= kFastTrigLimit)) trig = kTrigUnsafe;
         else if (t == kTrigWide) trig = kTrigWide;
     }
@@ -2190,12 +2281,15 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     G.model = c.model;
     G.advance = advance ? 1 : 0;
     G.trace_cap = CCV_MPPI_BATCH_TRACE_ROWS;
+    // (varied: the prologue takes each instance's v_ref from the parameter table and points its record's head at its row)
     if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
-        hipLaunchKernelGGL(k_finalize_advance_batch, dim3(finalize_blocks(bh->fin_args.R) + 1, B), dim3(kBlock), 0, h->stream,
-                           bh->fin_args, G);
+        const dim3 grid(finalize_blocks(bh->fin_args.R) + 1, B);
+        if (bh->varied) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, h->stream, bh->fin_args, G, bh->d_params);
+        else hipLaunchKernelGGL(k_finalize_advance_batch, grid, dim3(kBlock), 0, h->stream, bh->fin_args, G);
         bh->fin_pending = false;
     } else {
-        hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, h->stream, G);
+        if (bh->varied) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, h->stream, G, bh->d_params);
+        else hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, h->stream, G);
     }
     HIP_TRY(h, hipGetLastError());
     bh->res_steps += 1;

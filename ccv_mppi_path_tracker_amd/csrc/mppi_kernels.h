@@ -78,6 +78,7 @@ struct ResidentFrame {
 // instances.  What differs per instance travels in a record in device memory, one per instance, batch_record_doubles(H)
 // doubles apart: a BatchHead (two 64-byte lines), then the window coefficients a[H], b[H], c[H].  A batched rollout is
 // launched with RolloutArgs::frame pointing at record 0 and takes its instance's record in batch_view() below.
+struct BatchParams;
 struct BatchHead {
     double x0[5];
     double yaw_ref0;
@@ -85,7 +86,18 @@ struct BatchHead {
     uint32_t seed_lo, seed_hi;
     int32_t K, k_offset;        // b * Kpad + K and -b * Kpad (see batch_view)
     const double* nominal;      // the instance's warm start
+    const BatchParams* params;  // the instance's row of the parameter table (ccv_mppi_batch_set_params; VARIED kernels only)
 };
+// Per-instance controller parameters of a batch handle (ccv_mppi_batch_set_params): one row per instance, three 64-byte lines,
+// the RolloutArgs fields fill_args() forms from a configuration -- ROLL_OFF's zero weights and the fast-clamp test included.
+// A VARIED kernel takes its instance's row in batch_view() and is the single handle's code from there on.
+struct alignas(64) BatchParams {
+    double sigma, lambda, v_ref;
+    double umin[5], umax[5];
+    double w_path, w_v, w_zmp, w_rollv, w_back, w_yaw;
+    int32_t fast_clamp, pad;
+};
+static_assert(sizeof(BatchParams) == 192, "three 64-byte lines per instance");
 constexpr int kBatchHeadDoubles = 16;
 __host__ __device__ constexpr int batch_record_doubles(int H) { return kBatchHeadDoubles + ((3 * H + 7) & ~7); }
 
@@ -156,6 +168,9 @@ __device__ __forceinline__ RolloutArgs with_resident_pose(const RolloutArgs& Ak)
 // LOCAL index, the counter word of noise_spec.h.  The partials stay [(R+1)][nparts] with nparts = B * the instance's
 // workgroups: column blockIdx.x, each instance's columns contiguous (k_finalize_batch).  Workgroup 0 of the launch
 // (instance 0) writes nominal_used; the batch has no read-back of the controls that would need the other instances'.
+// VARIED: the controller parameters (sigma, lambda, v_ref, bounds, weights, the clamp form) from the instance's row of the
+// parameter table too, whose address the head holds -- read through the constant address space as well.
+template <bool VARIED = false>
 __device__ __forceinline__ RolloutArgs batch_view(const RolloutArgs& Ak, const int inst) {
     RolloutArgs A = Ak;
     const double* rec = reinterpret_cast<const double*>(Ak.frame) + (size_t)inst * batch_record_doubles(Ak.H);
@@ -174,12 +189,31 @@ __device__ __forceinline__ RolloutArgs batch_view(const RolloutArgs& Ak, const i
     A.K = hd.K;
     A.k_offset = hd.k_offset;
     A.nominal = hd.nominal;
+    if constexpr (VARIED) {
+        typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
+        const auto& P = *(ConstParams)(const void*)hd.params;
+        A.sigma = P.sigma;
+        A.lambda = P.lambda;
+        A.v_ref = P.v_ref;
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+            A.umin[d] = P.umin[d];
+            A.umax[d] = P.umax[d];
+        }
+        A.w_path = P.w_path;
+        A.w_v = P.w_v;
+        A.w_zmp = P.w_zmp;
+        A.w_rollv = P.w_rollv;
+        A.w_back = P.w_back;
+        A.w_yaw = P.w_yaw;
+        A.fast_clamp = P.fast_clamp;
+    }
     return A;
 }
 // the kernel arguments of a workgroup of 64 samples: batched (instance = workgroup / workgroups per instance) or not
-template <int MODEL, bool BATCH>
+template <int MODEL, bool BATCH, bool VARIED = false>
 __device__ __forceinline__ RolloutArgs rollout_view(const RolloutArgs& Ak) {
-    if constexpr (BATCH) return batch_view(Ak, (int)blockIdx.x / ((Ak.K + 63) >> 6));
+    if constexpr (BATCH) return batch_view<VARIED>(Ak, (int)blockIdx.x / ((Ak.K + 63) >> 6));
     else return with_resident_pose(Ak);
 }
 
@@ -269,14 +303,15 @@ __device__ __forceinline__ void window_min(const double (&px)[kTU], const double
     }
 }
 
-// BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view)
-template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false>
+// BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters
+template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
     static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
+    static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     constexpr int UD = udim_of(MODEL);
     __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
     __shared__ double s_c[LDSWIN ? kMaxH : 1];
-    const RolloutArgs A = BATCH ? batch_view(Ak, (int)blockIdx.y) : Ak;
+    const RolloutArgs A = BATCH ? batch_view<VARIED>(Ak, (int)blockIdx.y) : Ak;
     const int H = A.H;
     if constexpr (BATCH) {
         const double* win = reinterpret_cast<const double*>(A.frame) + kBatchHeadDoubles;

@@ -1,5 +1,5 @@
 // Launchers of the rollout kernel families.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip,
-// k_r4_fb.hip, k_pc_fb.hip, k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip: batch forms): hipcc spends over a minute on all instantiations in one file, the
+// k_r4_fb.hip, k_pc_fb.hip, k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip: batch forms): hipcc spends over a minute on all instantiations in one file, the
 // units compile side by side (build.py).  ccv_mppi_capi.hip -- the C ABI -- selects the family and calls these.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +29,10 @@ void launch_sample(int model, hipStream_t stream, const RolloutArgs& A);
 void launch_rollout_r4_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
 void launch_rollout_solo_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
 void launch_rollout_plain_batch(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+// ... and their forms with per-instance parameters (k_batch_varied.hip; the records' heads point at the parameter table)
+void launch_rollout_r4_batch_varied(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+void launch_rollout_solo_batch_varied(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+void launch_rollout_plain_batch_varied(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
 
 template <class KERNEL>
 inline void launch_at(KERNEL kernel, const dim3 grid, const dim3 block, const LaunchAt& at, const RolloutArgs& A, const Window& W) {

@@ -212,8 +212,12 @@ struct BatchAdvanceArgs {
 
 constexpr int kBatchAdvanceThreads = kBlock;   // (the lexicographic reduction is exact: any width gives the same index)
 
-// instance b's view of the batch: its AdvanceArgs, and the fields of its record that do not depend on the pose
-__device__ __forceinline__ AdvanceArgs batch_advance_view(const BatchAdvanceArgs& G, const int b, double*& rec) {
+// instance b's view of the batch: its AdvanceArgs, and the fields of its record that do not depend on the pose.  VARIED
+// (per-instance parameters, P = the table of ccv_mppi_batch_set_params): the window stride takes the instance's v_ref, and the
+// record's head the address of the instance's row, which the VARIED rollout kernels read (batch_view)
+template <bool VARIED = false>
+__device__ __forceinline__ AdvanceArgs batch_advance_view(const BatchAdvanceArgs& G, const int b, double*& rec,
+                                                          const BatchParams* P = nullptr) {
     const BatchInstance in = G.inst[b];
     AdvanceArgs A;
     A.frame = G.frames + b;
@@ -222,7 +226,8 @@ __device__ __forceinline__ AdvanceArgs batch_advance_view(const BatchAdvanceArgs
     A.nominal = G.nominal + (size_t)b * G.R;
     A.trace = G.trace + (size_t)b * G.trace_cap * 6;
     A.dt = G.dt;
-    A.v_ref = G.v_ref;
+    if constexpr (VARIED) A.v_ref = P[b].v_ref;
+    else A.v_ref = G.v_ref;
     A.resolution = in.resolution;
     A.n_path = in.n_path;
     A.H = G.H;
@@ -239,6 +244,7 @@ __device__ __forceinline__ AdvanceArgs batch_advance_view(const BatchAdvanceArgs
         hd->K = b * G.kpad + G.K;
         hd->k_offset = -b * G.kpad;
         hd->nominal = G.nominal + (size_t)b * G.R;
+        if constexpr (VARIED) hd->params = P + b;
     }
     return A;
 }
@@ -253,7 +259,8 @@ __global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch(const Ba
 // The batched k_finalize_advance: grid (finalize_blocks(R) + 1, B).  Blocks x < finalize_blocks(R) are k_finalize_batch
 // (fused partials) for instance y; block x = finalize_blocks(R) forms instance y's command from the instance's own partial
 // columns in k_finalize_batch's order (the bits its waves write into u*[y][0]) and runs the instance's prologue with it.
-__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs G) {
+template <bool VARIED = false>
+__device__ __forceinline__ void finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs& G, const BatchParams* P = nullptr) {
     const size_t b = blockIdx.y;
     const size_t stride = (size_t)gridDim.y * F.nchunks;
     F.partial += b * F.nchunks;
@@ -278,8 +285,22 @@ __global__ __launch_bounds__(kBlock) void k_finalize_advance_batch(FinalizeArgs 
     }
     __syncthreads();
     double* rec;
-    const AdvanceArgs A = batch_advance_view(G, (int)b, rec);
+    const AdvanceArgs A = batch_advance_view<VARIED>(G, (int)b, rec, P);
     advance_body<kBlock, true>(A, cmd, rec);
+}
+__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs G) {
+    finalize_advance_batch(F, G);
+}
+
+// the two prologue kernels of a batch with per-instance parameters (ccv_mppi_batch_set_params): P = the parameter table [B]
+__global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch_varied(const BatchAdvanceArgs G, const BatchParams* P) {
+    double* rec;
+    const AdvanceArgs A = batch_advance_view<true>(G, (int)blockIdx.x, rec, P);
+    advance_body<kBatchAdvanceThreads, true>(A, A.nominal, rec);
+}
+__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_varied(FinalizeArgs F, const BatchAdvanceArgs G,
+                                                                           const BatchParams* P) {
+    finalize_advance_batch<true>(F, G, P);
 }
 
 }  // namespace ccv

@@ -233,8 +233,8 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // samples per CU, where the reference's own operating point lies (K = 10 000: 157 blocks on 256 CUs; in the two-wave kernel every
 // wave was alone on its SIMD there too, and its producer made the 40 normals of a block itself).
 // BATCH (fused iteration): workgroup blockIdx.x serves instance blockIdx.x / (its workgroups per instance) of a batch handle
-// (batch_view, mppi_kernels.h); everything else is the single handle's code
-template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false>
+// (batch_view, mppi_kernels.h); everything else is the single handle's code.  VARIED: the batch's per-instance parameters
+template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
@@ -242,10 +242,11 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     static_assert(!WIDE || (MODEL == CCV_MPPI_DIFF_DRIVE && MODE == MODE_FUSED), "the wide-turn form exists for the fused diff-drive iteration");
     static_assert(!TAIL || MODE == MODE_FUSED, "the stage-wise modes carry the masked producer anyway");
     static_assert(!BATCH || MODE == MODE_FUSED, "batch handles run the fused iteration only");
+    static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     __shared__ R4Shared<MODEL> sh;
     static_assert(offsetof(R4Shared<MODEL>, zs) + sizeof(sh.zs) >= kR4Waves * kR4RB<MODEL> * (kPcSamples + 2) * sizeof(double), "epilogue buffers");
     touch_rollout_args();
-    const RolloutArgs A = rollout_view<MODEL, BATCH>(Ak);
+    const RolloutArgs A = rollout_view<MODEL, BATCH, VARIED>(Ak);
     // The prologue runs in all sixteen waves of a CU at once and SIMD arbitration is oldest first: the workgroup dispatched last
     // to a CU was through it 1.5 us after the first (stamps: staging barrier passed at 1.4 / 1.7 / 2.0 / 3.0 us by dispatch
     // rank) and carried that lag to the end of the kernel, which ends with the slowest.  Until the loops' rotation takes over,

@@ -24,14 +24,16 @@ struct SoloShared {
     alignas(32) double nom[(kMaxH + 8) * udim_of(MODEL)];  // warm start u*
 };
 
-// WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h)
-template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false>
+// WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h);
+// VARIED: with the batch's per-instance parameters
+template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false>
 __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArgs Ak, const Window Wk) {
     static_assert(MODE == MODE_FUSED, "the stage-wise modes use k_rollout_pc");
+    static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     __shared__ SoloShared<MODEL> sh;
     static_assert(sizeof(sh.p) >= kUpdRB * (kPcSamples + 2) * sizeof(double), "epilogue buffer");
-    const RolloutArgs A = rollout_view<MODEL, BATCH>(Ak);
+    const RolloutArgs A = rollout_view<MODEL, BATCH, VARIED>(Ak);
     const int H = A.H;
     const int lane = threadIdx.x;
     stage_window<BATCH>(A, Wk, sh, kPcSamples);

@@ -229,7 +229,8 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 
 /* ---- batch handles: B independent problems in one launch -------------------------------------------------------- */
 /* B controllers that share one configuration (model, K = num_samples per instance, H, sigma, lambda, bounds, weights, flags)
- * and differ in pose, dt, reference window, warm start and noise seed: one call runs all of them with one rollout launch and
+ * -- or, after ccv_mppi_batch_set_params, only its model, K, H and flags, each instance with its own sigma, lambda, v_ref,
+ * bounds and weights -- and differ in pose, dt, reference window, warm start and noise seed: one call runs all of them with one rollout launch and
  * one update launch -- what a process that serves N robots, or sweeps N scenarios, would otherwise spend N handles and N
  * blocking round trips on.  Instance b computes what a single handle with the same configuration computes for the same
  * (x0[b], dt[b], x_ref[b], y_ref[b], yaw_ref0[b], seed[b], iter) from the same warm start: its noise is that of noise_spec.h
@@ -247,6 +248,7 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_BATCH_KERNEL_ONE_WAVE 1
 #define CCV_MPPI_BATCH_KERNEL_FOUR_WAVE 4
 #define CCV_MPPI_BATCH_KERNEL_WIDE 16
+#define CCV_MPPI_BATCH_KERNEL_VARIED 32 /* ORed in: the kernels with per-instance parameters ran (ccv_mppi_batch_set_params) */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
 
@@ -263,6 +265,18 @@ int ccv_mppi_batch_last_kernel(const ccv_mppi_batch* b);
 /* warm starts, layout [B][(H-1)][u_dim] */
 int ccv_mppi_batch_set_nominal(ccv_mppi_batch* b, const double* u);
 int ccv_mppi_batch_get_nominal(ccv_mppi_batch* b, double* u);
+/* Per-instance parameters: cfgs[B], instance b's configuration.  Its abi_version, model, num_samples, horizon,
+ * sample_offset, device and flags must equal the creation configuration's (otherwise CCV_MPPI_ERR_INVALID_ARG, the first
+ * offending instance and field in _last_error, the handle unchanged); control_noise, lambda, v_ref, u_min, u_max and the six
+ * weights are the instance's own from the next iteration on.  Instance b then computes what a single handle created with
+ * cfgs[b] computes for the same inputs and warm start (bit for bit where both run the same kernel family), and no parameter
+ * of one instance changes an output bit of another.  The decisions one instance makes for the batch (plain kernel, wide-turn
+ * form, the resident loop's stride and angle checks) take each instance's own bounds and v_ref; the two-instruction clamp is
+ * chosen per instance.  cfgs == NULL returns to the creation configuration and the shared kernels.  Flushes a pending resident
+ * update and may synchronise; warm starts, paths, poses, step counters and traces stay. */
+int ccv_mppi_batch_set_params(ccv_mppi_batch* b, const ccv_mppi_config* cfgs);
+/* out[B]: every instance's effective configuration (B copies of the creation configuration before any _set_params) */
+int ccv_mppi_batch_get_params(ccv_mppi_batch* b, ccv_mppi_config* out);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
