@@ -1,0 +1,659 @@
+// translation unit: the small kernels around the rollout (declared in mppi_update.h and mppi_resident.h, launched by the
+// host units of the C ABI): weighted update, re-derivation of the controls from the stored normals, MIN_SHIFT
+// re-weighting, the read-back helpers, and the prologue of the device-resident loop.  Not templates: every kernel is
+// defined here and nowhere else.
+#include "fast_trig.h"
+#include "mppi_resident.h"
+
+namespace ccv {
+
+// ---- re-derivation of the controls (MaterializeArgs, mppi_update.h) ---------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_materialize_controls(const MaterializeArgs A) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const int n = blockIdx.y;
+    if (k >= A.K) return;
+    const int d = n % A.udim;
+    double v = (double)A.z[(size_t)n * A.pitch + k] * A.sigma + A.nominal_used[n];
+    v = clampd(v, A.umin[d], A.umax[d]);
+    if (d == A.zero_dim) v = 0.0;
+    A.u[(size_t)n * A.pitch + k] = v;
+}
+
+// ---- weighted update -------------------------------------------------------------------------------------------
+// grid (nchunks, R+1).  Row n < R: sum_k w_k*u[n][k] over this chunk; row R: sum_k w_k (+ cost stats).
+// Fixed reduction order => bitwise reproducible (no atomics).
+__device__ __forceinline__ void update_partials(const UpdateArgs& A) {
+    __shared__ double red[4][4];
+    const int row = blockIdx.y;
+    const int chunk = blockIdx.x;
+    const int base = chunk * kChunk;
+    const bool wrow = row == A.R;
+    const double* urow = A.u + (size_t)row * A.pitch;
+    double acc = 0.0, mn = INFINITY, mx = -INFINITY, nz = 0.0;
+#pragma unroll
+    for (int i = 0; i < kChunk / (2 * kBlock); ++i) {
+        const int k = base + i * 2 * kBlock + threadIdx.x * 2;
+        if (k + 1 < A.K) {
+            const double2 wv = *reinterpret_cast<const double2*>(A.w + k);
+            if (wrow) {
+                acc += wv.x;
+                acc += wv.y;
+                const double2 cv = *reinterpret_cast<const double2*>(A.cost + k);
+                mn = fmin(mn, fmin(cv.x, cv.y));
+                mx = fmax(mx, fmax(cv.x, cv.y));
+                nz += (wv.x == 0.0 ? 1.0 : 0.0) + (wv.y == 0.0 ? 1.0 : 0.0);
+            } else {
+                const double2 uv = *reinterpret_cast<const double2*>(urow + k);
+                acc += wv.x * uv.x;
+                acc += wv.y * uv.y;
+            }
+        } else if (k < A.K) {
+            const double wv = A.w[k];
+            if (wrow) {
+                acc += wv;
+                const double cv = A.cost[k];
+                mn = fmin(mn, cv);
+                mx = fmax(mx, cv);
+                nz += (wv == 0.0 ? 1.0 : 0.0);
+            } else {
+                acc += wv * urow[k];
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    acc = wave_sum(acc);
+    if (wrow) {
+        mn = wave_min(mn);
+        mx = wave_max(mx);
+        nz = wave_sum(nz);
+    }
+    if (lane == 0) {
+        red[0][wid] = acc;
+        red[1][wid] = mn;
+        red[2][wid] = mx;
+        red[3][wid] = nz;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        A.partial[(size_t)row * A.nchunks + chunk] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        if (wrow) {
+            A.statpart[chunk * 3 + 0] = fmin(fmin(red[1][0], red[1][1]), fmin(red[1][2], red[1][3]));
+            A.statpart[chunk * 3 + 1] = fmax(fmax(red[2][0], red[2][1]), fmax(red[2][2], red[2][3]));
+            A.statpart[chunk * 3 + 2] = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+        }
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_update_partials(const UpdateArgs A) { update_partials(A); }
+// Batch handles (the plain kernel's iteration): grid (nchunks, R+1, B).  Instance blockIdx.z owns the columns
+// [z * kpad, z * kpad + K) of the shared rows and a block of partials [(R+1)][nchunks] and statistics [nchunks][3] of its own:
+// the single handle's reduction, instance by instance.
+__global__ __launch_bounds__(kBlock) void k_update_partials_batch(UpdateArgs A, const int kpad) {
+    const size_t b = blockIdx.z;
+    A.u += b * kpad;
+    A.w += b * kpad;
+    A.cost += b * kpad;
+    A.partial += b * (size_t)(A.R + 1) * A.nchunks;
+    A.statpart += b * (size_t)A.nchunks * 3;
+    update_partials(A);
+}
+
+__device__ __forceinline__ void mail_post(const FinalizeArgs& A, const int slot, const double value) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(value);
+    unsigned long long* dst = A.mail + 2 * (size_t)slot;
+    __hip_atomic_store(dst + 0, (bits & 0xFFFFFFFF00000000ull) | A.mail_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(dst + 1, (bits << 32) | A.mail_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One wave per row n: lanes read the chunk partials of the row (fixed order => bitwise reproducible), wave-reduce them,
+// and re-derive S = sum w the same way, so no cross-block hand-off is needed.  u*[n] = V_n / S
+// (== sum_i (w_i/S) u_i of dd:222,234 up to rounding; S == 0 gives NaN exactly as dd:222 does).
+// sums of two rows of n partials each (lane l takes columns l, l+64, ...): up to 1024 columns per pass, all 32 loads of a
+// lane issued before the first add (one memory latency for both rows, not one per row)
+__device__ __forceinline__ void lane_partial_sum2(const double* row_a, const double* row_b, int n, int lane, double& sum_a,
+                                                  double& sum_b) {
+    double acc_a = 0.0, acc_b = 0.0;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        double va[16], vb[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = min(c0 + lane + 64 * i, n - 1);   // (clamped: the loads carry no branch)
+            va[i] = row_a[c];
+            vb[i] = row_b[c];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const bool in = c0 + lane + 64 * i < n;
+            acc_a += in ? va[i] : 0.0;
+            acc_b += in ? vb[i] : 0.0;
+        }
+    }
+    sum_a = acc_a;
+    sum_b = acc_b;
+}
+
+// min / max cost and the zero-weight count over the per-workgroup statistics: a wave of its own (n == R + 1), so that its
+// loads run beside the row reductions instead of after one of them
+__device__ __forceinline__ void finalize_cost_stats(const FinalizeArgs& A, const int lane) {
+    double mn = INFINITY, mx = -INFINITY, nz = 0.0;
+    for (int c0 = 0; c0 < A.nchunks; c0 += 1024) {
+        double a[16], b[16], z[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {   // all loads first: one memory latency per 1024 partials
+            const int c = min(c0 + lane + 64 * i, A.nchunks - 1);
+            a[i] = A.statpart[c * 3 + 0];
+            b[i] = A.statpart[c * 3 + 1];
+            z[i] = A.statpart[c * 3 + 2];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const bool in = c0 + lane + 64 * i < A.nchunks;
+            mn = fmin(mn, in ? a[i] : INFINITY);
+            mx = fmax(mx, in ? b[i] : -INFINITY);
+            nz += in ? z[i] : 0.0;
+        }
+    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    nz = wave_sum(nz);
+    if (lane == 0) {
+        A.stats[1] = mn;
+        A.stats[2] = mx;
+        A.stats[3] = nz;
+        if (A.mail) {
+            mail_post(A, A.R + 1, mn);
+            mail_post(A, A.R + 2, mx);
+            mail_post(A, A.R + 3, nz);
+        }
+    }
+}
+
+// (stride: the row pitch of the partials, nchunks but for a batch handle's fused partials)
+__device__ __forceinline__ void finalize_rows(const FinalizeArgs& A, const size_t stride) {
+    const int lane = threadIdx.x & 63;
+    // rows 0..R-1: one wave each; wave R: sum w; wave R + 1: the cost statistics
+    const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (n > A.R) {
+        if (n == A.R + 1) finalize_cost_stats(A, lane);
+        return;
+    }
+    const int nrow = n < A.R ? n : A.R;
+    // S = sum w and this wave's row are fetched together
+    double s, v;
+    lane_partial_sum2(A.partial + (size_t)A.R * stride, A.partial + (size_t)nrow * stride, A.nchunks, lane, s, v);
+    s = wave_sum(s);
+    v = wave_sum(v);
+    if (n < A.R && lane == 0) {
+        A.vec[1 + n] = v;
+        if (A.normalise) {
+            const double q = v / s;
+            A.nominal[n] = q;
+            if (A.mail) mail_post(A, n, q);
+        }
+    }
+    if (n == A.R && lane == 0) {
+        A.vec[0] = s;
+        A.stats[0] = s;
+        if (A.mail) mail_post(A, A.R, s);
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_finalize(const FinalizeArgs A) { finalize_rows(A, (size_t)A.nchunks); }
+// Batch handles: grid (finalize_blocks(R), B); instance blockIdx.y reduces its own nchunks columns of the partials in the
+// single handle's order (the same bits) into its slices of u* [B][R], vec [B][R+1], stats [B][4] and mailbox slots [B][R+4] --
+// every packet under the launch's one sequence number.  Partials: `fused` -- the rollout kernels' [(R+1)][B * nchunks],
+// instance b in columns b * nchunks ...; otherwise k_update_partials_batch's [B][(R+1)][nchunks].  Statistics [B][nchunks][3].
+__global__ __launch_bounds__(kBlock) void k_finalize_batch(FinalizeArgs A, const int fused) {
+    const size_t b = blockIdx.y;
+    const size_t stride = fused ? (size_t)gridDim.y * A.nchunks : (size_t)A.nchunks;
+    A.partial += fused ? b * A.nchunks : b * (size_t)(A.R + 1) * A.nchunks;
+    A.statpart += b * (size_t)A.nchunks * 3;
+    A.nominal += b * A.R;
+    A.vec += b * (size_t)(A.R + 1);
+    A.stats += b * 4;
+    if (A.mail) A.mail += 2 * b * (size_t)(A.R + 4);
+    finalize_rows(A, stride);
+}
+
+// ---- direct exchange (ExchangeBox, ExchangeArgs: mppi_update.h) ---------------------------------------------------------
+__device__ __forceinline__ unsigned long long load_system(const unsigned long long* p) {   // past every cache
+    unsigned long long v;
+    asm volatile("global_load_dwordx2 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
+    return v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_finalize_exchange(const FinalizeArgs A, const ExchangeArgs X) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);   // rows 0..R-1; wave R: sum w; wave R + 1: cost statistics
+    if (n > A.R) {
+        if (n == A.R + 1) finalize_cost_stats(A, lane);   // (this device's samples only)
+        return;
+    }
+    const int nrow = n < A.R ? n : A.R;
+    double s, v;
+    lane_partial_sum2(A.partial + (size_t)A.R * A.nchunks, A.partial + (size_t)nrow * A.nchunks, A.nchunks, lane, s, v);
+    s = wave_sum(s);
+    v = wave_sum(v);
+    // ---- this wave's value into slot [rank] of every peer's box: lane d writes to rank d
+    const int slot = n < A.R ? 1 + n : 0;
+    const double mine = n < A.R ? v : s;
+    if (lane < X.world) {
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(mine);
+        unsigned long long* dst = &X.peer[lane]->pkt[X.parity][X.rank][slot][0];
+        __hip_atomic_store(dst + 0, (bits & 0xFFFFFFFF00000000ull) | X.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(dst + 1, (bits << 32) | X.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (lane == 0) {   // (this device's share)
+        A.vec[slot] = mine;
+        if (n == A.R) A.stats[0] = s;
+    }
+    // ---- the peers' values of the same slot: lane r polls rank r's two packets in the local box
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long* src = &X.local->pkt[X.parity][lane < X.world ? lane : 0][slot][0];
+    unsigned long long hi = 0, lo = 0;
+    bool arrived = lane >= X.world;
+    while (true) {
+        if (!arrived) {
+            hi = load_system(src + 0);
+            lo = load_system(src + 1);
+            arrived = (uint32_t)hi == X.seq && (uint32_t)lo == X.seq;
+        }
+        if (__all(arrived)) break;
+        if (__builtin_amdgcn_s_memrealtime() - t0 > X.timeout_ticks) break;
+        __builtin_amdgcn_s_sleep(4);
+    }
+    const bool ok = __all(arrived);
+    const double theirs = __longlong_as_double((long long)((hi & 0xFFFFFFFF00000000ull) | (lo >> 32)));
+    double acc = 0.0;
+    for (int r = 0; r < X.world; ++r) acc += lane_value(theirs, r);   // rank order on every device
+    if (lane == 0) {
+        X.reduced[slot] = ok ? acc : __builtin_nan("");
+        if (!ok && X.timeout_flag) __hip_atomic_store(X.timeout_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (pinned host memory)
+    }
+}
+
+// After the cross-device all-reduce of [sum w, sum w*u]: u* = V / S on every device.
+__global__ __launch_bounds__(kBlock) void k_apply_partials(const double* vec, double* nominal, double* stats, int R) {
+    const double S = vec[0];
+    if (threadIdx.x == 0) stats[0] = S;
+    for (int n = threadIdx.x; n < R; n += kBlock) nominal[n] = vec[1 + n] / S;
+}
+
+// ---- optional underflow-safe weights (CCV_MPPI_FLAG_MIN_SHIFT; not reference behaviour) --------------------------
+__global__ __launch_bounds__(1024) void k_min_cost(const double* cost, int K, double* out_min) {
+    __shared__ double red[16];
+    double mn = INFINITY;
+    for (int k = threadIdx.x; k < K; k += 1024) mn = fmin(mn, cost[k]);
+    mn = wave_min(mn);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = red[0];
+        for (int i = 1; i < 16; ++i) r = fmin(r, red[i]);
+        *out_min = r;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_reweight(const double* cost, const double* cmin, double lambda, int K, double* w) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k < K) w[k] = exp(-(cost[k] - *cmin) / lambda);
+}
+
+// ---- read-back helpers -----------------------------------------------------------------------------------------
+// out[c][t][2] = (xs[t][first + c*stride], ys[t][...])
+__global__ __launch_bounds__(kBlock) void k_gather_xy(const double* xs, const double* ys, int pitch, int H, int first,
+                                                      int count, int stride, double* out) {
+    const int idx = blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= count * H) return;
+    const int c = idx / H, t = idx % H;
+    const size_t src = (size_t)t * pitch + first + (size_t)c * stride;
+    out[(size_t)idx * 2 + 0] = xs[src];
+    out[(size_t)idx * 2 + 1] = ys[src];
+}
+
+// ---- top-N candidates by weight (publish_CandidatePath() feed, dd:265-294: at K = 65 536 rviz can only draw a few) ----
+// One workgroup.  Radix select on the weights' bit patterns (w >= 0, so the IEEE order is the integer order; NaN sorts
+// above everything and is reported first, as a reader of a NaN iteration should see): eight 8-bit passes find the N-th
+// largest key T and how many samples equal to T belong to the answer; a last pass writes the sample indices, "greater
+// than T" first and then the lowest-index "equal to T" ones -- positions come from block-wide prefix sums in index
+// order, so the output is the same on every run.  The host sorts the N pairs.
+__global__ __launch_bounds__(kTopBlock) void k_top_weights(const double* w, int K, int N, int* idx_out, double* w_out) {
+    __shared__ unsigned int hist[256];
+    __shared__ unsigned long long s_prefix;
+    __shared__ int s_remaining;
+    __shared__ int wsum[kTopBlock / 64][2];
+    __shared__ int s_base[2];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) {
+        s_prefix = 0ull;
+        s_remaining = N;
+    }
+    __syncthreads();
+    for (int pass = 7; pass >= 0; --pass) {
+        if (tid < 256) hist[tid] = 0u;
+        __syncthreads();
+        const unsigned long long prefix = s_prefix;
+        for (int i = tid; i < K; i += kTopBlock) {
+            const unsigned long long key = (unsigned long long)__double_as_longlong(w[i]);
+            const bool match = pass == 7 || (key >> (8 * (pass + 1))) == prefix;
+            if (match) atomicAdd(&hist[(unsigned int)(key >> (8 * pass)) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int rem = s_remaining, b = 255;
+            for (; b > 0; --b) {
+                if ((int)hist[b] >= rem) break;
+                rem -= (int)hist[b];
+            }
+            s_remaining = rem;                 // how many of bin b (and, after the last pass, of key T) are still wanted
+            s_prefix = (prefix << 8) | (unsigned long long)b;
+        }
+        __syncthreads();
+    }
+    const unsigned long long T = s_prefix;
+    const int n_equal = s_remaining, n_greater = N - n_equal;
+    if (tid == 0) s_base[0] = s_base[1] = 0;
+    __syncthreads();
+    for (int i0 = 0; i0 < K; i0 += kTopBlock) {
+        const int i = i0 + tid;
+        const unsigned long long key = i < K ? (unsigned long long)__double_as_longlong(w[i]) : 0ull;
+        const int fg = (i < K && key > T) ? 1 : 0, fe = (i < K && key == T) ? 1 : 0;
+        // exclusive prefix sums over the block in index order: wave ballots, then a scan of the 16 wave totals
+        const unsigned long long bg = __ballot(fg), be = __ballot(fe);
+        const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+        const int pg = __popcll(bg & below), pe = __popcll(be & below);
+        if (lane == 0) {
+            wsum[wv][0] = __popcll(bg);
+            wsum[wv][1] = __popcll(be);
+        }
+        __syncthreads();
+        int og = s_base[0], oe = s_base[1];
+        for (int j = 0; j < wv; ++j) {
+            og += wsum[j][0];
+            oe += wsum[j][1];
+        }
+        if (fg) {
+            idx_out[og + pg] = i;
+            w_out[og + pg] = w[i];
+        }
+        if (fe && oe + pe < n_equal) {
+            idx_out[n_greater + oe + pe] = i;
+            w_out[n_greater + oe + pe] = w[i];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int tg = 0, te = 0;
+            for (int j = 0; j < kTopBlock / 64; ++j) {
+                tg += wsum[j][0];
+                te += wsum[j][1];
+            }
+            s_base[0] += tg;
+            s_base[1] += te;
+        }
+        __syncthreads();
+    }
+}
+
+// gather of listed samples: out[c][t] = (x, y) of sample idx[c] at step t
+__global__ __launch_bounds__(kBlock) void k_gather_xy_list(const double* xs, const double* ys, int pitch, int H, const int* idx,
+                                                           int count, double* out) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= count * H) return;
+    const int c = j / H, t = j % H;
+    const size_t src = (size_t)t * pitch + idx[c];
+    out[(size_t)j * 2 + 0] = xs[src];
+    out[(size_t)j * 2 + 1] = ys[src];
+}
+
+__global__ __launch_bounds__(kBlock) void k_normalise_weights(const double* w, const double* stats, int first, int count,
+                                                             double* out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < count) out[i] = w[first + i] / stats[0];
+}
+
+// ---- device-resident closed loop (mppi_resident.h) ------------------------------------------------------------------
+// NT threads of one workgroup; cmd: the command u*[0][0 .. u_dim) (read only when A.advance).  BATCH: the window
+// coefficients go into the instance's batch record `rec` (BatchHead + a[H], b[H], c[H]) instead of A.frame->W, and the pose
+// and yaw_ref0 into its head as well -- what batch_enqueue() writes on the host for the same pose and window.
+template <int NT, bool BATCH = false>
+__device__ __forceinline__ void advance_body(const AdvanceArgs& A, const double* cmd, double* rec = nullptr) {
+    __shared__ double s_d[NT / 64];
+    __shared__ int s_i[NT / 64];
+    __shared__ int s_start;
+    ResidentFrame& F = *A.frame;
+    // ---- pose (every thread computes it: wave-uniform, no hand-off)
+    double x = F.x0[0], y = F.x0[1], yaw = F.x0[2], roll = F.x0[3], pitch = F.x0[4];
+    if (A.advance) {
+        const double v = cmd[0], w = cmd[1];
+        const double heading = A.model == CCV_MPPI_DIFF_DRIVE ? yaw : yaw + cmd[2];
+        double sn, cs;
+        fast_sincos(heading, sn, cs);
+        x = x + v * cs * A.dt;
+        y = y + v * sn * A.dt;
+        yaw = rebase_angle(yaw + w * A.dt);
+        if (A.model == CCV_MPPI_FULL_BODY) {
+            roll = rebase_angle(roll + cmd[3] * A.dt);
+            pitch = rebase_angle(pitch + cmd[4] * A.dt);
+        }
+    }
+    // ---- get_CurrentIndex(): strict '<' against a running minimum that starts at the 100 m gate
+    double best_d = 100.0;
+    int best_i = -1;
+    constexpr int kBatch = 4;   // loads in flight per thread: the scan is a chain of memory latencies otherwise
+    for (int i0 = threadIdx.x; i0 < A.n_path; i0 += NT * kBatch) {
+        double qx[kBatch], qy[kBatch];
+#pragma unroll
+        for (int b = 0; b < kBatch; ++b) {
+            const int i = min(i0 + b * NT, A.n_path - 1);
+            qx[b] = A.path_x[i];
+            qy[b] = A.path_y[i];
+        }
+#pragma unroll
+        for (int b = 0; b < kBatch; ++b) {
+            const int i = i0 + b * NT;
+            const double ex = x - qx[b], ey = y - qy[b];
+            const double d = sqrt(ex * ex + ey * ey);
+            if (i < A.n_path && d < best_d) {   // (ascending i within a thread: the first of equal distances stays)
+                best_d = d;
+                best_i = i;
+            }
+        }
+    }
+    // (distance, index) minimum, lexicographic: the smallest distance, and among equal distances the smallest index --
+    // what the serial scan's strict '<' keeps.  Two wave reductions per level (DPP), one LDS hand-off between the levels.
+    auto lexmin = [](double d, int i, double& d_out, int& i_out) {
+        const double dm = wave_min(d);                                   // (no candidate: d = 100, the gate)
+        const double im = wave_min((i >= 0 && d == dm) ? (double)i : 1.0e300);
+        d_out = dm;
+        i_out = im < 1.0e299 ? (int)im : -1;
+    };
+    double wd;
+    int wi;
+    lexmin(best_d, best_i, wd, wi);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+        s_d[wave] = wd;
+        s_i[wave] = wi;
+    }
+    __syncthreads();   // (also: every thread has read the old pose)
+    if (wave == 0) {
+        constexpr int NW = NT / 64;
+        const double d2 = lane < NW ? s_d[lane] : 100.0;
+        const int i2 = lane < NW ? s_i[lane] : -1;
+        double fd;
+        int fi;
+        lexmin(d2, i2, fd, fi);
+        if (lane == 0) s_start = fi < 0 ? 0 : fi;
+    }
+    __syncthreads();
+    const int start = s_start;
+    // ---- calc_RefPath(): the index is the truncation of a double; past the end the final pose repeats
+    const double stride = A.v_ref * A.dt / A.resolution;
+    for (int i = threadIdx.x; i < A.H; i += NT) {
+        const int idx = (int)(start + i * stride);   // (the host admits 0 < dt < inf only: idx >= 0)
+        const int src = idx < A.n_path ? idx : A.n_path - 1;
+        const double xr = A.path_x[src], yr = A.path_y[src];
+        F.x_ref[i] = xr;
+        F.y_ref[i] = yr;
+        const double xl = xr - x, yl = yr - y;
+        if constexpr (BATCH) {
+            double* win = rec + kBatchHeadDoubles;
+            win[i] = -2.0 * xl;
+            win[A.H + i] = -2.0 * yl;
+            win[2 * A.H + i] = xl * xl + yl * yl;
+        } else {
+            F.W.a[i] = -2.0 * xl;
+            F.W.b[i] = -2.0 * yl;
+            F.W.c[i] = xl * xl + yl * yl;
+        }
+    }
+    if (threadIdx.x == 0) {
+        const int i1 = (int)(start + 1 * stride), i0 = (int)(start + 0 * stride);
+        const int s1 = i1 < A.n_path ? i1 : A.n_path - 1, s0 = i0 < A.n_path ? i0 : A.n_path - 1;
+        const double yaw_ref0 = atan2(A.path_y[s1] - A.path_y[s0], A.path_x[s1] - A.path_x[s0]);
+        F.yaw_ref0 = yaw_ref0;
+        if constexpr (BATCH) {
+            BatchHead* hd = reinterpret_cast<BatchHead*>(rec);
+            hd->x0[0] = x;
+            hd->x0[1] = y;
+            hd->x0[2] = yaw;
+            hd->x0[3] = roll;
+            hd->x0[4] = pitch;
+            hd->yaw_ref0 = yaw_ref0;
+        }
+        F.x0[0] = x;
+        F.x0[1] = y;
+        F.x0[2] = yaw;
+        F.x0[3] = roll;
+        F.x0[4] = pitch;
+        F.index = start;
+        const int n = F.steps;
+        F.steps = n + 1;
+        if (A.trace) {
+            double* t = A.trace + (size_t)(n % A.trace_cap) * 6;
+            t[0] = x;
+            t[1] = y;
+            t[2] = yaw;
+            t[3] = roll;
+            t[4] = pitch;
+            t[5] = (double)start;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kAdvanceThreads) void k_advance(const AdvanceArgs A) { advance_body<kAdvanceThreads>(A, A.nominal); }
+
+// The update of tick i and the prologue of tick i+1 in ONE launch (the closed loop then costs two launches per tick, not
+// three): blocks 0 .. finalize_blocks(R)-1 are k_finalize; one more block forms the command u*[0][d] = V_d / S from the same
+// partial sums in the same order (the same bits the finalize waves write into the warm start -- it cannot wait for them)
+// and runs the prologue with it.
+__global__ __launch_bounds__(kBlock) void k_finalize_advance(const FinalizeArgs F, const AdvanceArgs A) {
+    if ((int)blockIdx.x < finalize_blocks(F.R)) {
+        finalize_rows(F, (size_t)F.nchunks);
+        return;
+    }
+    __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
+    if (A.advance) {
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(A.model);
+        for (int d = wv; d < ud; d += kBlock / 64) {
+            double s, v;
+            lane_partial_sum2(F.partial + (size_t)F.R * F.nchunks, F.partial + (size_t)d * F.nchunks, F.nchunks, lane, s, v);
+            s = wave_sum(s);
+            v = wave_sum(v);
+            if (lane == 0) cmd[d] = v / s;
+        }
+    }
+    __syncthreads();
+    advance_body<kBlock>(A, cmd);
+}
+
+// ---- batch handles: the same prologue for B instances, one workgroup each (BatchAdvanceArgs, mppi_resident.h) -----------
+// instance b's view of the batch: its AdvanceArgs, and the fields of its record that do not depend on the pose.  VARIED
+// (per-instance parameters, P = the table of ccv_mppi_batch_set_params): the window stride takes the instance's v_ref, and the
+// record's head the address of the instance's row, which the VARIED rollout kernels read (batch_view)
+template <bool VARIED = false>
+__device__ __forceinline__ AdvanceArgs batch_advance_view(const BatchAdvanceArgs& G, const int b, double*& rec,
+                                                          const BatchParams* P = nullptr) {
+    const BatchInstance in = G.inst[b];
+    AdvanceArgs A;
+    A.frame = G.frames + b;
+    A.path_x = G.path + in.path_off;
+    A.path_y = G.path + G.n_total + in.path_off;
+    A.nominal = G.nominal + (size_t)b * G.R;
+    A.trace = G.trace + (size_t)b * G.trace_cap * 6;
+    A.dt = G.dt;
+    if constexpr (VARIED) A.v_ref = P[b].v_ref;
+    else A.v_ref = G.v_ref;
+    A.resolution = in.resolution;
+    A.n_path = in.n_path;
+    A.H = G.H;
+    A.model = G.model;
+    A.advance = G.advance;
+    A.trace_cap = G.trace_cap;
+    rec = G.rec + (size_t)b * batch_record_doubles(G.H);
+    if (threadIdx.x == 0) {
+        BatchHead* hd = reinterpret_cast<BatchHead*>(rec);
+        hd->dt = G.dt;
+        hd->inv_dt = G.inv_dt;
+        hd->seed_lo = in.seed_lo;
+        hd->seed_hi = in.seed_hi;
+        hd->K = b * G.kpad + G.K;
+        hd->k_offset = -b * G.kpad;
+        hd->nominal = G.nominal + (size_t)b * G.R;
+        if constexpr (VARIED) hd->params = P + b;
+    }
+    return A;
+}
+
+// grid B: instance blockIdx.x, its command read from u*[b][0]
+__global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch(const BatchAdvanceArgs G) {
+    double* rec;
+    const AdvanceArgs A = batch_advance_view(G, (int)blockIdx.x, rec);
+    advance_body<kBatchAdvanceThreads, true>(A, A.nominal, rec);
+}
+
+// The batched k_finalize_advance: grid (finalize_blocks(R) + 1, B).  Blocks x < finalize_blocks(R) are k_finalize_batch
+// (fused partials) for instance y; block x = finalize_blocks(R) forms instance y's command from the instance's own partial
+// columns in k_finalize_batch's order (the bits its waves write into u*[y][0]) and runs the instance's prologue with it.
+template <bool VARIED = false>
+__device__ __forceinline__ void finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs& G, const BatchParams* P = nullptr) {
+    const size_t b = blockIdx.y;
+    const size_t stride = (size_t)gridDim.y * F.nchunks;
+    F.partial += b * F.nchunks;
+    if ((int)blockIdx.x < finalize_blocks(F.R)) {
+        F.statpart += b * (size_t)F.nchunks * 3;
+        F.nominal += b * F.R;
+        F.vec += b * (size_t)(F.R + 1);
+        F.stats += b * 4;
+        finalize_rows(F, stride);   // (no mailbox: a deferred update is never a blocking call's)
+        return;
+    }
+    __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
+    if (G.advance) {
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(G.model);
+        for (int d = wv; d < ud; d += kBlock / 64) {
+            double s, v;
+            lane_partial_sum2(F.partial + (size_t)F.R * stride, F.partial + (size_t)d * stride, F.nchunks, lane, s, v);
+            s = wave_sum(s);
+            v = wave_sum(v);
+            if (lane == 0) cmd[d] = v / s;
+        }
+    }
+    __syncthreads();
+    double* rec;
+    const AdvanceArgs A = batch_advance_view<VARIED>(G, (int)b, rec, P);
+    advance_body<kBlock, true>(A, cmd, rec);
+}
+__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs G) {
+    finalize_advance_batch(F, G);
+}
+
+// the two prologue kernels of a batch with per-instance parameters (ccv_mppi_batch_set_params): P = the parameter table [B]
+__global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch_varied(const BatchAdvanceArgs G, const BatchParams* P) {
+    double* rec;
+    const AdvanceArgs A = batch_advance_view<true>(G, (int)blockIdx.x, rec, P);
+    advance_body<kBatchAdvanceThreads, true>(A, A.nominal, rec);
+}
+__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_varied(FinalizeArgs F, const BatchAdvanceArgs G,
+                                                                           const BatchParams* P) {
+    finalize_advance_batch<true>(F, G, P);
+}
+
+}  // namespace ccv

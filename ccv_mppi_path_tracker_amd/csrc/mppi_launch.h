@@ -1,6 +1,7 @@
 // Launchers of the rollout kernel families.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip,
 // k_r4_fb.hip, k_pc_fb.hip, k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip: batch forms): hipcc spends over a minute on all instantiations in one file, the
-// units compile side by side (build.py).  ccv_mppi_capi.hip -- the C ABI -- selects the family and calls these.
+// units compile side by side (build.py).  The C ABI selects the family (select_kernels(), ccv_mppi_capi.hip) and
+// calls these (launch_rollout_model() there; batch_launch(), capi_batch.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

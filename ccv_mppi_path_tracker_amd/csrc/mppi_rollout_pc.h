@@ -158,7 +158,7 @@ __device__ __forceinline__ void pc_rotate_priority(const RolloutArgs& A, const i
 
 // four-wave kernel: the level from the workgroup's dispatch rank, the time block and the wave's role.
 //   prio_rotate >= 16: (rank + level[role] + b) mod 4 with level[] = the four base-4 digits of prio_rotate - 16 (digit 0: noise
-//   wave, 1: dynamics, 2: distance, 3: store) -- the default, with one table per model (ccv_mppi_capi.hip: kR4PrioLevels);
+//   wave, 1: dynamics, 2: distance, 3: store) -- the default, with one table per model (ccv_mppi_capi.hip: r4_prio_levels);
 //   2: level[role] = role, i.e. (rank + role + b); 5: (role - rank - b); 3, 4: the other two sign combinations (CCV_MPPI_PRIO).
 // What matters, measured at C2 on one box (gpurun_out/r3bn, r3bj): no priorities 36.6 us; the prologue's rank priorities only
 // 35.3; rank only, constant 34.5; (rank + role) 34.5; (rank + b) 32.4; (rank + role + b) 31.7; (rank + role - b) 32.9 -- the
