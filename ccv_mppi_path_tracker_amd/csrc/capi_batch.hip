@@ -1,35 +1,40 @@
 // C ABI, batch handles: B independent problems in one launch (ccv_mppi_batch_*; struct ccv_mppi_batch: capi_internal.h),
-// their device-resident closed loop included.  The plumbing is the single handle's (ccv_mppi_capi.hip), on the embedded handle.
+// their device-resident closed loop included.  The plumbing is the single handle's (ccv_mppi_capi.hip), on the core.
 #include <new>
 
 #include "capi_internal.h"
 
 namespace {
 
-int batch_fail(ccv_mppi_batch* b, int code, const char* what) { return fail(b ? &b->h : nullptr, code, what); }
-
 // instance b's configuration: its own under per-instance parameters, the creation configuration otherwise
-const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->h.cfg; }
+const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->cfg; }
+
+// CCV_MPPI_BATCH_KERNEL_* of a launch (ccv_mppi_batch_last_kernel)
+int batch_kernel_code(const RolloutPlan& p) {
+    const int family = p.family == KernelFamily::Plain     ? CCV_MPPI_BATCH_KERNEL_PLAIN
+                       : p.family == KernelFamily::OneWave ? CCV_MPPI_BATCH_KERNEL_ONE_WAVE
+                                                           : CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
+    return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0);
+}
 
 int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
                      const double* yaw_ref0, const uint64_t* seed) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    if (!x0 || !dt || !x_ref || !y_ref || !yaw_ref0 || !seed) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!x0 || !dt || !x_ref || !y_ref || !yaw_ref0 || !seed) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
     for (int b = 0; b < bh->B; ++b)
-        if (!(dt[b] == dt[b])) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "dt is NaN");
+        if (!(dt[b] == dt[b])) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "dt is NaN");
     return CCV_MPPI_OK;
 }
 
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, int trig, bool defer);
 
-// a deferred resident update (batch_launch) is launched now, as the plain k_finalize_batch of the fused partials
-int batch_flush(ccv_mppi_batch* bh) {
-    if (!bh->fin_pending) return CCV_MPPI_OK;
-    ccv_mppi_handle* h = &bh->h;
-    hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(h->R), bh->B), dim3(kBlock), 0, h->stream, bh->fin_args, 1);
-    bh->fin_pending = false;
-    HIP_TRY(h, hipGetLastError());
-    return CCV_MPPI_OK;
+// a deferred resident update (batch_launch) is launched now
+int batch_flush(ccv_mppi_batch* bh) { return flush_finalize(bh, bh->B); }
+
+// fast_trig_safe of instance b (its own clamp bounds), folded into the batch's: the worst instance decides
+int batch_trig(const ccv_mppi_batch* bh, const int b, const RolloutArgs& A, const int trig) {
+    const int t = fast_trig_safe(bh, batch_cfg(bh, b), A, MODE_FUSED, has_wide_form(*bh, MODE_FUSED));
+    return t == kTrigUnsafe || trig == kTrigUnsafe ? kTrigUnsafe : t == kTrigWide ? kTrigWide : trig;
 }
 
 // records -> device, rollout of all instances, per-instance update.  The kernel family is the single handle's rule applied to
@@ -37,16 +42,15 @@ int batch_flush(ccv_mppi_batch* bh) {
 // headings can leave the fast sin / cos's range, the wide-turn instantiation when one instance needs it.
 int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
                   const double* yaw_ref0, const uint64_t* seed, uint64_t iter) {
-    ccv_mppi_handle* h = &bh->h;
-    const int B = bh->B, H = h->H, nx = h->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+    const int B = bh->B, H = bh->H, nx = bh->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
     const int slot = bh->rec_next;
     bh->rec_next = (slot + 1) % ccv_mppi_batch::kRecSlots;
-    if (bh->rec_used[slot]) HIP_TRY(h, hipEventSynchronize(bh->rec_ev[slot]));
+    if (bh->rec_used[slot]) HIP_TRY(bh, hipEventSynchronize(bh->rec_ev[slot]));
     double* rec = bh->h_rec[slot];
     std::memset(rec, 0, (size_t)B * bh->rec_doubles * sizeof(double));
     RolloutArgs A;
-    fill_args(h, A, x0, dt[0], yaw_ref0[0], seed[0], iter);
-    int trig = h->coop ? kTrigSafe : kTrigUnsafe;
+    fill_args(bh, A, x0, dt[0], yaw_ref0[0], seed[0], iter);
+    int trig = bh->fused == KernelFamily::Plain ? kTrigUnsafe : kTrigSafe;
     for (int b = 0; b < B; ++b) {
         const double* xb = x0 + (size_t)5 * b;
         BatchHead* hd = reinterpret_cast<BatchHead*>(rec + (size_t)b * bh->rec_doubles);
@@ -56,21 +60,20 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
         hd->inv_dt = 1.0 / dt[b];
         hd->seed_lo = (uint32_t)seed[b];
         hd->seed_hi = (uint32_t)(seed[b] >> 32);
-        hd->K = b * bh->kpad + h->K;
+        hd->K = b * bh->kpad + bh->K;
         hd->k_offset = -b * bh->kpad;
-        hd->nominal = h->d_nominal + (size_t)b * h->R;
+        hd->nominal = bh->d_nominal + (size_t)b * bh->R;
         if (bh->varied) hd->params = bh->d_params + b;
         double* win = rec + (size_t)b * bh->rec_doubles + kBatchHeadDoubles;
         window_coeffs(H, x_ref + (size_t)b * H, y_ref + (size_t)b * H, hd->x0[0], hd->x0[1], win, win + H, win + 2 * H);
         if (trig != kTrigUnsafe) {
             for (int i = 0; i < 5; ++i) A.x0[i] = hd->x0[i];
             A.dt = dt[b];
-            const int t = fast_trig_safe(h, batch_cfg(bh, b), A, MODE_FUSED);   // (the instance's own bounds)
-            if (t == kTrigUnsafe || t == kTrigWide) trig = t;
+            trig = batch_trig(bh, b, A, trig);
         }
     }
-    HIP_TRY(h, hipMemcpyAsync(bh->d_rec, rec, (size_t)B * bh->rec_doubles * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipEventRecord(bh->rec_ev[slot], h->stream));
+    HIP_TRY(bh, hipMemcpyAsync(bh->d_rec, rec, (size_t)B * bh->rec_doubles * sizeof(double), hipMemcpyHostToDevice, bh->stream));
+    HIP_TRY(bh, hipEventRecord(bh->rec_ev[slot], bh->stream));
     bh->rec_used[slot] = true;
     return batch_launch(bh, A, trig, false);
 }
@@ -78,94 +81,76 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // the rollout of every instance from the records in d_rec, then the per-instance update; `defer` (resident ticks): the update
 // of the fused kernels waits in bh->fin_args for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
-    ccv_mppi_handle* h = &bh->h;
     const int B = bh->B;
-    const bool plain = trig == kTrigUnsafe;
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied);
+    const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
-    A.nparts = B * h->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
+    A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
     A.fuse_update = plain ? 0 : 1;
     A.store_u = 1;
-    A.store_xy = (h->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) ? 0 : 1;
+    A.store_xy = (bh->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) ? 0 : 1;
     A.do_cost = 1;
-    if (int rc = timing_begin(h)) return rc;
+    HIP_TRY(bh, timing_begin(*bh));
     static const Window kNoWindow{};   // (the windows are in the records)
     LaunchAt at;
-    if (int rc = timing_rollout_at(h, plain, at)) return rc;
-    // (varied: the same families with per-instance parameters, k_batch_varied.hip)
-    if (plain) {
-        if (bh->varied) launch_rollout_plain_batch_varied(h->cfg.model, B, at, A, kNoWindow);
-        else launch_rollout_plain_batch(h->cfg.model, B, at, A, kNoWindow);
-        if (int rc = timing_rollout_done(h, plain)) return rc;
-        bh->last_kernel = CCV_MPPI_BATCH_KERNEL_PLAIN;
-    } else if (h->solo) {
-        if (bh->varied) launch_rollout_solo_batch_varied(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
-        else launch_rollout_solo_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
-        bh->last_kernel = CCV_MPPI_BATCH_KERNEL_ONE_WAVE;
-    } else {
-        if (bh->varied) launch_rollout_r4_batch_varied(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
-        else launch_rollout_r4_batch(h->cfg.model, trig == kTrigWide, B, at, A, kNoWindow);
-        bh->last_kernel = CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
-    }
-    if (trig == kTrigWide) bh->last_kernel |= CCV_MPPI_BATCH_KERNEL_WIDE;
-    if (bh->varied) bh->last_kernel |= CCV_MPPI_BATCH_KERNEL_VARIED;
-    HIP_TRY(h, hipGetLastError());
-    int nparts = h->nblocks;
+    HIP_TRY(bh, timing_rollout_at(*bh, bh->stream, plain, at));
+    launch_rollout(plan, at, A, kNoWindow);
+    HIP_TRY(bh, timing_rollout_done(*bh, bh->stream, plain));
+    bh->last_kernel = batch_kernel_code(plan);
+    HIP_TRY(bh, hipGetLastError());
+    int nparts = bh->nblocks;
     if (plain) {   // the plain kernel stores w and the controls: the single handle's unfused reduction, instance by instance
-        hipLaunchKernelGGL(k_update_partials_batch, dim3(h->nchunks, h->R + 1, B), dim3(kBlock), 0, h->stream, update_args(h), bh->kpad);
-        nparts = h->nchunks;
+        hipLaunchKernelGGL(k_update_partials_batch, dim3(bh->nchunks, bh->R + 1, B), dim3(kBlock), 0, bh->stream, update_args(bh), bh->kpad);
+        nparts = bh->nchunks;
     }
-    FinalizeArgs F = finalize_args(h, h->d_vec, nparts, true);
+    FinalizeArgs F = finalize_args(bh, bh->d_vec, nparts, true);
     // The mailbox up to the largest one a single handle posts; beyond, one copy and a stream synchronisation are faster
     // (diff drive K = 1 000, H = 15, blocking us, mailbox vs copy, one box: B = 1 45 vs 51, B = 64 107 vs 66, B = 256 220 vs
     // 118; the mailbox_blocking_us / copy_blocking_us columns of profiles/batch_bench.json repeat the comparison)
-    const bool mail_fits = (size_t)B * (h->R + 4) <= (size_t)(CCV_MPPI_MAX_HORIZON - 1) * CCV_MPPI_MAX_UDIM + 4;
-    if (h->want_mail && h->use_mail && (mail_fits || bh->mail_any_size)) post_to_mail(h, F);
-    h->want_mail = false;
-    if (defer && !plain && !h->timed_now && !F.mail) {
+    const bool mail_fits = (size_t)B * (bh->R + 4) <= (size_t)(CCV_MPPI_MAX_HORIZON - 1) * CCV_MPPI_MAX_UDIM + 4;
+    if (bh->want_mail && bh->use_mail && (mail_fits || bh->mail_any_size)) post_to_mail(*bh, F);
+    bh->want_mail = false;
+    if (defer && !plain && !bh->timed_now && !F.mail) {
         bh->fin_args = F;
         bh->fin_pending = true;
     } else {
-        hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(h->R), B), dim3(kBlock), 0, h->stream, F, plain ? 0 : 1);
-        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(bh->R), B), dim3(kBlock), 0, bh->stream, F, plain ? 0 : 1);
+        HIP_TRY(bh, hipGetLastError());
     }
-    if (int rc = timing_end(h)) return rc;
-    if (int rc = throttle_tick(h)) return rc;
+    HIP_TRY(bh, timing_end(*bh, bh->stream));
+    HIP_TRY(bh, throttle_tick(*bh, bh->stream));
     bh->have_result = true;
     return CCV_MPPI_OK;
 }
 
 // u* [B][R] and the statistics of every instance: from the mailbox the update kernel posted into, or copied
 int batch_fetch(ccv_mppi_batch* bh, double* u_opt_out, ccv_mppi_stats* stats) {
-    ccv_mppi_handle* h = &bh->h;
-    const size_t B = (size_t)bh->B, R = (size_t)h->R;
-    double* v = h->h_pin;   // [B][R + 4]
-    if (h->mail_pending) {
-        h->mail_pending = false;
-        if (int rc = wait_mail(h, B * (R + 4))) return rc;
-        decode_mail(h, B * (R + 4), v);
+    const size_t B = (size_t)bh->B, R = (size_t)bh->R;
+    double* v = bh->h_pin;   // [B][R + 4]
+    if (bh->mail_pending) {
+        bh->mail_pending = false;
+        if (int rc = read_mail(bh, B * (R + 4), v)) return rc;
     } else {
         double* u = v + B * (R + 4);
         double* st = u + B * R;
-        HIP_TRY(h, hipMemcpyAsync(u, h->d_nominal, B * R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(st, h->d_stats, B * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(bh, hipMemcpyAsync(u, bh->d_nominal, B * R * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
+        HIP_TRY(bh, hipMemcpyAsync(st, bh->d_stats, B * 4 * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
+        HIP_TRY(bh, hipStreamSynchronize(bh->stream));
         for (size_t b = 0; b < B; ++b) {
             std::memcpy(v + b * (R + 4), u + b * R, R * sizeof(double));
             std::memcpy(v + b * (R + 4) + R, st + b * 4, 4 * sizeof(double));
         }
     }
-    if (stats && h->timing) {
-        if (int rc = timing_collect(h)) return rc;
-    }
+    if (stats && bh->timing) HIP_TRY(bh, timing_collect(*bh, bh->stream));
     for (size_t b = 0; b < B; ++b)
-        unpack_result(h, v + b * (R + 4), u_opt_out ? u_opt_out + b * R : nullptr, stats ? stats + b : nullptr);
+        unpack_result(*bh, bh->R, v + b * (R + 4), u_opt_out ? u_opt_out + b * R : nullptr, stats ? stats + b : nullptr);
     return CCV_MPPI_OK;
 }
 
 int batch_check_read(ccv_mppi_batch* bh, int32_t instance, const void* out) {
     if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
-    if (instance < 0 || instance >= bh->B) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
-    if (!bh->have_result) return batch_fail(bh, CCV_MPPI_ERR_STATE, "no iteration yet");
+    if (instance < 0 || instance >= bh->B) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
+    if (!bh->have_result) return fail(bh, CCV_MPPI_ERR_STATE, "no iteration yet");
     return batch_flush(bh);
 }
 }  // namespace
@@ -186,33 +171,32 @@ int ccv_mppi_batch_create(const ccv_mppi_config* cfg, int32_t batch, ccv_mppi_ba
     ccv_mppi_batch* bh = new (std::nothrow) ccv_mppi_batch();
     if (!bh) return CCV_MPPI_ERR_ALLOC;
     const DeviceGuard guard(cfg->device);
-    ccv_mppi_handle* h = &bh->h;
-    set_shape(h, *cfg, /*pitch=*/batch * kpad, /*workgroups per instance=*/kpad / kPcSamples);
+    set_shape(*bh, *cfg, /*pitch=*/batch * kpad, /*workgroups per instance=*/kpad / kPcSamples);
     bh->B = batch;
     bh->kpad = kpad;
-    bh->rec_doubles = batch_record_doubles(h->H);
+    bh->rec_doubles = batch_record_doubles(bh->H);
     // the single handle's selection on the batch's workgroups; CCV_MPPI_KERNEL=v1 selects the plain kernel, its other values
     // and CCV_MPPI_WINDOW / _PRIO / _PRUNE / _FAST_CLAMP are ignored here
-    select_kernels(h, (int64_t)batch * h->nblocks, /*batched=*/true);
+    select_kernels(*bh, *bh, (int64_t)batch * bh->nblocks, /*batched=*/true);
 
     auto bail = [&](int code) {
-        std::fprintf(stderr, "ccv_mppi_batch_create: %s\n", h->err.c_str());
+        std::fprintf(stderr, "ccv_mppi_batch_create: %s\n", bh->err.c_str());
         ccv_mppi_batch_destroy(bh);
         return code;
     };
     hipError_t e;
-    if ((e = hipSetDevice(cfg->device)) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_NO_DEVICE, "hipSetDevice", e));
-    const size_t B = (size_t)batch, R = (size_t)h->R;
-    const size_t nparts_max = B * (size_t)(h->nblocks > h->nchunks ? h->nblocks : h->nchunks);
+    if ((e = hipSetDevice(cfg->device)) != hipSuccess) return bail(fail(bh, CCV_MPPI_ERR_NO_DEVICE, "hipSetDevice", e));
+    const size_t B = (size_t)batch, R = (size_t)bh->R;
+    const size_t nparts_max = B * (size_t)(bh->nblocks > bh->nchunks ? bh->nblocks : bh->nchunks);
     const size_t pad = (size_t)(CCV_MPPI_MAX_HORIZON + 8) * CCV_MPPI_MAX_UDIM;   // (u* is read 4 at a time)
     // (pinned staging: the mailbox's values, or the two copies of the fall-back path)
-    if (int rc = create_buffers(h, BufferCounts{nparts_max, /*nominal=*/B * R + pad, /*vec=*/B * (R + 1), /*stats=*/B * 4, &bh->d_rec,
+    if (int rc = create_buffers(bh, BufferCounts{nparts_max, /*nominal=*/B * R + pad, /*vec=*/B * (R + 1), /*stats=*/B * 4, &bh->d_rec,
                                                 B * bh->rec_doubles, /*pin_doubles=*/B * (R + 4) * 2, /*mail_slots=*/B * (R + 4)}))
         return bail(rc);
     for (int s = 0; s < ccv_mppi_batch::kRecSlots; ++s) {
-        if ((e = hipEventCreateWithFlags(&bh->rec_ev[s], hipEventDisableTiming)) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_HIP, "hipEventCreate", e));
+        if ((e = hipEventCreateWithFlags(&bh->rec_ev[s], hipEventDisableTiming)) != hipSuccess) return bail(fail(bh, CCV_MPPI_ERR_HIP, "hipEventCreate", e));
         if ((e = hipHostMalloc(&bh->h_rec[s], B * bh->rec_doubles * sizeof(double), hipHostMallocDefault)) != hipSuccess)
-            return bail(fail(h, CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e));
+            return bail(fail(bh, CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e));
     }
     if (const char* mv = std::getenv("CCV_MPPI_BATCH_MAIL")) bh->mail_any_size = std::strcmp(mv, "1") == 0;
     *out = bh;
@@ -221,11 +205,10 @@ int ccv_mppi_batch_create(const ccv_mppi_config* cfg, int32_t batch, ccv_mppi_ba
 
 int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
-    const DeviceGuard guard(h->cfg.device);
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)batch_flush(bh);
-    release_buffers(h);
+    const DeviceGuard guard(bh->cfg.device);
+    (void)hipSetDevice(bh->cfg.device);
+    if (bh->stream) (void)batch_flush(bh);
+    release_buffers(bh);
     for (int s = 0; s < ccv_mppi_batch::kRecSlots; ++s) {
         if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
@@ -237,7 +220,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     return CCV_MPPI_OK;
 }
 
-const char* ccv_mppi_batch_last_error(const ccv_mppi_batch* bh) { return bh ? bh->h.err.c_str() : "null handle"; }
+const char* ccv_mppi_batch_last_error(const ccv_mppi_batch* bh) { return bh ? bh->err.c_str() : "null handle"; }
 
 int ccv_mppi_batch_size(const ccv_mppi_batch* bh) { return bh ? bh->B : CCV_MPPI_ERR_INVALID_ARG; }
 
@@ -246,38 +229,30 @@ int ccv_mppi_batch_last_kernel(const ccv_mppi_batch* bh) { return bh ? bh->last_
 int ccv_mppi_batch_set_stream(ccv_mppi_batch* bh, void* hip_stream) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     if (int rc = batch_flush(bh)) return rc;
-    return set_stream(&bh->h, hip_stream);
+    return set_stream(bh, hip_stream);
 }
 
 int ccv_mppi_batch_synchronize(ccv_mppi_batch* bh) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(&bh->h, hipStreamSynchronize(bh->h.stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_set_nominal(ccv_mppi_batch* bh, const double* u) {
     if (!bh || !u) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
     if (int rc = batch_flush(bh)) return rc;   // (a deferred resident update must not land on top of it)
-    HIP_TRY(h, hipMemcpyAsync(h->d_nominal, u, (size_t)bh->B * h->R * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    // (the resident plant integrates u*[b][0]: its angle bounds must cover what the caller put there; NaN sticks)
-    for (int d = 0; d < CCV_MPPI_MAX_UDIM; ++d) h->nom_absmax[d] = 0.0;
-    for (size_t n = 0; n < (size_t)bh->B * h->R; ++n) {
-        const int d = (int)(n % (size_t)h->udim);
-        const double a = std::fabs(u[n]), m = h->nom_absmax[d];
-        if (a != a || (m == m && a > m)) h->nom_absmax[d] = a;
-    }
+    HIP_TRY(bh, hipMemcpyAsync(bh->d_nominal, u, (size_t)bh->B * bh->R * sizeof(double), hipMemcpyHostToDevice, bh->stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+    track_absmax(u, (size_t)bh->B * bh->R, bh->udim, bh->nom_absmax);
     return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
     if (!bh || !u) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(h, hipMemcpyAsync(u, h->d_nominal, (size_t)bh->B * h->R * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(bh, hipMemcpyAsync(u, bh->d_nominal, (size_t)bh->B * bh->R * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     return CCV_MPPI_OK;
 }
 
@@ -285,7 +260,6 @@ int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
 
 int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
     const int B = bh->B;
     if (!cfgs) {   // back to the creation configuration and the shared kernels
         if (int rc = batch_flush(bh)) return rc;
@@ -295,7 +269,7 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     }
     // the fields that fix the layout, the kernel family and the compile-time shape stay the creation configuration's; every
     // check comes before anything changes
-    const ccv_mppi_config& c0 = h->cfg;
+    const ccv_mppi_config& c0 = bh->cfg;
     for (int b = 0; b < B; ++b) {
         const ccv_mppi_config& c = cfgs[b];
         const char* field = c.abi_version != c0.abi_version       ? "abi_version"
@@ -309,14 +283,14 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
         if (field) {
             char msg[128];
             std::snprintf(msg, sizeof(msg), "set_params: instance %d: %s differs from the creation configuration", b, field);
-            return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, msg);
+            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, msg);
         }
     }
     std::vector<BatchParams> rows((size_t)B);
     for (int b = 0; b < B; ++b) {
         RolloutArgs A;
         std::memset(&A, 0, sizeof(A));
-        fill_params(cfgs[b], h->fast_clamp_allowed, A);   // (per instance: the clamp form of its own sigma and bounds)
+        fill_params(cfgs[b], bh->fast_clamp_allowed, A);   // (per instance: the clamp form of its own sigma and bounds)
         BatchParams& P = rows[(size_t)b];
         std::memset(&P, 0, sizeof(P));
         P.sigma = A.sigma;
@@ -335,9 +309,9 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
         P.fast_clamp = A.fast_clamp;
     }
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a queued rollout or prologue may still read the old table)
-    if (!bh->d_params) HIP_TRY(h, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
-    HIP_TRY(h, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the old table)
+    if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
+    HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
     bh->cfgs.assign(cfgs, cfgs + B);
     bh->varied = true;
     return CCV_MPPI_OK;
@@ -354,9 +328,9 @@ int ccv_mppi_batch_iterate(ccv_mppi_batch* bh, const double* x0, const double* d
     int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
     if (rc) return rc;
     if ((rc = batch_flush(bh))) return rc;   // (the rollout reads u*)
-    bh->h.want_mail = !(stats && bh->h.timing);   // (a timed call synchronises for its events anyway)
+    bh->want_mail = !(stats && bh->timing);   // (a timed call synchronises for its events anyway)
     rc = batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
-    bh->h.want_mail = false;
+    bh->want_mail = false;
     if (rc) return rc;
     return batch_fetch(bh, u_opt_out, stats);
 }
@@ -371,52 +345,41 @@ int ccv_mppi_batch_iterate_enqueue(ccv_mppi_batch* bh, const double* x0, const d
 
 int ccv_mppi_batch_read_costs(ccv_mppi_batch* bh, int32_t instance, int32_t first, int32_t count, double* out) {
     if (int rc = batch_check_read(bh, instance, out)) return rc;
-    ccv_mppi_handle* h = &bh->h;
-    if (first < 0 || count < 0 || (int64_t)first + count > h->K) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
+    if (first < 0 || count < 0 || (int64_t)first + count > bh->K) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
     const size_t col = (size_t)instance * bh->kpad + first;
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_cost + col, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(bh, hipMemcpyAsync(out, bh->d_cost + col, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_read_weights(ccv_mppi_batch* bh, int32_t instance, int32_t first, int32_t count, double* out) {
     if (int rc = batch_check_read(bh, instance, out)) return rc;
-    ccv_mppi_handle* h = &bh->h;
-    if (first < 0 || count < 0 || (int64_t)first + count > h->K) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
+    if (first < 0 || count < 0 || (int64_t)first + count > bh->K) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
     if (count == 0) return CCV_MPPI_OK;
-    if (int rc = ensure_scratch(h, (size_t)count * sizeof(double))) return rc;
-    hipLaunchKernelGGL(k_normalise_weights, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream,
-                       h->d_w + (size_t)instance * bh->kpad, h->d_stats + (size_t)instance * 4, first, count, h->d_scratch);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_scratch, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(bh, ensure_scratch(*bh, (size_t)count * sizeof(double)));
+    hipLaunchKernelGGL(k_normalise_weights, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, bh->stream,
+                       bh->d_w + (size_t)instance * bh->kpad, bh->d_stats + (size_t)instance * 4, first, count, bh->d_scratch);
+    HIP_TRY(bh, hipGetLastError());
+    HIP_TRY(bh, hipMemcpyAsync(out, bh->d_scratch, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_read_candidates(ccv_mppi_batch* bh, int32_t instance, int32_t first, int32_t count, int32_t stride,
                                    double* xy_out) {
     if (int rc = batch_check_read(bh, instance, xy_out)) return rc;
-    ccv_mppi_handle* h = &bh->h;
-    if (first < 0 || count < 0 || stride < 1) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "first < 0, count < 0 or stride < 1");
-    if (h->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) return batch_fail(bh, CCV_MPPI_ERR_STATE, "state buffer disabled (NO_STATE_STORE)");
+    if (first < 0 || count < 0 || stride < 1) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "first < 0, count < 0 or stride < 1");
+    if (bh->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) return fail(bh, CCV_MPPI_ERR_STATE, "state buffer disabled (NO_STATE_STORE)");
     if (count == 0) return CCV_MPPI_OK;
-    if ((int64_t)first + (int64_t)(count - 1) * stride >= h->K) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "candidate range exceeds num_samples");
-    const size_t n = (size_t)count * h->H * 2;
-    if (int rc = ensure_scratch(h, n * sizeof(double))) return rc;
-    hipLaunchKernelGGL(k_gather_xy, dim3((count * h->H + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->d_xs, h->d_ys,
-                       h->pitch, h->H, instance * bh->kpad + first, count, stride, h->d_scratch);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(xy_out, h->d_scratch, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if ((int64_t)first + (int64_t)(count - 1) * stride >= bh->K) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "candidate range exceeds num_samples");
+    const size_t n = (size_t)count * bh->H * 2;
+    HIP_TRY(bh, ensure_scratch(*bh, n * sizeof(double)));
+    hipLaunchKernelGGL(k_gather_xy, dim3((count * bh->H + kBlock - 1) / kBlock), dim3(kBlock), 0, bh->stream, bh->d_xs, bh->d_ys,
+                       bh->pitch, bh->H, instance * bh->kpad + first, count, stride, bh->d_scratch);
+    HIP_TRY(bh, hipGetLastError());
+    HIP_TRY(bh, hipMemcpyAsync(xy_out, bh->d_scratch, n * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     return CCV_MPPI_OK;
-}
-
-int ccv_mppi_batch_timing_enable(ccv_mppi_batch* bh, int32_t on) {
-    return bh ? ccv_mppi_timing_enable(&bh->h, on) : CCV_MPPI_ERR_INVALID_ARG;
-}
-
-int ccv_mppi_batch_timing_read(ccv_mppi_batch* bh, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset) {
-    return bh ? ccv_mppi_timing_read(&bh->h, rollout_us_sum, iter_us_sum, n_iters, reset) : CCV_MPPI_ERR_INVALID_ARG;
 }
 
 // ---- batch handles: device-resident closed loop of every instance (mppi_resident.h) ---------------------------------
@@ -424,14 +387,13 @@ int ccv_mppi_batch_timing_read(ccv_mppi_batch* bh, double* rollout_us_sum, doubl
 int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* bh, const double* path_x, const double* path_y, const int32_t* n_path,
                                       const double* resolution) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
-    if (!path_x || !path_y || !n_path || !resolution) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!path_x || !path_y || !n_path || !resolution) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
     const int B = bh->B;
     std::vector<BatchInstance> inst((size_t)B);
     int64_t total = 0;
     for (int b = 0; b < B; ++b) {
         if (n_path[b] < 1 || !(resolution[b] > 0.0))
-            return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "paths: an empty path or a resolution <= 0");
+            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "paths: an empty path or a resolution <= 0");
         inst[b] = BatchInstance{};
         inst[b].path_off = total;
         inst[b].n_path = n_path[b];
@@ -443,25 +405,25 @@ int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* bh, const double* path_x, 
         total += n_path[b];
     }
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a queued prologue may still read the old paths)
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued prologue may still read the old paths)
     if (total > bh->n_total || !bh->d_rpath) {
-        if (bh->d_rpath) HIP_TRY(h, hipFree(bh->d_rpath));
+        if (bh->d_rpath) HIP_TRY(bh, hipFree(bh->d_rpath));
         bh->d_rpath = nullptr;
         bh->have_paths = false;
-        HIP_TRY(h, hipMalloc(&bh->d_rpath, (size_t)2 * total * sizeof(double)));
+        HIP_TRY(bh, hipMalloc(&bh->d_rpath, (size_t)2 * total * sizeof(double)));
     }
     bh->n_total = total;   // (the y half starts at n_total; a shorter set reuses the array, a longer one reallocates it)
-    HIP_TRY(h, hipMemcpy(bh->d_rpath, path_x, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(bh->d_rpath + total, path_y, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipMemcpy(bh->d_rpath, path_x, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipMemcpy(bh->d_rpath + total, path_y, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
     if (!bh->d_rframe) {
         const size_t trace_bytes = (size_t)B * CCV_MPPI_BATCH_TRACE_ROWS * 6 * sizeof(double);
-        HIP_TRY(h, hipMalloc(&bh->d_rframe, (size_t)B * sizeof(ResidentFrame)));
-        HIP_TRY(h, hipMemset(bh->d_rframe, 0, (size_t)B * sizeof(ResidentFrame)));
-        HIP_TRY(h, hipMalloc(&bh->d_inst, (size_t)B * sizeof(BatchInstance)));
-        HIP_TRY(h, hipMalloc(&bh->d_rtrace, trace_bytes));
-        HIP_TRY(h, hipMemset(bh->d_rtrace, 0, trace_bytes));
+        HIP_TRY(bh, hipMalloc(&bh->d_rframe, (size_t)B * sizeof(ResidentFrame)));
+        HIP_TRY(bh, hipMemset(bh->d_rframe, 0, (size_t)B * sizeof(ResidentFrame)));
+        HIP_TRY(bh, hipMalloc(&bh->d_inst, (size_t)B * sizeof(BatchInstance)));
+        HIP_TRY(bh, hipMalloc(&bh->d_rtrace, trace_bytes));
+        HIP_TRY(bh, hipMemset(bh->d_rtrace, 0, trace_bytes));
     }
-    HIP_TRY(h, hipMemcpy(bh->d_inst, inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipMemcpy(bh->d_inst, inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
     bh->inst.swap(inst);
     bh->have_paths = true;
     return CCV_MPPI_OK;
@@ -469,10 +431,9 @@ int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* bh, const double* path_x, 
 
 int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, const uint64_t* seed) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
-    if (!state || !seed) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-    if (!bh->have_paths) return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths first");
-    const int B = bh->B, nx = h->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+    if (!state || !seed) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->have_paths) return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths first");
+    const int B = bh->B, nx = bh->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
     std::vector<FrameHead> heads((size_t)B);   // (as ccv_mppi_resident_set_pose)
     std::vector<double> angles((size_t)B * 3);
     for (int b = 0; b < B; ++b) {
@@ -483,10 +444,10 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
         bh->inst[b].seed_hi = (uint32_t)(seed[b] >> 32);
     }
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy2D(bh->d_rframe, sizeof(ResidentFrame), heads.data(), sizeof(FrameHead), sizeof(FrameHead), (size_t)B,
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+    HIP_TRY(bh, hipMemcpy2D(bh->d_rframe, sizeof(ResidentFrame), heads.data(), sizeof(FrameHead), sizeof(FrameHead), (size_t)B,
                            hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
     bh->res_angle_abs.swap(angles);
     bh->res_steps = 0;
     bh->have_poses = true;
@@ -495,49 +456,46 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
 
 int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t iter, int32_t advance) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
-    const ccv_mppi_config& c = h->cfg;
+    const ccv_mppi_config& c = bh->cfg;
     const int B = bh->B;
     // every check that can refuse the step comes before anything is launched: no pose moves on a refusal
-    if (!(dt >= 0.0) || !std::isfinite(dt)) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: dt must be finite and not negative");
+    if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: dt must be finite and not negative");
     if (!bh->have_paths || !bh->have_poses)
-        return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
+        return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
     for (int b = 0; b < B; ++b) {
         const double stride = batch_cfg(bh, b).v_ref * dt / bh->inst[b].resolution;   // (the instance's own v_ref)
-        if (!std::isfinite(stride) || stride < 0.0 || stride * h->H > 2.0e9)
-            return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: v_ref * dt / resolution is not a usable window stride");
+        if (!std::isfinite(stride) || stride < 0.0 || stride * bh->H > 2.0e9)
+            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "resident step: v_ref * dt / resolution is not a usable window stride");
     }
     // the angle bounds of a single handle's resident step (resident_bounds), instance by instance and with the instance's own
     // clamp bounds; the batch's kernel rule (select_kernels) with no plain kernel: the wide-turn instantiation when one
     // instance needs it, a refusal where the plain kernel would be needed
     std::vector<double> nb(bh->res_angle_abs);
-    int trig = h->coop ? kTrigSafe : kTrigUnsafe;
+    int trig = bh->fused == KernelFamily::Plain ? kTrigUnsafe : kTrigSafe;
     RolloutArgs A;
     const double zero[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    fill_args(h, A, zero, dt, 0.0, 0, iter);   // (the instance's pose, window and key: its record, batch_view)
+    fill_args(bh, A, zero, dt, 0.0, 0, iter);   // (the instance's pose, window and key: its record, batch_view)
     for (int b = 0; b < B && trig != kTrigUnsafe; ++b) {
-        const ResidentBounds r = resident_bounds(h, batch_cfg(bh, b), bh->res_angle_abs.data() + (size_t)b * 3, dt, advance);
+        const ResidentBounds r = resident_bounds(*bh, batch_cfg(bh, b), bh->res_angle_abs.data() + (size_t)b * 3, dt, advance);
         for (int i = 0; i < 3; ++i) A.x0[2 + i] = nb[(size_t)b * 3 + i] = r.angle[i];
-        const int t = fast_trig_safe(h, batch_cfg(bh, b), A, MODE_FUSED);
-        if (t == kTrigUnsafe || !(r.heading <= kFastTrigLimit)) trig = kTrigUnsafe;
-        else if (t == kTrigWide) trig = kTrigWide;
+        trig = r.heading <= kFastTrigLimit ? batch_trig(bh, b, A, trig) : kTrigUnsafe;
     }
     if (trig == kTrigUnsafe)
-        return batch_fail(bh, CCV_MPPI_ERR_STATE, "the resident loop needs the cooperative kernels and bounded pose angles / commands");
+        return fail(bh, CCV_MPPI_ERR_STATE, "the resident loop needs the cooperative kernels and bounded pose angles / commands");
     BatchAdvanceArgs G;
     G.frames = bh->d_rframe;
     G.rec = bh->d_rec;
     G.inst = bh->d_inst;
     G.path = bh->d_rpath;
-    G.nominal = h->d_nominal;
+    G.nominal = bh->d_nominal;
     G.trace = bh->d_rtrace;
     G.n_total = bh->n_total;
     G.dt = dt;
     G.inv_dt = 1.0 / dt;
     G.v_ref = c.v_ref;
-    G.H = h->H;
-    G.R = h->R;
-    G.K = h->K;
+    G.H = bh->H;
+    G.R = bh->R;
+    G.K = bh->K;
     G.kpad = bh->kpad;
     G.model = c.model;
     G.advance = advance ? 1 : 0;
@@ -545,14 +503,14 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     // (varied: the prologue takes each instance's v_ref from the parameter table and points its record's head at its row)
     if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
         const dim3 grid(finalize_blocks(bh->fin_args.R) + 1, B);
-        if (bh->varied) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, h->stream, bh->fin_args, G, bh->d_params);
-        else hipLaunchKernelGGL(k_finalize_advance_batch, grid, dim3(kBlock), 0, h->stream, bh->fin_args, G);
+        if (bh->varied) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G, bh->d_params);
+        else hipLaunchKernelGGL(k_finalize_advance_batch, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G);
         bh->fin_pending = false;
     } else {
-        if (bh->varied) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, h->stream, G, bh->d_params);
-        else hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, h->stream, G);
+        if (bh->varied) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);
+        else hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G);
     }
-    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(bh, hipGetLastError());
     bh->res_steps += 1;
     bh->res_angle_abs.swap(nb);
     // the rollout reads every instance's record (batch_view): pose, window, dt, noise key, warm start
@@ -563,14 +521,13 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
 int ccv_mppi_batch_resident_read(ccv_mppi_batch* bh, double* state, int32_t* current_index, double* x_ref, double* y_ref,
                                  double* yaw_ref0, int64_t* steps) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
     if (!bh->have_paths || !bh->have_poses)
-        return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
-    const int B = bh->B, H = h->H, nx = h->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
+        return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
+    const int B = bh->B, H = bh->H, nx = bh->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
     std::vector<ResidentFrame> F((size_t)B);
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(F.data(), bh->d_rframe, (size_t)B * sizeof(ResidentFrame), hipMemcpyDeviceToHost));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+    HIP_TRY(bh, hipMemcpy(F.data(), bh->d_rframe, (size_t)B * sizeof(ResidentFrame), hipMemcpyDeviceToHost));
     for (int b = 0; b < B; ++b) {
         if (state) {
             for (int i = 0; i < 5; ++i) state[(size_t)b * 5 + i] = i < nx ? F[b].x0[i] : 0.0;
@@ -586,15 +543,15 @@ int ccv_mppi_batch_resident_read(ccv_mppi_batch* bh, double* state, int32_t* cur
 
 int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* bh, int32_t instance, int32_t max_rows, double* rows, int32_t* n_rows) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    ccv_mppi_handle* h = &bh->h;
-    if (!rows || !n_rows || max_rows < 0) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "rows / n_rows null or max_rows < 0");
-    if (instance < 0 || instance >= bh->B) return batch_fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
+    if (!rows || !n_rows || max_rows < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "rows / n_rows null or max_rows < 0");
+    if (instance < 0 || instance >= bh->B) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
     if (!bh->have_paths || !bh->have_poses)
-        return batch_fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
+        return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_paths and _set_poses first");
     if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     const int64_t cap = CCV_MPPI_BATCH_TRACE_ROWS;
-    return read_trace_ring(h, bh->d_rtrace + (size_t)instance * cap * 6, cap, bh->res_steps, max_rows, rows, n_rows);
+    HIP_TRY(bh, read_trace_ring(bh->d_rtrace + (size_t)instance * cap * 6, cap, bh->res_steps, max_rows, rows, n_rows));
+    return CCV_MPPI_OK;
 }
 
 }  // extern "C"

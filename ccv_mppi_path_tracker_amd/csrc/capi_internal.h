@@ -1,9 +1,11 @@
 // Internal to the host side of the C ABI (include/ccv_mppi.h): the two handle types and the plumbing their units share.
-//   ccv_mppi_capi.hip    life cycle, kernel selection, the fused iteration and its update, result fetch
+//   ccv_mppi_capi.hip    life cycle, kernel-family rule and launch plan, the fused iteration and its update, result fetch
 //   capi_exchange.hip    direct exchange of the partial vectors between the devices of a node
 //   capi_resident.hip    device-resident closed loop of a single handle
 //   capi_stage.hip       stage-wise calls, read-back, timing
 //   capi_batch.hip       batch handles (ccv_mppi_batch_*), their resident loop included
+// A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
+// take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,21 +26,29 @@
 #include "mppi_update.h"
 #include "mppi_resident.h"
 
-using namespace ccv;
+namespace ccv {
 
-struct ccv_mppi_handle {
+// K, H, R of one problem; pitch: the columns of the sample axis; nblocks: the workgroups of one problem's K
+struct Shape {
     ccv_mppi_config cfg{};
     int udim = 0, K = 0, H = 0, R = 0, pitch = 0, nchunks = 0, nblocks = 0;
-    int nparts_last = 0;   // number of partial columns the last cost evaluation produced (fused: workgroups, else: chunks)
+    int cu_count = 256;   // the device's CUs (set_shape): the kernel-family thresholds hang on it
+};
+
+// What select_kernels() decides at create; nothing assigns the families afterwards.  A launch's kernel: make_plan().
+struct KernelChoice {
+    KernelFamily stagewise = KernelFamily::FourWave;   // family of MODE_ROLLOUT / MODE_COST launches
+    KernelFamily fused = KernelFamily::FourWave;       // family of the fused iteration: the same, or OneWave
+    int lds_window = 1;                // CCV_MPPI_WINDOW=scalar -> 0: the plain kernel's scalar-load window variant (experiments)
+    bool fast_clamp_allowed = true;    // clampd_fast (mppi_kernels.h) unless CCV_MPPI_FAST_CLAMP=0
+    int prio_rotate = 0;               // pc_rotate_priority (mppi_rollout_pc.h)
+    int prune = 0;                     // pc_prune_window (mppi_rollout_pc.h)
+};
+
+struct DeviceBuffers {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    // device buffers
     double* d_nominal = nullptr;
-    const double* pending_vec = nullptr;   // deferred apply_partials: u* = pending_vec[1..] / pending_vec[0] (see flush_pending)
-    // device-resident loop: the update of a tick is launched together with the next tick's prologue (k_finalize_advance);
-    // anything else that needs u* / the statistics first gets a plain k_finalize (flush_pending)
-    bool fin_pending = false;
-    FinalizeArgs fin_args{};
     double* d_u = nullptr;
     void* d_arena = nullptr;           // one allocation behind u, z, xs, ys, cost, w, partial (2 MB-aligned pieces)
     float* d_z = nullptr;              // the fused iteration stores the normals in place of the controls (mppi_kernels.h)
@@ -52,9 +62,72 @@ struct ccv_mppi_handle {
     double* d_statpart = nullptr;
     double* d_vec = nullptr;
     double* d_stats = nullptr;
-    double* d_cmin = nullptr;
     unsigned long long* d_dbg = nullptr;   // -DCCV_DIAG builds only (mppi_diag.h): the kernels' stamp buffer
-    // device-resident closed loop (mppi_resident.h)
+    double* d_scratch = nullptr;           // read-back staging (ensure_scratch)
+    size_t scratch_bytes = 0;
+    int nparts_last = 0;   // number of partial columns the last cost evaluation produced (fused: workgroups, else: chunks)
+    double inj_absmax[CCV_MPPI_MAX_UDIM] = {0, 0, 0, 0, 0};   // largest |control| per dimension in the buffer (sampled: clamp bound)
+    double nom_absmax[CCV_MPPI_MAX_UDIM] = {0, 0, 0, 0, 0};   // largest |u*| per dimension a caller has put there (track_absmax)
+};
+
+// result mailbox of the blocking calls (FinalizeArgs::mail): pinned host-mapped memory the update kernel writes; and the pinned
+// host staging the result is decoded or copied into
+struct Mailbox {
+    double* h_pin = nullptr;
+    size_t pin_doubles = 0;
+    unsigned long long* h_mail = nullptr;
+    unsigned long long* d_mail = nullptr;   // its device address
+    uint32_t mail_seq = 0;
+    bool want_mail = false;      // the next plain update launch posts its result (set by the blocking entry points)
+    bool mail_pending = false;   // ... and that launch is in flight: read_mail() polls the mailbox
+    bool use_mail = true;        // CCV_MPPI_MAILBOX=0: copy + stream synchronisation instead (experiments)
+};
+
+// queue-depth throttle for the asynchronous entry points: beyond a few dozen iterations in flight the HIP runtime's
+// enqueue path slows down several-fold (measured: 12 us/call at depth <= 64, 90 us/call at depth 512), so every
+// kThrottleEvery-th enqueue records an event and waits for the one recorded kThrottleSlots marks earlier
+struct Throttle {
+    static constexpr int kThrottleEvery = 16, kThrottleSlots = 3;
+    hipEvent_t throttle_ev[kThrottleSlots] = {nullptr, nullptr, nullptr};
+    bool throttle_used[kThrottleSlots] = {false, false, false};
+    uint64_t enqueued = 0;
+    bool throttle = true;   // CCV_MPPI_THROTTLE=0 disables (experiments)
+};
+
+struct Timing {
+    bool timing = false;
+    int timing_every = 1;     // record events on every n-th iteration only
+    int64_t timing_count = 0;
+    std::vector<hipEvent_t> ev;  // triples: rollout kernel begin, rollout kernel end, end of the launch sequence
+    bool timed_now = false;      // the launch being enqueued is timed (timing_begin .. timing_end): its triple is
+    size_t ev_slot = 0;          // ev[ev_slot .. ev_slot + 2]
+    size_t ev_used = 0;
+    double t_roll_sum = 0.0, t_iter_sum = 0.0;
+    int64_t t_n = 0;
+    float last_iter_us = 0.f, last_roll_us = 0.f;
+};
+
+// device-resident loops: the update of a tick is launched together with the next tick's prologue (k_finalize_advance[_batch]);
+// anything else that needs u*, the statistics or the stream first gets a plain k_finalize[_batch] (flush_finalize)
+struct DeferredUpdate {
+    bool fin_pending = false;
+    FinalizeArgs fin_args{};
+};
+
+struct Core : Shape, KernelChoice, DeviceBuffers, Mailbox, Throttle, Timing, DeferredUpdate {
+    std::string err;
+};
+
+// ---- a single handle only ------------------------------------------------------------------------------------------------
+struct StageState {
+    bool have_controls = false, have_rollout = false, have_weights = false;
+    double st_x0[5] = {0, 0, 0, 0, 0};
+    double st_dt = 0.1;
+    double* d_cmin = nullptr;   // CCV_MPPI_FLAG_MIN_SHIFT: the global minimum cost
+};
+
+// device-resident closed loop (mppi_resident.h)
+struct ResidentLoop {
     ResidentFrame* d_frame = nullptr;
     double* d_path = nullptr;    // [2][n_path]: x then y
     double* d_trace = nullptr;   // [kTraceRows][6]
@@ -64,7 +137,10 @@ struct ccv_mppi_handle {
     bool have_pose = false;
     int64_t res_steps = 0;                 // k_advance launches since the pose was set
     double res_angle_abs[3] = {0, 0, 0};   // conservative bounds on |yaw|, |roll|, |pitch| of the resident pose (fast_trig_safe)
-    // direct exchange of the partial vectors between the devices of a node (k_finalize_exchange, mppi_kernels.h)
+};
+
+// direct exchange of the partial vectors between the devices of a node (k_finalize_exchange, mppi_kernels.h)
+struct Exchange {
     ExchangeBox* d_box = nullptr;                   // this device's box (peers write into it)
     ExchangeBox* box_peer[kMaxRanks] = {nullptr};   // every rank's box as mapped here ([xchg_rank] = d_box)
     bool box_opened[kMaxRanks] = {false};           // mapped with hipIpcOpenMemHandle (to be closed)
@@ -79,61 +155,23 @@ struct ccv_mppi_handle {
     uint32_t xchg_base = 0;                         // sequence numbers start here: a restarted job does not match old packets
     unsigned long long xchg_seq = 0;
     unsigned long long xchg_timeout_ticks = 1000000000ull;   // 10 s of the 100 MHz clock (CCV_MPPI_EXCHANGE_TIMEOUT_MS: tests)
-    // queue-depth throttle for the asynchronous entry points: beyond a few dozen iterations in flight the HIP runtime's
-    // enqueue path slows down several-fold (measured: 12 us/call at depth <= 64, 90 us/call at depth 512), so every
-    // kThrottleEvery-th enqueue records an event and waits for the one recorded kThrottleSlots marks earlier
-    static constexpr int kThrottleEvery = 16, kThrottleSlots = 3;
-    hipEvent_t throttle_ev[kThrottleSlots] = {nullptr, nullptr, nullptr};
-    bool throttle_used[kThrottleSlots] = {false, false, false};
-    uint64_t enqueued = 0;
-    bool throttle = true;   // CCV_MPPI_THROTTLE=0 disables (experiments)
-    double* d_scratch = nullptr;  // read-back staging
-    size_t scratch_bytes = 0;
-    // pinned host staging
-    double* h_pin = nullptr;
-    size_t pin_doubles = 0;
-    // result mailbox of the blocking calls (FinalizeArgs::mail): pinned host-mapped memory the update kernel writes
-    unsigned long long* h_mail = nullptr;
-    unsigned long long* d_mail = nullptr;   // its device address
-    uint32_t mail_seq = 0;
-    bool want_mail = false;      // the next plain k_finalize launch posts its result (set by the blocking entry points)
-    bool mail_pending = false;   // ... and that launch is in flight: fetch_result() polls the mailbox
-    bool use_mail = true;        // CCV_MPPI_MAILBOX=0: copy + stream synchronisation instead (experiments)
-    // stage-wise state
-    bool have_controls = false, have_rollout = false, have_weights = false;
-    double st_x0[5] = {0, 0, 0, 0, 0};
-    double st_dt = 0.1;
-    // kernel selection (experiments): CCV_MPPI_KERNEL=v1 -> one-sample-per-lane k_rollout_cost,
-    // CCV_MPPI_WINDOW=scalar -> its scalar-load window variant; default = k_rollout_pc
-    int lds_window = 1;
-    int coop = 1;
-    bool solo = false;   // fused iterations run k_rollout_solo (one wave per 64 samples) instead of coop's kernel
-    bool wide_turn = false;   // this launch: diff drive beyond |w|max dt = pi/4 -> the full-range sin / cos instantiation
-    bool fast_clamp_allowed = true;   // clampd_fast (mppi_kernels.h) unless CCV_MPPI_FAST_CLAMP=0
-    int prio_rotate = 0, cu_count = 256;   // pc_rotate_priority (mppi_rollout_pc.h)
-    int prune = 0;                         // pc_prune_window (mppi_rollout_pc.h)
-    double inj_absmax[CCV_MPPI_MAX_UDIM] = {0, 0, 0, 0, 0};   // largest |control| per dimension in the buffer (sampled: clamp bound)
-    double nom_absmax[CCV_MPPI_MAX_UDIM] = {0, 0, 0, 0, 0};   // largest |u*| per dimension a caller has put there (ccv_mppi_set_nominal)
-    // timing
-    bool timing = false;
-    int timing_every = 1;     // record events on every n-th iteration only
-    int64_t timing_count = 0;
-    std::vector<hipEvent_t> ev;  // triples: rollout kernel begin, rollout kernel end, end of the launch sequence
-    bool timed_now = false;      // the launch being enqueued is timed (timing_begin .. timing_end): its triple is
-    size_t ev_slot = 0;          // ev[ev_slot .. ev_slot + 2]
-    size_t ev_used = 0;
-    double t_roll_sum = 0.0, t_iter_sum = 0.0;
-    int64_t t_n = 0;
-    float last_iter_us = 0.f, last_roll_us = 0.f;
-    std::string err;
+};
+
+}  // namespace ccv
+
+using namespace ccv;
+
+struct ccv_mppi_handle : Core, StageState, ResidentLoop, Exchange {
+    // deferred division: u* = pending_vec[1..] / pending_vec[0] (ccv_mppi_apply_partials_enqueue, the exchange); the next fused
+    // rollout divides while it stages the warm start, any other reader gets k_apply_partials first (flush_division)
+    const double* pending_vec = nullptr;
 };
 
 // One configuration, B instances on one sample axis of B * Kpad columns (Kpad = K rounded up to 64; mppi_kernels.h,
-// batch_view): the buffers, the stream, the mailbox and the timing of a ccv_mppi_handle whose K is the instance's and whose
+// batch_view): the core of a single handle, whose K is the instance's and whose
 // pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
 // one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
-struct ccv_mppi_batch {
-    ccv_mppi_handle h;
+struct ccv_mppi_batch : Core {
     int B = 0, kpad = 0, rec_doubles = 0;
     double* d_rec = nullptr;                        // [B][rec_doubles]: BatchHead + window a[H], b[H], c[H] per instance
     static constexpr int kRecSlots = 4;             // pinned staging of the records, in rotation: a slot is refilled only
@@ -144,11 +182,7 @@ struct ccv_mppi_batch {
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
     bool have_result = false;
-    // device-resident closed loop of every instance (ccv_mppi_batch_resident_*, mppi_resident.h): the update of a resident
-    // tick is launched together with the next tick's prologue (k_finalize_advance_batch); anything else that needs u*, the
-    // statistics or the stream first gets a plain k_finalize_batch (batch_flush)
-    bool fin_pending = false;
-    FinalizeArgs fin_args{};
+    // device-resident closed loop of every instance (ccv_mppi_batch_resident_*, mppi_resident.h)
     ResidentFrame* d_rframe = nullptr;      // [B]
     BatchInstance* d_inst = nullptr;        // [B]
     double* d_rpath = nullptr;              // [2][n_total]
@@ -159,7 +193,7 @@ struct ccv_mppi_batch {
     bool have_paths = false, have_poses = false;
     int64_t res_steps = 0;                  // resident ticks since the poses were set (every instance's step count)
     // per-instance parameters (ccv_mppi_batch_set_params): the VARIED kernels read instance b's row of d_params through the
-    // pointer in its record's head; without them (varied = false) every instance has h.cfg and the shared kernels run
+    // pointer in its record's head; without them (varied = false) every instance has cfg and the shared kernels run
     bool varied = false;
     std::vector<ccv_mppi_config> cfgs;      // [B] the instances' configurations while varied
     BatchParams* d_params = nullptr;        // [B], allocated at the first _set_params, freed at destroy
@@ -167,7 +201,7 @@ struct ccv_mppi_batch {
 
 namespace ccv {
 
-inline int fail(ccv_mppi_handle* h, int code, const char* what, hipError_t e = hipSuccess) {
+inline int fail(Core* h, int code, const char* what, hipError_t e = hipSuccess) {
     if (h) {
         h->err = what;
         if (e != hipSuccess) {
@@ -201,8 +235,8 @@ struct DeviceGuard {
 // ---- life cycle (ccv_mppi_capi.hip) -------------------------------------------------------------------------------------
 int check_config(const ccv_mppi_config* cfg);   // abi_version, model, num_samples, horizon: before a device is looked at
 int check_device(int device);                   // CCV_MPPI_ERR_NO_DEVICE unless `device` exists
-void set_shape(ccv_mppi_handle* h, const ccv_mppi_config& cfg, int pitch, int nblocks);
-void select_kernels(ccv_mppi_handle* h, int64_t workgroups, bool batched);
+void set_shape(Shape& s, const ccv_mppi_config& cfg, int pitch, int nblocks);
+void select_kernels(KernelChoice& k, const Shape& s, int64_t workgroups, bool batched);
 // element counts of the device and pinned buffers whose size differs between a single handle and a batch
 struct BufferCounts {
     size_t nparts_max;   // partial columns (workgroups or chunks, whichever is more)
@@ -211,39 +245,57 @@ struct BufferCounts {
     size_t n_extra;
     size_t pin_doubles, mail_slots;
 };
-int create_buffers(ccv_mppi_handle* h, const BufferCounts& n);
-void release_buffers(ccv_mppi_handle* h);
-int set_stream(ccv_mppi_handle* h, void* hip_stream);
-int ensure_scratch(ccv_mppi_handle* h, size_t bytes);
+int create_buffers(Core* h, const BufferCounts& n);
+void release_buffers(Core* h);
+int set_stream(Core* h, void* hip_stream);
+hipError_t ensure_scratch(DeviceBuffers& d, size_t bytes);
+
+// ---- the launch plan (ccv_mppi_capi.hip) --------------------------------------------------------------------------------
+enum : int { kTrigUnsafe = 0, kTrigSafe = 1, kTrigWide = 2 };
+// has_wide: the launch's family has a wide-turn form (has_wide_form)
+int fast_trig_safe(const Core* h, const ccv_mppi_config& c, const RolloutArgs& A, int mode, bool has_wide);
+inline KernelFamily family_of(const KernelChoice& k, const int mode) { return mode == MODE_FUSED ? k.fused : k.stagewise; }
+inline bool has_wide_form(const KernelChoice& k, const int mode) {
+    return mode == MODE_FUSED && (k.fused == KernelFamily::FourWave || k.fused == KernelFamily::OneWave);
+}
+// The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
+// (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
+inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied) {
+    const KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
+    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied, k.lds_window != 0};
+}
+
+RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);   // a single handle's
 
 // ---- the fused iteration and its update (ccv_mppi_capi.hip) -------------------------------------------------------------
 void fill_params(const ccv_mppi_config& c, bool fast_clamp_allowed, RolloutArgs& A);
-void fill_args(const ccv_mppi_handle* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed, uint64_t iter);
+void fill_args(const Core* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed, uint64_t iter);
 void window_coeffs(int H, const double* x_ref, const double* y_ref, double px, double py, double* a, double* b, double* c);
-enum : int { kTrigUnsafe = 0, kTrigSafe = 1, kTrigWide = 2 };
-int fast_trig_safe(const ccv_mppi_handle* h, const ccv_mppi_config& c, const RolloutArgs& A, int mode);
-int fast_trig_safe(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);
-int flush_pending(ccv_mppi_handle* h);
+void track_absmax(const double* u, size_t n, int udim, double* absmax);
+int flush_finalize(Core* h, int batch);     // the deferred update now: k_finalize, or k_finalize_batch of `batch` instances
+int flush_division(ccv_mppi_handle* h);     // the deferred division now: k_apply_partials
+int flush_pending(ccv_mppi_handle* h);      // both, in that order
 int materialize_controls(ccv_mppi_handle* h);
 int launch_rollout(ccv_mppi_handle* h, const RolloutArgs& A, const Window& W, int mode);
 int launch_sample(ccv_mppi_handle* h, const RolloutArgs& A);
-UpdateArgs update_args(const ccv_mppi_handle* h);
-FinalizeArgs finalize_args(const ccv_mppi_handle* h, double* vec, int nparts, bool normalise);
-void post_to_mail(ccv_mppi_handle* h, FinalizeArgs& F);
+UpdateArgs update_args(const Core* h);
+FinalizeArgs finalize_args(const Core* h, double* vec, int nparts, bool normalise);
+void post_to_mail(Mailbox& m, FinalizeArgs& F);
 int launch_update(ccv_mppi_handle* h, bool normalise, double* vec_out, bool exchange = false, bool defer = false);
 int check_iter_args(ccv_mppi_handle* h, const double* x0, double dt, const double* x_ref, const double* y_ref);
 int enqueue_iteration(ccv_mppi_handle* h, const double* x0, double dt, const double* x_ref, const double* y_ref, double yaw_ref0,
                       uint64_t seed, uint64_t iter, bool normalise, double* vec_out, bool resident = false, bool exchange = false);
-int throttle_tick(ccv_mppi_handle* h);
+hipError_t throttle_tick(Throttle& t, hipStream_t stream);
 // a timed launch: begin .. rollout kernel (its LaunchAt from timing_rollout_at, then timing_rollout_done) .. update .. end
-int timing_begin(ccv_mppi_handle* h);
-int timing_rollout_at(ccv_mppi_handle* h, bool plain, LaunchAt& at);
-int timing_rollout_done(ccv_mppi_handle* h, bool plain);
-int timing_end(ccv_mppi_handle* h);
-int timing_collect(ccv_mppi_handle* h);
-int wait_mail(ccv_mppi_handle* h, size_t n_slots);
-void decode_mail(const ccv_mppi_handle* h, size_t n_slots, double* out);
-void unpack_result(const ccv_mppi_handle* h, const double* v, double* u_opt_out, ccv_mppi_stats* stats);
+hipError_t timing_begin(Timing& t);
+hipError_t timing_rollout_at(const Timing& t, hipStream_t stream, bool plain, LaunchAt& at);
+hipError_t timing_rollout_done(const Timing& t, hipStream_t stream, bool plain);
+hipError_t timing_end(Timing& t, hipStream_t stream);
+hipError_t timing_collect(Timing& t, hipStream_t stream);
+int timing_enable(Core* h, int32_t on);   // ccv_mppi_timing_enable / _read and their batch forms (capi_stage.hip)
+int timing_read(Core* h, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset);
+int read_mail(Core* h, size_t n_slots, double* out);
+void unpack_result(const Timing& t, int R, const double* v, double* u_opt_out, ccv_mppi_stats* stats);
 int fetch_result(ccv_mppi_handle* h, double* u_opt_out, ccv_mppi_stats* stats);
 
 // ---- direct exchange (capi_exchange.hip) --------------------------------------------------------------------------------
@@ -262,7 +314,7 @@ struct ResidentBounds {
     double angle[3];   // bounds on |yaw|, |roll|, |pitch| after this tick
     double heading;    // bound on the heading the prologue itself takes sin / cos of
 };
-ResidentBounds resident_bounds(const ccv_mppi_handle* h, const ccv_mppi_config& c, const double* angle_abs, double dt, int32_t advance);
-int read_trace_ring(ccv_mppi_handle* h, const double* d_ring, int64_t cap, int64_t steps, int32_t max_rows, double* rows, int32_t* n_rows);
+ResidentBounds resident_bounds(const DeviceBuffers& d, const ccv_mppi_config& c, const double* angle_abs, double dt, int32_t advance);
+hipError_t read_trace_ring(const double* d_ring, int64_t cap, int64_t steps, int32_t max_rows, double* rows, int32_t* n_rows);
 
 }  // namespace ccv

@@ -8,12 +8,12 @@ namespace ccv {
 // of clamped samples (or what ccv_mppi_set_nominal put there), and the plant takes an angle modulo 2 pi once it leaves
 // +-kAngleRebase (rebase_angle), so the bounds stay below kAngleRebase + one step for a loop of any length.
 // angle_abs: the three bounds before this tick; c: the configuration whose clamp bounds apply (an instance's own in a batch).
-ResidentBounds resident_bounds(const ccv_mppi_handle* h, const ccv_mppi_config& c, const double* angle_abs, const double dt,
+ResidentBounds resident_bounds(const DeviceBuffers& buf, const ccv_mppi_config& c, const double* angle_abs, const double dt,
                                const int32_t advance) {
     auto lim = [&](int d) {
         const double a = std::fmax(std::fabs(c.u_min[d]), std::fabs(c.u_max[d]));
-        const double b = std::fmax(h->inj_absmax[d], h->nom_absmax[d]);
-        return (b == b) ? std::fmax(a, b) : b;   // NaN sticks
+        const double i = buf.inj_absmax[d], n = buf.nom_absmax[d];
+        return (i == i && n == n) ? std::fmax(a, std::fmax(i, n)) : NAN;   // NaN sticks (fmax alone would drop it)
     };
     ResidentBounds nb{{angle_abs[0], angle_abs[1], angle_abs[2]}, 0.0};
     if (advance) {
@@ -33,18 +33,18 @@ ResidentBounds resident_bounds(const ccv_mppi_handle* h, const ccv_mppi_config& 
 }
 
 // the last min(steps, cap, max_rows) rows of a trace ring of `cap` rows on the device, oldest first (after a synchronisation)
-int read_trace_ring(ccv_mppi_handle* h, const double* d_ring, const int64_t cap, const int64_t steps, const int32_t max_rows,
-                    double* rows, int32_t* n_rows) {
+hipError_t read_trace_ring(const double* d_ring, const int64_t cap, const int64_t steps, const int32_t max_rows, double* rows,
+                           int32_t* n_rows) {
     const int64_t have = steps < cap ? steps : cap;
     const int64_t n = have < max_rows ? have : max_rows;
     std::vector<double> ring((size_t)cap * 6);
-    HIP_TRY(h, hipMemcpy(ring.data(), d_ring, ring.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (hipError_t e = hipMemcpy(ring.data(), d_ring, ring.size() * sizeof(double), hipMemcpyDeviceToHost)) return e;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t step = steps - n + i;
         std::memcpy(rows + i * 6, ring.data() + (step % cap) * 6, 6 * sizeof(double));
     }
     *n_rows = (int32_t)n;
-    return CCV_MPPI_OK;
+    return hipSuccess;
 }
 
 }  // namespace ccv
@@ -98,13 +98,13 @@ int resident_step(ccv_mppi_handle* h, double dt, uint64_t seed, uint64_t iter, i
     if (!h->d_frame || !h->have_pose) return fail(h, CCV_MPPI_ERR_STATE, "ccv_mppi_resident_set_path and _set_pose first");
     if (!std::isfinite(stride) || stride < 0.0 || stride * h->H > 2.0e9)
         return fail(h, CCV_MPPI_ERR_INVALID_ARG, "resident step: v_ref * dt / resolution is not a usable window stride");
-    const ResidentBounds nb = resident_bounds(h, h->cfg, h->res_angle_abs, dt, advance);
+    const ResidentBounds nb = resident_bounds(*h, h->cfg, h->res_angle_abs, dt, advance);
     const double bounds[5] = {0.0, 0.0, nb.angle[0], nb.angle[1], nb.angle[2]};
     // everything that can refuse the step is checked BEFORE k_advance moves the pose
     {
         RolloutArgs chk;
         fill_args(h, chk, bounds, dt, 0.0, seed, iter);
-        if (!h->coop || fast_trig_safe(h, chk, MODE_FUSED) == kTrigUnsafe || !(nb.heading <= kFastTrigLimit))
+        if (plan_of(h, chk, MODE_FUSED).family == KernelFamily::Plain || !(nb.heading <= kFastTrigLimit))
             return fail(h, CCV_MPPI_ERR_STATE, "the resident loop needs the cooperative kernels and bounded pose angles / commands");
     }
     const bool fuse = h->fin_pending && !h->pending_vec;   // the last tick's update is still to be launched: together with this prologue
@@ -180,7 +180,8 @@ int ccv_mppi_resident_read_trace(ccv_mppi_handle* h, int32_t max_rows, double* r
     if (!rows || !n_rows || max_rows < 0) return fail(h, CCV_MPPI_ERR_INVALID_ARG, "rows / n_rows null or max_rows < 0");
     if (!h->d_frame || !h->have_pose) return fail(h, CCV_MPPI_ERR_STATE, "ccv_mppi_resident_set_path and _set_pose first");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return read_trace_ring(h, h->d_trace, ccv_mppi_handle::kTraceRows, h->res_steps, max_rows, rows, n_rows);
+    HIP_TRY(h, read_trace_ring(h->d_trace, ccv_mppi_handle::kTraceRows, h->res_steps, max_rows, rows, n_rows));
+    return CCV_MPPI_OK;
 }
 
 }  // extern "C"

@@ -103,8 +103,7 @@ int ccv_mppi_read_candidates(ccv_mppi_handle* h, int32_t first, int32_t count, i
     if (count == 0) return CCV_MPPI_OK;
     if ((int64_t)first + (int64_t)(count - 1) * stride >= h->K) return fail(h, CCV_MPPI_ERR_INVALID_ARG, "candidate range exceeds num_samples");
     const size_t n = (size_t)count * h->H * 2;
-    int rc = ensure_scratch(h, n * sizeof(double));
-    if (rc) return rc;
+    HIP_TRY(h, ensure_scratch(*h, n * sizeof(double)));
     hipLaunchKernelGGL(k_gather_xy, dim3((count * h->H + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->d_xs, h->d_ys,
                        h->pitch, h->H, first, count, stride, h->d_scratch);
     HIP_TRY(h, hipGetLastError());
@@ -121,8 +120,7 @@ int ccv_mppi_read_top_candidates(ccv_mppi_handle* h, int32_t count, int32_t* sam
     if (count == 0) return CCV_MPPI_OK;
     // scratch: [count] indices (as 8-byte slots) | [count] weights | [count][H][2] states
     const size_t n_xy = xy_out ? (size_t)count * h->H * 2 : 0;
-    int rc = ensure_scratch(h, ((size_t)count * 2 + n_xy) * sizeof(double));
-    if (rc) return rc;
+    HIP_TRY(h, ensure_scratch(*h, ((size_t)count * 2 + n_xy) * sizeof(double)));
     int* d_idx = reinterpret_cast<int*>(h->d_scratch);
     double* d_wsel = h->d_scratch + count;
     double* d_xy = h->d_scratch + 2 * (size_t)count;
@@ -176,8 +174,7 @@ int ccv_mppi_read_weights(ccv_mppi_handle* h, int32_t first, int32_t count, doub
     if (!h->have_weights) return fail(h, CCV_MPPI_ERR_STATE, "no weights yet");
     if (count == 0) return CCV_MPPI_OK;
     if ((rc = flush_pending(h)) != CCV_MPPI_OK) return rc;   // (sum w)
-    rc = ensure_scratch(h, (size_t)count * sizeof(double));
-    if (rc) return rc;
+    HIP_TRY(h, ensure_scratch(*h, (size_t)count * sizeof(double)));
     hipLaunchKernelGGL(k_normalise_weights, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->d_w, h->d_stats,
                        first, count, h->d_scratch);
     HIP_TRY(h, hipGetLastError());
@@ -234,28 +231,16 @@ extern "C" int ccv_mppi_debug_blocks(ccv_mppi_handle* h, unsigned long long* out
 
 // ---- measurement ------------------------------------------------------------------------------------------------
 
-int ccv_mppi_timing_enable(ccv_mppi_handle* h, int32_t on) {
-    if (!h) return CCV_MPPI_ERR_INVALID_ARG;
-    int rc = timing_collect(h);
-    if (rc) return rc;
-    h->timing = on != 0;
-    h->timing_every = on > 1 ? on : 1;   // on = n > 1: sample every n-th iteration
-    h->timing_count = 0;
-    return CCV_MPPI_OK;
-}
+int ccv_mppi_timing_enable(ccv_mppi_handle* h, int32_t on) { return h ? timing_enable(h, on) : CCV_MPPI_ERR_INVALID_ARG; }
 
 int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset) {
-    if (!h) return CCV_MPPI_ERR_INVALID_ARG;
-    int rc = timing_collect(h);
-    if (rc) return rc;
-    if (rollout_us_sum) *rollout_us_sum = h->t_roll_sum;
-    if (iter_us_sum) *iter_us_sum = h->t_iter_sum;
-    if (n_iters) *n_iters = h->t_n;
-    if (reset) {
-        h->t_roll_sum = h->t_iter_sum = 0.0;
-        h->t_n = 0;
-    }
-    return CCV_MPPI_OK;
+    return h ? timing_read(h, rollout_us_sum, iter_us_sum, n_iters, reset) : CCV_MPPI_ERR_INVALID_ARG;
+}
+
+int ccv_mppi_batch_timing_enable(ccv_mppi_batch* bh, int32_t on) { return bh ? timing_enable(bh, on) : CCV_MPPI_ERR_INVALID_ARG; }
+
+int ccv_mppi_batch_timing_read(ccv_mppi_batch* bh, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset) {
+    return bh ? timing_read(bh, rollout_us_sum, iter_us_sum, n_iters, reset) : CCV_MPPI_ERR_INVALID_ARG;
 }
 
 }  // extern "C"

@@ -9,14 +9,16 @@
 
 namespace ccv {
 
-int ensure_scratch(ccv_mppi_handle* h, size_t bytes) {
-    if (bytes <= h->scratch_bytes) return CCV_MPPI_OK;
-    if (h->d_scratch) HIP_TRY(h, hipFree(h->d_scratch));
-    h->d_scratch = nullptr;
-    h->scratch_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->d_scratch, bytes));
-    h->scratch_bytes = bytes;
-    return CCV_MPPI_OK;
+hipError_t ensure_scratch(DeviceBuffers& d, size_t bytes) {
+    if (bytes <= d.scratch_bytes) return hipSuccess;
+    if (d.d_scratch) {
+        if (hipError_t e = hipFree(d.d_scratch)) return e;
+    }
+    d.d_scratch = nullptr;
+    d.scratch_bytes = 0;
+    if (hipError_t e = hipMalloc(&d.d_scratch, bytes)) return e;
+    d.scratch_bytes = bytes;
+    return hipSuccess;
 }
 
 // the controller parameters of configuration c (sigma, lambda, v_ref, bounds, clamp form, weights) into A: fill_args(), and
@@ -44,7 +46,7 @@ void fill_params(const ccv_mppi_config& c, const bool fast_clamp_allowed, Rollou
     A.w_yaw = c.yaw_weight;
 }
 
-void fill_args(const ccv_mppi_handle* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed,
+void fill_args(const Core* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed,
                uint64_t iter) {
     const ccv_mppi_config& c = h->cfg;
     std::memset(&A, 0, sizeof(A));
@@ -103,50 +105,30 @@ void window_coeffs(const int H, const double* x_ref, const double* y_ref, const 
     }
 }
 
-// mode: MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h).  The kernels live in translation units of their own
-// (mppi_launch.h); a timed fused launch carries its events on the dispatch itself (timing_rollout_at).
-static int launch_rollout_model(ccv_mppi_handle* h, const RolloutArgs& A, const Window& W, int mode) {
-    const int model = h->cfg.model;
-    LaunchAt at{h->stream, nullptr, nullptr};
-    if (mode == MODE_FUSED) {
-        if (int rc = timing_rollout_at(h, /*plain=*/!h->coop, at)) return rc;
-    }
-    if (h->solo && h->coop && mode == MODE_FUSED) {
-        // one wave per 64 samples (mppi_rollout_solo.h): K provides two or more such waves per SIMD
-        launch_rollout_solo(model, h->wide_turn, at, A, W);
-        return CCV_MPPI_OK;
-    }
-    if (h->coop == 3) {   // four-wave kernel (mppi_rollout_r4.h)
-        launch_rollout_r4(model, mode, h->wide_turn, at, A, W);
-        return CCV_MPPI_OK;
-    }
-    if (model != CCV_MPPI_FULL_BODY && h->coop == 2) {   // three-wave kernel (mppi_rollout_r3.h); not built for full body
-        launch_rollout_r3(model, mode, at, A, W);
-        return CCV_MPPI_OK;
-    }
-    if (h->coop) {   // two-wave kernel (mppi_rollout_pc.h)
-        launch_rollout_pc(model, mode, at, A, W);
-        return CCV_MPPI_OK;
-    }
-    // plain one-sample-per-lane kernel: the path of unbounded headings (fast_trig_safe) and CCV_MPPI_KERNEL=v1
-    // (timed launch: events recorded around it -- the fallback must deliver kernel times too)
-    launch_rollout_plain(model, mode == MODE_FUSED, h->lds_window != 0, at, A, W);
-    return mode == MODE_FUSED ? timing_rollout_done(h, /*plain=*/true) : CCV_MPPI_OK;
+// The deferred update of a resident tick (DeferredUpdate) is launched now, as the plain update of the fused partials.
+int flush_finalize(Core* h, const int batch) {
+    if (!h->fin_pending) return CCV_MPPI_OK;
+    const unsigned blocks = finalize_blocks(h->fin_args.R);
+    if (batch) hipLaunchKernelGGL(k_finalize_batch, dim3(blocks, batch), dim3(kBlock), 0, h->stream, h->fin_args, 1);
+    else hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(kBlock), 0, h->stream, h->fin_args);
+    h->fin_pending = false;
+    HIP_TRY(h, hipGetLastError());
+    return CCV_MPPI_OK;
 }
 
 // A deferred ccv_mppi_apply_partials_enqueue is normally consumed by the next fused rollout launch (pc_stage_nominal);
 // anything else that reads the warm start first gets it materialised here.
-int flush_pending(ccv_mppi_handle* h) {
-    if (h->fin_pending) {
-        hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(h->fin_args.R)), dim3(kBlock), 0, h->stream, h->fin_args);
-        h->fin_pending = false;
-        HIP_TRY(h, hipGetLastError());
-    }
+int flush_division(ccv_mppi_handle* h) {
     if (!h->pending_vec) return CCV_MPPI_OK;
     hipLaunchKernelGGL(k_apply_partials, dim3(1), dim3(kBlock), 0, h->stream, h->pending_vec, h->d_nominal, h->d_stats, h->R);
     h->pending_vec = nullptr;
     HIP_TRY(h, hipGetLastError());
     return CCV_MPPI_OK;
+}
+
+int flush_pending(ccv_mppi_handle* h) {
+    if (int rc = flush_finalize(h, 0)) return rc;
+    return flush_division(h);
 }
 
 // The fused kernels store the normals, not the controls; whoever needs the controls as an array (the stage-wise calls after a
@@ -177,11 +159,12 @@ int materialize_controls(ccv_mppi_handle* h) {
 // reach is bounded by the start angle plus (H-1) steps at the largest control magnitude, so the decision is made here,
 // once per call; anything else (huge or non-finite angles, unbounded injected controls) runs the plain
 // one-sample-per-lane kernel with OCML's sincos.
-// Returns kTrigUnsafe (plain kernel), kTrigSafe, or kTrigWide: diff drive, fused iteration, four-wave or one-wave kernel,
-// every heading inside the range but a turn per step beyond pi/4 -- the instantiation that evaluates sin / cos of every
-// heading in full (as the steering model's does) instead of advancing them by the step's turn.
+// Returns kTrigUnsafe (plain kernel), kTrigSafe, or kTrigWide: diff drive, a family with a wide-turn form (has_wide: the fused
+// iteration of the four-wave or one-wave kernel), every heading inside the range but a turn per step beyond pi/4 -- the
+// instantiation that evaluates sin / cos of every heading in full (as the steering model's does) instead of advancing them by
+// the step's turn.
 // (c: the configuration whose clamp bounds apply -- h->cfg, or an instance's of a batch with per-instance parameters)
-int fast_trig_safe(const ccv_mppi_handle* h, const ccv_mppi_config& c, const RolloutArgs& A, int mode) {
+int fast_trig_safe(const Core* h, const ccv_mppi_config& c, const RolloutArgs& A, const int mode, const bool has_wide) {
     const int ud = h->udim;
     double umax[CCV_MPPI_MAX_UDIM];
     for (int d = 0; d < ud; ++d) {
@@ -197,7 +180,7 @@ int fast_trig_safe(const ccv_mppi_handle* h, const ccv_mppi_config& c, const Rol
     // diff drive advances (sin, cos) of the heading by the step's turn angle: needs |w| dt <= pi/4 (fast_trig.h)
     bool wide = false;
     if (h->cfg.model == CCV_MPPI_DIFF_DRIVE && !(umax[1] * std::fabs(A.dt) <= kSmallTurnLimit)) {
-        if (!(mode == MODE_FUSED && (h->coop == 3 || h->solo))) return kTrigUnsafe;   // (the stage-wise and the experiment kernels have no wide form)
+        if (!has_wide) return kTrigUnsafe;   // (the stage-wise and the experiment kernels have no wide form)
         wide = true;
     }
     // full body: the same for yaw, roll and pitch, and the direction angle itself is evaluated without range reduction
@@ -211,41 +194,41 @@ int fast_trig_safe(const ccv_mppi_handle* h, const ccv_mppi_config& c, const Rol
     if (!(bound <= kFastTrigLimit)) return kTrigUnsafe;   // (also for NaN)
     return wide ? kTrigWide : kTrigSafe;
 }
-int fast_trig_safe(const ccv_mppi_handle* h, const RolloutArgs& A, int mode) { return fast_trig_safe(h, h->cfg, A, mode); }
 
+// the plan of a single handle's launch
+RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, const int mode) {
+    return make_plan(*h, h->cfg.model, mode, fast_trig_safe(h, h->cfg, A, mode, has_wide_form(*h, mode)), 0, false);
+}
+
+// mode: MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h).  A timed fused launch carries its events on the dispatch
+// itself (timing_rollout_at).
 int launch_rollout(ccv_mppi_handle* h, const RolloutArgs& A_in, const Window& W, int mode) {
     RolloutArgs A = A_in;
-    const int saved = h->coop;
-    const int trig = h->coop ? fast_trig_safe(h, A, mode) : kTrigUnsafe;
-    if (h->coop && trig == kTrigUnsafe) h->coop = 0;
-    h->wide_turn = trig == kTrigWide;
-    struct Restore { ccv_mppi_handle* h; int v; ~Restore() { h->coop = v; h->wide_turn = false; } } restore{h, saved};
+    const RolloutPlan plan = plan_of(h, A, mode);
+    const bool coop = plan.family != KernelFamily::Plain;
     // the production kernel also reduces its workgroup's share of sum w and sum w*u (no second pass over the controls);
     // the underflow-safe MIN_SHIFT mode needs the global minimum first and keeps the separate update kernels
-    A.fuse_update = (h->coop && mode != MODE_ROLLOUT && !(h->cfg.flags & CCV_MPPI_FLAG_MIN_SHIFT)) ? 1 : 0;
-    if (h->fin_pending) {   // (the kernel reads the warm start)
-        const double* keep = h->pending_vec;
-        h->pending_vec = nullptr;
-        int rc = flush_pending(h);
-        h->pending_vec = keep;
-        if (rc) return rc;
-    }
+    A.fuse_update = (coop && mode != MODE_ROLLOUT && !(h->cfg.flags & CCV_MPPI_FLAG_MIN_SHIFT)) ? 1 : 0;
+    if (int rc = flush_finalize(h, 0)) return rc;   // (the kernel reads the warm start)
     if (h->pending_vec) {
-        if (h->coop && mode == MODE_FUSED) {   // the kernel divides while it stages u* (and writes it back)
+        if (coop && mode == MODE_FUSED) {   // the kernel divides while it stages u* (and writes it back)
             A.pending_vec = h->pending_vec;
             h->pending_vec = nullptr;
         } else {
-            int rc = flush_pending(h);
-            if (rc) return rc;
+            if (int rc = flush_division(h)) return rc;
         }
     }
     if (mode != MODE_ROLLOUT) h->nparts_last = A.fuse_update ? h->nblocks : 0;
     if (mode != MODE_FUSED) {   // the stage-wise kernels read the controls as an array
         if (int rc = materialize_controls(h)) return rc;
     }
-    if (int rc = launch_rollout_model(h, A, W, mode)) return rc;
+    // (a timed launch of the plain kernel: events recorded around it -- the fallback must deliver kernel times too)
+    LaunchAt at{h->stream, nullptr, nullptr};
+    if (mode == MODE_FUSED) HIP_TRY(h, timing_rollout_at(*h, h->stream, !coop, at));
+    launch_rollout(plan, at, A, W);
+    if (mode == MODE_FUSED) HIP_TRY(h, timing_rollout_done(*h, h->stream, !coop));
     HIP_TRY(h, hipGetLastError());
-    if (mode == MODE_FUSED) h->controls_in_z = h->coop != 0;   // (the plain kernel writes u itself)
+    if (mode == MODE_FUSED) h->controls_in_z = coop;   // (the plain kernel writes u itself)
     return CCV_MPPI_OK;
 }
 
@@ -257,7 +240,7 @@ int launch_sample(ccv_mppi_handle* h, const RolloutArgs& A) {
 }
 
 // weights -> [sum w, sum w*u] (-> u* when `normalise`); vec_out may be a caller-owned device buffer.
-UpdateArgs update_args(const ccv_mppi_handle* h) {
+UpdateArgs update_args(const Core* h) {
     UpdateArgs U;
     U.u = h->d_u;
     U.w = h->d_w;
@@ -272,7 +255,7 @@ UpdateArgs update_args(const ccv_mppi_handle* h) {
 }
 
 // (a batch: the first instance's slices; k_finalize_batch offsets them)
-FinalizeArgs finalize_args(const ccv_mppi_handle* h, double* vec, const int nparts, const bool normalise) {
+FinalizeArgs finalize_args(const Core* h, double* vec, const int nparts, const bool normalise) {
     FinalizeArgs F;
     F.partial = h->d_partial;
     F.statpart = h->d_statpart;
@@ -288,11 +271,11 @@ FinalizeArgs finalize_args(const ccv_mppi_handle* h, double* vec, const int npar
 }
 
 // this update posts its result into the mailbox under the next sequence number (never 0): fetch_result() / batch_fetch() poll
-void post_to_mail(ccv_mppi_handle* h, FinalizeArgs& F) {
-    if (++h->mail_seq == 0) h->mail_seq = 1;
-    F.mail = h->d_mail;
-    F.mail_seq = h->mail_seq;
-    h->mail_pending = true;
+void post_to_mail(Mailbox& m, FinalizeArgs& F) {
+    if (++m.mail_seq == 0) m.mail_seq = 1;
+    F.mail = m.d_mail;
+    F.mail_seq = m.mail_seq;
+    m.mail_pending = true;
 }
 
 int launch_update(ccv_mppi_handle* h, bool normalise, double* vec_out, bool exchange, bool defer) {
@@ -314,7 +297,7 @@ int launch_update(ccv_mppi_handle* h, bool normalise, double* vec_out, bool exch
     FinalizeArgs F = finalize_args(h, vec_out ? vec_out : h->d_vec, nparts, normalise);
     const bool post = h->want_mail && h->use_mail && normalise && !exchange && !defer && h->d_mail;
     h->want_mail = false;
-    if (post) post_to_mail(h, F);
+    if (post) post_to_mail(*h, F);
     if (exchange) {
         ExchangeArgs X;
         for (int r = 0; r < kMaxRanks; ++r) X.peer[r] = h->box_peer[r];
@@ -344,67 +327,87 @@ int launch_update(ccv_mppi_handle* h, bool normalise, double* vec_out, bool exch
 
 // Is the launch that starts here timed (every timing_every-th is)?  Then a triple of events is reserved for it: rollout
 // kernel begin, rollout kernel end, end of the launch sequence.
-int timing_begin(ccv_mppi_handle* h) {
-    h->timed_now = h->timing && (h->timing_count++ % h->timing_every) == 0;
-    if (!h->timed_now) return CCV_MPPI_OK;
-    const size_t slot = h->ev_slot = h->ev_used;
-    if (h->ev.size() < slot + 3) {
+hipError_t timing_begin(Timing& t) {
+    t.timed_now = t.timing && (t.timing_count++ % t.timing_every) == 0;
+    if (!t.timed_now) return hipSuccess;
+    const size_t slot = t.ev_slot = t.ev_used;
+    if (t.ev.size() < slot + 3) {
         for (int i = 0; i < 3; ++i) {
             hipEvent_t e;
-            HIP_TRY(h, hipEventCreate(&e));
-            h->ev.push_back(e);
+            if (hipError_t err = hipEventCreate(&e)) return err;
+            t.ev.push_back(e);
         }
     }
-    h->ev_used += 3;
-    return CCV_MPPI_OK;
+    t.ev_used += 3;
+    return hipSuccess;
 }
 
 // The rollout kernel's first two events: the cooperative kernels carry them on the dispatch itself (LaunchAt), the plain kernel
 // has them recorded around it -- the fallback must deliver kernel times too.
-int timing_rollout_at(ccv_mppi_handle* h, const bool plain, LaunchAt& at) {
-    at = LaunchAt{h->stream, nullptr, nullptr};
-    if (!h->timed_now) return CCV_MPPI_OK;
-    if (plain) HIP_TRY(h, hipEventRecord(h->ev[h->ev_slot], h->stream));
-    else at = LaunchAt{h->stream, h->ev[h->ev_slot], h->ev[h->ev_slot + 1]};
-    return CCV_MPPI_OK;
+hipError_t timing_rollout_at(const Timing& t, hipStream_t stream, const bool plain, LaunchAt& at) {
+    at = LaunchAt{stream, nullptr, nullptr};
+    if (!t.timed_now) return hipSuccess;
+    if (plain) return hipEventRecord(t.ev[t.ev_slot], stream);
+    at = LaunchAt{stream, t.ev[t.ev_slot], t.ev[t.ev_slot + 1]};
+    return hipSuccess;
 }
 
-int timing_rollout_done(ccv_mppi_handle* h, const bool plain) {
-    if (h->timed_now && plain) HIP_TRY(h, hipEventRecord(h->ev[h->ev_slot + 1], h->stream));
-    return CCV_MPPI_OK;
+hipError_t timing_rollout_done(const Timing& t, hipStream_t stream, const bool plain) {
+    return t.timed_now && plain ? hipEventRecord(t.ev[t.ev_slot + 1], stream) : hipSuccess;
 }
 
-int timing_end(ccv_mppi_handle* h) {
-    const bool timed = h->timed_now;
-    h->timed_now = false;
-    if (timed) HIP_TRY(h, hipEventRecord(h->ev[h->ev_slot + 2], h->stream));
-    return CCV_MPPI_OK;
+hipError_t timing_end(Timing& t, hipStream_t stream) {
+    const bool timed = t.timed_now;
+    t.timed_now = false;
+    return timed ? hipEventRecord(t.ev[t.ev_slot + 2], stream) : hipSuccess;
 }
 
-// queue-depth throttle of the asynchronous entry points (ccv_mppi_handle::kThrottleEvery: why)
-int throttle_tick(ccv_mppi_handle* h) {
-    if (!h->throttle || ++h->enqueued % ccv_mppi_handle::kThrottleEvery != 0) return CCV_MPPI_OK;
-    const int ts = (int)((h->enqueued / ccv_mppi_handle::kThrottleEvery) % ccv_mppi_handle::kThrottleSlots);
-    if (h->throttle_used[ts]) HIP_TRY(h, hipEventSynchronize(h->throttle_ev[ts]));
-    HIP_TRY(h, hipEventRecord(h->throttle_ev[ts], h->stream));
-    h->throttle_used[ts] = true;
-    return CCV_MPPI_OK;
-}
-
-int timing_collect(ccv_mppi_handle* h) {
-    if (h->ev_used == 0) return CCV_MPPI_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (size_t s = 0; s + 3 <= h->ev_used; s += 3) {
-        float a = 0.f, b = 0.f;
-        HIP_TRY(h, hipEventElapsedTime(&a, h->ev[s], h->ev[s + 1]));
-        HIP_TRY(h, hipEventElapsedTime(&b, h->ev[s], h->ev[s + 2]));
-        h->t_roll_sum += (double)a * 1000.0;
-        h->t_iter_sum += (double)b * 1000.0;
-        h->t_n += 1;
-        h->last_roll_us = a * 1000.f;
-        h->last_iter_us = b * 1000.f;
+// queue-depth throttle of the asynchronous entry points (Throttle: why)
+hipError_t throttle_tick(Throttle& t, hipStream_t stream) {
+    if (!t.throttle || ++t.enqueued % Throttle::kThrottleEvery != 0) return hipSuccess;
+    const int ts = (int)((t.enqueued / Throttle::kThrottleEvery) % Throttle::kThrottleSlots);
+    if (t.throttle_used[ts]) {
+        if (hipError_t e = hipEventSynchronize(t.throttle_ev[ts])) return e;
     }
-    h->ev_used = 0;
+    if (hipError_t e = hipEventRecord(t.throttle_ev[ts], stream)) return e;
+    t.throttle_used[ts] = true;
+    return hipSuccess;
+}
+
+hipError_t timing_collect(Timing& t, hipStream_t stream) {
+    if (t.ev_used == 0) return hipSuccess;
+    if (hipError_t e = hipStreamSynchronize(stream)) return e;
+    for (size_t s = 0; s + 3 <= t.ev_used; s += 3) {
+        float a = 0.f, b = 0.f;
+        if (hipError_t e = hipEventElapsedTime(&a, t.ev[s], t.ev[s + 1])) return e;
+        if (hipError_t e = hipEventElapsedTime(&b, t.ev[s], t.ev[s + 2])) return e;
+        t.t_roll_sum += (double)a * 1000.0;
+        t.t_iter_sum += (double)b * 1000.0;
+        t.t_n += 1;
+        t.last_roll_us = a * 1000.f;
+        t.last_iter_us = b * 1000.f;
+    }
+    t.ev_used = 0;
+    return hipSuccess;
+}
+
+int timing_enable(Core* h, const int32_t on) {
+    HIP_TRY(h, timing_collect(*h, h->stream));
+    h->timing = on != 0;
+    h->timing_every = on > 1 ? on : 1;   // on = n > 1: sample every n-th iteration
+    h->timing_count = 0;
+    return CCV_MPPI_OK;
+}
+
+int timing_read(Core* h, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, const int32_t reset) {
+    HIP_TRY(h, timing_collect(*h, h->stream));
+    if (rollout_us_sum) *rollout_us_sum = h->t_roll_sum;
+    if (iter_us_sum) *iter_us_sum = h->t_iter_sum;
+    if (n_iters) *n_iters = h->t_n;
+    if (reset) {
+        h->t_roll_sum = h->t_iter_sum = 0.0;
+        h->t_n = 0;
+    }
     return CCV_MPPI_OK;
 }
 
@@ -426,7 +429,7 @@ int enqueue_iteration(ccv_mppi_handle* h, const double* x0, double dt, const dou
     if (resident) {
         std::memset(&W, 0, sizeof(W));
         A.frame = h->d_frame;
-        if (!h->coop || fast_trig_safe(h, A, MODE_FUSED) == kTrigUnsafe)
+        if (plan_of(h, A, MODE_FUSED).family == KernelFamily::Plain)
             return fail(h, CCV_MPPI_ERR_STATE, "the resident loop needs the cooperative kernels and bounded pose angles");
     } else {
         window_coeffs(h->H, x_ref, y_ref, x0[0], x0[1], W.a, W.b, W.c);
@@ -434,13 +437,13 @@ int enqueue_iteration(ccv_mppi_handle* h, const double* x0, double dt, const dou
     A.store_u = 1;
     A.store_xy = (h->cfg.flags & CCV_MPPI_FLAG_NO_STATE_STORE) ? 0 : 1;
     A.do_cost = 1;
-    int rc = timing_begin(h);
+    HIP_TRY(h, timing_begin(*h));
+    int rc = launch_rollout(h, A, W, MODE_FUSED);
     if (rc) return rc;
-    if ((rc = launch_rollout(h, A, W, MODE_FUSED))) return rc;
     rc = launch_update(h, normalise, vec_out, exchange, /*defer=*/resident && normalise && !vec_out && !exchange && !h->timed_now);
     if (rc) return rc;
-    if ((rc = timing_end(h))) return rc;
-    if ((rc = throttle_tick(h))) return rc;
+    HIP_TRY(h, timing_end(*h, h->stream));
+    HIP_TRY(h, throttle_tick(*h, h->stream));
     std::memcpy(h->st_x0, A.x0, sizeof(h->st_x0));
     h->st_dt = dt;
     h->have_controls = h->have_rollout = h->have_weights = true;
@@ -452,15 +455,16 @@ int enqueue_iteration(ccv_mppi_handle* h, const double* x0, double dt, const dou
 // kernel's last store instead of two copy-engine transfers and a stream synchronisation (C2: 72 -> ~50 us per blocking
 // iteration; the reference defaults, K = 1 000, H = 15: 34 -> ~25 us).  A kernel that never posts (a fault, a lost device)
 // is found by the stream query / synchronisation the poll falls back to, so the call returns an error instead of spinning.
-int wait_mail(ccv_mppi_handle* h, const size_t n_slots) {
+// Then the values of the n_slots slots go to `out`: each travels as two packets {32 data bits, 32-bit sequence number}.
+int read_mail(Core* h, const size_t n_slots, double* out) {
     const uint32_t seq = h->mail_seq;
     volatile unsigned long long* m = h->h_mail;
     const auto t0 = std::chrono::steady_clock::now();
     size_t next = 0;
     bool synced = false;
-    for (unsigned spin = 0;; ++spin) {
+    for (unsigned spin = 0; next < n_slots; ++spin) {
         while (next < n_slots && (uint32_t)m[2 * next] == seq && (uint32_t)m[2 * next + 1] == seq) ++next;
-        if (next == n_slots) return CCV_MPPI_OK;
+        if (next == n_slots) break;
         if (synced) return fail(h, CCV_MPPI_ERR_HIP, "the update kernel finished without posting its result");
         asm volatile("" ::: "memory");
         if ((spin & 1023u) == 1023u) {
@@ -472,21 +476,18 @@ int wait_mail(ccv_mppi_handle* h, const size_t n_slots) {
             }
         }
     }
-}
-
-// the values of the first n_slots mailbox slots: each travels as two packets {32 data bits, 32-bit sequence number}
-void decode_mail(const ccv_mppi_handle* h, const size_t n_slots, double* out) {
     for (size_t i = 0; i < n_slots; ++i) {
         const unsigned long long hi = h->h_mail[2 * i], lo = h->h_mail[2 * i + 1];
         const unsigned long long bits = (hi & 0xFFFFFFFF00000000ull) | (lo >> 32);
         std::memcpy(&out[i], &bits, sizeof(double));
     }
+    return CCV_MPPI_OK;
 }
 
 // one instance's [u* | sum w, min cost, max cost, zero-weight count] -> the caller's u* and statistics (either may be null);
 // the times are those of the last timing_collect()
-void unpack_result(const ccv_mppi_handle* h, const double* v, double* u_opt_out, ccv_mppi_stats* stats) {
-    const size_t n = (size_t)h->R;
+void unpack_result(const Timing& t, const int R, const double* v, double* u_opt_out, ccv_mppi_stats* stats) {
+    const size_t n = (size_t)R;
     int nonfinite = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!std::isfinite(v[i])) nonfinite = 1;
@@ -499,9 +500,9 @@ void unpack_result(const ccv_mppi_handle* h, const double* v, double* u_opt_out,
     stats->max_cost = v[n + 2];
     stats->n_zero_weight = (int64_t)v[n + 3];
     stats->nonfinite = nonfinite;
-    if (h->timing) {
-        stats->device_us = h->last_iter_us;
-        stats->rollout_us = h->last_roll_us;
+    if (t.timing) {
+        stats->device_us = t.last_iter_us;
+        stats->rollout_us = t.last_roll_us;
     }
 }
 
@@ -510,18 +511,15 @@ int fetch_result(ccv_mppi_handle* h, double* u_opt_out, ccv_mppi_stats* stats) {
     const size_t n = (size_t)h->R;
     if (h->mail_pending) {
         h->mail_pending = false;
-        if (int rc = wait_mail(h, n + (stats ? 4 : 0))) return rc;
-        decode_mail(h, n + (stats ? 4u : 0u), h->h_pin);
+        if (int rc = read_mail(h, n + (stats ? 4u : 0u), h->h_pin)) return rc;
     } else {
         // one D2H of [u* | stats] through pinned memory, then a stream sync
         HIP_TRY(h, hipMemcpyAsync(h->h_pin, h->d_nominal, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipMemcpyAsync(h->h_pin + n, h->d_stats, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    if (stats && h->timing) {
-        if (int rc = timing_collect(h)) return rc;
-    }
-    unpack_result(h, h->h_pin, u_opt_out, stats);
+    if (stats && h->timing) HIP_TRY(h, timing_collect(*h, h->stream));
+    unpack_result(*h, h->R, h->h_pin, u_opt_out, stats);
     return CCV_MPPI_OK;
 }
 
@@ -533,26 +531,27 @@ static int r4_prio_levels(int model) {
 }
 
 // ---- kernel-family rule ---------------------------------------------------------------------------------------------
-// From the model, the workgroups (blocks of 64 samples) of one launch, the device's CUs (h->cu_count) and CCV_MPPI_KERNEL to
-// h->coop (0: plain one-sample-per-lane kernel, 1: two-wave, 2: three-wave, 3: four-wave) and h->solo (the one-wave kernel runs
-// the fused iteration); the defaults of h->prio_rotate and h->prune follow.  `batched`: a batch handle's launch -- the same rule
+// From the model, the workgroups (blocks of 64 samples) of one launch, the device's CUs (s.cu_count) and CCV_MPPI_KERNEL to
+// k.stagewise (Plain: one sample per lane, TwoWave, ThreeWave, FourWave) and k.fused (the same, or OneWave: the one-wave kernel
+// runs the fused iteration); the defaults of k.prio_rotate and k.prune follow.  `batched`: a batch handle's launch -- the same rule
 // on the batch's total number of workgroups, except that the two-wave kernel has no batched form (a full-body batch beyond one
 // workgroup per CU takes the one-wave kernel at once) and that CCV_MPPI_KERNEL=v1 is the only value honoured.
-void select_kernels(ccv_mppi_handle* h, const int64_t workgroups, const bool batched) {
-    const int64_t cus = h->cu_count;
-    const bool fb = h->cfg.model == CCV_MPPI_FULL_BODY;
+void select_kernels(KernelChoice& k, const Shape& s, const int64_t workgroups, const bool batched) {
+    const int64_t cus = s.cu_count;
+    const bool fb = s.cfg.model == CCV_MPPI_FULL_BODY;
     const char* kenv = getenv("CCV_MPPI_KERNEL");
-    h->coop = !(kenv && std::strcmp(kenv, "v1") == 0) && h->lds_window;
-    const char* forced = batched ? nullptr : kenv;
+    const bool coop = !(kenv && std::strcmp(kenv, "v1") == 0) && k.lds_window;
+    const char* forced = batched || !coop ? nullptr : kenv;
+    KernelFamily f = coop ? KernelFamily::TwoWave : KernelFamily::Plain;
     // diff-drive, steering: the four-wave kernel (noise / dynamics / distance / store wave, mppi_rollout_r4.h; round 2: -6 %
     // against the three-wave kernel at C2 and, unlike it, the same time in every process at C3).  Full body: its dynamics batch
     // needs 250 VGPRs, so the four-wave kernel is built for one wave per SIMD there, one workgroup per CU -- used up to that many
     // blocks of 64 samples (round 3; the reference's own K = 10 000 is 157 blocks), the two-wave kernel up to four per CU.
     // CCV_MPPI_KERNEL=pc / r3 / r4 force one where built (experiments, tests)
-    if (h->coop && (!fb || workgroups <= cus)) h->coop = 3;
-    if (h->coop && forced && std::strcmp(forced, "r4") == 0) h->coop = 3;
-    if (h->coop && forced && std::strcmp(forced, "r3") == 0 && !fb) h->coop = 2;
-    if (h->coop && forced && std::strcmp(forced, "pc") == 0) h->coop = 1;
+    if (coop && (!fb || workgroups <= cus)) f = KernelFamily::FourWave;
+    if (forced && std::strcmp(forced, "r4") == 0) f = KernelFamily::FourWave;
+    if (forced && std::strcmp(forced, "r3") == 0 && !fb) f = KernelFamily::ThreeWave;
+    if (forced && std::strcmp(forced, "pc") == 0) f = KernelFamily::TwoWave;
     // More blocks of 64 samples than the multi-wave kernels can hold at once (4 workgroups per CU): one wave does
     // everything for its samples (mppi_rollout_solo.h) -- the SIMDs are kept busy by independent waves then, and the
     // hand-off between the waves of a workgroup is pure loss.  Measured on 256 CUs (kernel us, multi-wave vs one-wave):
@@ -560,17 +559,19 @@ void select_kernels(ccv_mppi_handle* h, const int64_t workgroups, const bool bat
     // 117; full body 65 536: 169 vs 192; 98 304: 316 vs 291; 131 072 (C4): 374 vs 335.  CCV_MPPI_KERNEL=solo forces it.
     // (round 2, four-wave kernel against one-wave kernel, diff drive, kernel us: K = 81 920 61.0 vs 64.2; 98 304 66.0 vs 64.3;
     //  131 072 75.2 vs 71.0; 196 608 104 vs 99; steering 131 072 90.1 vs 84.0 -- the switch sits at five blocks per CU there)
-    h->solo = h->coop && !forced && workgroups > (fb ? (batched ? 1 : 4) : 5) * cus;
-    if (h->coop && forced && std::strcmp(forced, "solo") == 0) h->solo = true;
+    bool solo = coop && !forced && workgroups > (fb ? (batched ? 1 : 4) : 5) * cus;
+    if (forced && std::strcmp(forced, "solo") == 0) solo = true;
+    k.stagewise = f;
+    k.fused = solo ? KernelFamily::OneWave : f;
     // wave priorities (pc_rotate_priority): measured -4 us on the three-wave kernel (C2), -3 % on the two-wave one (C4), and
     // with four levels -5 us on the four-wave kernel (43.4 -> 38.3 us at C2)
     // four-wave kernel: the roles' levels per model (r4_prio_levels)
-    h->prio_rotate = h->coop == 3 ? r4_prio_levels(h->cfg.model) : h->coop ? 1 : 0;
+    k.prio_rotate = f == KernelFamily::FourWave ? r4_prio_levels(s.cfg.model) : coop ? 1 : 0;
     // Exact window pruning in the distance loop (pc_prune_window).  Measured on one box, kernel us off -> on: diff drive
     // K = 65 536 49.0 -> 42.7, steering 61.7 -> 57.3 (three-wave kernels).
     // (not for windows of 16 points or fewer -- the reference default H = 15: the test costs a block about what the whole loop
     //  over such a window does; per iteration 14.6 -> 14.2 us (dd), 16.0 -> 15.3 (sd), 21.3 -> 21.0 (fb) without it)
-    h->prune = (h->coop && h->H > 16) ? 1 : 0;
+    k.prune = (coop && s.H > 16) ? 1 : 0;
 }
 
 // ---- what ccv_mppi_create and ccv_mppi_batch_create share -------------------------------------------------------------
@@ -589,22 +590,24 @@ int check_device(const int device) {
 }
 
 // K, H, R of one problem; pitch: the columns of the sample axis, nblocks: the workgroups of one problem's K; the device's CUs
-void set_shape(ccv_mppi_handle* h, const ccv_mppi_config& cfg, const int pitch, const int nblocks) {
-    h->cfg = cfg;
-    h->udim = udim_of(cfg.model);
-    h->K = cfg.num_samples;
-    h->H = cfg.horizon;
-    h->R = (h->H - 1) * h->udim;
-    h->pitch = pitch;
-    h->nchunks = (h->K + kChunk - 1) / kChunk;
-    h->nblocks = nblocks;
+void set_shape(Shape& s, const ccv_mppi_config& cfg, const int pitch, const int nblocks) {
+    s.cfg = cfg;
+    s.udim = udim_of(cfg.model);
+    s.K = cfg.num_samples;
+    s.H = cfg.horizon;
+    s.R = (s.H - 1) * s.udim;
+    s.pitch = pitch;
+    s.nchunks = (s.K + kChunk - 1) / kChunk;
+    s.nblocks = nblocks;
+    // The kernel-family thresholds of select_kernels() are multiples of this count.  If the query fails, the default stays: 256,
+    // the CUs of the device the thresholds were measured on -- silently, since a device that cannot be queried fails create soon after.
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) h->cu_count = prop.multiProcessorCount;
+    if (hipGetDeviceProperties(&prop, cfg.device) == hipSuccess && prop.multiProcessorCount > 0) s.cu_count = prop.multiProcessorCount;
 }
 
 // The handle's stream, device buffers, throttle events, pinned staging and mailbox, on the current device.  On an error the
 // message is in h->err and whatever exists by then is left to release_buffers().
-int create_buffers(ccv_mppi_handle* h, const BufferCounts& n) {
+int create_buffers(Core* h, const BufferCounts& n) {
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipStreamCreate", e);
     h->stream = h->own_stream;
@@ -662,7 +665,7 @@ int create_buffers(ccv_mppi_handle* h, const BufferCounts& n) {
 }
 
 // waits for the handle's work, then gives back what create_buffers() made (and the scratch and timing events made since)
-void release_buffers(ccv_mppi_handle* h) {
+void release_buffers(Core* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream && h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -678,11 +681,21 @@ void release_buffers(ccv_mppi_handle* h) {
 }
 
 // (the caller has launched whatever was deferred)
-int set_stream(ccv_mppi_handle* h, void* hip_stream) {
+int set_stream(Core* h, void* hip_stream) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->stream = hip_stream ? (hipStream_t)hip_stream : h->own_stream;
     for (bool& u : h->throttle_used) u = false;   // marks recorded on the old stream are complete (synchronised above)
     return CCV_MPPI_OK;
+}
+
+// The largest |u| per control dimension of rows [n / udim][udim] a caller puts into the warm start: the resident plant
+// integrates u*[0], so its angle bounds must cover it (resident_bounds).  NaN sticks: no later value replaces it.
+void track_absmax(const double* u, const size_t n, const int udim, double* absmax) {
+    for (int d = 0; d < CCV_MPPI_MAX_UDIM; ++d) absmax[d] = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        const double a = std::fabs(u[i]), m = absmax[i % (size_t)udim];
+        if (a != a || (m == m && a > m)) absmax[i % (size_t)udim] = a;
+    }
 }
 
 }  // namespace ccv
@@ -706,14 +719,14 @@ int ccv_mppi_create(const ccv_mppi_config* cfg, ccv_mppi_handle** out) {
     if (int rc = check_device(cfg->device)) return rc;
     ccv_mppi_handle* h = new (std::nothrow) ccv_mppi_handle();
     if (!h) return CCV_MPPI_ERR_ALLOC;
-    set_shape(h, *cfg, round_up(cfg->num_samples, 64), (cfg->num_samples + kPcSamples - 1) / kPcSamples);
+    set_shape(*h, *cfg, round_up(cfg->num_samples, 64), (cfg->num_samples + kPcSamples - 1) / kPcSamples);
     // kernel selection (experiments): CCV_MPPI_WINDOW=scalar -> the plain kernel's scalar-load window variant
     const char* env = getenv("CCV_MPPI_WINDOW");
     h->lds_window = !(env && std::strcmp(env, "scalar") == 0);
-    select_kernels(h, h->nblocks, /*batched=*/false);
+    select_kernels(*h, *h, h->nblocks, /*batched=*/false);
     if (const char* pv = std::getenv("CCV_MPPI_PRIO")) {   // 0: off; 2 .. 5: the formula schedules; 16 + digits: a level table
         const int v = std::atoi(pv);
-        h->prio_rotate = v == 0 ? 0 : (((v >= 2 && v <= 5) || (v >= 16 && v < 16 + 256)) && h->coop == 3) ? v : h->prio_rotate;
+        h->prio_rotate = v == 0 ? 0 : (((v >= 2 && v <= 5) || (v >= 16 && v < 16 + 256)) && h->stagewise == KernelFamily::FourWave) ? v : h->prio_rotate;
     }
     // CCV_MPPI_PRUNE=0/1 forces the window pruning (experiments; results do not depend on it, tested)
     if (const char* pv = std::getenv("CCV_MPPI_PRUNE")) h->prune = std::strcmp(pv, "0") != 0;
@@ -724,6 +737,7 @@ int ccv_mppi_create(const ccv_mppi_config* cfg, ccv_mppi_handle** out) {
         ccv_mppi_destroy(h);
         return code;
     };
+    const DeviceGuard guard(cfg->device);   // (the caller's current device is put back)
     hipError_t e;
     if ((e = hipSetDevice(cfg->device)) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_NO_DEVICE, "hipSetDevice", e));
     const size_t nparts_max = (size_t)(h->nblocks > h->nchunks ? h->nblocks : h->nchunks);
@@ -777,12 +791,7 @@ int ccv_mppi_set_nominal(ccv_mppi_handle* h, const double* u) {
     if (int rc = flush_pending(h)) return rc;   // (a deferred update of the resident loop must not land on top of it)
     HIP_TRY(h, hipMemcpyAsync(h->d_nominal, u, (size_t)h->R * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    // (the resident loop's plant integrates u*[0]: its angle bounds must cover what the caller put there; NaN sticks)
-    for (int d = 0; d < CCV_MPPI_MAX_UDIM; ++d) h->nom_absmax[d] = 0.0;
-    for (int n = 0; n < h->R; ++n) {
-        const int d = n % h->udim;
-        if (!(std::fabs(u[n]) <= h->nom_absmax[d])) h->nom_absmax[d] = std::fabs(u[n]);
-    }
+    track_absmax(u, (size_t)h->R, h->udim, h->nom_absmax);
     return CCV_MPPI_OK;
 }
 
@@ -829,8 +838,7 @@ int ccv_mppi_apply_partials_enqueue(ccv_mppi_handle* h, const double* dev_partia
     if (!h || !dev_partials) return CCV_MPPI_ERR_INVALID_ARG;
     // deferred: the next fused rollout launch on this handle forms u* = V / S while it stages the warm start (one kernel
     // launch less per iteration); any other reader of the warm start triggers k_apply_partials first (flush_pending)
-    int rc = flush_pending(h);
-    if (rc) return rc;
+    if (int rc = flush_pending(h)) return rc;
     h->pending_vec = dev_partials;
     return CCV_MPPI_OK;
 }

@@ -7,23 +7,25 @@
 
 namespace ccv {
 
-void launch_rollout_solo_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
-    const dim3 grid = blocks_of_64(A, batch), block(kPcSamples);
-    if (model == CCV_MPPI_DIFF_DRIVE) {
-        if (wide) launch_at(k_rollout_solo<CCV_MPPI_DIFF_DRIVE, MODE_FUSED, true, true>, grid, block, at, A, W);
-        else launch_at(k_rollout_solo<CCV_MPPI_DIFF_DRIVE, MODE_FUSED, false, true>, grid, block, at, A, W);
-    } else if (model == CCV_MPPI_STEERING_DIFF_DRIVE) {
-        launch_at(k_rollout_solo<CCV_MPPI_STEERING_DIFF_DRIVE, MODE_FUSED, false, true>, grid, block, at, A, W);
-    } else {
-        launch_at(k_rollout_solo<CCV_MPPI_FULL_BODY, MODE_FUSED, false, true>, grid, block, at, A, W);
-    }
+template <int MODEL, bool WIDE>
+static void launch_solo_batch(const RolloutPlan& p, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
+    launch_at(k_rollout_solo<MODEL, MODE_FUSED, WIDE, true>, blocks_of_64(A, p.batch), dim3(kPcSamples), at, A, W);
 }
 
-void launch_rollout_r4_fb_batch(int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
-    constexpr int MODEL = CCV_MPPI_FULL_BODY;
-    const dim3 grid = blocks_of_64(A, batch), block(kR4Waves * 64);
-    if ((A.H - 1) % kTU >= kPartialMin) launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, true, true>, grid, block, at, A, W);
-    else launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, false, true>, grid, block, at, A, W);
+void launch_batch(const RolloutPlan& p, bool tail, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
+    if (p.family == KernelFamily::FourWave) {   // full body
+        constexpr int MODEL = CCV_MPPI_FULL_BODY;
+        const dim3 grid = blocks_of_64(A, p.batch), block(kR4Waves * 64);
+        if (tail) launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, true, true>, grid, block, at, A, W);
+        else launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, false, true>, grid, block, at, A, W);
+    } else if (p.model == CCV_MPPI_DIFF_DRIVE) {
+        if (p.wide) launch_solo_batch<CCV_MPPI_DIFF_DRIVE, true>(p, at, A, W);
+        else launch_solo_batch<CCV_MPPI_DIFF_DRIVE, false>(p, at, A, W);
+    } else if (p.model == CCV_MPPI_STEERING_DIFF_DRIVE) {
+        launch_solo_batch<CCV_MPPI_STEERING_DIFF_DRIVE, false>(p, at, A, W);
+    } else {
+        launch_solo_batch<CCV_MPPI_FULL_BODY, false>(p, at, A, W);
+    }
 }
 
 }  // namespace ccv

@@ -5,29 +5,22 @@
 namespace ccv {
 
 template <int MODEL>
-static void launch_plain_model(bool philox, bool lds_window, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
-    const dim3 grid((unsigned)((A.K + kBlock - 1) / kBlock)), block(kBlock);
-    if (philox) {
-        if (lds_window) launch_at(k_rollout_cost<MODEL, SRC_PHILOX, true>, grid, block, at, A, W);
+static void launch_plain_model(const RolloutPlan& p, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
+    const dim3 grid = blocks_plain(A, p.batch), block(kBlock);
+    if (p.batch) launch_at(k_rollout_cost<MODEL, SRC_PHILOX, true, true>, grid, block, at, A, W);
+    else if (p.mode == MODE_FUSED) {   // device noise; the stage-wise modes read the controls from the buffer
+        if (p.lds_window) launch_at(k_rollout_cost<MODEL, SRC_PHILOX, true>, grid, block, at, A, W);
         else launch_at(k_rollout_cost<MODEL, SRC_PHILOX, false>, grid, block, at, A, W);
     } else {
-        if (lds_window) launch_at(k_rollout_cost<MODEL, SRC_BUFFER, true>, grid, block, at, A, W);
+        if (p.lds_window) launch_at(k_rollout_cost<MODEL, SRC_BUFFER, true>, grid, block, at, A, W);
         else launch_at(k_rollout_cost<MODEL, SRC_BUFFER, false>, grid, block, at, A, W);
     }
 }
 
-void launch_rollout_plain(int model, bool philox, bool lds_window, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
-    if (model == CCV_MPPI_DIFF_DRIVE) launch_plain_model<CCV_MPPI_DIFF_DRIVE>(philox, lds_window, at, A, W);
-    else if (model == CCV_MPPI_STEERING_DIFF_DRIVE) launch_plain_model<CCV_MPPI_STEERING_DIFF_DRIVE>(philox, lds_window, at, A, W);
-    else launch_plain_model<CCV_MPPI_FULL_BODY>(philox, lds_window, at, A, W);
-}
-
-// batch handles: grid (workgroups per instance, instances)
-void launch_rollout_plain_batch(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
-    const dim3 grid((unsigned)((A.K + kBlock - 1) / kBlock), (unsigned)batch), block(kBlock);
-    if (model == CCV_MPPI_DIFF_DRIVE) launch_at(k_rollout_cost<CCV_MPPI_DIFF_DRIVE, SRC_PHILOX, true, true>, grid, block, at, A, W);
-    else if (model == CCV_MPPI_STEERING_DIFF_DRIVE) launch_at(k_rollout_cost<CCV_MPPI_STEERING_DIFF_DRIVE, SRC_PHILOX, true, true>, grid, block, at, A, W);
-    else launch_at(k_rollout_cost<CCV_MPPI_FULL_BODY, SRC_PHILOX, true, true>, grid, block, at, A, W);
+void launch_plain(const RolloutPlan& p, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
+    if (p.model == CCV_MPPI_DIFF_DRIVE) launch_plain_model<CCV_MPPI_DIFF_DRIVE>(p, at, A, W);
+    else if (p.model == CCV_MPPI_STEERING_DIFF_DRIVE) launch_plain_model<CCV_MPPI_STEERING_DIFF_DRIVE>(p, at, A, W);
+    else launch_plain_model<CCV_MPPI_FULL_BODY>(p, at, A, W);
 }
 
 void launch_sample(int model, hipStream_t stream, const RolloutArgs& A) {

@@ -4,8 +4,8 @@
 
 namespace ccv {
 
-void launch_rollout_solo_fb(const LaunchAt& at, const RolloutArgs& A, const Window& W) {
-    launch_at(k_rollout_solo<CCV_MPPI_FULL_BODY, MODE_FUSED>, blocks_of_64(A), dim3(kPcSamples), at, A, W);
+void launch_solo_fb(const RolloutPlan&, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
+    launch_at(k_rollout_solo<CCV_MPPI_FULL_BODY, MODE_FUSED>, blocks_of_64(A, 0), dim3(kPcSamples), at, A, W);
 }
 
 }  // namespace ccv

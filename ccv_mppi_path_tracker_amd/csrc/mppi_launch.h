@@ -1,7 +1,9 @@
-// Launchers of the rollout kernel families.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip,
-// k_r4_fb.hip, k_pc_fb.hip, k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip: batch forms): hipcc spends over a minute on all instantiations in one file, the
-// units compile side by side (build.py).  The C ABI selects the family (select_kernels(), ccv_mppi_capi.hip) and
-// calls these (launch_rollout_model() there; batch_launch(), capi_batch.hip).
+// Launching a rollout kernel.  Which kernel a launch runs is a value, RolloutPlan; launch_rollout() (mppi_launch.hip) is a
+// switch over it.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip, k_r4_fb.hip, k_pc_fb.hip,
+// k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip: batch forms): hipcc spends over a minute on all
+// instantiations in one file, the units compile side by side (build.py), and an instantiation placed beside others can change
+// the code generated for those.  The C ABI picks the family at create (select_kernels(), ccv_mppi_capi.hip) and makes the plan
+// of each launch from it (make_plan(), capi_internal.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -17,30 +19,34 @@ struct LaunchAt {
     hipEvent_t ev_start, ev_stop;
 };
 
-// mode: MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h).  K, H, ... come from the arguments themselves.
-void launch_rollout_r4(int model, int mode, bool wide, const LaunchAt& at, const RolloutArgs& A, const Window& W);   // all models
-void launch_rollout_r3(int model, int mode, const LaunchAt& at, const RolloutArgs& A, const Window& W);              // dd, sd
-void launch_rollout_pc(int model, int mode, const LaunchAt& at, const RolloutArgs& A, const Window& W);              // all models
-void launch_rollout_solo(int model, bool wide, const LaunchAt& at, const RolloutArgs& A, const Window& W);           // fused only
-// the plain one-sample-per-lane kernel: philox = device noise (fused iteration) or controls read from the buffer
-void launch_rollout_plain(int model, bool philox, bool lds_window, const LaunchAt& at, const RolloutArgs& A, const Window& W);
-void launch_sample(int model, hipStream_t stream, const RolloutArgs& A);
-// batch handles (the fused iteration of `batch` instances of A.K samples each; A.frame = their records, batch_view): the
-// four-wave kernel, the one-wave kernel and the plain kernel (unbounded headings)
-void launch_rollout_r4_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
-void launch_rollout_solo_batch(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
-void launch_rollout_plain_batch(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
-// ... and their forms with per-instance parameters (k_batch_varied.hip; the records' heads point at the parameter table)
-void launch_rollout_r4_batch_varied(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
-void launch_rollout_solo_batch_varied(int model, bool wide, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
-void launch_rollout_plain_batch_varied(int model, int batch, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+// Plain: one sample per lane, OCML sincos (unbounded headings, CCV_MPPI_KERNEL=v1); TwoWave: mppi_rollout_pc.h; ThreeWave:
+// mppi_rollout_r3.h (diff drive, steering); FourWave: mppi_rollout_r4.h; OneWave: mppi_rollout_solo.h (fused iteration only)
+enum class KernelFamily : int { Plain, TwoWave, ThreeWave, FourWave, OneWave };
 
+struct RolloutPlan {
+    KernelFamily family;
+    int model;
+    int mode;          // MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h)
+    bool wide;         // diff drive, fused, four- or one-wave: a turn per step beyond pi/4 -> sin / cos of every heading in full
+    int batch;         // instances of a batch handle's launch (A.frame = their records, batch_view); 0 = a single handle
+    bool varied;       // batch: per-instance parameters (the records' heads point at the parameter table)
+    bool lds_window;   // Plain: the window from LDS (false: CCV_MPPI_WINDOW=scalar)
+};
+
+// K, H, ... come from the arguments themselves.  Plain: device noise in the fused iteration, else the controls of the buffer.
+// Built: batches -- Plain, FourWave, OneWave, fused; ThreeWave -- not full body; OneWave -- fused.
+void launch_rollout(const RolloutPlan& plan, const LaunchAt& at, const RolloutArgs& A, const Window& W);
+void launch_sample(int model, hipStream_t stream, const RolloutArgs& A);
+
+// ---- for the kernel units --------------------------------------------------------------------------------------------
 template <class KERNEL>
 inline void launch_at(KERNEL kernel, const dim3 grid, const dim3 block, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
     if (at.ev_start) hipExtLaunchKernelGGL(kernel, grid, block, 0, at.stream, at.ev_start, at.ev_stop, 0, A, W);
     else hipLaunchKernelGGL(kernel, grid, block, 0, at.stream, A, W);
 }
-inline dim3 blocks_of_64(const RolloutArgs& A) { return dim3((unsigned)((A.K + 63) / 64)); }
-inline dim3 blocks_of_64(const RolloutArgs& A, const int batch) { return dim3((unsigned)batch * (unsigned)((A.K + 63) / 64)); }
+// workgroups of 64 samples: a single handle's K, or `batch` instances of it on one axis
+inline dim3 blocks_of_64(const RolloutArgs& A, const int batch) { return dim3((unsigned)(batch ? batch : 1) * (unsigned)((A.K + 63) / 64)); }
+// the plain kernel's grid: (workgroups per instance, instances)
+inline dim3 blocks_plain(const RolloutArgs& A, const int batch) { return dim3((unsigned)((A.K + kBlock - 1) / kBlock), (unsigned)(batch ? batch : 1)); }
 
 }  // namespace ccv

@@ -303,6 +303,33 @@ def test_resident_batch_refusals_move_nothing(monkeypatch):
     v1.close()
 
 
+def test_resident_batch_refuses_a_nan_command_in_the_warm_start():
+    """As the single handle's test: a NaN in row 0 of one instance's warm start, finite values everywhere else, is refused
+    with the state error before any pose moves."""
+    p = configs.diff_drive_defaults(256, 20)
+    B = 3
+    s0, seeds = start_poses(p, B)
+    bat = BatchController(p, B)
+    bat.resident_set_paths([path_of(b) for b in range(B)])
+    bat.resident_set_poses(s0, seeds)
+    bat.resident_step_enqueue(p.dt, 0, advance=False)
+    u = np.full((B, p.horizon - 1, p.udim), 0.1)
+    u[1, 0, 1] = np.nan
+    bat.set_nominal(u)
+    before = bat.resident_read()
+    with pytest.raises(MPPIError) as e:
+        bat.resident_step_enqueue(p.dt, 1)
+    assert e.value.code == capi.ERR_STATE
+    after = bat.resident_read()
+    np.testing.assert_array_equal(before[0], after[0])
+    np.testing.assert_array_equal(before[1], after[1])
+    assert before[5] == after[5] == 1
+    bat.set_nominal(np.full((B, p.horizon - 1, p.udim), 0.1))
+    bat.resident_step_enqueue(p.dt, 1)
+    assert np.all(np.isfinite(bat.resident_read()[0]))
+    bat.close()
+
+
 def test_resident_batch_mixing_and_flush_points():
     """resident steps -> get_nominal -> iterate (host records) -> resident steps -> set_nominal -> resident steps ->
     read_costs: at every read the u* (and pose) of the same sequence with synchronize() after every step, where no update is

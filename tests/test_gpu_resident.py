@@ -324,6 +324,31 @@ def test_resident_refuses_unbounded_angles_and_commands():
     assert np.all(np.isfinite(gs.get_nominal()))
 
 
+def test_resident_refuses_a_nan_command_in_the_warm_start():
+    """A NaN in row 0 of a caller's warm start is the command u*[0] of the next advancing step: refused with the state error
+    before the pose moves, however many finite values of the same control dimension follow it (the bound on |u*| keeps the
+    NaN)."""
+    p = configs.diff_drive_defaults(256, 30)
+    px, py = amd.make_path("straight")
+    g = MPPIController(p)
+    g.resident_set_path(px, py)
+    g.resident_set_pose([0.3, 0.1, 0.2])
+    g.resident_step_enqueue(p.dt, 1, 0, advance=False)
+    u = np.full((p.horizon - 1, p.udim), 0.1)
+    u[0, 1] = np.nan
+    g.set_nominal(u)
+    before = g.resident_read()
+    with pytest.raises(MPPIError) as e:
+        g.resident_step_enqueue(p.dt, 1, 1, advance=True)
+    assert e.value.code == capi.ERR_STATE
+    after = g.resident_read()
+    np.testing.assert_array_equal(before[0], after[0])
+    assert before[5] == after[5] == 1
+    g.set_nominal(np.full((p.horizon - 1, p.udim), 0.1))
+    g.resident_step_enqueue(p.dt, 1, 1, advance=True)
+    assert np.all(np.isfinite(g.resident_read()[0]))
+
+
 def test_resident_closed_loop_at_full_c2_size():
     """The device-resident closed loop at the headline size (C2: K = 65 536, T = 50, sinusoid), as bench.py's closed_loop leg
     runs it: 512 ticks back to back with no host data, the pose fed back every tick.  The robot must track the course
