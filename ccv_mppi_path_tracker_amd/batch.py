@@ -36,9 +36,10 @@ def check_shared(seq, first=None):
 
 class BatchController:
     """`batch` controllers on one device: one MPPIParams shared by all, or a sequence of `batch` MPPIParams that agree in
-    SHARED_FIELDS (per-instance sigma, lambda, v_ref, bounds and weights; K = num_samples per instance)."""
+    SHARED_FIELDS (per-instance sigma, lambda, v_ref, bounds and weights; K = num_samples per instance).  min_shift: the
+    underflow-safe weights from the first iteration on (set_min_shift)."""
 
-    def __init__(self, params, batch, device=0, num_samples=None, no_state_store=False):
+    def __init__(self, params, batch, device=0, num_samples=None, no_state_store=False, min_shift=False):
         seq = None
         if not isinstance(params, MPPIParams):
             seq = list(params)
@@ -64,6 +65,8 @@ class BatchController:
             raise MPPIError(rc, "ccv_mppi_batch_create failed (bad arguments, or no usable MI355X/HIP device) -- there is no CPU fallback")
         if seq is not None:
             self.set_params(seq)
+        if min_shift:
+            self.set_min_shift(True)
 
     # ---- plumbing ----
     def _check(self, rc):
@@ -121,6 +124,16 @@ class BatchController:
                                v_weight=c.v_weight, zmp_weight=c.zmp_weight, roll_v_weight=c.roll_v_weight,
                                back_weight=c.back_weight, yaw_weight=c.yaw_weight))
         return out
+
+    # ---- underflow-safe weights (ccv_mppi_batch_set_min_shift) ----
+    def set_min_shift(self, on=True):
+        """on: every instance weighs its samples relative to its own smallest cost, w = exp(-(c - min c) / lambda_b) -- a finite
+        cost always gives a finite u*; off: back to the reference's weights.  Flushes a pending resident update; warm starts,
+        paths, poses and per-instance parameters stay."""
+        self._check(self.lib.ccv_mppi_batch_set_min_shift(self._h, 1 if on else 0))
+
+    def get_min_shift(self):
+        return bool(self.lib.ccv_mppi_batch_get_min_shift(self._h))
 
     # ---- warm starts [B][H-1][u_dim] ----
     def set_nominal(self, u):

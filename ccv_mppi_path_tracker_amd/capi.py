@@ -26,6 +26,7 @@ FLAG_ROLL_OFF, FLAG_STEER_OFF, FLAG_MIN_SHIFT, FLAG_NO_STATE_STORE = 0x1, 0x2, 0
 BATCH_MAX_SAMPLES = 1 << 29
 BATCH_KERNEL_PLAIN, BATCH_KERNEL_ONE_WAVE, BATCH_KERNEL_FOUR_WAVE, BATCH_KERNEL_WIDE = 0, 1, 4, 16
 BATCH_KERNEL_VARIED = 32
+BATCH_KERNEL_SHIFT = 64
 BATCH_TRACE_ROWS = 1024
 
 
@@ -106,6 +107,8 @@ SIGNATURES = {
     "ccv_mppi_batch_get_nominal": (C.c_int, [_H, _dp]),
     "ccv_mppi_batch_set_params": (C.c_int, [_H, C.POINTER(Config)]),
     "ccv_mppi_batch_get_params": (C.c_int, [_H, C.POINTER(Config)]),
+    "ccv_mppi_batch_set_min_shift": (C.c_int, [_H, C.c_int32]),
+    "ccv_mppi_batch_get_min_shift": (C.c_int, [_H]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),

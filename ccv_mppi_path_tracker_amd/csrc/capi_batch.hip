@@ -14,7 +14,42 @@ int batch_kernel_code(const RolloutPlan& p) {
     const int family = p.family == KernelFamily::Plain     ? CCV_MPPI_BATCH_KERNEL_PLAIN
                        : p.family == KernelFamily::OneWave ? CCV_MPPI_BATCH_KERNEL_ONE_WAVE
                                                            : CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
-    return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0);
+    return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0) |
+           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0);
+}
+
+// whether the kernels read the parameter table: per-instance parameters, or shifted weights (B copies of cfg in the table then)
+bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift; }
+
+// the parameter table [B] on the device from B configurations (null: B copies of the creation configuration).  The caller has
+// flushed and synchronised: a queued rollout or prologue may still read the old table.
+int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
+    const int B = bh->B;
+    std::vector<BatchParams> rows((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        RolloutArgs A;
+        std::memset(&A, 0, sizeof(A));
+        fill_params(cfgs ? cfgs[b] : bh->cfg, bh->fast_clamp_allowed, A);   // (per instance: the clamp form of its own sigma and bounds)
+        BatchParams& P = rows[(size_t)b];
+        std::memset(&P, 0, sizeof(P));
+        P.sigma = A.sigma;
+        P.lambda = A.lambda;
+        P.v_ref = A.v_ref;
+        for (int d = 0; d < 5; ++d) {
+            P.umin[d] = A.umin[d];
+            P.umax[d] = A.umax[d];
+        }
+        P.w_path = A.w_path;
+        P.w_v = A.w_v;
+        P.w_zmp = A.w_zmp;
+        P.w_rollv = A.w_rollv;
+        P.w_back = A.w_back;
+        P.w_yaw = A.w_yaw;
+        P.fast_clamp = A.fast_clamp;
+    }
+    if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
+    HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
+    return CCV_MPPI_OK;
 }
 
 int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
@@ -63,7 +98,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
         hd->K = b * bh->kpad + bh->K;
         hd->k_offset = -b * bh->kpad;
         hd->nominal = bh->d_nominal + (size_t)b * bh->R;
-        if (bh->varied) hd->params = bh->d_params + b;
+        if (uses_table(bh)) hd->params = bh->d_params + b;
         double* win = rec + (size_t)b * bh->rec_doubles + kBatchHeadDoubles;
         window_coeffs(H, x_ref + (size_t)b * H, y_ref + (size_t)b * H, hd->x0[0], hd->x0[1], win, win + H, win + 2 * H);
         if (trig != kTrigUnsafe) {
@@ -82,7 +117,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // of the fused kernels waits in bh->fin_args for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
-    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied);
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift);
     const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -99,7 +134,14 @@ int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool 
     bh->last_kernel = batch_kernel_code(plan);
     HIP_TRY(bh, hipGetLastError());
     int nparts = bh->nblocks;
+    const bool shift = plan.shift && !plain;   // (the update over block-relative partials)
     if (plain) {   // the plain kernel stores w and the controls: the single handle's unfused reduction, instance by instance
+        if (plan.shift) {   // ... over weights re-formed around every instance's exact minimum cost (the single handle's MIN_SHIFT)
+            if (!bh->d_cmin) HIP_TRY(bh, hipMalloc(&bh->d_cmin, (size_t)B * sizeof(double)));
+            hipLaunchKernelGGL(k_min_cost_batch, dim3(B), dim3(1024), 0, bh->stream, bh->d_cost, bh->K, bh->kpad, bh->d_cmin);
+            hipLaunchKernelGGL(k_reweight_batch, dim3((bh->K + kBlock - 1) / kBlock, B), dim3(kBlock), 0, bh->stream, bh->d_cost,
+                               bh->d_cmin, bh->d_params, bh->K, bh->kpad, bh->d_w);
+        }
         hipLaunchKernelGGL(k_update_partials_batch, dim3(bh->nchunks, bh->R + 1, B), dim3(kBlock), 0, bh->stream, update_args(bh), bh->kpad);
         nparts = bh->nchunks;
     }
@@ -110,11 +152,15 @@ int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool 
     const bool mail_fits = (size_t)B * (bh->R + 4) <= (size_t)(CCV_MPPI_MAX_HORIZON - 1) * CCV_MPPI_MAX_UDIM + 4;
     if (bh->want_mail && bh->use_mail && (mail_fits || bh->mail_any_size)) post_to_mail(*bh, F);
     bh->want_mail = false;
+    bh->shift_result = shift;
     if (defer && !plain && !bh->timed_now && !F.mail) {
         bh->fin_args = F;
+        bh->fin_shift = shift ? bh->d_params : nullptr;
+        bh->fin_K = bh->K;
         bh->fin_pending = true;
     } else {
-        hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(bh->R), B), dim3(kBlock), 0, bh->stream, F, plain ? 0 : 1);
+        if (shift) hipLaunchKernelGGL(k_finalize_batch_shift, dim3(finalize_blocks(bh->R), B), dim3(kBlock), 0, bh->stream, F, bh->d_params, bh->K);
+        else hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(bh->R), B), dim3(kBlock), 0, bh->stream, F, plain ? 0 : 1);
         HIP_TRY(bh, hipGetLastError());
     }
     HIP_TRY(bh, timing_end(*bh, bh->stream));
@@ -213,7 +259,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
-    void* bufs[] = {bh->d_rec, bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace, bh->d_params};
+    void* bufs[] = {bh->d_rec, bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace, bh->d_params, bh->d_cmin};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete bh;
@@ -261,8 +307,12 @@ int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
 int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     const int B = bh->B;
-    if (!cfgs) {   // back to the creation configuration and the shared kernels
+    if (!cfgs) {   // back to the creation configuration; the shared kernels, or in shifted-weight mode B copies in the table
         if (int rc = batch_flush(bh)) return rc;
+        if (bh->min_shift) {
+            HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+            if (int rc = upload_params(bh, nullptr)) return rc;
+        }
         bh->varied = false;
         bh->cfgs.clear();
         return CCV_MPPI_OK;
@@ -286,36 +336,32 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
             return fail(bh, CCV_MPPI_ERR_INVALID_ARG, msg);
         }
     }
-    std::vector<BatchParams> rows((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        RolloutArgs A;
-        std::memset(&A, 0, sizeof(A));
-        fill_params(cfgs[b], bh->fast_clamp_allowed, A);   // (per instance: the clamp form of its own sigma and bounds)
-        BatchParams& P = rows[(size_t)b];
-        std::memset(&P, 0, sizeof(P));
-        P.sigma = A.sigma;
-        P.lambda = A.lambda;
-        P.v_ref = A.v_ref;
-        for (int d = 0; d < 5; ++d) {
-            P.umin[d] = A.umin[d];
-            P.umax[d] = A.umax[d];
-        }
-        P.w_path = A.w_path;
-        P.w_v = A.w_v;
-        P.w_zmp = A.w_zmp;
-        P.w_rollv = A.w_rollv;
-        P.w_back = A.w_back;
-        P.w_yaw = A.w_yaw;
-        P.fast_clamp = A.fast_clamp;
-    }
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the old table)
-    if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
-    HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
+    if (int rc = upload_params(bh, cfgs)) return rc;
     bh->cfgs.assign(cfgs, cfgs + B);
     bh->varied = true;
     return CCV_MPPI_OK;
 }
+
+// ---- shifted weights -----------------------------------------------------------------------------------------------------
+
+int ccv_mppi_batch_set_min_shift(ccv_mppi_batch* bh, int32_t on) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const bool want = on != 0;
+    if (want == bh->min_shift) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;   // (the pending update is the old mode's)
+    if (want && !bh->varied) {                 // the SHIFT kernels read the table: B copies of the creation configuration
+        HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+        if (int rc = upload_params(bh, nullptr)) return rc;
+    }
+    bh->min_shift = want;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_get_min_shift(const ccv_mppi_batch* bh) { return bh ? (bh->min_shift ? 1 : 0) : CCV_MPPI_ERR_INVALID_ARG; }
 
 int ccv_mppi_batch_get_params(ccv_mppi_batch* bh, ccv_mppi_config* out) {
     if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
@@ -357,8 +403,14 @@ int ccv_mppi_batch_read_weights(ccv_mppi_batch* bh, int32_t instance, int32_t fi
     if (first < 0 || count < 0 || (int64_t)first + count > bh->K) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "range exceeds num_samples");
     if (count == 0) return CCV_MPPI_OK;
     HIP_TRY(bh, ensure_scratch(*bh, (size_t)count * sizeof(double)));
-    hipLaunchKernelGGL(k_normalise_weights, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, bh->stream,
-                       bh->d_w + (size_t)instance * bh->kpad, bh->d_stats + (size_t)instance * 4, first, count, bh->d_scratch);
+    const dim3 grid((count + kBlock - 1) / kBlock);
+    if (bh->shift_result)   // (the last launch left block-relative weights: the SHIFT rollout kernels)
+        hipLaunchKernelGGL(k_normalise_weights_shift, grid, dim3(kBlock), 0, bh->stream, bh->d_w + (size_t)instance * bh->kpad,
+                           bh->d_statpart + (size_t)instance * bh->nblocks * 3, bh->d_stats + (size_t)instance * 4,
+                           batch_cfg(bh, instance).lambda, first, count, bh->d_scratch);
+    else
+        hipLaunchKernelGGL(k_normalise_weights, grid, dim3(kBlock), 0, bh->stream, bh->d_w + (size_t)instance * bh->kpad,
+                           bh->d_stats + (size_t)instance * 4, first, count, bh->d_scratch);
     HIP_TRY(bh, hipGetLastError());
     HIP_TRY(bh, hipMemcpyAsync(out, bh->d_scratch, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));
@@ -503,11 +555,12 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     // (varied: the prologue takes each instance's v_ref from the parameter table and points its record's head at its row)
     if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
         const dim3 grid(finalize_blocks(bh->fin_args.R) + 1, B);
-        if (bh->varied) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G, bh->d_params);
+        if (bh->fin_shift) hipLaunchKernelGGL(k_finalize_advance_batch_shift, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G, bh->d_params);
+        else if (uses_table(bh)) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G, bh->d_params);
         else hipLaunchKernelGGL(k_finalize_advance_batch, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G);
         bh->fin_pending = false;
     } else {
-        if (bh->varied) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);
+        if (uses_table(bh)) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);
         else hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G);
     }
     HIP_TRY(bh, hipGetLastError());

@@ -112,6 +112,8 @@ struct Timing {
 struct DeferredUpdate {
     bool fin_pending = false;
     FinalizeArgs fin_args{};
+    const BatchParams* fin_shift = nullptr;   // a batch's shifted-weight update (k_finalize_batch_shift): its parameter table
+    int fin_K = 0;                            // ... and the instance's K
 };
 
 struct Core : Shape, KernelChoice, DeviceBuffers, Mailbox, Throttle, Timing, DeferredUpdate {
@@ -196,7 +198,12 @@ struct ccv_mppi_batch : Core {
     // pointer in its record's head; without them (varied = false) every instance has cfg and the shared kernels run
     bool varied = false;
     std::vector<ccv_mppi_config> cfgs;      // [B] the instances' configurations while varied
-    BatchParams* d_params = nullptr;        // [B], allocated at the first _set_params, freed at destroy
+    BatchParams* d_params = nullptr;        // [B], allocated at the first _set_params or _set_min_shift(1), freed at destroy
+    // shifted weights (ccv_mppi_batch_set_min_shift): the SHIFT rollout kernels and the _shift update kernels, always over the
+    // parameter table -- B copies of cfg in it while `varied` is false
+    bool min_shift = false;
+    double* d_cmin = nullptr;               // [B]: the plain family's exact instance minima (k_min_cost_batch)
+    bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
 };
 
 namespace ccv {
@@ -260,9 +267,11 @@ inline bool has_wide_form(const KernelChoice& k, const int mode) {
 }
 // The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
 // (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
-inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied) {
+// shift (a batch in shifted-weight mode): always with the per-instance-parameter kernels.
+inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied,
+                             const bool shift = false) {
     const KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
-    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied, k.lds_window != 0};
+    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift, shift, k.lds_window != 0};
 }
 
 RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);   // a single handle's
@@ -272,7 +281,7 @@ void fill_params(const ccv_mppi_config& c, bool fast_clamp_allowed, RolloutArgs&
 void fill_args(const Core* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed, uint64_t iter);
 void window_coeffs(int H, const double* x_ref, const double* y_ref, double px, double py, double* a, double* b, double* c);
 void track_absmax(const double* u, size_t n, int udim, double* absmax);
-int flush_finalize(Core* h, int batch);     // the deferred update now: k_finalize, or k_finalize_batch of `batch` instances
+int flush_finalize(Core* h, int batch);     // the deferred update now: k_finalize, or k_finalize_batch[_shift] of `batch` instances
 int flush_division(ccv_mppi_handle* h);     // the deferred division now: k_apply_partials
 int flush_pending(ccv_mppi_handle* h);      // both, in that order
 int materialize_controls(ccv_mppi_handle* h);

@@ -109,7 +109,8 @@ void window_coeffs(const int H, const double* x_ref, const double* y_ref, const 
 int flush_finalize(Core* h, const int batch) {
     if (!h->fin_pending) return CCV_MPPI_OK;
     const unsigned blocks = finalize_blocks(h->fin_args.R);
-    if (batch) hipLaunchKernelGGL(k_finalize_batch, dim3(blocks, batch), dim3(kBlock), 0, h->stream, h->fin_args, 1);
+    if (batch && h->fin_shift) hipLaunchKernelGGL(k_finalize_batch_shift, dim3(blocks, batch), dim3(kBlock), 0, h->stream, h->fin_args, h->fin_shift, h->fin_K);
+    else if (batch) hipLaunchKernelGGL(k_finalize_batch, dim3(blocks, batch), dim3(kBlock), 0, h->stream, h->fin_args, 1);
     else hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(kBlock), 0, h->stream, h->fin_args);
     h->fin_pending = false;
     HIP_TRY(h, hipGetLastError());

@@ -213,6 +213,148 @@ __global__ __launch_bounds__(kBlock) void k_finalize_batch(FinalizeArgs A, const
     finalize_rows(A, stride);
 }
 
+// ---- batch handles, shifted weights (ccv_mppi_batch_set_min_shift) ------------------------------------------------------
+// The SHIFT rollout kernels (pc_shifted_weight) leave, per workgroup g of 64 samples, sums of weights relative to the
+// workgroup's own minimum cost m_g = statpart[g][0].  Relative to the instance's minimum m = min_g m_g the workgroup's sums
+// carry the scale s_g = exp(-(m_g - m) / lambda): the best sample's weight and its workgroup's scale are exactly 1, so S >= 1.
+// Sums of two rows of n scaled partials, columns and order as lane_partial_sum2.  Up to 1024 columns the three loads of a
+// column (m_g, both rows) are all issued before the first compare: one memory latency for the minimum and the sums together;
+// beyond, the minimum takes passes of its own first (all loads of a pass before its first compare) and the later columns
+// are fetched again.  m_g = +inf (no finite cost in the workgroup): s_g = 0 against partials of 0; m = +inf: NaN.
+__device__ __forceinline__ void shift_scaled_sum2(const double* row_a, const double* row_b, const double* statpart,
+                                                  const double lambda, const int n, const int lane, double& sum_a,
+                                                  double& sum_b, double& m_out) {
+    double va[16], vb[16], mg[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int c = min(lane + 64 * i, n - 1);   // (clamped: the loads carry no branch)
+        mg[i] = statpart[c * 3 + 0];
+        va[i] = row_a[c];
+        vb[i] = row_b[c];
+    }
+    double mn = INFINITY;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mn = fmin(mn, lane + 64 * i < n ? mg[i] : INFINITY);
+    for (int c0 = 1024; c0 < n; c0 += 1024) {
+        double a[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = statpart[min(c0 + lane + 64 * i, n - 1) * 3 + 0];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mn = fmin(mn, c0 + lane + 64 * i < n ? a[i] : INFINITY);
+    }
+    const double m = wave_min(mn);
+    double acc_a = 0.0, acc_b = 0.0;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        if (c0 != 0) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int c = min(c0 + lane + 64 * i, n - 1);
+                mg[i] = statpart[c * 3 + 0];
+                va[i] = row_a[c];
+                vb[i] = row_b[c];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const bool in = c0 + lane + 64 * i < n;
+            const double sg = exp(-(mg[i] - m) / lambda);
+            acc_a += in ? sg * va[i] : 0.0;
+            acc_b += in ? sg * vb[i] : 0.0;
+        }
+    }
+    sum_a = acc_a;
+    sum_b = acc_b;
+    m_out = m;
+}
+
+// the statistics wave in shifted-weight mode: min_cost = m, max_cost, and the zero-weight count -- the live samples whose
+// block-relative weight is 0 in the workgroups whose scale is not 0 (statpart[g][2]), plus every live sample (64, or what is
+// left of K in the last workgroup) of a workgroup whose scale is 0
+__device__ __forceinline__ void finalize_cost_stats_shift(const FinalizeArgs& A, const double lambda, const int K, const int lane) {
+    double mn = INFINITY;
+    for (int c0 = 0; c0 < A.nchunks; c0 += 1024) {
+        double a[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = A.statpart[min(c0 + lane + 64 * i, A.nchunks - 1) * 3 + 0];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mn = fmin(mn, c0 + lane + 64 * i < A.nchunks ? a[i] : INFINITY);
+    }
+    const double m = wave_min(mn);
+    double mx = -INFINITY, nz = 0.0;
+    for (int c0 = 0; c0 < A.nchunks; c0 += 1024) {
+        double a[16], b[16], z[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = min(c0 + lane + 64 * i, A.nchunks - 1);
+            a[i] = A.statpart[c * 3 + 0];
+            b[i] = A.statpart[c * 3 + 1];
+            z[i] = A.statpart[c * 3 + 2];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = c0 + lane + 64 * i;
+            const bool in = c < A.nchunks;
+            const double sg = exp(-(a[i] - m) / lambda);
+            const double all = (double)min(kPcSamples, K - c * kPcSamples);
+            mx = fmax(mx, in ? b[i] : -INFINITY);
+            nz += in ? (sg == 0.0 ? all : z[i]) : 0.0;
+        }
+    }
+    mx = wave_max(mx);
+    nz = wave_sum(nz);
+    if (lane == 0) {
+        A.stats[1] = m;
+        A.stats[2] = mx;
+        A.stats[3] = nz;
+        if (A.mail) {
+            mail_post(A, A.R + 1, m);
+            mail_post(A, A.R + 2, mx);
+            mail_post(A, A.R + 3, nz);
+        }
+    }
+}
+
+// finalize_rows over scaled partials (stride: the row pitch of the fused partials)
+__device__ __forceinline__ void finalize_rows_shift(const FinalizeArgs& A, const size_t stride, const double lambda, const int K) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (n > A.R) {
+        if (n == A.R + 1) finalize_cost_stats_shift(A, lambda, K, lane);
+        return;
+    }
+    const int nrow = n < A.R ? n : A.R;
+    double s, v, m;
+    shift_scaled_sum2(A.partial + (size_t)A.R * stride, A.partial + (size_t)nrow * stride, A.statpart, lambda, A.nchunks, lane, s, v, m);
+    s = wave_sum(s);
+    v = wave_sum(v);
+    if (n < A.R && lane == 0) {
+        A.vec[1 + n] = v;
+        if (A.normalise) {
+            const double q = v / s;
+            A.nominal[n] = q;
+            if (A.mail) mail_post(A, n, q);
+        }
+    }
+    if (n == A.R && lane == 0) {
+        A.vec[0] = s;
+        A.stats[0] = s;
+        if (A.mail) mail_post(A, A.R, s);
+    }
+}
+// k_finalize_batch over the SHIFT rollout kernels' partials (always the fused layout): grid (finalize_blocks(R), B);
+// P: the parameter table (instance y's lambda), K: samples per instance
+__global__ __launch_bounds__(kBlock) void k_finalize_batch_shift(FinalizeArgs A, const BatchParams* P, const int K) {
+    const size_t b = blockIdx.y;
+    const size_t stride = (size_t)gridDim.y * A.nchunks;
+    A.partial += b * A.nchunks;
+    A.statpart += b * (size_t)A.nchunks * 3;
+    A.nominal += b * A.R;
+    A.vec += b * (size_t)(A.R + 1);
+    A.stats += b * 4;
+    if (A.mail) A.mail += 2 * b * (size_t)(A.R + 4);
+    finalize_rows_shift(A, stride, P[b].lambda, K);
+}
+
 // ---- direct exchange (ExchangeBox, ExchangeArgs: mppi_update.h) ---------------------------------------------------------
 __device__ __forceinline__ unsigned long long load_system(const unsigned long long* p) {   // past every cache
     unsigned long long v;
@@ -294,6 +436,30 @@ __global__ __launch_bounds__(1024) void k_min_cost(const double* cost, int K, do
 __global__ __launch_bounds__(kBlock) void k_reweight(const double* cost, const double* cmin, double lambda, int K, double* w) {
     const int k = blockIdx.x * kBlock + threadIdx.x;
     if (k < K) w[k] = exp(-(cost[k] - *cmin) / lambda);
+}
+
+// batch handles in shifted-weight mode, plain family: the exact minimum of every instance (grid B) and its weights re-formed
+// around it with the instance's own lambda (grid (ceil(K / kBlock), B)), in front of k_update_partials_batch -- the single
+// handle's MIN_SHIFT arithmetic, instance by instance
+__global__ __launch_bounds__(1024) void k_min_cost_batch(const double* cost, int K, int kpad, double* out_min) {
+    __shared__ double red[16];
+    cost += (size_t)blockIdx.x * kpad;
+    double mn = INFINITY;
+    for (int k = threadIdx.x; k < K; k += 1024) mn = fmin(mn, cost[k]);
+    mn = wave_min(mn);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = red[0];
+        for (int i = 1; i < 16; ++i) r = fmin(r, red[i]);
+        out_min[blockIdx.x] = r;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_reweight_batch(const double* cost, const double* cmin, const BatchParams* P, int K,
+                                                          int kpad, double* w) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    const size_t b = blockIdx.y;
+    if (k < K) w[b * kpad + k] = exp(-(cost[b * kpad + k] - cmin[b]) / P[b].lambda);
 }
 
 // ---- read-back helpers -----------------------------------------------------------------------------------------
@@ -406,6 +572,17 @@ __global__ __launch_bounds__(kBlock) void k_normalise_weights(const double* w, c
                                                              double* out) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i < count) out[i] = w[first + i] / stats[0];
+}
+
+// shifted-weight mode of a batch handle (fused kernels): w holds block-relative weights; the normalised weight of sample k of
+// workgroup g = k / 64 is w[k] * s_g / S with s_g as in shift_scaled_sum2 (statpart, stats: the instance's; stats[1] = m)
+__global__ __launch_bounds__(kBlock) void k_normalise_weights_shift(const double* w, const double* statpart, const double* stats,
+                                                                   double lambda, int first, int count, double* out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const int k = first + i;
+    const double sg = exp(-(statpart[(k / kPcSamples) * 3 + 0] - stats[1]) / lambda);
+    out[i] = (w[k] * sg) / stats[0];
 }
 
 // ---- device-resident closed loop (mppi_resident.h) ------------------------------------------------------------------
@@ -654,6 +831,38 @@ __global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch_varied(c
 __global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_varied(FinalizeArgs F, const BatchAdvanceArgs G,
                                                                            const BatchParams* P) {
     finalize_advance_batch<true>(F, G, P);
+}
+
+// k_finalize_advance_batch_varied over the SHIFT rollout kernels' partials: the update blocks are k_finalize_batch_shift's, and
+// the extra block forms the command with shift_scaled_sum2 as well -- the bits the finalize waves store into u*[y][0]
+__global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_shift(FinalizeArgs F, const BatchAdvanceArgs G, const BatchParams* P) {
+    const size_t b = blockIdx.y;
+    const size_t stride = (size_t)gridDim.y * F.nchunks;
+    const double lambda = P[b].lambda;
+    F.partial += b * F.nchunks;
+    F.statpart += b * (size_t)F.nchunks * 3;
+    if ((int)blockIdx.x < finalize_blocks(F.R)) {
+        F.nominal += b * F.R;
+        F.vec += b * (size_t)(F.R + 1);
+        F.stats += b * 4;
+        finalize_rows_shift(F, stride, lambda, G.K);   // (no mailbox: a deferred update is never a blocking call's)
+        return;
+    }
+    __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
+    if (G.advance) {
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(G.model);
+        for (int d = wv; d < ud; d += kBlock / 64) {
+            double s, v, m;
+            shift_scaled_sum2(F.partial + (size_t)F.R * stride, F.partial + (size_t)d * stride, F.statpart, lambda, F.nchunks, lane, s, v, m);
+            s = wave_sum(s);
+            v = wave_sum(v);
+            if (lane == 0) cmd[d] = v / s;
+        }
+    }
+    __syncthreads();
+    double* rec;
+    const AdvanceArgs A = batch_advance_view<true>(G, (int)b, rec, P);
+    advance_body<kBlock, true>(A, cmd, rec);
 }
 
 }  // namespace ccv

@@ -72,5 +72,7 @@ __global__ void k_finalize_advance_batch(FinalizeArgs F, BatchAdvanceArgs G);
 // the two prologue kernels of a batch with per-instance parameters (ccv_mppi_batch_set_params): P = the parameter table [B]
 __global__ void k_advance_batch_varied(BatchAdvanceArgs G, const BatchParams* P);
 __global__ void k_finalize_advance_batch_varied(FinalizeArgs F, BatchAdvanceArgs G, const BatchParams* P);
+// ... and of a batch in shifted-weight mode (k_finalize_batch_shift's update; its prologue is k_advance_batch_varied)
+__global__ void k_finalize_advance_batch_shift(FinalizeArgs F, BatchAdvanceArgs G, const BatchParams* P);
 
 }  // namespace ccv

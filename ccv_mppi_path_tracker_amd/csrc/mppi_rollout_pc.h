@@ -1080,6 +1080,17 @@ __device__ __forceinline__ void pc_block_stats(const RolloutArgs& A, const int R
     }
 }
 
+// Shifted weights of a batch handle (ccv_mppi_batch_set_min_shift): relative to the minimum cost m_g of the workgroup's 64
+// samples -- the value pc_block_stats posts as statpart[g][0], formed by the same reduction, so every wave that holds the
+// workgroup's totals gets the same bits without a hand-off.  The best sample of the workgroup has weight exp(-0) = 1; the
+// update rescales the workgroup's sums by exp(-(m_g - m) / lambda), m = the instance's minimum (k_finalize_batch_shift).
+// A workgroup without a finite cost (m_g = +inf) keeps the unshifted form: its +inf costs weigh 0, a NaN cost stays NaN.
+__device__ __forceinline__ double pc_shifted_weight(const RolloutArgs& A, const double total, const bool live) {
+    const double mg = wave_min(live ? total : INFINITY);
+    const double shift = mg < INFINITY ? mg : 0.0;
+    return live ? exp(-(total - shift) / A.lambda) : 0.0;
+}
+
 template <int MODEL, class T>
 __device__ __forceinline__ void pc_partial_update(const RolloutArgs& A, PcShared<MODEL>& sh, T (&v)[kUpdCH],
                                                   const UpdRows<MODEL>& rows, const int mcount, const double wgt,

@@ -234,7 +234,8 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // wave was alone on its SIMD there too, and its producer made the 40 normals of a block itself).
 // BATCH (fused iteration): workgroup blockIdx.x serves instance blockIdx.x / (its workgroups per instance) of a batch handle
 // (batch_view, mppi_kernels.h); everything else is the single handle's code.  VARIED: the batch's per-instance parameters
-template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false>
+// SHIFT (on VARIED): block-relative weights exp(-(total - m_g) / lambda), m_g = the workgroup's minimum cost (pc_shifted_weight)
+template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
@@ -243,6 +244,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     static_assert(!TAIL || MODE == MODE_FUSED, "the stage-wise modes carry the masked producer anyway");
     static_assert(!BATCH || MODE == MODE_FUSED, "batch handles run the fused iteration only");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
+    static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
     __shared__ R4Shared<MODEL> sh;
     static_assert(offsetof(R4Shared<MODEL>, zs) + sizeof(sh.zs) >= kR4Waves * kR4RB<MODEL> * (kPcSamples + 2) * sizeof(double), "epilogue buffers");
     touch_rollout_args();
@@ -536,7 +538,10 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         }
         if (!from_lds && (MODE != MODE_FUSED || wv >= 2 || nb_early == 0) && mcount > 0) r4_fetch0(A, upd, rows, kk);
         const double total = ((sh.cost[0][lane] + sh.cost[1][lane]) + sh.cost[2][lane]) + sh.cost[3][lane];
-        const double wgt = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)
+        double wgt_;
+        if constexpr (SHIFT) wgt_ = pc_shifted_weight(A, total, live);   // (every wave: the same 64 totals, the same minimum)
+        else wgt_ = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)
+        const double wgt = wgt_;
         if (wv == 0 && live) {
             A.cost[k] = total;
             A.w[k] = wgt;

@@ -25,11 +25,12 @@ struct SoloShared {
 };
 
 // WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h);
-// VARIED: with the batch's per-instance parameters
-template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false>
+// VARIED: with the batch's per-instance parameters; SHIFT (on VARIED): block-relative weights (pc_shifted_weight)
+template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false>
 __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArgs Ak, const Window Wk) {
     static_assert(MODE == MODE_FUSED, "the stage-wise modes use k_rollout_pc");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
+    static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     __shared__ SoloShared<MODEL> sh;
     static_assert(sizeof(sh.p) >= kUpdRB * (kPcSamples + 2) * sizeof(double), "epilogue buffer");
@@ -107,7 +108,10 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
     const int mcount = A.fuse_update ? rows.count() : 0;
     if (mcount > 0) pc_update_fetch(A, upd, rows, 0, mcount, kk);   // (in flight during the exp below)
     const double total = cost;
-    const double wgt = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)
+    double wgt_;
+    if constexpr (SHIFT) wgt_ = pc_shifted_weight(A, total, live);
+    else wgt_ = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)
+    const double wgt = wgt_;
     if (live) {
         A.cost[k] = total;
         A.w[k] = wgt;

@@ -50,6 +50,10 @@ struct FinalizeArgs {
 constexpr int finalize_blocks(int R) { return (R + 2 + kBlock / 64 - 1) / (kBlock / 64); }   // waves: R rows, sum w, statistics
 __global__ void k_finalize(FinalizeArgs A);                  // grid finalize_blocks(R)
 __global__ void k_finalize_batch(FinalizeArgs A, int fused);   // grid (finalize_blocks(R), B)
+// batch handles in shifted-weight mode (ccv_mppi_batch_set_min_shift): k_finalize_batch over the SHIFT rollout kernels'
+// block-relative partials, rescaled column by column with exp(-(m_g - m) / lambda_b); P: the parameter table [B], K: samples
+// per instance (the zero-weight count of a workgroup whose scale is 0)
+__global__ void k_finalize_batch_shift(FinalizeArgs A, const BatchParams* P, int K);   // grid (finalize_blocks(R), B)
 
 // ---- K sharded over the GPUs of one node without a collective library call ---------------------------
 // The exchanged message is 1 + (H-1)*u_dim doubles (<= 3.2 KB): far below the size at which a ring all-reduce pays, and a
@@ -82,6 +86,9 @@ __global__ void k_apply_partials(const double* vec, double* nominal, double* sta
 // ---- optional underflow-safe weights (CCV_MPPI_FLAG_MIN_SHIFT; not reference behaviour) --------------------------
 __global__ void k_min_cost(const double* cost, int K, double* out_min);   // one workgroup of 1024
 __global__ void k_reweight(const double* cost, const double* cmin, double lambda, int K, double* w);
+// batch handles in shifted-weight mode, plain family: instance minima [B] and the weights around them (per-instance lambda)
+__global__ void k_min_cost_batch(const double* cost, int K, int kpad, double* out_min);   // grid B, workgroups of 1024
+__global__ void k_reweight_batch(const double* cost, const double* cmin, const BatchParams* P, int K, int kpad, double* w);   // grid (ceil(K / kBlock), B)
 
 // ---- read-back helpers -----------------------------------------------------------------------------------------
 // out[c][t][2] = (xs[t][first + c*stride], ys[t][...])
@@ -92,5 +99,8 @@ __global__ void k_top_weights(const double* w, int K, int N, int* idx_out, doubl
 // gather of listed samples: out[c][t] = (x, y) of sample idx[c] at step t
 __global__ void k_gather_xy_list(const double* xs, const double* ys, int pitch, int H, const int* idx, int count, double* out);
 __global__ void k_normalise_weights(const double* w, const double* stats, int first, int count, double* out);
+// ... of one instance of a batch in shifted-weight mode (fused kernels): w[k] * s_g / S from the block-relative weights
+__global__ void k_normalise_weights_shift(const double* w, const double* statpart, const double* stats, double lambda, int first,
+                                          int count, double* out);
 
 }  // namespace ccv

@@ -249,11 +249,12 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_BATCH_KERNEL_FOUR_WAVE 4
 #define CCV_MPPI_BATCH_KERNEL_WIDE 16
 #define CCV_MPPI_BATCH_KERNEL_VARIED 32 /* ORed in: the kernels with per-instance parameters ran (ccv_mppi_batch_set_params) */
+#define CCV_MPPI_BATCH_KERNEL_SHIFT 64   /* ORed into ccv_mppi_batch_last_kernel(): the shifted-weight kernels ran */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
 
-/* batch >= 1; cfg->sample_offset must be 0; CCV_MPPI_FLAG_MIN_SHIFT is refused (CCV_MPPI_ERR_INVALID_ARG: the stabilised
- * weights are not built for batches); batch * ceil(K / 64) * 64 <= CCV_MPPI_BATCH_MAX_SAMPLES.  Arguments are checked before
+/* batch >= 1; cfg->sample_offset must be 0; CCV_MPPI_FLAG_MIN_SHIFT is refused (CCV_MPPI_ERR_INVALID_ARG: a batch's
+ * underflow-safe weights are a mode of the handle, ccv_mppi_batch_set_min_shift, not a creation flag); batch * ceil(K / 64) * 64 <= CCV_MPPI_BATCH_MAX_SAMPLES.  Arguments are checked before
  * any device is touched; without a device: CCV_MPPI_ERR_NO_DEVICE. */
 int ccv_mppi_batch_create(const ccv_mppi_config* cfg, int32_t batch, ccv_mppi_batch** out);
 int ccv_mppi_batch_destroy(ccv_mppi_batch* b);
@@ -277,6 +278,26 @@ int ccv_mppi_batch_get_nominal(ccv_mppi_batch* b, double* u);
 int ccv_mppi_batch_set_params(ccv_mppi_batch* b, const ccv_mppi_config* cfgs);
 /* out[B]: every instance's effective configuration (B copies of the creation configuration before any _set_params) */
 int ccv_mppi_batch_get_params(ccv_mppi_batch* b, ccv_mppi_config* out);
+/* Underflow-safe weights (NOT reference behaviour), a mode of the handle switched at run time: on != 0 -> from the next
+ * iteration on every instance weighs its samples with w = exp(-(c - min c) / lambda_b), min c the instance's own smallest cost
+ * and lambda_b its own lambda, so an instance with one finite cost always yields a finite u* (an instance whose costs are all
+ * infinite, or that has a NaN cost, yields NaN and nonfinite = 1 as without the mode, and only in that instance).  The fused
+ * iteration keeps its two launches and writes no controls: every workgroup of 64 samples forms its weights relative to its own
+ * minimum cost and the update rescales the workgroup's sums by exp(-(workgroup minimum - instance minimum) / lambda_b); the
+ * plain kernel (CCV_MPPI_KERNEL=v1, unbounded headings) is followed by the exact shift, as CCV_MPPI_FLAG_MIN_SHIFT of a single
+ * handle.  The mode always runs the per-instance-parameter kernels (_last_kernel: SHIFT | VARIED | family); a handle without
+ * _set_params has B copies of its configuration in the table, and _set_params(NULL) in this mode keeps the mode and returns to
+ * those.  Results agree with the mode off to rounding wherever the plain weights do not underflow, not bit for bit; on = 0
+ * returns to the kernels and the bits of a handle that never switched.  In this mode the statistics mean: min_cost / max_cost
+ * as always; sum_w = sum_i exp(-(cost_i - min_cost) / lambda_b), hence >= 1 for a finite min_cost; n_zero_weight = the number
+ * of samples whose weight relative to their workgroup's minimum cost is 0, counted in the workgroups whose scale
+ * exp(-(workgroup minimum - min_cost) / lambda_b) is not 0, plus every sample of the workgroups whose scale is 0 (plain
+ * kernel: the samples whose shifted weight is 0) -- a sample whose two factors are both above 0 while their product would
+ * underflow is not counted.  ccv_mppi_batch_read_weights returns the normalised weights as always.  Flushes a pending
+ * resident update, like _set_params, and may synchronise; warm starts, paths, poses, step counters, traces and per-instance
+ * parameters stay.  _get_min_shift: 0 / 1, or CCV_MPPI_ERR_INVALID_ARG for a null handle. */
+int ccv_mppi_batch_set_min_shift(ccv_mppi_batch* b, int32_t on);
+int ccv_mppi_batch_get_min_shift(const ccv_mppi_batch* b);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
