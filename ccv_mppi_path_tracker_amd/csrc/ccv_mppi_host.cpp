@@ -25,7 +25,8 @@ int nearest_index(const double* px, const double* py, int n, double x, double y)
 
 // sin and cos as the device computes them (csrc/fast_trig.h fast_sincos, restated operation by operation: three-step
 // Cody-Waite reduction by pi/2, fdlibm kernel polynomials, quadrant selection), so that a pose advanced here and one
-// advanced by k_advance on the device are the same bits.  |x| <= 1e5 as on the device; at most 1 ulp from libm.
+// advanced by k_advance on the device are the same bits.  |x| <= 1e5 as on the device; absolute error <= 2 * 2^-53 (measured
+// 1.33: csrc/fast_trig.h).
 // csrc/fast_trig.h rebase_angle(), restated (this file is compiled without the HIP headers)
 double rebase_angle(double a) {
     if (!(std::fabs(a) > 1.0e4)) return a;
