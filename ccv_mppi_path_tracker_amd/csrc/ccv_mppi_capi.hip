@@ -716,7 +716,8 @@ int ccv_mppi_create(const ccv_mppi_config* cfg, ccv_mppi_handle** out) {
     if (!cfg || !out) return CCV_MPPI_ERR_INVALID_ARG;
     *out = nullptr;
     if (int rc = check_config(cfg)) return rc;
-    if (cfg->sample_offset < 0) return CCV_MPPI_ERR_INVALID_ARG;
+    // the kernels form the global sample id sample_offset + k (k < K) in int32 before it becomes the Philox counter word
+    if (cfg->sample_offset < 0 || cfg->sample_offset > INT32_MAX - cfg->num_samples) return CCV_MPPI_ERR_INVALID_ARG;
     if (int rc = check_device(cfg->device)) return rc;
     ccv_mppi_handle* h = new (std::nothrow) ccv_mppi_handle();
     if (!h) return CCV_MPPI_ERR_ALLOC;

@@ -64,7 +64,8 @@ typedef struct ccv_mppi_config {
     int32_t model;              /* CCV_MPPI_DIFF_DRIVE ... */
     int32_t num_samples;        /* K on THIS device (param "num_samples", dd:19) */
     int32_t horizon;            /* H: number of states, H-1 control steps (param "horizon", dd:18); 3..CCV_MPPI_MAX_HORIZON */
-    int32_t sample_offset;      /* global id of local sample 0 when K is sharded over devices (0 otherwise) */
+    int32_t sample_offset;      /* global id of local sample 0 when K is sharded over devices (0 otherwise);
+                                 * 0 <= sample_offset and sample_offset + num_samples <= 2^31 - 1, else CCV_MPPI_ERR_INVALID_ARG */
     int32_t device;             /* HIP device ordinal */
     int32_t flags;              /* CCV_MPPI_FLAG_* */
     int32_t reserved;

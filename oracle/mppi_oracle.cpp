@@ -583,6 +583,16 @@ void orc_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out) 
     for (int i = 0; i < 4; ++i) out[i] = o.w[i];
 }
 void orc_normal_pair(uint32_t a, uint32_t b, float* z) { orc_noise::normal_pair(a, b, &z[0], &z[1]); }
+// bulk forms of the two above for the noise tests: loops over the same functions
+void orc_normal_pairs(size_t n, const uint32_t* a, const uint32_t* b, float* z0, float* z1) {
+    for (size_t i = 0; i < n; ++i) orc_noise::normal_pair(a[i], b[i], &z0[i], &z1[i]);
+}
+void orc_radius_args(size_t n, const uint32_t* a, float* x) {
+    for (size_t i = 0; i < n; ++i) x[i] = orc_noise::radius_arg(a[i]);
+}
+void orc_philox_blocks(size_t n, const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
+    for (size_t i = 0; i < n; ++i) orc_philox4x32_10(ctr + 4 * i, key, out + 4 * i);
+}
 void orc_normals(uint64_t seed, uint64_t iter, uint32_t k0, uint32_t nk, uint32_t n_per, float* out) {
     for (uint32_t k = 0; k < nk; ++k)
         for (uint32_t n = 0; n < n_per; ++n) out[(size_t)k * n_per + n] = orc_noise::normal_at(seed, iter, k0 + k, n);

@@ -81,6 +81,10 @@ def lib():
         u32p = C.POINTER(C.c_uint32)
         L.orc_philox4x32_10.argtypes = [u32p, u32p, u32p]
         L.orc_normal_pair.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        fp = C.POINTER(C.c_float)
+        L.orc_normal_pairs.argtypes = [C.c_size_t, u32p, u32p, fp, fp]
+        L.orc_radius_args.argtypes = [C.c_size_t, u32p, fp]
+        L.orc_philox_blocks.argtypes = [C.c_size_t, u32p, u32p, u32p]
         L.orc_normals.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         _lib = L
     return _lib
@@ -262,6 +266,37 @@ def normal_pair(a, b):
     z = (C.c_float * 2)()
     lib().orc_normal_pair(a, b, z)
     return np.float32(z[0]), np.float32(z[1])
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def normal_pairs(a, b):
+    """normal_pair over arrays of words -> (z0, z1), float32 arrays of the same length"""
+    a, b = np.ascontiguousarray(a, dtype=np.uint32).ravel(), np.ascontiguousarray(b, dtype=np.uint32).ravel()
+    assert a.shape == b.shape
+    z0, z1 = np.empty(a.size, dtype=np.float32), np.empty(a.size, dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    lib().orc_normal_pairs(a.size, _u32p(a), _u32p(b), z0.ctypes.data_as(fp), z1.ctypes.data_as(fp))
+    return z0, z1
+
+
+def radius_args(a):
+    """the fp32 argument of normal_pair's square root, -2 ln u1, per word"""
+    a = np.ascontiguousarray(a, dtype=np.uint32).ravel()
+    x = np.empty(a.size, dtype=np.float32)
+    lib().orc_radius_args(a.size, _u32p(a), x.ctypes.data_as(C.POINTER(C.c_float)))
+    return x
+
+
+def philox_blocks(ctr, key):
+    """philox4x32_10 over counters [n][4] under one key (two words) -> uint32 [n][4]"""
+    ctr = np.ascontiguousarray(ctr, dtype=np.uint32).reshape(-1, 4)
+    key = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+    out = np.empty_like(ctr)
+    lib().orc_philox_blocks(ctr.shape[0], _u32p(ctr), _u32p(key), _u32p(out))
+    return out
 
 
 def normals(seed, iteration, k0, nk, n_per):

@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE ONLY (see oracle/README.md).  Independent CPU restatement
 // of the repo's OWN counter-based noise spec (DESIGN.md "Noise spec"): Philox4x32-10
 // (Salmon et al., SC'11 -- published algorithm, Random123 known-answer vectors are
-// checked in tests/test_noise_spec.py) followed by an exactly-specified fp32
-// polynomial Box-Muller.  This is NOT part of the reference (the reference draws
+// checked in tests/test_oracle.py and tests/test_noise_reference.py, and on the
+// device in tests/test_gpu_noise.py) followed by an exactly-specified fp32
+// polynomial Box-Muller (held to the exact transform by tests/noise_reference.py).  This is NOT part of the reference (the reference draws
 // from std::mt19937, src/diff_drive_mppi.cpp:83-90); it exists so the GPU
 // sampler can be checked bit-for-bit on the CPU.  Written separately from
 // ccv_mppi_path_tracker_amd/csrc/noise_spec.h on purpose: two implementations,
@@ -37,10 +38,9 @@ static const float kQ[9] = {0x1.715476p+0f, -0x1.715476p-1f, 0x1.ec73e0p-2f, -0x
 static const float kS[4] = {-0x1.555556p-3f, 0x1.11110ep-7f, -0x1.a013a2p-13f, 0x1.6dbc3ep-19f};
 static const float kC[4] = {-0x1.000000p-1f, 0x1.55554cp-5f, -0x1.6c0df8p-10f, 0x1.9a6a98p-16f};
 
-// Two words -> two standard normals (fp32 resolution).  Every step is an IEEE-754
-// basic operation (or an integer op), so the result is bit-reproducible.
-inline void normal_pair(uint32_t a, uint32_t b, float* z0, float* z1) {
-    // radius: r = sqrt(-2 ln u1), u1 = max(a,1) * 2^-32
+// The argument of the radius' square root, -2 ln u1 in fp32, u1 = max(a,1) * 2^-32 (normal_pair's first half; the noise tests
+// hand it to the device's square root on its own)
+inline float radius_arg(uint32_t a) {
     uint32_t a1 = a ? a : 1u;
     int lz = __builtin_clz(a1);
     uint32_t m = a1 << lz;                           // u1 = m * 2^(-32-lz), top bit of m set
@@ -52,7 +52,14 @@ inline void normal_pair(uint32_t a, uint32_t b, float* z0, float* z1) {
     float q = kQ[8];
     for (int i = 7; i >= 0; --i) q = fmaf(q, t, kQ[i]);
     float L = fmaf(-t, q, L0);                      // -log2(u1)
-    float r = sqrtf(L * 0x1.62e430p+0f);            // * 2 ln 2
+    return L * 0x1.62e430p+0f;                      // * 2 ln 2
+}
+
+// Two words -> two standard normals (fp32 resolution).  Every step is an IEEE-754
+// basic operation (or an integer op), so the result is bit-reproducible.
+inline void normal_pair(uint32_t a, uint32_t b, float* z0, float* z1) {
+    // radius: r = sqrt(-2 ln u1), u1 = max(a,1) * 2^-32
+    float r = sqrtf(radius_arg(a));
     // angle: quadrant from the two top bits, centred remainder in [-pi/4, pi/4)
     uint32_t quad = b >> 30;
     int32_t f = (int32_t)(b & 0x3FFFFFFFu) - (1 << 29);

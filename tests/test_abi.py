@@ -98,6 +98,22 @@ def test_invalid_config_is_rejected_before_touching_a_device():
     assert lib.ccv_mppi_destroy(None) == capi.ERR_INVALID_ARG
 
 
+def test_sample_offset_whose_global_sample_id_leaves_int32_is_rejected():
+    """The kernels form sample_offset + k, k < K, in int32 (the Philox counter word): sample_offset + K <= 2^31 - 1 is the
+    largest shard create admits (tests/test_gpu_noise.py runs it), one more is an invalid argument."""
+    lib = capi.load()
+    for K in (1, 65, 130, 65536):
+        good = configs.diff_drive_defaults(K, 9)
+        h = capi._H()
+        for off in (2 ** 31 - K, 2 ** 31 - 1):
+            assert lib.ccv_mppi_create(C.byref(make_config(good, sample_offset=off)), C.byref(h)) == capi.ERR_INVALID_ARG
+            assert not h.value
+        rc = lib.ccv_mppi_create(C.byref(make_config(good, sample_offset=2 ** 31 - 1 - K)), C.byref(h))
+        assert rc != capi.ERR_INVALID_ARG          # (OK with a device, CCV_MPPI_ERR_NO_DEVICE without one)
+        if h.value:
+            lib.ccv_mppi_destroy(h)
+
+
 def test_no_cpu_fallback_without_a_device():
     import torch
     if torch.cuda.is_available():
