@@ -64,7 +64,7 @@ int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, con
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, int trig, bool defer);
 
 // a deferred resident update (batch_launch) is launched now
-int batch_flush(ccv_mppi_batch* bh) { return flush_finalize(bh, bh->B); }
+int batch_flush(ccv_mppi_batch* bh) { return flush_finalize(bh); }
 
 // fast_trig_safe of instance b (its own clamp bounds), folded into the batch's: the worst instance decides
 int batch_trig(const ccv_mppi_batch* bh, const int b, const RolloutArgs& A, const int trig) {
@@ -114,7 +114,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 }
 
 // the rollout of every instance from the records in d_rec, then the per-instance update; `defer` (resident ticks): the update
-// of the fused kernels waits in bh->fin_args for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
+// of the fused kernels waits in bh->fin for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
     const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift);
@@ -153,14 +153,12 @@ int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool 
     if (bh->want_mail && bh->use_mail && (mail_fits || bh->mail_any_size)) post_to_mail(*bh, F);
     bh->want_mail = false;
     bh->shift_result = shift;
+    const UpdatePlan up{F, B, !plain, shift ? bh->d_params : nullptr, bh->K};
     if (defer && !plain && !bh->timed_now && !F.mail) {
-        bh->fin_args = F;
-        bh->fin_shift = shift ? bh->d_params : nullptr;
-        bh->fin_K = bh->K;
+        bh->fin = up;
         bh->fin_pending = true;
     } else {
-        if (shift) hipLaunchKernelGGL(k_finalize_batch_shift, dim3(finalize_blocks(bh->R), B), dim3(kBlock), 0, bh->stream, F, bh->d_params, bh->K);
-        else hipLaunchKernelGGL(k_finalize_batch, dim3(finalize_blocks(bh->R), B), dim3(kBlock), 0, bh->stream, F, plain ? 0 : 1);
+        launch_finalize(*bh, up);
         HIP_TRY(bh, hipGetLastError());
     }
     HIP_TRY(bh, timing_end(*bh, bh->stream));
@@ -554,10 +552,7 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     G.trace_cap = CCV_MPPI_BATCH_TRACE_ROWS;
     // (varied: the prologue takes each instance's v_ref from the parameter table and points its record's head at its row)
     if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
-        const dim3 grid(finalize_blocks(bh->fin_args.R) + 1, B);
-        if (bh->fin_shift) hipLaunchKernelGGL(k_finalize_advance_batch_shift, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G, bh->d_params);
-        else if (uses_table(bh)) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G, bh->d_params);
-        else hipLaunchKernelGGL(k_finalize_advance_batch, grid, dim3(kBlock), 0, bh->stream, bh->fin_args, G);
+        launch_finalize_advance(*bh, bh->fin, G, uses_table(bh) ? bh->d_params : nullptr);
         bh->fin_pending = false;
     } else {
         if (uses_table(bh)) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);

@@ -107,13 +107,21 @@ struct Timing {
     float last_iter_us = 0.f, last_roll_us = 0.f;
 };
 
-// device-resident loops: the update of a tick is launched together with the next tick's prologue (k_finalize_advance[_batch]);
-// anything else that needs u*, the statistics or the stream first gets a plain k_finalize[_batch] (flush_finalize)
+// One update launch as a value (the update side's RolloutPlan): launch_finalize() and launch_finalize_advance() are the only
+// places that turn it into a kernel.
+struct UpdatePlan {
+    FinalizeArgs args{};
+    int batch = 0;                        // instances (the grid's y), 0: a single handle
+    bool fused = true;                    // a batch's partial layout: the rollout kernels' (k_finalize_batch) or k_update_partials_batch's
+    const BatchParams* shift = nullptr;   // a batch's shifted-weight update (the _shift kernels): its parameter table
+    int K = 0;                            // ... and the instance's K
+};
+
+// device-resident loops: the update of a tick is launched together with the next tick's prologue (launch_finalize_advance);
+// anything else that needs u*, the statistics or the stream first gets the plain update (flush_finalize)
 struct DeferredUpdate {
     bool fin_pending = false;
-    FinalizeArgs fin_args{};
-    const BatchParams* fin_shift = nullptr;   // a batch's shifted-weight update (k_finalize_batch_shift): its parameter table
-    int fin_K = 0;                            // ... and the instance's K
+    UpdatePlan fin{};
 };
 
 struct Core : Shape, KernelChoice, DeviceBuffers, Mailbox, Throttle, Timing, DeferredUpdate {
@@ -281,7 +289,13 @@ void fill_params(const ccv_mppi_config& c, bool fast_clamp_allowed, RolloutArgs&
 void fill_args(const Core* h, RolloutArgs& A, const double* x0, double dt, double yaw_ref0, uint64_t seed, uint64_t iter);
 void window_coeffs(int H, const double* x_ref, const double* y_ref, double px, double py, double* a, double* b, double* c);
 void track_absmax(const double* u, size_t n, int udim, double* absmax);
-int flush_finalize(Core* h, int batch);     // the deferred update now: k_finalize, or k_finalize_batch[_shift] of `batch` instances
+// the update kernel of a plan: k_finalize, k_finalize_batch or k_finalize_batch_shift
+void launch_finalize(Core& h, const UpdatePlan& p);
+// ... together with the next tick's prologue: k_finalize_advance (V), or k_finalize_advance_batch / _varied / _shift (G; table:
+// the per-instance parameters the prologue reads, or null)
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const AdvanceArgs& V);
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, const BatchParams* table);
+int flush_finalize(Core* h);                // the deferred update now (launch_finalize)
 int flush_division(ccv_mppi_handle* h);     // the deferred division now: k_apply_partials
 int flush_pending(ccv_mppi_handle* h);      // both, in that order
 int materialize_controls(ccv_mppi_handle* h);

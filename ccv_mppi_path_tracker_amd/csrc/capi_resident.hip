@@ -126,7 +126,7 @@ int resident_step(ccv_mppi_handle* h, double dt, uint64_t seed, uint64_t iter, i
     V.advance = advance ? 1 : 0;
     V.trace_cap = ccv_mppi_handle::kTraceRows;
     if (fuse) {
-        hipLaunchKernelGGL(k_finalize_advance, dim3(finalize_blocks(h->fin_args.R) + 1), dim3(kBlock), 0, h->stream, h->fin_args, V);
+        launch_finalize_advance(*h, h->fin, V);
         h->fin_pending = false;
     } else {
         if (int rc = flush_pending(h)) return rc;

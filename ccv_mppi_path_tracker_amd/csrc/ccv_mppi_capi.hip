@@ -105,13 +105,28 @@ void window_coeffs(const int H, const double* x_ref, const double* y_ref, const 
     }
 }
 
+void launch_finalize(Core& h, const UpdatePlan& p) {
+    const unsigned blocks = finalize_blocks(p.args.R);
+    if (p.batch && p.shift) hipLaunchKernelGGL(k_finalize_batch_shift, dim3(blocks, p.batch), dim3(kBlock), 0, h.stream, p.args, p.shift, p.K);
+    else if (p.batch) hipLaunchKernelGGL(k_finalize_batch, dim3(blocks, p.batch), dim3(kBlock), 0, h.stream, p.args, p.fused ? 1 : 0);
+    else hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(kBlock), 0, h.stream, p.args);
+}
+
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const AdvanceArgs& V) {
+    hipLaunchKernelGGL(k_finalize_advance, dim3(finalize_blocks(p.args.R) + 1), dim3(kBlock), 0, h.stream, p.args, V);
+}
+
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, const BatchParams* table) {
+    const dim3 grid(finalize_blocks(p.args.R) + 1, p.batch);
+    if (p.shift) hipLaunchKernelGGL(k_finalize_advance_batch_shift, grid, dim3(kBlock), 0, h.stream, p.args, G, p.shift);
+    else if (table) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, h.stream, p.args, G, table);
+    else hipLaunchKernelGGL(k_finalize_advance_batch, grid, dim3(kBlock), 0, h.stream, p.args, G);
+}
+
 // The deferred update of a resident tick (DeferredUpdate) is launched now, as the plain update of the fused partials.
-int flush_finalize(Core* h, const int batch) {
+int flush_finalize(Core* h) {
     if (!h->fin_pending) return CCV_MPPI_OK;
-    const unsigned blocks = finalize_blocks(h->fin_args.R);
-    if (batch && h->fin_shift) hipLaunchKernelGGL(k_finalize_batch_shift, dim3(blocks, batch), dim3(kBlock), 0, h->stream, h->fin_args, h->fin_shift, h->fin_K);
-    else if (batch) hipLaunchKernelGGL(k_finalize_batch, dim3(blocks, batch), dim3(kBlock), 0, h->stream, h->fin_args, 1);
-    else hipLaunchKernelGGL(k_finalize, dim3(blocks), dim3(kBlock), 0, h->stream, h->fin_args);
+    launch_finalize(*h, h->fin);
     h->fin_pending = false;
     HIP_TRY(h, hipGetLastError());
     return CCV_MPPI_OK;
@@ -128,7 +143,7 @@ int flush_division(ccv_mppi_handle* h) {
 }
 
 int flush_pending(ccv_mppi_handle* h) {
-    if (int rc = flush_finalize(h, 0)) return rc;
+    if (int rc = flush_finalize(h)) return rc;
     return flush_division(h);
 }
 
@@ -210,7 +225,7 @@ int launch_rollout(ccv_mppi_handle* h, const RolloutArgs& A_in, const Window& W,
     // the production kernel also reduces its workgroup's share of sum w and sum w*u (no second pass over the controls);
     // the underflow-safe MIN_SHIFT mode needs the global minimum first and keeps the separate update kernels
     A.fuse_update = (coop && mode != MODE_ROLLOUT && !(h->cfg.flags & CCV_MPPI_FLAG_MIN_SHIFT)) ? 1 : 0;
-    if (int rc = flush_finalize(h, 0)) return rc;   // (the kernel reads the warm start)
+    if (int rc = flush_finalize(h)) return rc;   // (the kernel reads the warm start)
     if (h->pending_vec) {
         if (coop && mode == MODE_FUSED) {   // the kernel divides while it stages u* (and writes it back)
             A.pending_vec = h->pending_vec;
@@ -317,11 +332,11 @@ int launch_update(ccv_mppi_handle* h, bool normalise, double* vec_out, bool exch
         return CCV_MPPI_OK;
     }
     if (defer && nparts == h->nblocks && normalise) {   // fused partials, plain update: launched with the next tick's prologue
-        h->fin_args = F;
+        h->fin = UpdatePlan{F};
         h->fin_pending = true;
         return CCV_MPPI_OK;
     }
-    hipLaunchKernelGGL(k_finalize, dim3(finalize_blocks(h->R)), dim3(kBlock), 0, h->stream, F);
+    launch_finalize(*h, UpdatePlan{F});
     HIP_TRY(h, hipGetLastError());
     return CCV_MPPI_OK;
 }

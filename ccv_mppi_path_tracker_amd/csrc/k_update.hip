@@ -1,7 +1,7 @@
 // translation unit: the small kernels around the rollout (declared in mppi_update.h and mppi_resident.h, launched by the
 // host units of the C ABI): weighted update, re-derivation of the controls from the stored normals, MIN_SHIFT
-// re-weighting, the read-back helpers, and the prologue of the device-resident loop.  Not templates: every kernel is
-// defined here and nowhere else.
+// re-weighting, the read-back helpers, and the prologue of the device-resident loop.  No entry point is a template: every
+// kernel is defined here and nowhere else (the device functions they share are templates over the weight mode).
 #include "fast_trig.h"
 #include "mppi_resident.h"
 
@@ -97,11 +97,15 @@ __global__ __launch_bounds__(kBlock) void k_update_partials_batch(UpdateArgs A, 
     update_partials(A);
 }
 
-__device__ __forceinline__ void mail_post(const FinalizeArgs& A, const int slot, const double value) {
+// a value as two self-validating packets {32 data bits, 32-bit sequence number}, each one atomic store: the mailbox's and
+// the exchange's format (mppi_update.h).  (seq by reference: read at each store, where the writers have always read it)
+__device__ __forceinline__ void store_packets(unsigned long long* dst, const double value, const uint32_t& seq) {
     const unsigned long long bits = (unsigned long long)__double_as_longlong(value);
-    unsigned long long* dst = A.mail + 2 * (size_t)slot;
-    __hip_atomic_store(dst + 0, (bits & 0xFFFFFFFF00000000ull) | A.mail_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(dst + 1, (bits << 32) | A.mail_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(dst + 0, (bits & 0xFFFFFFFF00000000ull) | seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(dst + 1, (bits << 32) | seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void mail_post(const FinalizeArgs& A, const int slot, const double value) {
+    store_packets(A.mail + 2 * (size_t)slot, value, A.mail_seq);
 }
 
 // One wave per row n: lanes read the chunk partials of the row (fixed order => bitwise reproducible), wave-reduce them,
@@ -131,88 +135,6 @@ __device__ __forceinline__ void lane_partial_sum2(const double* row_a, const dou
     sum_b = acc_b;
 }
 
-// min / max cost and the zero-weight count over the per-workgroup statistics: a wave of its own (n == R + 1), so that its
-// loads run beside the row reductions instead of after one of them
-__device__ __forceinline__ void finalize_cost_stats(const FinalizeArgs& A, const int lane) {
-    double mn = INFINITY, mx = -INFINITY, nz = 0.0;
-    for (int c0 = 0; c0 < A.nchunks; c0 += 1024) {
-        double a[16], b[16], z[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {   // all loads first: one memory latency per 1024 partials
-            const int c = min(c0 + lane + 64 * i, A.nchunks - 1);
-            a[i] = A.statpart[c * 3 + 0];
-            b[i] = A.statpart[c * 3 + 1];
-            z[i] = A.statpart[c * 3 + 2];
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const bool in = c0 + lane + 64 * i < A.nchunks;
-            mn = fmin(mn, in ? a[i] : INFINITY);
-            mx = fmax(mx, in ? b[i] : -INFINITY);
-            nz += in ? z[i] : 0.0;
-        }
-    }
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    nz = wave_sum(nz);
-    if (lane == 0) {
-        A.stats[1] = mn;
-        A.stats[2] = mx;
-        A.stats[3] = nz;
-        if (A.mail) {
-            mail_post(A, A.R + 1, mn);
-            mail_post(A, A.R + 2, mx);
-            mail_post(A, A.R + 3, nz);
-        }
-    }
-}
-
-// (stride: the row pitch of the partials, nchunks but for a batch handle's fused partials)
-__device__ __forceinline__ void finalize_rows(const FinalizeArgs& A, const size_t stride) {
-    const int lane = threadIdx.x & 63;
-    // rows 0..R-1: one wave each; wave R: sum w; wave R + 1: the cost statistics
-    const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (n > A.R) {
-        if (n == A.R + 1) finalize_cost_stats(A, lane);
-        return;
-    }
-    const int nrow = n < A.R ? n : A.R;
-    // S = sum w and this wave's row are fetched together
-    double s, v;
-    lane_partial_sum2(A.partial + (size_t)A.R * stride, A.partial + (size_t)nrow * stride, A.nchunks, lane, s, v);
-    s = wave_sum(s);
-    v = wave_sum(v);
-    if (n < A.R && lane == 0) {
-        A.vec[1 + n] = v;
-        if (A.normalise) {
-            const double q = v / s;
-            A.nominal[n] = q;
-            if (A.mail) mail_post(A, n, q);
-        }
-    }
-    if (n == A.R && lane == 0) {
-        A.vec[0] = s;
-        A.stats[0] = s;
-        if (A.mail) mail_post(A, A.R, s);
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_finalize(const FinalizeArgs A) { finalize_rows(A, (size_t)A.nchunks); }
-// Batch handles: grid (finalize_blocks(R), B); instance blockIdx.y reduces its own nchunks columns of the partials in the
-// single handle's order (the same bits) into its slices of u* [B][R], vec [B][R+1], stats [B][4] and mailbox slots [B][R+4] --
-// every packet under the launch's one sequence number.  Partials: `fused` -- the rollout kernels' [(R+1)][B * nchunks],
-// instance b in columns b * nchunks ...; otherwise k_update_partials_batch's [B][(R+1)][nchunks].  Statistics [B][nchunks][3].
-__global__ __launch_bounds__(kBlock) void k_finalize_batch(FinalizeArgs A, const int fused) {
-    const size_t b = blockIdx.y;
-    const size_t stride = fused ? (size_t)gridDim.y * A.nchunks : (size_t)A.nchunks;
-    A.partial += fused ? b * A.nchunks : b * (size_t)(A.R + 1) * A.nchunks;
-    A.statpart += b * (size_t)A.nchunks * 3;
-    A.nominal += b * A.R;
-    A.vec += b * (size_t)(A.R + 1);
-    A.stats += b * 4;
-    if (A.mail) A.mail += 2 * b * (size_t)(A.R + 4);
-    finalize_rows(A, stride);
-}
-
 // ---- batch handles, shifted weights (ccv_mppi_batch_set_min_shift) ------------------------------------------------------
 // The SHIFT rollout kernels (pc_shifted_weight) leave, per workgroup g of 64 samples, sums of weights relative to the
 // workgroup's own minimum cost m_g = statpart[g][0].  Relative to the instance's minimum m = min_g m_g the workgroup's sums
@@ -223,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_finalize_batch(FinalizeArgs A, const
 // are fetched again.  m_g = +inf (no finite cost in the workgroup): s_g = 0 against partials of 0; m = +inf: NaN.
 __device__ __forceinline__ void shift_scaled_sum2(const double* row_a, const double* row_b, const double* statpart,
                                                   const double lambda, const int n, const int lane, double& sum_a,
-                                                  double& sum_b, double& m_out) {
+                                                  double& sum_b) {
     double va[16], vb[16], mg[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -264,9 +186,48 @@ __device__ __forceinline__ void shift_scaled_sum2(const double* row_a, const dou
     }
     sum_a = acc_a;
     sum_b = acc_b;
-    m_out = m;
 }
 
+// what a statistics wave leaves (lane 0)
+__device__ __forceinline__ void post_cost_stats(const FinalizeArgs& A, const int lane, const double mn, const double mx, const double nz) {
+    if (lane == 0) {
+        A.stats[1] = mn;
+        A.stats[2] = mx;
+        A.stats[3] = nz;
+        if (A.mail) {
+            mail_post(A, A.R + 1, mn);
+            mail_post(A, A.R + 2, mx);
+            mail_post(A, A.R + 3, nz);
+        }
+    }
+}
+
+// min / max cost and the zero-weight count over the per-workgroup statistics: a wave of its own (n == R + 1), so that its
+// loads run beside the row reductions instead of after one of them
+__device__ __forceinline__ void finalize_cost_stats(const FinalizeArgs& A, const int lane) {
+    double mn = INFINITY, mx = -INFINITY, nz = 0.0;
+    for (int c0 = 0; c0 < A.nchunks; c0 += 1024) {
+        double a[16], b[16], z[16];
+        #pragma unroll
+        for (int i = 0; i < 16; ++i) {   // all loads first: one memory latency per 1024 partials
+            const int c = min(c0 + lane + 64 * i, A.nchunks - 1);
+            a[i] = A.statpart[c * 3 + 0];
+            b[i] = A.statpart[c * 3 + 1];
+            z[i] = A.statpart[c * 3 + 2];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const bool in = c0 + lane + 64 * i < A.nchunks;
+            mn = fmin(mn, in ? a[i] : INFINITY);
+            mx = fmax(mx, in ? b[i] : -INFINITY);
+            nz += in ? z[i] : 0.0;
+        }
+    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    nz = wave_sum(nz);
+    post_cost_stats(A, lane, mn, mx, nz);
+}
 // the statistics wave in shifted-weight mode: min_cost = m, max_cost, and the zero-weight count -- the live samples whose
 // block-relative weight is 0 in the workgroups whose scale is not 0 (statpart[g][2]), plus every live sample (64, or what is
 // left of K in the last workgroup) of a workgroup whose scale is 0
@@ -302,31 +263,33 @@ __device__ __forceinline__ void finalize_cost_stats_shift(const FinalizeArgs& A,
     }
     mx = wave_max(mx);
     nz = wave_sum(nz);
-    if (lane == 0) {
-        A.stats[1] = m;
-        A.stats[2] = mx;
-        A.stats[3] = nz;
-        if (A.mail) {
-            mail_post(A, A.R + 1, m);
-            mail_post(A, A.R + 2, mx);
-            mail_post(A, A.R + 3, nz);
-        }
-    }
+    post_cost_stats(A, lane, m, mx, nz);
 }
 
-// finalize_rows over scaled partials (stride: the row pitch of the fused partials)
-__device__ __forceinline__ void finalize_rows_shift(const FinalizeArgs& A, const size_t stride, const double lambda, const int K) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if (n > A.R) {
-        if (n == A.R + 1) finalize_cost_stats_shift(A, lambda, K, lane);
-        return;
+// The weight mode of an update: how a wave sums S = row R and one more row of the partials, and its statistics wave.
+// (stride: the row pitch of the partials, nchunks but for a batch handle's fused partials; lambda, K: the instance's, SHIFT only)
+template <bool SHIFT>
+struct RowSum {
+    double lambda = 0.0;
+    int K = 0;
+    __device__ __forceinline__ void operator()(const FinalizeArgs& A, const size_t stride, const int row, const int lane, double& s,
+                                               double& v) const {
+        const double* row_s = A.partial + (size_t)A.R * stride;
+        const double* row_v = A.partial + (size_t)row * stride;
+        if constexpr (SHIFT) shift_scaled_sum2(row_s, row_v, A.statpart, lambda, A.nchunks, lane, s, v);
+        else lane_partial_sum2(row_s, row_v, A.nchunks, lane, s, v);
+        s = wave_sum(s);
+        v = wave_sum(v);
     }
-    const int nrow = n < A.R ? n : A.R;
-    double s, v, m;
-    shift_scaled_sum2(A.partial + (size_t)A.R * stride, A.partial + (size_t)nrow * stride, A.statpart, lambda, A.nchunks, lane, s, v, m);
-    s = wave_sum(s);
-    v = wave_sum(v);
+    __device__ __forceinline__ void stats(const FinalizeArgs& A, const int lane) const {
+        if constexpr (SHIFT) finalize_cost_stats_shift(A, lambda, K, lane);
+        else finalize_cost_stats(A, lane);
+    }
+};
+
+// what an update wave leaves: row n < R's V_n (and u*[n] = V_n / S), wave R's S
+__device__ __forceinline__ void publish_row(const FinalizeArgs& A, const int n, const double s, const double v) {
+    const int lane = threadIdx.x & 63;
     if (n < A.R && lane == 0) {
         A.vec[1 + n] = v;
         if (A.normalise) {
@@ -341,6 +304,33 @@ __device__ __forceinline__ void finalize_rows_shift(const FinalizeArgs& A, const
         if (A.mail) mail_post(A, A.R, s);
     }
 }
+template <class Sum>
+__device__ __forceinline__ void finalize_rows(const FinalizeArgs& A, const size_t stride, const Sum& sum) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (n > A.R) {
+        if (n == A.R + 1) sum.stats(A, lane);
+        return;
+    }
+    double s, v;
+    sum(A, stride, n < A.R ? n : A.R, lane, s, v);
+    publish_row(A, n, s, v);
+}
+__global__ __launch_bounds__(kBlock) void k_finalize(const FinalizeArgs A) { finalize_rows(A, (size_t)A.nchunks, RowSum<false>{}); }
+
+// grid (finalize_blocks(R), B); instance blockIdx.y reduces its own columns in the single handle's order (the same bits), every
+// packet under the launch's one sequence number
+__global__ __launch_bounds__(kBlock) void k_finalize_batch(FinalizeArgs A, const int fused) {
+    const size_t b = blockIdx.y;
+    const size_t stride = fused ? (size_t)gridDim.y * A.nchunks : (size_t)A.nchunks;
+    A.partial += fused ? b * A.nchunks : b * (size_t)(A.R + 1) * A.nchunks;
+    A.statpart += b * (size_t)A.nchunks * 3;
+    A.nominal += b * A.R;
+    A.vec += b * (size_t)(A.R + 1);
+    A.stats += b * 4;
+    if (A.mail) A.mail += 2 * b * (size_t)(A.R + 4);
+    finalize_rows(A, stride, RowSum<false>{});
+}
 // k_finalize_batch over the SHIFT rollout kernels' partials (always the fused layout): grid (finalize_blocks(R), B);
 // P: the parameter table (instance y's lambda), K: samples per instance
 __global__ __launch_bounds__(kBlock) void k_finalize_batch_shift(FinalizeArgs A, const BatchParams* P, const int K) {
@@ -352,7 +342,7 @@ __global__ __launch_bounds__(kBlock) void k_finalize_batch_shift(FinalizeArgs A,
     A.vec += b * (size_t)(A.R + 1);
     A.stats += b * 4;
     if (A.mail) A.mail += 2 * b * (size_t)(A.R + 4);
-    finalize_rows_shift(A, stride, P[b].lambda, K);
+    finalize_rows(A, stride, RowSum<true>{P[b].lambda, K});
 }
 
 // ---- direct exchange (ExchangeBox, ExchangeArgs: mppi_update.h) ---------------------------------------------------------
@@ -369,19 +359,14 @@ __global__ __launch_bounds__(kBlock) void k_finalize_exchange(const FinalizeArgs
         if (n == A.R + 1) finalize_cost_stats(A, lane);   // (this device's samples only)
         return;
     }
-    const int nrow = n < A.R ? n : A.R;
     double s, v;
-    lane_partial_sum2(A.partial + (size_t)A.R * A.nchunks, A.partial + (size_t)nrow * A.nchunks, A.nchunks, lane, s, v);
-    s = wave_sum(s);
-    v = wave_sum(v);
+    RowSum<false>{}(A, (size_t)A.nchunks, n < A.R ? n : A.R, lane, s, v);
     // ---- this wave's value into slot [rank] of every peer's box: lane d writes to rank d
     const int slot = n < A.R ? 1 + n : 0;
     const double mine = n < A.R ? v : s;
     if (lane < X.world) {
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(mine);
-        unsigned long long* dst = &X.peer[lane]->pkt[X.parity][X.rank][slot][0];
-        __hip_atomic_store(dst + 0, (bits & 0xFFFFFFFF00000000ull) | X.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(dst + 1, (bits << 32) | X.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const uint32_t seq = X.seq;
+        store_packets(&X.peer[lane]->pkt[X.parity][X.rank][slot][0], mine, seq);
     }
     if (lane == 0) {   // (this device's share)
         A.vec[slot] = mine;
@@ -420,18 +405,23 @@ __global__ __launch_bounds__(kBlock) void k_apply_partials(const double* vec, do
 }
 
 // ---- optional underflow-safe weights (CCV_MPPI_FLAG_MIN_SHIFT; not reference behaviour) --------------------------
-__global__ __launch_bounds__(1024) void k_min_cost(const double* cost, int K, double* out_min) {
+// the minimum of cost[0 .. K): one workgroup of 1024, the result in thread 0
+__device__ __forceinline__ double block_min_cost(const double* cost, const int K) {
     __shared__ double red[16];
     double mn = INFINITY;
     for (int k = threadIdx.x; k < K; k += 1024) mn = fmin(mn, cost[k]);
     mn = wave_min(mn);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
     __syncthreads();
+    double r = red[0];
     if (threadIdx.x == 0) {
-        double r = red[0];
         for (int i = 1; i < 16; ++i) r = fmin(r, red[i]);
-        *out_min = r;
     }
+    return r;
+}
+__global__ __launch_bounds__(1024) void k_min_cost(const double* cost, int K, double* out_min) {
+    const double r = block_min_cost(cost, K);
+    if (threadIdx.x == 0) *out_min = r;
 }
 __global__ __launch_bounds__(kBlock) void k_reweight(const double* cost, const double* cmin, double lambda, int K, double* w) {
     const int k = blockIdx.x * kBlock + threadIdx.x;
@@ -442,18 +432,8 @@ __global__ __launch_bounds__(kBlock) void k_reweight(const double* cost, const d
 // around it with the instance's own lambda (grid (ceil(K / kBlock), B)), in front of k_update_partials_batch -- the single
 // handle's MIN_SHIFT arithmetic, instance by instance
 __global__ __launch_bounds__(1024) void k_min_cost_batch(const double* cost, int K, int kpad, double* out_min) {
-    __shared__ double red[16];
-    cost += (size_t)blockIdx.x * kpad;
-    double mn = INFINITY;
-    for (int k = threadIdx.x; k < K; k += 1024) mn = fmin(mn, cost[k]);
-    mn = wave_min(mn);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = red[0];
-        for (int i = 1; i < 16; ++i) r = fmin(r, red[i]);
-        out_min[blockIdx.x] = r;
-    }
+    const double r = block_min_cost(cost + (size_t)blockIdx.x * kpad, K);
+    if (threadIdx.x == 0) out_min[blockIdx.x] = r;
 }
 __global__ __launch_bounds__(kBlock) void k_reweight_batch(const double* cost, const double* cmin, const BatchParams* P, int K,
                                                           int kpad, double* w) {
@@ -717,26 +697,27 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& A, const double*
 
 __global__ __launch_bounds__(kAdvanceThreads) void k_advance(const AdvanceArgs A) { advance_body<kAdvanceThreads>(A, A.nominal); }
 
+// the command u*[0][d] = V_d / S, d < udim_of(model), by the waves of one workgroup: finalize_rows' sums of the same partials in the same
+// order, so the bits its waves write into the warm start (the prologue cannot wait for them)
+template <class Sum>
+__device__ __forceinline__ void form_command(double* cmd, const FinalizeArgs& F, const size_t stride, const int model, const Sum& sum) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(model);
+    for (int d = wv; d < ud; d += kBlock / 64) {
+        double s, v;
+        sum(F, stride, d, lane, s, v);
+        if (lane == 0) cmd[d] = v / s;
+    }
+}
+
 // The update of tick i and the prologue of tick i+1 in ONE launch (the closed loop then costs two launches per tick, not
-// three): blocks 0 .. finalize_blocks(R)-1 are k_finalize; one more block forms the command u*[0][d] = V_d / S from the same
-// partial sums in the same order (the same bits the finalize waves write into the warm start -- it cannot wait for them)
-// and runs the prologue with it.
+// three): blocks 0 .. finalize_blocks(R)-1 are k_finalize; one more block forms the command and runs the prologue with it.
 __global__ __launch_bounds__(kBlock) void k_finalize_advance(const FinalizeArgs F, const AdvanceArgs A) {
     if ((int)blockIdx.x < finalize_blocks(F.R)) {
-        finalize_rows(F, (size_t)F.nchunks);
+        finalize_rows(F, (size_t)F.nchunks, RowSum<false>{});
         return;
     }
     __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
-    if (A.advance) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(A.model);
-        for (int d = wv; d < ud; d += kBlock / 64) {
-            double s, v;
-            lane_partial_sum2(F.partial + (size_t)F.R * F.nchunks, F.partial + (size_t)d * F.nchunks, F.nchunks, lane, s, v);
-            s = wave_sum(s);
-            v = wave_sum(v);
-            if (lane == 0) cmd[d] = v / s;
-        }
-    }
+    if (A.advance) form_command(cmd, F, (size_t)F.nchunks, A.model, RowSum<false>{});
     __syncthreads();
     advance_body<kBlock>(A, cmd);
 }
@@ -787,39 +768,31 @@ __global__ __launch_bounds__(kBatchAdvanceThreads) void k_advance_batch(const Ba
 }
 
 // The batched k_finalize_advance: grid (finalize_blocks(R) + 1, B).  Blocks x < finalize_blocks(R) are k_finalize_batch
-// (fused partials) for instance y; block x = finalize_blocks(R) forms instance y's command from the instance's own partial
-// columns in k_finalize_batch's order (the bits its waves write into u*[y][0]) and runs the instance's prologue with it.
-template <bool VARIED = false>
-__device__ __forceinline__ void finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs& G, const BatchParams* P = nullptr) {
+// (fused partials) for instance y; block x = finalize_blocks(R) forms instance y's command from
+// the instance's own partial columns and runs the instance's prologue with it.
+template <bool VARIED>
+__device__ __forceinline__ void finalize_advance_batch(FinalizeArgs I, const BatchAdvanceArgs& G, const BatchParams* P) {
     const size_t b = blockIdx.y;
-    const size_t stride = (size_t)gridDim.y * F.nchunks;
-    F.partial += b * F.nchunks;
-    if ((int)blockIdx.x < finalize_blocks(F.R)) {
-        F.statpart += b * (size_t)F.nchunks * 3;
-        F.nominal += b * F.R;
-        F.vec += b * (size_t)(F.R + 1);
-        F.stats += b * 4;
-        finalize_rows(F, stride);   // (no mailbox: a deferred update is never a blocking call's)
+    const size_t stride = (size_t)gridDim.y * I.nchunks;
+    const RowSum<false> sum{};
+    I.partial += b * I.nchunks;
+    if ((int)blockIdx.x < finalize_blocks(I.R)) {
+        I.statpart += b * (size_t)I.nchunks * 3;
+        I.nominal += b * I.R;
+        I.vec += b * (size_t)(I.R + 1);
+        I.stats += b * 4;
+        finalize_rows(I, stride, sum);   // (no mailbox: a deferred update is never a blocking call's)
         return;
     }
     __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
-    if (G.advance) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(G.model);
-        for (int d = wv; d < ud; d += kBlock / 64) {
-            double s, v;
-            lane_partial_sum2(F.partial + (size_t)F.R * stride, F.partial + (size_t)d * stride, F.nchunks, lane, s, v);
-            s = wave_sum(s);
-            v = wave_sum(v);
-            if (lane == 0) cmd[d] = v / s;
-        }
-    }
+    if (G.advance) form_command(cmd, I, stride, G.model, sum);
     __syncthreads();
     double* rec;
     const AdvanceArgs A = batch_advance_view<VARIED>(G, (int)b, rec, P);
     advance_body<kBlock, true>(A, cmd, rec);
 }
 __global__ __launch_bounds__(kBlock) void k_finalize_advance_batch(FinalizeArgs F, const BatchAdvanceArgs G) {
-    finalize_advance_batch(F, G);
+    finalize_advance_batch<false>(F, G, nullptr);
 }
 
 // the two prologue kernels of a batch with per-instance parameters (ccv_mppi_batch_set_params): P = the parameter table [B]
@@ -833,8 +806,9 @@ __global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_varied(Finali
     finalize_advance_batch<true>(F, G, P);
 }
 
-// k_finalize_advance_batch_varied over the SHIFT rollout kernels' partials: the update blocks are k_finalize_batch_shift's, and
-// the extra block forms the command with shift_scaled_sum2 as well -- the bits the finalize waves store into u*[y][0]
+// ... over the SHIFT rollout kernels' partials: the update blocks are k_finalize_batch_shift's, and the extra block forms the
+// command with shift_scaled_sum2 as well.  (A body and a command loop of its own: through finalize_advance_batch and
+// form_command the compiler lays the same instructions out in another order.)
 __global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_shift(FinalizeArgs F, const BatchAdvanceArgs G, const BatchParams* P) {
     const size_t b = blockIdx.y;
     const size_t stride = (size_t)gridDim.y * F.nchunks;
@@ -845,15 +819,15 @@ __global__ __launch_bounds__(kBlock) void k_finalize_advance_batch_shift(Finaliz
         F.nominal += b * F.R;
         F.vec += b * (size_t)(F.R + 1);
         F.stats += b * 4;
-        finalize_rows_shift(F, stride, lambda, G.K);   // (no mailbox: a deferred update is never a blocking call's)
+        finalize_rows(F, stride, RowSum<true>{lambda, G.K});   // (no mailbox: a deferred update is never a blocking call's)
         return;
     }
     __shared__ double cmd[CCV_MPPI_MAX_UDIM + 3];
     if (G.advance) {
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, ud = udim_of(G.model);
         for (int d = wv; d < ud; d += kBlock / 64) {
-            double s, v, m;
-            shift_scaled_sum2(F.partial + (size_t)F.R * stride, F.partial + (size_t)d * stride, F.statpart, lambda, F.nchunks, lane, s, v, m);
+            double s, v;
+            shift_scaled_sum2(F.partial + (size_t)F.R * stride, F.partial + (size_t)d * stride, F.statpart, lambda, F.nchunks, lane, s, v);
             s = wave_sum(s);
             v = wave_sum(v);
             if (lane == 0) cmd[d] = v / s;

@@ -1,6 +1,6 @@
 // The small kernels around the rollout: weighted update (k_update_partials / k_finalize / k_finalize_exchange /
 // k_apply_partials), re-derivation of the controls from the stored normals, MIN_SHIFT re-weighting and the read-back
-// helpers.  Not templates: every kernel is DEFINED in one translation unit, k_update.hip; this header has the argument
+// helpers.  No entry point is a template: every kernel is DEFINED in one translation unit, k_update.hip; this header has the argument
 // structs and the declarations through which the host units of the C ABI (capi_internal.h) launch them.  The rollout
 // kernels' translation units (k_*.hip) include mppi_kernels.h alone.
 #pragma once

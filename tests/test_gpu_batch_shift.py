@@ -104,13 +104,16 @@ def family_code(kernel, model, K, B):
 
 # 1. against the extended-precision reference ------------------------------------------------------------------------------
 # four-wave: dd tail (H = 15), dd no tail (H = 50), dd wide (dt = 0.41), sd tail / no tail, fb tail / no tail; one-wave: dd, sd
-# (13 x 100 workgroups: test_gpu_update.batch_inputs has poses for 14 instances), fb (3 x 157); plain: dd, sd, fb
+# (13 x 100 workgroups: test_gpu_update.batch_inputs has poses for 14 instances), fb (3 x 157); plain: dd, sd, fb;
+# K = 65 537: 1025 workgroups per instance, the smallest count that takes the update's second pass over the partial columns
+# (shift_scaled_sum2 and the statistics wave beyond 1024 columns), the last workgroup with one live sample
 CASES = [(None, "diff_drive", 1000, 15, 8, {}), (None, "diff_drive", 1000, 50, 3, {}), (None, "diff_drive", 1000, 50, 3, {"dt": 0.41}),
          (None, "steering_diff_drive", 1000, 15, 3, {}), (None, "steering_diff_drive", 1000, 50, 3, {}),
          (None, "full_body", 1000, 15, 3, {}), (None, "full_body", 130, 9, 3, {}),
          (None, "diff_drive", 6400, 15, 13, {}), (None, "steering_diff_drive", 6400, 25, 13, {}), (None, "full_body", 10000, 15, 3, {}),
          (None, "diff_drive", 63, 17, 3, {}), (None, "diff_drive", 1000, 15, 1, {}),
-         ("v1", "diff_drive", 1000, 15, 3, {}), ("v1", "steering_diff_drive", 1000, 25, 1, {}), ("v1", "full_body", 63, 9, 8, {})]
+         ("v1", "diff_drive", 1000, 15, 3, {}), ("v1", "steering_diff_drive", 1000, 25, 1, {}), ("v1", "full_body", 63, 9, 8, {}),
+         (None, "diff_drive", 65537, 15, 2, {})]   # (last: the ids of the cases above carry their position)
 
 
 @pytest.mark.parametrize("varied", [False, True], ids=["shared", "varied"])
@@ -344,7 +347,7 @@ def test_resident_loop_with_shift_equals_the_host_prologue():
 
 
 @pytest.mark.parametrize("varied", [False, True], ids=["shared", "varied"])
-@pytest.mark.parametrize("model,K,H,B", [("diff_drive", 1000, 15, 3), ("steering_diff_drive", 1000, 17, 8)])
+@pytest.mark.parametrize("model,K,H,B", [("diff_drive", 1000, 15, 3), ("steering_diff_drive", 1000, 17, 8), ("diff_drive", 65537, 15, 2)])
 def test_shift_resident_tick_pair(model, K, H, B, varied):
     """test_gpu_update.test_batch_resident_tick_pair in shifted-weight mode: tick 0's update runs inside
     k_finalize_advance_batch_shift, whose extra block forms the command that moves the pose, and tick 1 samples around the u*
