@@ -34,6 +34,33 @@ def check_shared(seq, first=None):
                                  % (b, f, getattr(p, f), getattr(first, f)))
 
 
+def pack_obstacles(discs, weight, batch):
+    """The arguments of ccv_mppi_batch_set_obstacles from `batch` arrays of (ox, oy, r) rows (instance b's discs; an empty
+    sequence or None: none) and a weight per instance (or one for all): xyr [B][max_n][3] (rows past an instance's count
+    zero), n [B] int32, max_n = the largest count, weight [B].  ValueError for a wrong number of instances, rows that are not
+    triples or more than capi.MAX_OBSTACLES discs; the values themselves are the library's to refuse."""
+    discs = list(discs)
+    if len(discs) != int(batch):
+        raise ValueError("obstacles: expected %d arrays of (ox, oy, r) rows, got %d" % (int(batch), len(discs)))
+    rows = []
+    for b, d in enumerate(discs):
+        a = np.zeros((0, 3)) if d is None else np.asarray(d, dtype=np.float64)
+        if a.size == 0:
+            a = np.zeros((0, 3))
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("obstacles[%d]: expected shape (n, 3), got %s" % (b, a.shape))
+        if a.shape[0] > capi.MAX_OBSTACLES:
+            raise ValueError("obstacles[%d]: %d discs, at most %d" % (b, a.shape[0], capi.MAX_OBSTACLES))
+        rows.append(a)
+    n = np.ascontiguousarray([a.shape[0] for a in rows], dtype=np.int32)
+    max_n = int(n.max()) if len(rows) else 0
+    xyr = np.zeros((int(batch), max_n, 3))
+    for b, a in enumerate(rows):
+        xyr[b, :a.shape[0]] = a
+    w = capi.as_f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), (int(batch),)))
+    return xyr, n, max_n, w
+
+
 class BatchController:
     """`batch` controllers on one device: one MPPIParams shared by all, or a sequence of `batch` MPPIParams that agree in
     SHARED_FIELDS (per-instance sigma, lambda, v_ref, bounds and weights; K = num_samples per instance).  min_shift: the
@@ -134,6 +161,28 @@ class BatchController:
 
     def get_min_shift(self):
         return bool(self.lib.ccv_mppi_batch_get_min_shift(self._h))
+
+    # ---- per-instance disc obstacles (ccv_mppi_batch_set_obstacles) ----
+    def set_obstacles(self, discs, weight=0.0):
+        """discs: B arrays of (ox, oy, r) rows in world coordinates (an instance without discs: an empty one), or None: the term
+        off and the kernels that ran before; weight: one value or [B], >= 0.  The cost of every state the path term covers gains
+        weight_b * max(max_j(r_j^2 - |p - o_j|^2), 0).  A weight that matters needs set_min_shift(True).  Flushes a pending
+        resident update; warm starts, paths, poses and per-instance parameters stay."""
+        if discs is None:
+            self._check(self.lib.ccv_mppi_batch_set_obstacles(self._h, None, None, 0, None))
+            return
+        xyr, n, max_n, w = pack_obstacles(discs, weight, self.B)
+        self._check(self.lib.ccv_mppi_batch_set_obstacles(self._h, capi.dptr(xyr), n.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          max_n, capi.dptr(w)))
+
+    def get_obstacles(self):
+        """(list of B arrays [n_b][3], weight [B]) as the library holds them; empty arrays and zeros while the term is off."""
+        n = np.zeros(self.B, dtype=np.int32)
+        w = np.zeros(self.B)
+        xyr = np.zeros((self.B, capi.MAX_OBSTACLES, 3))
+        self._check(self.lib.ccv_mppi_batch_get_obstacles(self._h, capi.dptr(xyr), n.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          capi.MAX_OBSTACLES, capi.dptr(w)))
+        return [xyr[b, :n[b]].copy() for b in range(self.B)], w
 
     # ---- warm starts [B][H-1][u_dim] ----
     def set_nominal(self, u):

@@ -27,6 +27,8 @@ BATCH_MAX_SAMPLES = 1 << 29
 BATCH_KERNEL_PLAIN, BATCH_KERNEL_ONE_WAVE, BATCH_KERNEL_FOUR_WAVE, BATCH_KERNEL_WIDE = 0, 1, 4, 16
 BATCH_KERNEL_VARIED = 32
 BATCH_KERNEL_SHIFT = 64
+BATCH_KERNEL_OBST = 128
+MAX_OBSTACLES = 32
 BATCH_TRACE_ROWS = 1024
 
 
@@ -109,6 +111,8 @@ SIGNATURES = {
     "ccv_mppi_batch_get_params": (C.c_int, [_H, C.POINTER(Config)]),
     "ccv_mppi_batch_set_min_shift": (C.c_int, [_H, C.c_int32]),
     "ccv_mppi_batch_get_min_shift": (C.c_int, [_H]),
+    "ccv_mppi_batch_set_obstacles": (C.c_int, [_H, _dp, C.POINTER(C.c_int32), C.c_int32, _dp]),
+    "ccv_mppi_batch_get_obstacles": (C.c_int, [_H, _dp, C.POINTER(C.c_int32), C.c_int32, _dp]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),

@@ -15,11 +15,12 @@ int batch_kernel_code(const RolloutPlan& p) {
                        : p.family == KernelFamily::OneWave ? CCV_MPPI_BATCH_KERNEL_ONE_WAVE
                                                            : CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
     return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0) |
-           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0);
+           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0) | (p.obst ? CCV_MPPI_BATCH_KERNEL_OBST : 0);
 }
 
-// whether the kernels read the parameter table: per-instance parameters, or shifted weights (B copies of cfg in the table then)
-bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift; }
+// whether the kernels read the parameter table: per-instance parameters, or shifted weights or obstacles (B copies of cfg in
+// the table then)
+bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift || bh->obst; }
 
 // the parameter table [B] on the device from B configurations (null: B copies of the creation configuration).  The caller has
 // flushed and synchronised: a queued rollout or prologue may still read the old table.
@@ -46,6 +47,11 @@ int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
         P.w_back = A.w_back;
         P.w_yaw = A.w_yaw;
         P.fast_clamp = A.fast_clamp;
+        if (bh->obst) {   // (every upload keeps the obstacle fields: ccv_mppi_batch_set_obstacles)
+            P.n_obst = bh->obst_n[(size_t)b];
+            P.obst = bh->d_obst + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 3;
+            P.w_obs = bh->obst_w[(size_t)b];
+        }
     }
     if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
     HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
@@ -117,7 +123,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // of the fused kernels waits in bh->fin for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
-    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift);
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, bh->obst);
     const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -257,7 +263,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
-    void* bufs[] = {bh->d_rec, bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace, bh->d_params, bh->d_cmin};
+    void* bufs[] = {bh->d_rec, bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace, bh->d_params, bh->d_cmin, bh->d_obst};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete bh;
@@ -307,7 +313,7 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     const int B = bh->B;
     if (!cfgs) {   // back to the creation configuration; the shared kernels, or in shifted-weight mode B copies in the table
         if (int rc = batch_flush(bh)) return rc;
-        if (bh->min_shift) {
+        if (bh->min_shift || bh->obst) {
             HIP_TRY(bh, hipStreamSynchronize(bh->stream));
             if (int rc = upload_params(bh, nullptr)) return rc;
         }
@@ -351,7 +357,7 @@ int ccv_mppi_batch_set_min_shift(ccv_mppi_batch* bh, int32_t on) {
     const DeviceGuard guard(bh->cfg.device);
     HIP_TRY(bh, hipSetDevice(bh->cfg.device));
     if (int rc = batch_flush(bh)) return rc;   // (the pending update is the old mode's)
-    if (want && !bh->varied) {                 // the SHIFT kernels read the table: B copies of the creation configuration
+    if (want && !uses_table(bh)) {             // the SHIFT kernels read the table: B copies of the creation configuration
         HIP_TRY(bh, hipStreamSynchronize(bh->stream));
         if (int rc = upload_params(bh, nullptr)) return rc;
     }
@@ -360,6 +366,74 @@ int ccv_mppi_batch_set_min_shift(ccv_mppi_batch* bh, int32_t on) {
 }
 
 int ccv_mppi_batch_get_min_shift(const ccv_mppi_batch* bh) { return bh ? (bh->min_shift ? 1 : 0) : CCV_MPPI_ERR_INVALID_ARG; }
+
+// ---- disc obstacles -------------------------------------------------------------------------------------------------------
+
+int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const int32_t* n, int32_t max_n, const double* weight) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    const bool off = !xyr || max_n == 0;
+    // every check comes before anything changes
+    if (!off) {
+        if (max_n < 0 || max_n > M) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: max_n outside [0, CCV_MPPI_MAX_OBSTACLES]");
+        if (!n || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+        for (int b = 0; b < B; ++b) {
+            if (!(weight[b] >= 0.0) || !std::isfinite(weight[b]))
+                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a weight is negative or not finite");
+            if (n[b] < 0 || n[b] > max_n) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a count outside [0, max_n]");
+            for (int j = 0; j < n[b]; ++j) {
+                const double* o = xyr + ((size_t)b * max_n + j) * 3;
+                if (!std::isfinite(o[0]) || !std::isfinite(o[1]))
+                    return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a centre is not finite");
+                if (!(o[2] >= 0.0) || !std::isfinite(o[2]))
+                    return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a radius is negative or not finite");
+            }
+        }
+    }
+    if (off && !bh->obst) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table and discs)
+    if (off) {
+        bh->obst = false;
+        bh->obst_xyr.clear();
+        bh->obst_n.clear();
+        bh->obst_w.clear();
+        if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (null / 0 / 0 in every row)
+        return CCV_MPPI_OK;
+    }
+    std::vector<double> rows((size_t)B * M * 3, 0.0);
+    for (int b = 0; b < B; ++b)
+        for (int j = 0; j < n[b]; ++j) std::memcpy(&rows[((size_t)b * M + j) * 3], xyr + ((size_t)b * max_n + j) * 3, 3 * sizeof(double));
+    if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, rows.size() * sizeof(double)));
+    HIP_TRY(bh, hipMemcpy(bh->d_obst, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+    bh->obst_xyr.swap(rows);
+    bh->obst_n.assign(n, n + B);
+    bh->obst_w.assign(weight, weight + B);
+    bh->obst = true;
+    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+}
+
+int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* bh, double* xyr, int32_t* n, int32_t max_n, double* weight) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    if (max_n < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacles: max_n < 0");
+    for (int b = 0; b < B && bh->obst; ++b)
+        if (xyr && bh->obst_n[(size_t)b] > max_n) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacles: max_n below an instance's count");
+    for (int b = 0; b < B; ++b) {
+        const int nb = bh->obst ? bh->obst_n[(size_t)b] : 0;
+        if (n) n[b] = nb;
+        if (weight) weight[b] = bh->obst ? bh->obst_w[(size_t)b] : 0.0;
+        if (xyr) {
+            std::memset(xyr + (size_t)b * max_n * 3, 0, (size_t)max_n * 3 * sizeof(double));
+            if (nb > 0) std::memcpy(xyr + (size_t)b * max_n * 3, &bh->obst_xyr[(size_t)b * M * 3], (size_t)nb * 3 * sizeof(double));
+        }
+    }
+    return CCV_MPPI_OK;
+}
 
 int ccv_mppi_batch_get_params(ccv_mppi_batch* bh, ccv_mppi_config* out) {
     if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;

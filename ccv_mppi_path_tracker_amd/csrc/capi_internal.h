@@ -211,6 +211,13 @@ struct ccv_mppi_batch : Core {
     // parameter table -- B copies of cfg in it while `varied` is false
     bool min_shift = false;
     double* d_cmin = nullptr;               // [B]: the plain family's exact instance minima (k_min_cost_batch)
+    // disc obstacles (ccv_mppi_batch_set_obstacles): the OBST rollout kernels, always over the parameter table too; the rows of
+    // the table point into d_obst
+    bool obst = false;
+    double* d_obst = nullptr;               // [B][CCV_MPPI_MAX_OBSTACLES][3], allocated at the first _set_obstacles, freed at destroy
+    std::vector<double> obst_xyr;           // [B][CCV_MPPI_MAX_OBSTACLES][3] host copy while obst
+    std::vector<int32_t> obst_n;            // [B]
+    std::vector<double> obst_w;             // [B]
     bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
 };
 
@@ -275,11 +282,12 @@ inline bool has_wide_form(const KernelChoice& k, const int mode) {
 }
 // The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
 // (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
-// shift (a batch in shifted-weight mode): always with the per-instance-parameter kernels.
+// shift (a batch in shifted-weight mode), obst (a batch with obstacles): always with the per-instance-parameter kernels.
 inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied,
-                             const bool shift = false) {
+                             const bool shift = false, const bool obst = false) {
     const KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
-    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift, shift, k.lds_window != 0};
+    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift || obst, shift, obst,
+                       k.lds_window != 0};
 }
 
 RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);   // a single handle's

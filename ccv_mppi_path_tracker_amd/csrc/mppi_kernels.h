@@ -91,11 +91,15 @@ struct BatchHead {
 // Per-instance controller parameters of a batch handle (ccv_mppi_batch_set_params): one row per instance, three 64-byte lines,
 // the RolloutArgs fields fill_args() forms from a configuration -- ROLL_OFF's zero weights and the fast-clamp test included.
 // A VARIED kernel takes its instance's row in batch_view() and is the single handle's code from there on.
+// obst / n_obst / w_obs (ccv_mppi_batch_set_obstacles; OBST kernels only): the instance's discs, rows (ox, oy, r) of a device
+// table, and the weight of their penalty; null / 0 / 0 without obstacles.
 struct alignas(64) BatchParams {
     double sigma, lambda, v_ref;
     double umin[5], umax[5];
     double w_path, w_v, w_zmp, w_rollv, w_back, w_yaw;
-    int32_t fast_clamp, pad;
+    int32_t fast_clamp, n_obst;
+    const double* obst;
+    double w_obs;
 };
 static_assert(sizeof(BatchParams) == 192, "three 64-byte lines per instance");
 constexpr int kBatchHeadDoubles = 16;
@@ -278,6 +282,96 @@ __device__ __forceinline__ double clampd_as(double v, double lo, double hi) {
     else return clampd(v, lo, hi);
 }
 
+// ---- per-instance disc obstacles of a batch handle (OBST kernels) -----------------------------
+// The power of a point p with respect to disc j, |p - o_j|^2 - r_j^2, is |p|^2 + a_j px + b_j py + c_j in pose-relative
+// coordinates -- the window distance's form with c_j = |o_j - x0|^2 - r_j^2 -- so the deepest penetration over the discs is
+// a second minimum of the same kind over a second, short coefficient list.
+constexpr int kMaxObst = CCV_MPPI_MAX_OBSTACLES;
+struct ObstLds {
+    double2 ab[kMaxObst];
+    double c[kMaxObst];
+};
+// the instance's obstacle fields, from the row of the parameter table its record's head points at (A.frame: batch_view);
+// wave-uniform, read through the constant address space
+struct ObstRow {
+    const double* xyr;
+    double w;
+    int n;
+};
+__device__ __forceinline__ ObstRow obst_row(const RolloutArgs& A) {
+    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
+    typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
+    const auto& P = *(ConstParams)(const void*)((ConstHead)(const void*)A.frame)->params;
+    const int n = P.n_obst;
+    return ObstRow{P.obst, P.w_obs, n < 0 ? 0 : (n > kMaxObst ? kMaxObst : n)};
+}
+// staging, once per workgroup: thread j = 0 .. kMaxObst-1 writes disc j's coefficients relative to the pose the kernel holds,
+// or the padding a = b = 0, c = +inf (never the minimum) past the instance's count
+__device__ __forceinline__ void obst_stage(const RolloutArgs& A, ObstLds& ob, const int j) {
+    const ObstRow o = obst_row(A);
+    double a = 0.0, b = 0.0, c = INFINITY;
+    if (j < o.n) {
+        const double ox = o.xyr[3 * j], oy = o.xyr[3 * j + 1], r = o.xyr[3 * j + 2];
+        const double dx = ox - A.x0[0], dy = oy - A.x0[1];
+        a = -2.0 * dx;
+        b = -2.0 * dy;
+        c = fma(dx, dx, dy * dy) - r * r;
+    }
+    ob.ab[j] = make_double2(a, b);
+    ob.c[j] = c;
+}
+// cost += w_obs * max(max_j(r_j^2 - |p - o_j|^2), 0) for states i < nv of the NV held in registers (p relative to the pose).
+// m: registers for the running minima (the window loop's, dead by now).  Four discs per iteration over the padded list; a NaN
+// position gives s = NaN and v_max_f64(-NaN, 0) = 0.
+template <int NV, int NM, bool MASK = false>   // MASK: only the first nv of the NV states count (the plain kernel's blocks)
+__device__ __forceinline__ void obst_term(const RolloutArgs& A, const ObstLds& ob, const double (&px)[NM], const double (&py)[NM],
+                                          double (&m)[NM], double& cost, const int nv = NV) {
+    const ObstRow o = obst_row(A);
+    const int n4 = (o.n + 3) & ~3;
+    if (n4 == 0) return;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) m[i] = INFINITY;
+    if constexpr (MASK) {
+        // the plain kernel: one disc per iteration, as window_min -- four at a time cost it 21 registers and a wave per SIMD
+#pragma unroll 1
+        for (int j = 0; j < n4; ++j) {
+            const double2 ab = ob.ab[j];
+            const double c = ob.c[j];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const double t = fma(ab.x, px[i], fma(ab.y, py[i], c));
+                asm("v_min_f64 %0, %1, %2" : "=v"(m[i]) : "v"(m[i]), "v"(t));
+            }
+        }
+    } else {
+        for (int j = 0; j < n4; j += 4) {
+            double2 ab[4];
+            double c[4];
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                ab[jj] = ob.ab[j + jj];
+                c[jj] = ob.c[j + jj];
+            }
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const double f0 = fma(ab[0].x, px[i], fma(ab[0].y, py[i], c[0]));
+                const double f1 = fma(ab[1].x, px[i], fma(ab[1].y, py[i], c[1]));
+                const double f2 = fma(ab[2].x, px[i], fma(ab[2].y, py[i], c[2]));
+                const double f3 = fma(ab[3].x, px[i], fma(ab[3].y, py[i], c[3]));
+                const double t = fmin(fmin(f0, f1), fmin(f2, f3));
+                asm("v_min_f64 %0, %1, %2" : "=v"(m[i]) : "v"(m[i]), "v"(t));   // (two quiet operands: pc_consume)
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const double s = m[i] + fma(px[i], px[i], py[i] * py[i]);
+        double g;
+        asm("v_max_f64 %0, -%1, 0" : "=v"(g) : "v"(s));
+        if (!MASK || i < nv) cost = fma(o.w, g, cost);
+    }
+}
+
 // min over the H window points of (a_j*px + b_j*py + c_j) for NV trajectory points held in registers.
 // 2 FMA + 1 MIN per (point, window point): the O(K*H^2) core (calc_MinDistance, dd:183-192).
 template <int NV, bool LDSWIN>
@@ -303,21 +397,31 @@ __device__ __forceinline__ void window_min(const double (&px)[kTU], const double
     }
 }
 
-// BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters
-template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false>
+// BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters;
+// OBST (on VARIED): with the instance's disc obstacles (obst_term)
+template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false, bool OBST = false>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
     static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
+    static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
     constexpr int UD = udim_of(MODEL);
     __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
     __shared__ double s_c[LDSWIN ? kMaxH : 1];
     const RolloutArgs A = BATCH ? batch_view<VARIED>(Ak, (int)blockIdx.y) : Ak;
     const int H = A.H;
+    ObstLds* obst_lds = nullptr;
+    if constexpr (OBST) {
+        __shared__ ObstLds s_obst;
+        obst_lds = &s_obst;
+    }
     if constexpr (BATCH) {
         const double* win = reinterpret_cast<const double*>(A.frame) + kBatchHeadDoubles;
         for (int j = threadIdx.x; j < H; j += kBlock) {
             s_ab[j] = make_double2(win[j], win[H + j]);
             s_c[j] = win[2 * H + j];
+        }
+        if constexpr (OBST) {
+            if (threadIdx.x < kMaxObst) obst_stage(A, *obst_lds, (int)threadIdx.x);
         }
         __syncthreads();
     } else if constexpr (LDSWIN) {
@@ -466,6 +570,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, c
                         cost += A.w_path * d2;
                     }
                 }
+                if constexpr (OBST) obst_term<kTU, kTU, true>(A, *obst_lds, px, py, m, cost, nv);
             }
         }
     }

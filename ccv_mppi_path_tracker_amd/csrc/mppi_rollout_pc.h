@@ -806,11 +806,14 @@ __device__ __forceinline__ void pc_prune_window(const RolloutArgs& A, const SH& 
 // ---------------------------------------------------------------------------------------------------------------
 // LEAN (four-wave kernel, 128 VGPRs): two window points per register set instead of four and the running minimum taken
 // point pair by point pair -- 48 registers less; the same minima, hence the same bits.
-template <int NV, int MODEL, class SH, bool LEAN = false>
+// OBST (batch handles, on VARIED): after the block's path terms, the instance's disc-obstacle term of the same states from the
+// coefficients staged in `ob` (obst_term, mppi_kernels.h); the window pruning does not touch that list.
+template <int NV, int MODEL, class SH, bool LEAN = false, bool OBST = false>
 __device__ __forceinline__ void pc_consume(const RolloutArgs& A, const SH& sh, double& cost, const int b, const int lane,
                                            const int i0 = 0,          // states i0 .. i0+NV-1 of block b
                                            int* prune_on = nullptr,   // wave-uniform switch of the window pruning (below)
-                                           int* taken_flag = nullptr, const int taken_value = 0) {   // see below
+                                           int* taken_flag = nullptr, const int taken_value = 0,   // see below
+                                           const ObstLds* ob = nullptr) {
     const int H4 = (A.H + 3) & ~3;   // the window is padded with c = +inf: four points per iteration, no remainder
     double px[NV], py[NV], m[NV];
 #pragma unroll
@@ -939,6 +942,7 @@ __device__ __forceinline__ void pc_consume(const RolloutArgs& A, const SH& sh, d
             cost = fma(A.w_path, d2, cost);
         }
     }
+    if constexpr (OBST) obst_term<NV>(A, *ob, px, py, m, cost);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

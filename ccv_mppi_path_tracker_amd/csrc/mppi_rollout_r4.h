@@ -235,7 +235,10 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // BATCH (fused iteration): workgroup blockIdx.x serves instance blockIdx.x / (its workgroups per instance) of a batch handle
 // (batch_view, mppi_kernels.h); everything else is the single handle's code.  VARIED: the batch's per-instance parameters
 // SHIFT (on VARIED): block-relative weights exp(-(total - m_g) / lambda), m_g = the workgroup's minimum cost (pc_shifted_weight)
-template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false>
+// OBST (on VARIED): the instance's disc obstacles -- staged beside the window by the distance wave's first 32 lanes, from the
+// pose the kernel holds; their term in the distance wave (pc_consume, obst_term)
+template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false,
+          bool OBST = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
@@ -245,7 +248,13 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     static_assert(!BATCH || MODE == MODE_FUSED, "batch handles run the fused iteration only");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
+    static_assert(!OBST || (VARIED && MODE == MODE_FUSED), "the obstacle term is built on the per-instance-parameter kernels");
     __shared__ R4Shared<MODEL> sh;
+    ObstLds* obst_lds = nullptr;   // (an array of its own: R4Shared, and with it every other kernel's LDS, stays as it is)
+    if constexpr (OBST) {
+        __shared__ ObstLds s_obst;
+        obst_lds = &s_obst;
+    }
     static_assert(offsetof(R4Shared<MODEL>, zs) + sizeof(sh.zs) >= kR4Waves * kR4RB<MODEL> * (kPcSamples + 2) * sizeof(double), "epilogue buffers");
     touch_rollout_args();
     const RolloutArgs A = rollout_view<MODEL, BATCH, VARIED>(Ak);
@@ -293,6 +302,10 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             CCV_DIAG_STAMP(A, 1);
         }
         bad_nominal = r4_stage_commit<MODEL>(A, sh, (int)threadIdx.x, staged);
+        if constexpr (OBST) {
+            const int j = (int)threadIdx.x - 2 * 64;
+            if (j >= 0 && j < kMaxObst) obst_stage(A, *obst_lds, j);
+        }
         // a NaN in the warm start: every wave says what its threads saw, every wave reads all four words after the barrier
         const bool wave_bad = __builtin_amdgcn_ballot_w64(bad_nominal) != 0ull;
         if (r4_lane(A).lane == 0) sh.nan_seen[wv] = wave_bad ? 1 : 0;
@@ -424,14 +437,14 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
                 const int nv = min(kR3CStates, nstates - b * kTU);
                 taken = nv > 0;
                 switch (nv) {
-                    case 8: pc_consume<8, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 7: pc_consume<7, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 6: pc_consume<6, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 5: pc_consume<5, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 4: pc_consume<4, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 3: pc_consume<3, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 2: pc_consume<2, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 1: pc_consume<1, MODEL, R4Shared<MODEL>, true>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
+                    case 8: pc_consume<8, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 7: pc_consume<7, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 6: pc_consume<6, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 5: pc_consume<5, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 4: pc_consume<4, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 3: pc_consume<3, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 2: pc_consume<2, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 1: pc_consume<1, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
                     default: break;
                 }
             }

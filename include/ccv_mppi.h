@@ -251,6 +251,8 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_BATCH_KERNEL_WIDE 16
 #define CCV_MPPI_BATCH_KERNEL_VARIED 32 /* ORed in: the kernels with per-instance parameters ran (ccv_mppi_batch_set_params) */
 #define CCV_MPPI_BATCH_KERNEL_SHIFT 64   /* ORed into ccv_mppi_batch_last_kernel(): the shifted-weight kernels ran */
+#define CCV_MPPI_BATCH_KERNEL_OBST 128   /* ORed in: the kernels with the disc-obstacle term ran (ccv_mppi_batch_set_obstacles) */
+#define CCV_MPPI_MAX_OBSTACLES 32        /* discs per instance */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
 
@@ -299,6 +301,24 @@ int ccv_mppi_batch_get_params(ccv_mppi_batch* b, ccv_mppi_config* out);
  * parameters stay.  _get_min_shift: 0 / 1, or CCV_MPPI_ERR_INVALID_ARG for a null handle. */
 int ccv_mppi_batch_set_min_shift(ccv_mppi_batch* b, int32_t on);
 int ccv_mppi_batch_get_min_shift(const ccv_mppi_batch* b);
+/* Per-instance disc obstacles (NOT reference behaviour; off by default; batch handles only).  Instance b has n[b] discs
+ * (ox, oy, r) in world coordinates, static until the next call, and a weight weight[b] >= 0.  For every state p the path term
+ * is taken over (the same states, the same step ranges) the cost gains
+ *     weight[b] * max( max_j ( r_j^2 - |p - o_j|^2 ), 0 )
+ * -- the deepest penetration, not a sum over the discs; a NaN position contributes 0; the caller inflates r by the robot's own
+ * radius and a margin.  The term touches the cost only: noise, controls and states keep their bits, an instance with n[b] = 0
+ * or weight[b] = 0 keeps every bit of its result, and no disc of one instance changes a bit of another.  A weight large enough
+ * to matter pushes costs past 745 lambda, where the plain weights are all 0 and u* is NaN: use ccv_mppi_batch_set_min_shift.
+ * xyr: [B][max_n][3], n: [B] counts (0 <= n[b] <= max_n <= CCV_MPPI_MAX_OBSTACLES), weight: [B].  The term always runs the
+ * per-instance-parameter kernels (_last_kernel: OBST | VARIED | family, | SHIFT, | WIDE); a handle without _set_params has B
+ * copies of its configuration in the table, and _set_params keeps the obstacles.  xyr == NULL or max_n == 0 turns the term off
+ * and returns to the kernels, and the bits, that ran before.  A negative or non-finite weight or r, a non-finite centre, n[b]
+ * outside [0, max_n] or max_n above the limit: CCV_MPPI_ERR_INVALID_ARG, nothing changes.  Flushes a pending resident update
+ * and synchronises, like _set_params; the resident loop sees the discs from the next step on.
+ * _get_obstacles: xyr [B][max_n][3] (rows past n[b] zero), n [B], weight [B]; max_n must hold the largest count (all zero / 0
+ * while the term is off); any of the three may be NULL. */
+int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* b, const double* xyr, const int32_t* n, int32_t max_n, const double* weight);
+int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* b, double* xyr, int32_t* n, int32_t max_n, double* weight);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
