@@ -301,6 +301,36 @@ class BatchController:
         self._check(self.lib.ccv_mppi_batch_resident_read_trace(self._h, int(instance), max_rows, capi.dptr(rows), C.byref(n)))
         return rows[:n.value].copy()
 
+    # ---- fleet term: the robots of the batch keep clear of each other (ccv_mppi_batch_resident_set_fleet) ----
+    def resident_set_fleet(self, radius, range=0.0, max_neighbours=0, weight=0.0):
+        """radius: one value or [B], or None (with max_neighbours = 0): the term off.  Every resident tick then appends to
+        instance y's discs up to max_neighbours discs (q_j, radius[y] + radius[j]) for the nearest other robots within `range`
+        of its pose at the start of the tick; weight (one value or [B]) becomes the instances' obstacle weight.  Flushes a
+        pending resident update; iterate() / iterate_enqueue() are refused while the term is on."""
+        reach = float(range)   # (the keyword is the C ABI's name and shadows the builtin here: use `reach` below)
+        if radius is None:
+            self._check(self.lib.ccv_mppi_batch_resident_set_fleet(self._h, None, reach, int(max_neighbours), None))
+            return
+        r = capi.as_f64(np.broadcast_to(np.asarray(radius, dtype=np.float64), (self.B,)))
+        w = capi.as_f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), (self.B,)))
+        self._check(self.lib.ccv_mppi_batch_resident_set_fleet(self._h, capi.dptr(r), reach, int(max_neighbours), capi.dptr(w)))
+
+    def resident_get_fleet(self):
+        """(radius [B], range, max_neighbours) as the library holds them; zeros while the term is off."""
+        r = np.zeros(self.B)
+        rng, m = C.c_double(), C.c_int32()
+        self._check(self.lib.ccv_mppi_batch_resident_get_fleet(self._h, capi.dptr(r), C.byref(rng), C.byref(m)))
+        return r, rng.value, m.value
+
+    def resident_read_fleet(self):
+        """(n_static [B], n_total [B], xyr [B][capi.MAX_OBSTACLES][3]): the disc lists the last tick's rollout was charged
+        with, the static discs first, rows past n_total zero; synchronises."""
+        ns, nt = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        xyr = np.zeros((self.B, capi.MAX_OBSTACLES, 3))
+        self._check(self.lib.ccv_mppi_batch_resident_read_fleet(self._h, ns.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                                nt.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(xyr)))
+        return ns, nt, xyr
+
     # ---- measurement ----
     def timing_enable(self, on=True, every=1):
         self._check(self.lib.ccv_mppi_batch_timing_enable(self._h, (max(1, int(every)) if on else 0)))

@@ -1,5 +1,5 @@
 """ctypes binding of libccv_mppi_hip.so -- exactly the symbols include/ccv_mppi.h and
-include/ccv_mppi_host.h declare.  No torch types cross this boundary; there is no CPU fallback:
+include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
 if the library is missing it is built with hipcc, and if that fails the import raises.
 """
 import ctypes as C
@@ -157,6 +157,12 @@ SIGNATURES = {
     "ccv_mppi_fb_estimator_update": (C.c_int, [_H, C.c_double, C.c_double, C.c_double, C.c_double]),
     "ccv_mppi_fb_estimator_read": (C.c_int, [_H, _dp]),
 }
+# include/ccv_mppi_fleet.h: the fleet term of the resident loop, a table of its own like its header
+FLEET_SIGNATURES = {
+    "ccv_mppi_batch_resident_set_fleet": (C.c_int, [_H, _dp, C.c_double, C.c_int32, _dp]),
+    "ccv_mppi_batch_resident_get_fleet": (C.c_int, [_H, _dp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "ccv_mppi_batch_resident_read_fleet": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
+}
 
 _lib = None
 
@@ -169,7 +175,7 @@ def load():
         if not os.path.exists(path):
             raise ImportError("libccv_mppi_hip.so is missing and could not be built; there is no CPU fallback")
         lib = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError = the .so does not export what the header declares
             fn.restype = res
             fn.argtypes = args

@@ -19,8 +19,12 @@ int batch_kernel_code(const RolloutPlan& p) {
 }
 
 // whether the kernels read the parameter table: per-instance parameters, or shifted weights or obstacles (B copies of cfg in
-// the table then)
-bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift || bh->obst; }
+// the table then), or the fleet term
+bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift || bh->obst || bh->fleet; }
+
+// whether the obstacle kernels run: static discs (ccv_mppi_batch_set_obstacles) or the fleet term (_resident_set_fleet); the
+// obst_* vectors and d_obst exist then
+bool obst_on(const ccv_mppi_batch* bh) { return bh->obst || bh->fleet; }
 
 // the parameter table [B] on the device from B configurations (null: B copies of the creation configuration).  The caller has
 // flushed and synchronised: a queued rollout or prologue may still read the old table.
@@ -47,7 +51,9 @@ int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
         P.w_back = A.w_back;
         P.w_yaw = A.w_yaw;
         P.fast_clamp = A.fast_clamp;
-        if (bh->obst) {   // (every upload keeps the obstacle fields: ccv_mppi_batch_set_obstacles)
+        // (every upload keeps the obstacle fields: ccv_mppi_batch_set_obstacles; under the fleet term n_obst is the static count
+        // until the next resident tick's prologue writes the tick's own)
+        if (obst_on(bh)) {
             P.n_obst = bh->obst_n[(size_t)b];
             P.obst = bh->d_obst + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 3;
             P.w_obs = bh->obst_w[(size_t)b];
@@ -123,7 +129,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // of the fused kernels waits in bh->fin for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
-    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, bh->obst);
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, obst_on(bh));
     const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -197,11 +203,21 @@ int batch_fetch(ccv_mppi_batch* bh, double* u_opt_out, ccv_mppi_stats* stats) {
     return CCV_MPPI_OK;
 }
 
+// the fleet's lists exist only where the poses live: the host-record calls are refused while the term is on
+const char kFleetHostRecord[] = "the fleet term is on: resident steps only (ccv_mppi_batch_resident_set_fleet)";
+
 int batch_check_read(ccv_mppi_batch* bh, int32_t instance, const void* out) {
     if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
     if (instance < 0 || instance >= bh->B) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "instance out of range");
     if (!bh->have_result) return fail(bh, CCV_MPPI_ERR_STATE, "no iteration yet");
     return batch_flush(bh);
+}
+
+// both halves of the fleet's position table from xy [B][2] (the stream is idle: the caller has synchronised)
+int fleet_write_positions(ccv_mppi_batch* bh, const std::vector<double>& xy) {
+    const size_t half = (size_t)bh->B * 2;
+    for (int h = 0; h < 2; ++h) HIP_TRY(bh, hipMemcpy(bh->d_fleet_xy + h * half, xy.data(), half * sizeof(double), hipMemcpyHostToDevice));
+    return CCV_MPPI_OK;
 }
 }  // namespace
 
@@ -263,7 +279,8 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
-    void* bufs[] = {bh->d_rec, bh->d_rframe, bh->d_inst, bh->d_rpath, bh->d_rtrace, bh->d_params, bh->d_cmin, bh->d_obst};
+    void* bufs[] = {bh->d_rec,  bh->d_rframe, bh->d_inst,     bh->d_rpath,        bh->d_rtrace,       bh->d_params,
+                    bh->d_cmin, bh->d_obst,   bh->d_fleet_xy, bh->d_fleet_radius, bh->d_fleet_nstatic};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete bh;
@@ -313,7 +330,7 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     const int B = bh->B;
     if (!cfgs) {   // back to the creation configuration; the shared kernels, or in shifted-weight mode B copies in the table
         if (int rc = batch_flush(bh)) return rc;
-        if (bh->min_shift || bh->obst) {
+        if (bh->min_shift || obst_on(bh)) {
             HIP_TRY(bh, hipStreamSynchronize(bh->stream));
             if (int rc = upload_params(bh, nullptr)) return rc;
         }
@@ -396,7 +413,7 @@ int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const in
     HIP_TRY(bh, hipSetDevice(bh->cfg.device));
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table and discs)
-    if (off) {
+    if (off && !bh->fleet) {
         bh->obst = false;
         bh->obst_xyr.clear();
         bh->obst_n.clear();
@@ -404,15 +421,18 @@ int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const in
         if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (null / 0 / 0 in every row)
         return CCV_MPPI_OK;
     }
+    // (off under the fleet term: the static discs go; table, weights and fleet stay)
     std::vector<double> rows((size_t)B * M * 3, 0.0);
-    for (int b = 0; b < B; ++b)
+    for (int b = 0; b < B && !off; ++b)
         for (int j = 0; j < n[b]; ++j) std::memcpy(&rows[((size_t)b * M + j) * 3], xyr + ((size_t)b * max_n + j) * 3, 3 * sizeof(double));
     if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, rows.size() * sizeof(double)));
     HIP_TRY(bh, hipMemcpy(bh->d_obst, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
     bh->obst_xyr.swap(rows);
-    bh->obst_n.assign(n, n + B);
-    bh->obst_w.assign(weight, weight + B);
-    bh->obst = true;
+    if (off) bh->obst_n.assign((size_t)B, 0);
+    else bh->obst_n.assign(n, n + B);
+    if (!off) bh->obst_w.assign(weight, weight + B);
+    bh->obst = !off;
+    if (bh->fleet) HIP_TRY(bh, hipMemcpy(bh->d_fleet_nstatic, bh->obst_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
     return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
 }
 
@@ -421,12 +441,13 @@ int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* bh, double* xyr, int32_t* n, in
     const int B = bh->B;
     constexpr int M = CCV_MPPI_MAX_OBSTACLES;
     if (max_n < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacles: max_n < 0");
-    for (int b = 0; b < B && bh->obst; ++b)
+    const bool on = obst_on(bh);   // (under the fleet term alone: no discs, the fleet's weights)
+    for (int b = 0; b < B && on; ++b)
         if (xyr && bh->obst_n[(size_t)b] > max_n) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacles: max_n below an instance's count");
     for (int b = 0; b < B; ++b) {
-        const int nb = bh->obst ? bh->obst_n[(size_t)b] : 0;
+        const int nb = on ? bh->obst_n[(size_t)b] : 0;
         if (n) n[b] = nb;
-        if (weight) weight[b] = bh->obst ? bh->obst_w[(size_t)b] : 0.0;
+        if (weight) weight[b] = on ? bh->obst_w[(size_t)b] : 0.0;
         if (xyr) {
             std::memset(xyr + (size_t)b * max_n * 3, 0, (size_t)max_n * 3 * sizeof(double));
             if (nb > 0) std::memcpy(xyr + (size_t)b * max_n * 3, &bh->obst_xyr[(size_t)b * M * 3], (size_t)nb * 3 * sizeof(double));
@@ -445,6 +466,7 @@ int ccv_mppi_batch_iterate(ccv_mppi_batch* bh, const double* x0, const double* d
                            const double* yaw_ref0, const uint64_t* seed, uint64_t iter, double* u_opt_out, ccv_mppi_stats* stats) {
     int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
     if (rc) return rc;
+    if (bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, kFleetHostRecord);
     if ((rc = batch_flush(bh))) return rc;   // (the rollout reads u*)
     bh->want_mail = !(stats && bh->timing);   // (a timed call synchronises for its events anyway)
     rc = batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
@@ -457,6 +479,7 @@ int ccv_mppi_batch_iterate_enqueue(ccv_mppi_batch* bh, const double* x0, const d
                                    const double* y_ref, const double* yaw_ref0, const uint64_t* seed, uint64_t iter) {
     int rc = batch_check_args(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed);
     if (rc) return rc;
+    if (bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, kFleetHostRecord);
     if ((rc = batch_flush(bh))) return rc;   // (the rollout reads u*)
     return batch_enqueue(bh, x0, dt, x_ref, y_ref, yaw_ref0, seed, iter);
 }
@@ -572,6 +595,11 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
     HIP_TRY(bh, hipMemcpy2D(bh->d_rframe, sizeof(ResidentFrame), heads.data(), sizeof(FrameHead), sizeof(FrameHead), (size_t)B,
                            hipMemcpyHostToDevice));
     HIP_TRY(bh, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    if (bh->fleet) {
+        std::vector<double> xy((size_t)B * 2);
+        for (int b = 0; b < B; ++b) std::memcpy(&xy[(size_t)b * 2], heads[b].x0, 2 * sizeof(double));
+        if (int rc = fleet_write_positions(bh, xy)) return rc;
+    }
     bh->res_angle_abs.swap(angles);
     bh->res_steps = 0;
     bh->have_poses = true;
@@ -624,12 +652,26 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     G.model = c.model;
     G.advance = advance ? 1 : 0;
     G.trace_cap = CCV_MPPI_BATCH_TRACE_ROWS;
+    // the fleet term: this tick's snapshot is half res_steps & 1 of the position table, the prologue writes the other
+    FleetArgs L{};
+    if (bh->fleet) {
+        const size_t half = (size_t)B * 2;
+        L.xy_in = bh->d_fleet_xy + (size_t)(bh->res_steps & 1) * half;
+        L.xy_out = bh->d_fleet_xy + (size_t)((bh->res_steps + 1) & 1) * half;
+        L.radius = bh->d_fleet_radius;
+        L.n_static = bh->d_fleet_nstatic;
+        L.obst = bh->d_obst;
+        L.range2 = bh->fleet_range * bh->fleet_range;
+        L.max_neighbours = bh->fleet_maxn;
+        L.B = B;
+    }
     // (varied: the prologue takes each instance's v_ref from the parameter table and points its record's head at its row)
     if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
-        launch_finalize_advance(*bh, bh->fin, G, uses_table(bh) ? bh->d_params : nullptr);
+        launch_finalize_advance(*bh, bh->fin, G, uses_table(bh) ? bh->d_params : nullptr, bh->fleet ? &L : nullptr);
         bh->fin_pending = false;
     } else {
-        if (uses_table(bh)) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);
+        if (bh->fleet) hipLaunchKernelGGL(k_advance_batch_fleet, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params, L);
+        else if (uses_table(bh)) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);
         else hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G);
     }
     HIP_TRY(bh, hipGetLastError());
@@ -673,6 +715,102 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* bh, int32_t instance, int
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     const int64_t cap = CCV_MPPI_BATCH_TRACE_ROWS;
     HIP_TRY(bh, read_trace_ring(bh->d_rtrace + (size_t)instance * cap * 6, cap, bh->res_steps, max_rows, rows, n_rows));
+    return CCV_MPPI_OK;
+}
+
+// ---- fleet term: the robots of one resident batch keep clear of each other (mppi_fleet.h) ---------------------------------
+
+int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, double range, int32_t max_neighbours, const double* weight) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    const bool off = !radius && max_neighbours == 0;
+    // every check comes before anything changes
+    if (!off) {
+        if (!radius || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+        if (max_neighbours < 1 || max_neighbours > M)
+            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: max_neighbours outside [1, CCV_MPPI_MAX_OBSTACLES]");
+        if (!(range >= 0.0) || !std::isfinite(range)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: range is negative or not finite");
+        if (B > kFleetMaxBatch) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: more than 1024 instances");
+        for (int b = 0; b < B; ++b) {
+            if (!(radius[b] >= 0.0) || !std::isfinite(radius[b]))
+                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: a radius is negative or not finite");
+            if (!(weight[b] >= 0.0) || !std::isfinite(weight[b]))
+                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: a weight is negative or not finite");
+        }
+    }
+    if (off && !bh->fleet) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the tables)
+    if (off) {
+        bh->fleet = false;
+        bh->fleet_radius.clear();
+        bh->fleet_range = 0.0;
+        bh->fleet_maxn = 0;
+        if (!bh->obst) {   // no static discs either: back to the kernels that ran before
+            bh->obst_xyr.clear();
+            bh->obst_n.clear();
+            bh->obst_w.clear();
+        }
+        if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (the static counts again)
+        return CCV_MPPI_OK;
+    }
+    if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, (size_t)B * M * 3 * sizeof(double)));
+    if (!obst_on(bh)) {   // no static discs: empty lists
+        bh->obst_xyr.assign((size_t)B * M * 3, 0.0);
+        bh->obst_n.assign((size_t)B, 0);
+        HIP_TRY(bh, hipMemcpy(bh->d_obst, bh->obst_xyr.data(), bh->obst_xyr.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!bh->d_fleet_xy) {
+        HIP_TRY(bh, hipMalloc(&bh->d_fleet_xy, (size_t)B * 4 * sizeof(double)));
+        HIP_TRY(bh, hipMalloc(&bh->d_fleet_radius, (size_t)B * sizeof(double)));
+        HIP_TRY(bh, hipMalloc(&bh->d_fleet_nstatic, (size_t)B * sizeof(int32_t)));
+    }
+    HIP_TRY(bh, hipMemcpy(bh->d_fleet_radius, radius, (size_t)B * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipMemcpy(bh->d_fleet_nstatic, bh->obst_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+    // the position table from the current frames (zeros before the first _set_poses, which writes it again)
+    std::vector<double> xy((size_t)B * 2, 0.0);
+    if (bh->have_poses)
+        HIP_TRY(bh, hipMemcpy2D(xy.data(), 2 * sizeof(double), bh->d_rframe, sizeof(ResidentFrame), 2 * sizeof(double), (size_t)B,
+                               hipMemcpyDeviceToHost));
+    if (int rc = fleet_write_positions(bh, xy)) return rc;
+    bh->obst_w.assign(weight, weight + B);
+    bh->fleet_radius.assign(radius, radius + B);
+    bh->fleet_range = range;
+    bh->fleet_maxn = max_neighbours;
+    bh->fleet = true;
+    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+}
+
+int ccv_mppi_batch_resident_get_fleet(ccv_mppi_batch* bh, double* radius, double* range, int32_t* max_neighbours) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    for (int b = 0; b < bh->B && radius; ++b) radius[b] = bh->fleet ? bh->fleet_radius[(size_t)b] : 0.0;
+    if (range) *range = bh->fleet_range;
+    if (max_neighbours) *max_neighbours = bh->fleet_maxn;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_resident_read_fleet(ccv_mppi_batch* bh, int32_t* n_static, int32_t* n_total, double* xyr) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_fleet first");
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+    std::vector<int32_t> total((size_t)B);
+    HIP_TRY(bh, hipMemcpy2D(total.data(), sizeof(int32_t), reinterpret_cast<const char*>(bh->d_params) + offsetof(BatchParams, n_obst),
+                           sizeof(BatchParams), sizeof(int32_t), (size_t)B, hipMemcpyDeviceToHost));
+    if (xyr) {
+        HIP_TRY(bh, hipMemcpy(xyr, bh->d_obst, (size_t)B * M * 3 * sizeof(double), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)   // (rows past the count: whatever an earlier tick left there)
+            for (int j = total[(size_t)b]; j < M; ++j) std::memset(xyr + ((size_t)b * M + j) * 3, 0, 3 * sizeof(double));
+    }
+    for (int b = 0; b < B; ++b) {
+        if (n_static) n_static[b] = bh->obst_n[(size_t)b];
+        if (n_total) n_total[b] = total[(size_t)b];
+    }
     return CCV_MPPI_OK;
 }
 

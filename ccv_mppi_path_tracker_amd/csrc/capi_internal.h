@@ -3,7 +3,7 @@
 //   capi_exchange.hip    direct exchange of the partial vectors between the devices of a node
 //   capi_resident.hip    device-resident closed loop of a single handle
 //   capi_stage.hip       stage-wise calls, read-back, timing
-//   capi_batch.hip       batch handles (ccv_mppi_batch_*), their resident loop included
+//   capi_batch.hip       batch handles (ccv_mppi_batch_*), their resident loop and its fleet term included
 // A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".
@@ -25,6 +25,7 @@
 #include "mppi_launch.h"
 #include "mppi_update.h"
 #include "mppi_resident.h"
+#include "mppi_fleet.h"
 
 namespace ccv {
 
@@ -219,6 +220,16 @@ struct ccv_mppi_batch : Core {
     std::vector<int32_t> obst_n;            // [B]
     std::vector<double> obst_w;             // [B]
     bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
+    // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
+    // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
+    // the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance)
+    bool fleet = false;
+    double* d_fleet_xy = nullptr;           // [2][B][2]: tick n reads half n & 1 and writes the other (n = res_steps)
+    double* d_fleet_radius = nullptr;       // [B]
+    int32_t* d_fleet_nstatic = nullptr;     // [B]: obst_n on the device, for the prologue
+    std::vector<double> fleet_radius;       // [B]
+    double fleet_range = 0.0;
+    int32_t fleet_maxn = 0;
 };
 
 namespace ccv {
@@ -300,9 +311,10 @@ void track_absmax(const double* u, size_t n, int udim, double* absmax);
 // the update kernel of a plan: k_finalize, k_finalize_batch or k_finalize_batch_shift
 void launch_finalize(Core& h, const UpdatePlan& p);
 // ... together with the next tick's prologue: k_finalize_advance (V), or k_finalize_advance_batch / _varied / _shift (G; table:
-// the per-instance parameters the prologue reads, or null)
+// the per-instance parameters the prologue reads, or null).
 void launch_finalize_advance(Core& h, const UpdatePlan& p, const AdvanceArgs& V);
-void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, const BatchParams* table);
+// fleet: the fleet forms of the _varied / _shift kernels (mppi_fleet.h; they write the table's n_obst), or null
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, BatchParams* table, const FleetArgs* fleet = nullptr);
 int flush_finalize(Core* h);                // the deferred update now (launch_finalize)
 int flush_division(ccv_mppi_handle* h);     // the deferred division now: k_apply_partials
 int flush_pending(ccv_mppi_handle* h);      // both, in that order

@@ -365,8 +365,11 @@ int ccv_mppi_batch_resident_read(ccv_mppi_batch* b, double* state, int32_t* curr
 /* one instance's last rows, oldest first, (x, y, yaw, roll, pitch, index); at most max_rows and at most
  * CCV_MPPI_BATCH_TRACE_ROWS */
 int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int32_t max_rows, double* rows, int32_t* n_rows);
+/* The fleet term of the resident loop -- the robots of one batch keep clear of each other,
+ * ccv_mppi_batch_resident_set_fleet / _get_fleet / _read_fleet -- is declared in ccv_mppi_fleet.h, included below. */
 
 #ifdef __cplusplus
 }
 #endif
+#include "ccv_mppi_fleet.h"
 #endif /* CCV_MPPI_H_ */
