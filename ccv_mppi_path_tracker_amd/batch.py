@@ -61,6 +61,33 @@ def pack_obstacles(discs, weight, batch):
     return xyr, n, max_n, w
 
 
+def pack_velocities(velocities, batch, counts=None):
+    """The arguments of ccv_mppi_batch_set_obstacle_velocities from `batch` arrays of (vx, vy) rows (instance b's discs in the
+    order of pack_obstacles; an empty sequence or None: none): vxy [B][max_n][2] (rows past an instance's count zero) and
+    max_n.  counts: the instances' disc counts, when the caller wants them checked.  ValueError for a wrong number of
+    instances, rows that are not pairs, more than capi.MAX_OBSTACLES rows or a count that differs."""
+    velocities = list(velocities)
+    if len(velocities) != int(batch):
+        raise ValueError("velocities: expected %d arrays of (vx, vy) rows, got %d" % (int(batch), len(velocities)))
+    rows = []
+    for b, v in enumerate(velocities):
+        a = np.zeros((0, 2)) if v is None else np.asarray(v, dtype=np.float64)
+        if a.size == 0:
+            a = np.zeros((0, 2))
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("velocities[%d]: expected shape (n, 2), got %s" % (b, a.shape))
+        if a.shape[0] > capi.MAX_OBSTACLES:
+            raise ValueError("velocities[%d]: %d rows, at most %d" % (b, a.shape[0], capi.MAX_OBSTACLES))
+        if counts is not None and a.shape[0] != int(counts[b]):
+            raise ValueError("velocities[%d]: %d rows for %d discs" % (b, a.shape[0], int(counts[b])))
+        rows.append(a)
+    max_n = max([a.shape[0] for a in rows], default=0)
+    vxy = np.zeros((int(batch), max_n, 2))
+    for b, a in enumerate(rows):
+        vxy[b, :a.shape[0]] = a
+    return vxy, max_n
+
+
 class BatchController:
     """`batch` controllers on one device: one MPPIParams shared by all, or a sequence of `batch` MPPIParams that agree in
     SHARED_FIELDS (per-instance sigma, lambda, v_ref, bounds and weights; K = num_samples per instance).  min_shift: the
@@ -163,17 +190,41 @@ class BatchController:
         return bool(self.lib.ccv_mppi_batch_get_min_shift(self._h))
 
     # ---- per-instance disc obstacles (ccv_mppi_batch_set_obstacles) ----
-    def set_obstacles(self, discs, weight=0.0):
+    def set_obstacles(self, discs, weight=0.0, velocities=None):
         """discs: B arrays of (ox, oy, r) rows in world coordinates (an instance without discs: an empty one), or None: the term
         off and the kernels that ran before; weight: one value or [B], >= 0.  The cost of every state the path term covers gains
-        weight_b * max(max_j(r_j^2 - |p - o_j|^2), 0).  A weight that matters needs set_min_shift(True).  Flushes a pending
-        resident update; warm starts, paths, poses and per-instance parameters stay."""
+        weight_b * max(max_j(r_j^2 - |p - o_j|^2), 0).  A weight that matters needs set_min_shift(True).  velocities: B arrays of
+        (vx, vy) rows, one per disc (set_obstacle_velocities), or None: the discs stand still.  Flushes a pending resident
+        update; warm starts, paths, poses and per-instance parameters stay."""
         if discs is None:
             self._check(self.lib.ccv_mppi_batch_set_obstacles(self._h, None, None, 0, None))
             return
         xyr, n, max_n, w = pack_obstacles(discs, weight, self.B)
+        if velocities is not None:
+            vxy, vmax = pack_velocities(velocities, self.B, n)   # (checked before the discs change)
         self._check(self.lib.ccv_mppi_batch_set_obstacles(self._h, capi.dptr(xyr), n.ctypes.data_as(C.POINTER(C.c_int32)),
                                                           max_n, capi.dptr(w)))
+        if velocities is not None:
+            self._check(self.lib.ccv_mppi_batch_set_obstacle_velocities(self._h, capi.dptr(vxy), vmax))
+
+    def set_obstacle_velocities(self, velocities):
+        """velocities: B arrays of (vx, vy) rows in world coordinates, one per disc of set_obstacles (constant over the
+        horizon: state k is charged against the disc at o + v k dt), or None: back to the static term and its bits.  Any table,
+        one of zeros too, runs the MOVING kernels.  Flushes a pending resident update."""
+        if velocities is None:
+            self._check(self.lib.ccv_mppi_batch_set_obstacle_velocities(self._h, None, 0))
+            return
+        vxy, max_n = pack_velocities(velocities, self.B)
+        self._check(self.lib.ccv_mppi_batch_set_obstacle_velocities(self._h, capi.dptr(vxy), max_n))
+
+    def get_obstacle_velocities(self):
+        """List of B arrays [n_b][2] as the library holds them; zeros while no velocities are set."""
+        n = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ccv_mppi_batch_get_obstacles(self._h, None, n.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          capi.MAX_OBSTACLES, None))
+        vxy = np.zeros((self.B, capi.MAX_OBSTACLES, 2))
+        self._check(self.lib.ccv_mppi_batch_get_obstacle_velocities(self._h, capi.dptr(vxy), capi.MAX_OBSTACLES))
+        return [vxy[b, :n[b]].copy() for b in range(self.B)]
 
     def get_obstacles(self):
         """(list of B arrays [n_b][3], weight [B]) as the library holds them; empty arrays and zeros while the term is off."""
@@ -330,6 +381,22 @@ class BatchController:
         self._check(self.lib.ccv_mppi_batch_resident_read_fleet(self._h, ns.ctypes.data_as(C.POINTER(C.c_int32)),
                                                                 nt.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(xyr)))
         return ns, nt, xyr
+
+    def resident_set_fleet_prediction(self, on=True):
+        """on: every neighbour's disc moves over the horizon with the velocity that robot had over the last resident tick (its
+        displacement times 1 / dt, formed on the device); off: the snapshot discs of resident_set_fleet and their bits.  Needs
+        the fleet term; flushes a pending resident update."""
+        self._check(self.lib.ccv_mppi_batch_set_fleet_prediction(self._h, 1 if on else 0))
+
+    def resident_get_fleet_prediction(self):
+        return bool(self.lib.ccv_mppi_batch_get_fleet_prediction(self._h))
+
+    def resident_read_fleet_velocities(self):
+        """vxy [B][capi.MAX_OBSTACLES][2]: the velocity rows the last tick's rollout was charged with, beside the disc rows of
+        resident_read_fleet (rows past n_total zero); synchronises."""
+        vxy = np.zeros((self.B, capi.MAX_OBSTACLES, 2))
+        self._check(self.lib.ccv_mppi_batch_read_fleet_velocities(self._h, capi.dptr(vxy)))
+        return vxy
 
     # ---- measurement ----
     def timing_enable(self, on=True, every=1):

@@ -28,6 +28,7 @@ BATCH_KERNEL_PLAIN, BATCH_KERNEL_ONE_WAVE, BATCH_KERNEL_FOUR_WAVE, BATCH_KERNEL_
 BATCH_KERNEL_VARIED = 32
 BATCH_KERNEL_SHIFT = 64
 BATCH_KERNEL_OBST = 128
+BATCH_KERNEL_MOVING = 256
 MAX_OBSTACLES = 32
 BATCH_TRACE_ROWS = 1024
 
@@ -113,6 +114,11 @@ SIGNATURES = {
     "ccv_mppi_batch_get_min_shift": (C.c_int, [_H]),
     "ccv_mppi_batch_set_obstacles": (C.c_int, [_H, _dp, C.POINTER(C.c_int32), C.c_int32, _dp]),
     "ccv_mppi_batch_get_obstacles": (C.c_int, [_H, _dp, C.POINTER(C.c_int32), C.c_int32, _dp]),
+    "ccv_mppi_batch_set_obstacle_velocities": (C.c_int, [_H, _dp, C.c_int32]),
+    "ccv_mppi_batch_get_obstacle_velocities": (C.c_int, [_H, _dp, C.c_int32]),
+    "ccv_mppi_batch_set_fleet_prediction": (C.c_int, [_H, C.c_int32]),
+    "ccv_mppi_batch_get_fleet_prediction": (C.c_int, [_H]),
+    "ccv_mppi_batch_read_fleet_velocities": (C.c_int, [_H, _dp]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),

@@ -15,7 +15,8 @@ int batch_kernel_code(const RolloutPlan& p) {
                        : p.family == KernelFamily::OneWave ? CCV_MPPI_BATCH_KERNEL_ONE_WAVE
                                                            : CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
     return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0) |
-           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0) | (p.obst ? CCV_MPPI_BATCH_KERNEL_OBST : 0);
+           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0) | (p.obst ? CCV_MPPI_BATCH_KERNEL_OBST : 0) |
+           (p.moving ? CCV_MPPI_BATCH_KERNEL_MOVING : 0);
 }
 
 // whether the kernels read the parameter table: per-instance parameters, or shifted weights or obstacles (B copies of cfg in
@@ -25,6 +26,34 @@ bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift |
 // whether the obstacle kernels run: static discs (ccv_mppi_batch_set_obstacles) or the fleet term (_resident_set_fleet); the
 // obst_* vectors and d_obst exist then
 bool obst_on(const ccv_mppi_batch* bh) { return bh->obst || bh->fleet; }
+
+// whether the MOVING kernels run: static velocities (ccv_mppi_batch_set_obstacle_velocities) or fleet prediction; d_obst_v exists
+// then and every row of it is defined
+bool moving_on(const ccv_mppi_batch* bh) { return obst_on(bh) && (bh->moving || bh->fleet_pred); }
+
+// the velocity table [B][32][2] on the device: the static rows from the host copy (zeros without one), every other row zero (the
+// fleet's rows are the prologue's to write, every tick).  The caller has flushed and synchronised.
+int upload_velocities(ccv_mppi_batch* bh) {
+    const size_t count = (size_t)bh->B * CCV_MPPI_MAX_OBSTACLES * 2;
+    const std::vector<double> zeros(bh->moving ? 0 : count, 0.0);
+    if (!bh->d_obst_v) HIP_TRY(bh, hipMalloc(&bh->d_obst_v, count * sizeof(double)));
+    HIP_TRY(bh, hipMemcpy(bh->d_obst_v, bh->moving ? bh->obst_vxy.data() : zeros.data(), count * sizeof(double), hipMemcpyHostToDevice));
+    return CCV_MPPI_OK;
+}
+
+// prediction has just gone off: the fleet's rows of the velocity table still hold what the last prologue with prediction wrote.
+// With static velocities the MOVING kernels go on reading them, beside disc rows the prologue now writes without a velocity, so
+// the table is written again (the static rows, zero elsewhere).  Without static velocities nothing reads the table until
+// upload_velocities writes all of it.  The caller has flushed and synchronised.
+int clear_fleet_velocity_rows(ccv_mppi_batch* bh) { return bh->moving ? upload_velocities(bh) : CCV_MPPI_OK; }
+
+// both halves of the fleet's velocity snapshot zero: no robot has moved yet
+int fleet_zero_velocities(ccv_mppi_batch* bh) {
+    const size_t bytes = (size_t)bh->B * 4 * sizeof(double);
+    if (!bh->d_fleet_v) HIP_TRY(bh, hipMalloc(&bh->d_fleet_v, bytes));
+    HIP_TRY(bh, hipMemset(bh->d_fleet_v, 0, bytes));
+    return CCV_MPPI_OK;
+}
 
 // the parameter table [B] on the device from B configurations (null: B copies of the creation configuration).  The caller has
 // flushed and synchronised: a queued rollout or prologue may still read the old table.
@@ -57,6 +86,7 @@ int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
             P.n_obst = bh->obst_n[(size_t)b];
             P.obst = bh->d_obst + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 3;
             P.w_obs = bh->obst_w[(size_t)b];
+            if (moving_on(bh)) P.obst_v = bh->d_obst_v + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 2;
         }
     }
     if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
@@ -129,7 +159,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // of the fused kernels waits in bh->fin for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
-    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, obst_on(bh));
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, obst_on(bh), moving_on(bh));
     const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -280,7 +310,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
     void* bufs[] = {bh->d_rec,  bh->d_rframe, bh->d_inst,     bh->d_rpath,        bh->d_rtrace,       bh->d_params,
-                    bh->d_cmin, bh->d_obst,   bh->d_fleet_xy, bh->d_fleet_radius, bh->d_fleet_nstatic};
+                    bh->d_cmin, bh->d_obst,   bh->d_fleet_xy, bh->d_fleet_radius, bh->d_fleet_nstatic, bh->d_obst_v, bh->d_fleet_v};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete bh;
@@ -413,6 +443,12 @@ int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const in
     HIP_TRY(bh, hipSetDevice(bh->cfg.device));
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table and discs)
+    // (a new list has no velocities until it is given some; without a list there are none)
+    bh->moving = false;
+    bh->obst_vxy.clear();
+    if (bh->fleet_pred) {   // (the static rows stand still again)
+        if (int rc = upload_velocities(bh)) return rc;
+    }
     if (off && !bh->fleet) {
         bh->obst = false;
         bh->obst_xyr.clear();
@@ -452,6 +488,63 @@ int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* bh, double* xyr, int32_t* n, in
             std::memset(xyr + (size_t)b * max_n * 3, 0, (size_t)max_n * 3 * sizeof(double));
             if (nb > 0) std::memcpy(xyr + (size_t)b * max_n * 3, &bh->obst_xyr[(size_t)b * M * 3], (size_t)nb * 3 * sizeof(double));
         }
+    }
+    return CCV_MPPI_OK;
+}
+
+// ---- moving discs ---------------------------------------------------------------------------------------------------------
+
+int ccv_mppi_batch_set_obstacle_velocities(ccv_mppi_batch* bh, const double* vxy, int32_t max_n) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    // every check comes before anything changes
+    if (!bh->obst) return fail(bh, CCV_MPPI_ERR_STATE, "set_obstacle_velocities: no discs are set (ccv_mppi_batch_set_obstacles)");
+    if (vxy) {
+        if (max_n < 0 || max_n > M)
+            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacle_velocities: max_n outside [0, CCV_MPPI_MAX_OBSTACLES]");
+        for (int b = 0; b < B; ++b)
+            for (int j = 0; j < bh->obst_n[(size_t)b] && j < max_n; ++j) {
+                const double* v = vxy + ((size_t)b * max_n + j) * 2;
+                if (!std::isfinite(v[0]) || !std::isfinite(v[1]))
+                    return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacle_velocities: a velocity is not finite");
+            }
+    }
+    if (!vxy && !bh->moving) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table and velocities)
+    if (!vxy) {   // back to the static kernels and their bits (under fleet prediction: the static rows stand still)
+        bh->moving = false;
+        bh->obst_vxy.clear();
+        if (bh->fleet_pred) {
+            if (int rc = upload_velocities(bh)) return rc;
+        }
+        return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+    }
+    // rows at or past an instance's count (the fleet term's rows among them) are zero
+    std::vector<double> rows((size_t)B * M * 2, 0.0);
+    for (int b = 0; b < B; ++b)
+        for (int j = 0; j < bh->obst_n[(size_t)b] && j < max_n; ++j)
+            std::memcpy(&rows[((size_t)b * M + j) * 2], vxy + ((size_t)b * max_n + j) * 2, 2 * sizeof(double));
+    bh->obst_vxy.swap(rows);
+    bh->moving = true;
+    if (int rc = upload_velocities(bh)) return rc;
+    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+}
+
+int ccv_mppi_batch_get_obstacle_velocities(ccv_mppi_batch* bh, double* vxy, int32_t max_n) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!vxy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    if (max_n < 0 || max_n > M) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacle_velocities: max_n outside [0, CCV_MPPI_MAX_OBSTACLES]");
+    std::memset(vxy, 0, (size_t)B * max_n * 2 * sizeof(double));
+    if (!bh->moving) return CCV_MPPI_OK;
+    for (int b = 0; b < B; ++b) {
+        const int nb = bh->obst_n[(size_t)b] < max_n ? bh->obst_n[(size_t)b] : max_n;
+        if (nb > 0) std::memcpy(vxy + (size_t)b * max_n * 2, &bh->obst_vxy[(size_t)b * M * 2], (size_t)nb * 2 * sizeof(double));
     }
     return CCV_MPPI_OK;
 }
@@ -599,6 +692,9 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
         std::vector<double> xy((size_t)B * 2);
         for (int b = 0; b < B; ++b) std::memcpy(&xy[(size_t)b * 2], heads[b].x0, 2 * sizeof(double));
         if (int rc = fleet_write_positions(bh, xy)) return rc;
+        if (bh->fleet_pred) {
+            if (int rc = fleet_zero_velocities(bh)) return rc;
+        }
     }
     bh->res_angle_abs.swap(angles);
     bh->res_steps = 0;
@@ -665,12 +761,21 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
         L.max_neighbours = bh->fleet_maxn;
         L.B = B;
     }
+    FleetPredArgs V{};
+    const bool pred = bh->fleet && bh->fleet_pred;
+    if (pred) {
+        const size_t half = (size_t)B * 2;
+        V.v_in = bh->d_fleet_v + (size_t)(bh->res_steps & 1) * half;
+        V.v_out = bh->d_fleet_v + (size_t)((bh->res_steps + 1) & 1) * half;
+        V.obst_v = bh->d_obst_v;
+    }
     // (varied: the prologue takes each instance's v_ref from the parameter table and points its record's head at its row)
     if (bh->fin_pending) {   // the last tick's update and this tick's prologue: one launch
-        launch_finalize_advance(*bh, bh->fin, G, uses_table(bh) ? bh->d_params : nullptr, bh->fleet ? &L : nullptr);
+        launch_finalize_advance(*bh, bh->fin, G, uses_table(bh) ? bh->d_params : nullptr, bh->fleet ? &L : nullptr, pred ? &V : nullptr);
         bh->fin_pending = false;
     } else {
-        if (bh->fleet) hipLaunchKernelGGL(k_advance_batch_fleet, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params, L);
+        if (pred) hipLaunchKernelGGL(k_advance_batch_fleet_pred, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params, L, V);
+        else if (bh->fleet) hipLaunchKernelGGL(k_advance_batch_fleet, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params, L);
         else if (uses_table(bh)) hipLaunchKernelGGL(k_advance_batch_varied, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G, bh->d_params);
         else hipLaunchKernelGGL(k_advance_batch, dim3(B), dim3(kBatchAdvanceThreads), 0, bh->stream, G);
     }
@@ -746,6 +851,10 @@ int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, 
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the tables)
     if (off) {
         bh->fleet = false;
+        if (bh->fleet_pred) {   // (prediction is the fleet term's)
+            bh->fleet_pred = false;
+            if (int rc = clear_fleet_velocity_rows(bh)) return rc;
+        }
         bh->fleet_radius.clear();
         bh->fleet_range = 0.0;
         bh->fleet_maxn = 0;
@@ -776,6 +885,9 @@ int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, 
         HIP_TRY(bh, hipMemcpy2D(xy.data(), 2 * sizeof(double), bh->d_rframe, sizeof(ResidentFrame), 2 * sizeof(double), (size_t)B,
                                hipMemcpyDeviceToHost));
     if (int rc = fleet_write_positions(bh, xy)) return rc;
+    if (bh->fleet_pred) {
+        if (int rc = fleet_zero_velocities(bh)) return rc;
+    }
     bh->obst_w.assign(weight, weight + B);
     bh->fleet_radius.assign(radius, radius + B);
     bh->fleet_range = range;
@@ -811,6 +923,48 @@ int ccv_mppi_batch_resident_read_fleet(ccv_mppi_batch* bh, int32_t* n_static, in
         if (n_static) n_static[b] = bh->obst_n[(size_t)b];
         if (n_total) n_total[b] = total[(size_t)b];
     }
+    return CCV_MPPI_OK;
+}
+
+// ---- fleet prediction: a neighbour's disc moves with the velocity its robot had over the last tick -------------------------
+
+int ccv_mppi_batch_set_fleet_prediction(ccv_mppi_batch* bh, int32_t on) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, "set_fleet_prediction: the fleet term is off (ccv_mppi_batch_resident_set_fleet)");
+    const bool want = on != 0;
+    if (want == bh->fleet_pred) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the tables)
+    bh->fleet_pred = want;
+    if (want) {
+        if (int rc = upload_velocities(bh)) return rc;       // every row defined: the static rows, zero elsewhere
+        if (int rc = fleet_zero_velocities(bh)) return rc;   // no robot has moved yet
+    } else if (int rc = clear_fleet_velocity_rows(bh)) return rc;
+    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+}
+
+int ccv_mppi_batch_get_fleet_prediction(const ccv_mppi_batch* bh) { return bh ? (bh->fleet_pred ? 1 : 0) : CCV_MPPI_ERR_INVALID_ARG; }
+
+int ccv_mppi_batch_read_fleet_velocities(ccv_mppi_batch* bh, double* vxy) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!vxy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_fleet first");
+    const int B = bh->B;
+    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+    std::memset(vxy, 0, (size_t)B * M * 2 * sizeof(double));
+    if (!moving_on(bh)) return CCV_MPPI_OK;   // (the static kernels ran: every disc stood still)
+    std::vector<int32_t> total((size_t)B);
+    HIP_TRY(bh, hipMemcpy2D(total.data(), sizeof(int32_t), reinterpret_cast<const char*>(bh->d_params) + offsetof(BatchParams, n_obst),
+                           sizeof(BatchParams), sizeof(int32_t), (size_t)B, hipMemcpyDeviceToHost));
+    HIP_TRY(bh, hipMemcpy(vxy, bh->d_obst_v, (size_t)B * M * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b)   // (rows past the count: whatever an earlier tick left there)
+        for (int j = total[(size_t)b] < 0 ? 0 : total[(size_t)b]; j < M; ++j) std::memset(vxy + ((size_t)b * M + j) * 2, 0, 2 * sizeof(double));
     return CCV_MPPI_OK;
 }
 

@@ -219,6 +219,11 @@ struct ccv_mppi_batch : Core {
     std::vector<double> obst_xyr;           // [B][CCV_MPPI_MAX_OBSTACLES][3] host copy while obst
     std::vector<int32_t> obst_n;            // [B]
     std::vector<double> obst_w;             // [B]
+    // moving discs (ccv_mppi_batch_set_obstacle_velocities): the MOVING rollout kernels while `moving`; the rows of the table
+    // point into d_obst_v.  Every row of d_obst_v is defined from its allocation on: zero unless the caller gave a velocity.
+    bool moving = false;
+    double* d_obst_v = nullptr;             // [B][CCV_MPPI_MAX_OBSTACLES][2], allocated at the first velocities, freed at destroy
+    std::vector<double> obst_vxy;           // [B][CCV_MPPI_MAX_OBSTACLES][2] host copy while moving
     bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
     // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
     // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
@@ -230,6 +235,11 @@ struct ccv_mppi_batch : Core {
     std::vector<double> fleet_radius;       // [B]
     double fleet_range = 0.0;
     int32_t fleet_maxn = 0;
+    // fleet prediction (ccv_mppi_batch_set_fleet_prediction): the velocities travel with the positions, a neighbour's disc moves
+    // with the velocity its robot had over the last tick, and the MOVING kernels run (over d_obst_v: the static rows the host's,
+    // zero without ccv_mppi_batch_set_obstacle_velocities; the fleet's rows written by the prologue every tick)
+    bool fleet_pred = false;
+    double* d_fleet_v = nullptr;            // [2][B][2]: tick n reads half n & 1 and writes the other, like d_fleet_xy
 };
 
 namespace ccv {
@@ -294,11 +304,12 @@ inline bool has_wide_form(const KernelChoice& k, const int mode) {
 // The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
 // (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
 // shift (a batch in shifted-weight mode), obst (a batch with obstacles): always with the per-instance-parameter kernels.
+// moving (a batch whose discs have velocities): always an obstacle plan.
 inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied,
-                             const bool shift = false, const bool obst = false) {
+                             const bool shift = false, const bool obst = false, const bool moving = false) {
     const KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
-    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift || obst, shift, obst,
-                       k.lds_window != 0};
+    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift || obst || moving, shift,
+                       obst || moving, moving, k.lds_window != 0};
 }
 
 RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);   // a single handle's
@@ -313,8 +324,10 @@ void launch_finalize(Core& h, const UpdatePlan& p);
 // ... together with the next tick's prologue: k_finalize_advance (V), or k_finalize_advance_batch / _varied / _shift (G; table:
 // the per-instance parameters the prologue reads, or null).
 void launch_finalize_advance(Core& h, const UpdatePlan& p, const AdvanceArgs& V);
-// fleet: the fleet forms of the _varied / _shift kernels (mppi_fleet.h; they write the table's n_obst), or null
-void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, BatchParams* table, const FleetArgs* fleet = nullptr);
+// fleet: the fleet forms of the _varied / _shift kernels (mppi_fleet.h; they write the table's n_obst), or null; pred (with
+// fleet): their prediction forms (k_fleet_pred.hip), or null
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, BatchParams* table, const FleetArgs* fleet = nullptr,
+                             const FleetPredArgs* pred = nullptr);
 int flush_finalize(Core* h);                // the deferred update now (launch_finalize)
 int flush_division(ccv_mppi_handle* h);     // the deferred division now: k_apply_partials
 int flush_pending(ccv_mppi_handle* h);      // both, in that order

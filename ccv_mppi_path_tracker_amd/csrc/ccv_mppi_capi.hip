@@ -116,9 +116,13 @@ void launch_finalize_advance(Core& h, const UpdatePlan& p, const AdvanceArgs& V)
     hipLaunchKernelGGL(k_finalize_advance, dim3(finalize_blocks(p.args.R) + 1), dim3(kBlock), 0, h.stream, p.args, V);
 }
 
-void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, BatchParams* table, const FleetArgs* fleet) {
+void launch_finalize_advance(Core& h, const UpdatePlan& p, const BatchAdvanceArgs& G, BatchParams* table, const FleetArgs* fleet,
+                             const FleetPredArgs* pred) {
     const dim3 grid(finalize_blocks(p.args.R) + 1, p.batch);
-    if (fleet && p.shift) hipLaunchKernelGGL(k_finalize_advance_batch_shift_fleet, grid, dim3(kBlock), 0, h.stream, p.args, G, table, *fleet);
+    if (fleet && pred && p.shift)
+        hipLaunchKernelGGL(k_finalize_advance_batch_shift_fleet_pred, grid, dim3(kBlock), 0, h.stream, p.args, G, table, *fleet, *pred);
+    else if (fleet && pred) hipLaunchKernelGGL(k_finalize_advance_batch_fleet_pred, grid, dim3(kBlock), 0, h.stream, p.args, G, table, *fleet, *pred);
+    else if (fleet && p.shift) hipLaunchKernelGGL(k_finalize_advance_batch_shift_fleet, grid, dim3(kBlock), 0, h.stream, p.args, G, table, *fleet);
     else if (fleet) hipLaunchKernelGGL(k_finalize_advance_batch_fleet, grid, dim3(kBlock), 0, h.stream, p.args, G, table, *fleet);
     else if (p.shift) hipLaunchKernelGGL(k_finalize_advance_batch_shift, grid, dim3(kBlock), 0, h.stream, p.args, G, p.shift);
     else if (table) hipLaunchKernelGGL(k_finalize_advance_batch_varied, grid, dim3(kBlock), 0, h.stream, p.args, G, table);

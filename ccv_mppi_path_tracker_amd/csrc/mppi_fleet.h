@@ -26,10 +26,22 @@ struct FleetArgs {
     int32_t max_neighbours, B;
 };
 
+// Fleet prediction (ccv_mppi_batch_set_fleet_prediction): the velocities travel with the positions, v[2][B][2]
+// double buffered like xy, and a selected neighbour's goes into the velocity row of its disc
+struct FleetPredArgs {
+    const double* v_in;    // [B][2]: every robot's velocity over the tick that made xy_in (zero where that tick did not move it)
+    double* v_out;         // [B][2]: block y writes instance y's velocity over this tick
+    double* obst_v;        // [B][CCV_MPPI_MAX_OBSTACLES][2]: the table BatchParams::obst_v points into
+};
+
 // k_advance_batch_varied, k_finalize_advance_batch_varied and k_finalize_advance_batch_shift with the fleet step in the
 // prologue workgroup; P: the parameter table [B], whose n_obst the step writes
 __global__ void k_advance_batch_fleet(BatchAdvanceArgs G, BatchParams* P, FleetArgs L);
 __global__ void k_finalize_advance_batch_fleet(FinalizeArgs F, BatchAdvanceArgs G, BatchParams* P, FleetArgs L);
 __global__ void k_finalize_advance_batch_shift_fleet(FinalizeArgs F, BatchAdvanceArgs G, BatchParams* P, FleetArgs L);
+// ... and with prediction (k_fleet_pred.hip)
+__global__ void k_advance_batch_fleet_pred(BatchAdvanceArgs G, BatchParams* P, FleetArgs L, FleetPredArgs V);
+__global__ void k_finalize_advance_batch_fleet_pred(FinalizeArgs F, BatchAdvanceArgs G, BatchParams* P, FleetArgs L, FleetPredArgs V);
+__global__ void k_finalize_advance_batch_shift_fleet_pred(FinalizeArgs F, BatchAdvanceArgs G, BatchParams* P, FleetArgs L, FleetPredArgs V);
 
 }  // namespace ccv

@@ -93,6 +93,8 @@ struct BatchHead {
 // A VARIED kernel takes its instance's row in batch_view() and is the single handle's code from there on.
 // obst / n_obst / w_obs (ccv_mppi_batch_set_obstacles; OBST kernels only): the instance's discs, rows (ox, oy, r) of a device
 // table, and the weight of their penalty; null / 0 / 0 without obstacles.
+// obst_v (ccv_mppi_batch_set_obstacle_velocities; MOVING kernels only): the discs' velocities, rows (vx, vy) of a device table
+// [B][32][2] beside the discs'; null while no velocities are set.  Every row of a non-null table is defined: zero unless given.
 struct alignas(64) BatchParams {
     double sigma, lambda, v_ref;
     double umin[5], umax[5];
@@ -100,6 +102,7 @@ struct alignas(64) BatchParams {
     int32_t fast_clamp, n_obst;
     const double* obst;
     double w_obs;
+    const double* obst_v;
 };
 static_assert(sizeof(BatchParams) == 192, "three 64-byte lines per instance");
 constexpr int kBatchHeadDoubles = 16;
@@ -372,6 +375,111 @@ __device__ __forceinline__ void obst_term(const RolloutArgs& A, const ObstLds& o
     }
 }
 
+// ---- moving discs (MOVING kernels, on OBST) -----------------------------------------------------
+// Disc j has a constant velocity v_j over the horizon: state k (k dynamics steps after the pose) is charged against the disc at
+// o_j + v_j tau_k, tau_k = k dt.  The power of the point stays linear in (px, py); its coefficients become polynomials in tau:
+//   a_j(tau) = a_j - 2 vx_j tau,  b_j(tau) = b_j - 2 vy_j tau,  c_j(tau) = c_j + 2 (d_j . v_j) tau + |v_j|^2 tau^2.
+// Seven doubles per disc are staged once per workgroup; the coefficients of a (disc, state) pair are formed per lane, 4 FMA,
+// from tau_k held wave-uniform.
+struct ObstMovLds {
+    double2 ab[kMaxObst];    // a, b
+    double2 vab[kMaxObst];   // -2 vx, -2 vy
+    double c[kMaxObst], c1[kMaxObst], c2[kMaxObst];   // c, 2 (d . v), |v|^2
+};
+__device__ __forceinline__ const double* obst_velocity_rows(const RolloutArgs& A) {
+    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
+    typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
+    return (*(ConstParams)(const void*)((ConstHead)(const void*)A.frame)->params).obst_v;
+}
+// staging: obst_stage's a, b, c, and the velocity's four coefficients; the padding has zero velocity
+__device__ __forceinline__ void obst_stage_moving(const RolloutArgs& A, ObstMovLds& ob, const int j) {
+    const ObstRow o = obst_row(A);
+    const double* vrows = obst_velocity_rows(A);
+    double a = 0.0, b = 0.0, c = INFINITY, va = 0.0, vb = 0.0, c1 = 0.0, c2 = 0.0;
+    if (j < o.n) {
+        const double ox = o.xyr[3 * j], oy = o.xyr[3 * j + 1], r = o.xyr[3 * j + 2];
+        const double vx = vrows[2 * j], vy = vrows[2 * j + 1];
+        const double dx = ox - A.x0[0], dy = oy - A.x0[1];
+        a = -2.0 * dx;
+        b = -2.0 * dy;
+        c = fma(dx, dx, dy * dy) - r * r;
+        va = -2.0 * vx;
+        vb = -2.0 * vy;
+        c1 = 2.0 * fma(dx, vx, dy * vy);
+        c2 = fma(vx, vx, vy * vy);
+    }
+    ob.ab[j] = make_double2(a, b);
+    ob.vab[j] = make_double2(va, vb);
+    ob.c[j] = c;
+    ob.c1[j] = c1;
+    ob.c2[j] = c2;
+}
+// a wave-uniform double into scalar registers (the compiler cannot see that a converted integer is uniform)
+__device__ __forceinline__ double uniform_f64(const double v) {
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+// obst_term with the discs where they are at each state's own time: state i of the NV held in registers is global step
+// k0 + i (k0: the block's first step, wave-uniform), tau = double(k0 + i) * dt, one rounding.  One disc per iteration over the
+// instance's own count; per (disc, state): at = fma(va, tau, a), bt = fma(vb, tau, b), ct = fma(fma(c2, tau, c1), tau, c),
+// f = fma(at, px, fma(bt, py, ct)).  The rest is obst_term's.  With v = 0 every at, bt, ct is a, b, c exactly (tau finite).
+template <int NV, int NM, bool MASK = false>
+__device__ __forceinline__ void obst_term_moving(const RolloutArgs& A, const ObstMovLds& ob, const double (&px)[NM], const double (&py)[NM],
+                                                 double (&m)[NM], double& cost, const int k0, const int nv = NV) {
+    const ObstRow o = obst_row(A);
+    if (o.n == 0) return;
+    double tau[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        tau[i] = uniform_f64((double)(k0 + i) * A.dt);
+        if constexpr (!MASK) m[i] = INFINITY;
+    }
+    if constexpr (MASK) {
+        // the plain kernel: state by state, one running minimum alive at a time -- the same pairs, hence the same minima; with
+        // all eight alive beside a disc's seven coefficients it needed 139 registers and lost a wave per SIMD
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            double mi = INFINITY;
+#pragma unroll 1
+            for (int j = 0; j < o.n; ++j) {
+                const double2 ab = ob.ab[j], vab = ob.vab[j];
+                const double c = ob.c[j], c1 = ob.c1[j], c2 = ob.c2[j];
+                const double at = fma(vab.x, tau[i], ab.x);
+                const double bt = fma(vab.y, tau[i], ab.y);
+                const double ct = fma(fma(c2, tau[i], c1), tau[i], c);
+                const double t = fma(at, px[i], fma(bt, py[i], ct));
+                asm("v_min_f64 %0, %1, %2" : "=v"(mi) : "v"(mi), "v"(t));
+            }
+            const double s = mi + fma(px[i], px[i], py[i] * py[i]);
+            double g;
+            asm("v_max_f64 %0, -%1, 0" : "=v"(g) : "v"(s));
+            if (i < nv) cost = fma(o.w, g, cost);
+        }
+    } else {
+        // the cooperative kernels: disc by disc, all NV running minima alive, every state counted
+#pragma unroll 1
+        for (int j = 0; j < o.n; ++j) {
+            const double2 ab = ob.ab[j], vab = ob.vab[j];
+            const double c = ob.c[j], c1 = ob.c1[j], c2 = ob.c2[j];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const double at = fma(vab.x, tau[i], ab.x);
+                const double bt = fma(vab.y, tau[i], ab.y);
+                const double ct = fma(fma(c2, tau[i], c1), tau[i], c);
+                const double t = fma(at, px[i], fma(bt, py[i], ct));
+                asm("v_min_f64 %0, %1, %2" : "=v"(m[i]) : "v"(m[i]), "v"(t));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const double s = m[i] + fma(px[i], px[i], py[i] * py[i]);
+            double g;
+            asm("v_max_f64 %0, -%1, 0" : "=v"(g) : "v"(s));
+            cost = fma(o.w, g, cost);
+        }
+    }
+}
+
 // min over the H window points of (a_j*px + b_j*py + c_j) for NV trajectory points held in registers.
 // 2 FMA + 1 MIN per (point, window point): the O(K*H^2) core (calc_MinDistance, dd:183-192).
 template <int NV, bool LDSWIN>
@@ -398,19 +506,24 @@ __device__ __forceinline__ void window_min(const double (&px)[kTU], const double
 }
 
 // BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters;
-// OBST (on VARIED): with the instance's disc obstacles (obst_term)
-template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false, bool OBST = false>
+// OBST (on VARIED): with the instance's disc obstacles (obst_term); MOVING (on OBST): the discs move (obst_term_moving)
+template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false, bool OBST = false, bool MOVING = false>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
     static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
+    static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
     constexpr int UD = udim_of(MODEL);
     __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
     __shared__ double s_c[LDSWIN ? kMaxH : 1];
     const RolloutArgs A = BATCH ? batch_view<VARIED>(Ak, (int)blockIdx.y) : Ak;
     const int H = A.H;
     ObstLds* obst_lds = nullptr;
-    if constexpr (OBST) {
+    ObstMovLds* obst_mov = nullptr;
+    if constexpr (MOVING) {
+        __shared__ ObstMovLds s_obst_mov;
+        obst_mov = &s_obst_mov;
+    } else if constexpr (OBST) {
         __shared__ ObstLds s_obst;
         obst_lds = &s_obst;
     }
@@ -420,7 +533,9 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, c
             s_ab[j] = make_double2(win[j], win[H + j]);
             s_c[j] = win[2 * H + j];
         }
-        if constexpr (OBST) {
+        if constexpr (MOVING) {
+            if (threadIdx.x < kMaxObst) obst_stage_moving(A, *obst_mov, (int)threadIdx.x);
+        } else if constexpr (OBST) {
             if (threadIdx.x < kMaxObst) obst_stage(A, *obst_lds, (int)threadIdx.x);
         }
         __syncthreads();
@@ -570,7 +685,8 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, c
                         cost += A.w_path * d2;
                     }
                 }
-                if constexpr (OBST) obst_term<kTU, kTU, true>(A, *obst_lds, px, py, m, cost, nv);
+                if constexpr (MOVING) obst_term_moving<kTU, kTU, true>(A, *obst_mov, px, py, m, cost, t0, nv);
+                else if constexpr (OBST) obst_term<kTU, kTU, true>(A, *obst_lds, px, py, m, cost, nv);
             }
         }
     }

@@ -808,12 +808,14 @@ __device__ __forceinline__ void pc_prune_window(const RolloutArgs& A, const SH& 
 // point pair by point pair -- 48 registers less; the same minima, hence the same bits.
 // OBST (batch handles, on VARIED): after the block's path terms, the instance's disc-obstacle term of the same states from the
 // coefficients staged in `ob` (obst_term, mppi_kernels.h); the window pruning does not touch that list.
-template <int NV, int MODEL, class SH, bool LEAN = false, bool OBST = false>
+// MOVING (on OBST): the discs move -- the coefficients staged in `obm`, state i0 + i of block b at step b * kTU + i0 + i of the
+// horizon (obst_term_moving)
+template <int NV, int MODEL, class SH, bool LEAN = false, bool OBST = false, bool MOVING = false>
 __device__ __forceinline__ void pc_consume(const RolloutArgs& A, const SH& sh, double& cost, const int b, const int lane,
                                            const int i0 = 0,          // states i0 .. i0+NV-1 of block b
                                            int* prune_on = nullptr,   // wave-uniform switch of the window pruning (below)
                                            int* taken_flag = nullptr, const int taken_value = 0,   // see below
-                                           const ObstLds* ob = nullptr) {
+                                           const ObstLds* ob = nullptr, const ObstMovLds* obm = nullptr) {
     const int H4 = (A.H + 3) & ~3;   // the window is padded with c = +inf: four points per iteration, no remainder
     double px[NV], py[NV], m[NV];
 #pragma unroll
@@ -942,7 +944,8 @@ __device__ __forceinline__ void pc_consume(const RolloutArgs& A, const SH& sh, d
             cost = fma(A.w_path, d2, cost);
         }
     }
-    if constexpr (OBST) obst_term<NV>(A, *ob, px, py, m, cost);
+    if constexpr (MOVING) obst_term_moving<NV>(A, *obm, px, py, m, cost, b * kTU + i0);
+    else if constexpr (OBST) obst_term<NV>(A, *ob, px, py, m, cost);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -237,8 +237,10 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // SHIFT (on VARIED): block-relative weights exp(-(total - m_g) / lambda), m_g = the workgroup's minimum cost (pc_shifted_weight)
 // OBST (on VARIED): the instance's disc obstacles -- staged beside the window by the distance wave's first 32 lanes, from the
 // pose the kernel holds; their term in the distance wave (pc_consume, obst_term)
+// MOVING (on OBST): the discs move with a constant velocity over the horizon (obst_stage_moving, obst_term_moving); the distance
+// wave takes whole blocks of kTU states whatever the dynamics wave's tail form, so state i of block b is step b * kTU + i
 template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false,
-          bool OBST = false>
+          bool OBST = false, bool MOVING = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
@@ -249,9 +251,14 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
     static_assert(!OBST || (VARIED && MODE == MODE_FUSED), "the obstacle term is built on the per-instance-parameter kernels");
+    static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
     __shared__ R4Shared<MODEL> sh;
     ObstLds* obst_lds = nullptr;   // (an array of its own: R4Shared, and with it every other kernel's LDS, stays as it is)
-    if constexpr (OBST) {
+    ObstMovLds* obst_mov = nullptr;
+    if constexpr (MOVING) {
+        __shared__ ObstMovLds s_obst_mov;
+        obst_mov = &s_obst_mov;
+    } else if constexpr (OBST) {
         __shared__ ObstLds s_obst;
         obst_lds = &s_obst;
     }
@@ -302,7 +309,10 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             CCV_DIAG_STAMP(A, 1);
         }
         bad_nominal = r4_stage_commit<MODEL>(A, sh, (int)threadIdx.x, staged);
-        if constexpr (OBST) {
+        if constexpr (MOVING) {
+            const int j = (int)threadIdx.x - 2 * 64;
+            if (j >= 0 && j < kMaxObst) obst_stage_moving(A, *obst_mov, j);
+        } else if constexpr (OBST) {
             const int j = (int)threadIdx.x - 2 * 64;
             if (j >= 0 && j < kMaxObst) obst_stage(A, *obst_lds, j);
         }
@@ -437,14 +447,14 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
                 const int nv = min(kR3CStates, nstates - b * kTU);
                 taken = nv > 0;
                 switch (nv) {
-                    case 8: pc_consume<8, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 7: pc_consume<7, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 6: pc_consume<6, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 5: pc_consume<5, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 4: pc_consume<4, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 3: pc_consume<3, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 2: pc_consume<2, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
-                    case 1: pc_consume<1, MODEL, R4Shared<MODEL>, true, OBST>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds); break;
+                    case 8: pc_consume<8, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 7: pc_consume<7, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 6: pc_consume<6, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 5: pc_consume<5, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 4: pc_consume<4, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 3: pc_consume<3, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 2: pc_consume<2, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
+                    case 1: pc_consume<1, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
                     default: break;
                 }
             }

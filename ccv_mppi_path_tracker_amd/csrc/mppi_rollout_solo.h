@@ -26,17 +26,24 @@ struct SoloShared {
 
 // WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h);
 // VARIED: with the batch's per-instance parameters; SHIFT (on VARIED): block-relative weights (pc_shifted_weight);
-// OBST (on VARIED): the instance's disc obstacles (obst_stage, obst_term)
-template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false, bool OBST = false>
+// OBST (on VARIED): the instance's disc obstacles (obst_stage, obst_term); MOVING (on OBST): the discs move (obst_stage_moving,
+// obst_term_moving)
+template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false, bool OBST = false,
+          bool MOVING = false>
 __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArgs Ak, const Window Wk) {
     static_assert(MODE == MODE_FUSED, "the stage-wise modes use k_rollout_pc");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
     static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
+    static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     __shared__ SoloShared<MODEL> sh;
     ObstLds* obst_lds = nullptr;   // (an array of its own: SoloShared stays as it is)
-    if constexpr (OBST) {
+    ObstMovLds* obst_mov = nullptr;
+    if constexpr (MOVING) {
+        __shared__ ObstMovLds s_obst_mov;
+        obst_mov = &s_obst_mov;
+    } else if constexpr (OBST) {
         __shared__ ObstLds s_obst;
         obst_lds = &s_obst;
     }
@@ -45,7 +52,9 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
     const int H = A.H;
     const int lane = threadIdx.x;
     stage_window<BATCH>(A, Wk, sh, kPcSamples);
-    if constexpr (OBST) {
+    if constexpr (MOVING) {
+        if (threadIdx.x < kMaxObst) obst_stage_moving(A, *obst_mov, (int)threadIdx.x);
+    } else if constexpr (OBST) {
         if (threadIdx.x < kMaxObst) obst_stage(A, *obst_lds, (int)threadIdx.x);
     }
     // two-instruction clamps (clampd_fast, mppi_kernels.h): the host has checked sigma and the bounds, this wave the warm start;
@@ -98,14 +107,14 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
         // ---------------- their distance to the window
         const int nv = min(kTU, nstates - b * kTU);
         switch (nv) {
-            case 8: pc_consume<8, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 7: pc_consume<7, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 6: pc_consume<6, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 5: pc_consume<5, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 4: pc_consume<4, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 3: pc_consume<3, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 2: pc_consume<2, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
-            case 1: pc_consume<1, MODEL, SoloShared<MODEL>, false, OBST>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds); break;
+            case 8: pc_consume<8, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 7: pc_consume<7, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 6: pc_consume<6, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 5: pc_consume<5, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 4: pc_consume<4, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 3: pc_consume<3, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 2: pc_consume<2, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
+            case 1: pc_consume<1, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
             default: break;
         }
     }

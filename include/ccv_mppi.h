@@ -252,6 +252,7 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_BATCH_KERNEL_VARIED 32 /* ORed in: the kernels with per-instance parameters ran (ccv_mppi_batch_set_params) */
 #define CCV_MPPI_BATCH_KERNEL_SHIFT 64   /* ORed into ccv_mppi_batch_last_kernel(): the shifted-weight kernels ran */
 #define CCV_MPPI_BATCH_KERNEL_OBST 128   /* ORed in: the kernels with the disc-obstacle term ran (ccv_mppi_batch_set_obstacles) */
+#define CCV_MPPI_BATCH_KERNEL_MOVING 256 /* ORed in (with OBST): the kernels with moving discs ran (ccv_mppi_batch_set_obstacle_velocities) */
 #define CCV_MPPI_MAX_OBSTACLES 32        /* discs per instance */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
@@ -319,6 +320,38 @@ int ccv_mppi_batch_get_min_shift(const ccv_mppi_batch* b);
  * while the term is off); any of the three may be NULL. */
 int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* b, const double* xyr, const int32_t* n, int32_t max_n, const double* weight);
 int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* b, double* xyr, int32_t* n, int32_t max_n, double* weight);
+/* Moving discs (NOT reference behaviour; off by default; batch handles only).  Disc j of instance b gets a velocity
+ * (vx, vy) in world coordinates, constant over the horizon: state k of a sample -- k dynamics steps after the pose, state 0 the
+ * pose itself, row k of ccv_mppi_batch_read_candidates -- is charged against the disc centred at o_j + v_j * (k * dt[b]), dt[b]
+ * the dt of the instance's rollout:
+ *     weight[b] * max( max_j ( r_j^2 - |p_k - o_j - v_j k dt|^2 ), 0 )
+ * over the same states as the static term, the deepest penetration, a NaN position 0.  vxy: [B][max_n][2] for the discs of
+ * _set_obstacles, rows at or past an instance's count ignored (max_n below a count: the remaining discs stand still).  A
+ * non-NULL table turns the MOVING kernels on (_last_kernel: MOVING | OBST | VARIED | family, | SHIFT, | WIDE), even one of all
+ * zeros -- whose results equal the static term's bit for bit; NULL returns to the static kernels and their bits.  A non-finite
+ * value or max_n outside [0, CCV_MPPI_MAX_OBSTACLES]: CCV_MPPI_ERR_INVALID_ARG; no discs set: CCV_MPPI_ERR_STATE; nothing
+ * changes either way.  _set_obstacles with a new list clears the velocities (a new list has none until it is given some),
+ * _set_obstacles(NULL) removes them with the discs, _set_params keeps them.  Discs the fleet term appends stand still.  Flushes a
+ * pending resident update and synchronises, like _set_obstacles.
+ * _get_obstacle_velocities: vxy [B][max_n][2], the host copy (rows past the count, and everything while none are set: zero). */
+int ccv_mppi_batch_set_obstacle_velocities(ccv_mppi_batch* b, const double* vxy, int32_t max_n);
+int ccv_mppi_batch_get_obstacle_velocities(ccv_mppi_batch* b, double* vxy, int32_t max_n);
+/* Fleet prediction (NOT reference behaviour; off by default): with the fleet term on (ccv_mppi_batch_resident_set_fleet,
+ * ccv_mppi_fleet.h), on != 0 makes every neighbour's disc move over the horizon with the velocity that robot had over the last
+ * resident tick, v = (position after the tick's advance - position before it) * (1 / dt), formed on the device by the robot's
+ * own prologue block (one fp64 subtraction and one multiplication per component; zero when the tick did not advance, when
+ * dt = 0, or when a component is not finite) and carried with its position through the double-buffered snapshot; the selection
+ * of the neighbours does not change.  While it is on the MOVING kernels run (_last_kernel: MOVING | OBST | ...); the static discs
+ * keep the velocities of _set_obstacle_velocities (zero without).  _resident_set_poses and _resident_set_fleet reset every
+ * robot's velocity to zero.  The setter gives CCV_MPPI_ERR_STATE while the fleet term is off; turning the fleet term off turns
+ * prediction off; prediction off returns to the kernels, and the bits, of a fleet run that never had it.  Flushes a pending
+ * resident update and synchronises.  _get_fleet_prediction: 0 / 1, or CCV_MPPI_ERR_INVALID_ARG for a null handle.
+ * _read_fleet_velocities: vxy [B][CCV_MPPI_MAX_OBSTACLES][2], the velocity rows the last tick's rollout was charged with, beside
+ * the disc rows of _resident_read_fleet (rows past an instance's total count zero; all zero while the static kernels run); a
+ * flush point; CCV_MPPI_ERR_STATE while the fleet term is off. */
+int ccv_mppi_batch_set_fleet_prediction(ccv_mppi_batch* b, int32_t on);
+int ccv_mppi_batch_get_fleet_prediction(const ccv_mppi_batch* b);
+int ccv_mppi_batch_read_fleet_velocities(ccv_mppi_batch* b, double* vxy);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,

@@ -19,7 +19,9 @@ extern "C" {
  * ccv_mppi_batch_set_obstacles, unchanged, then up to M_y = min(max_neighbours, CCV_MPPI_MAX_OBSTACLES - n_static[y]) discs for
  * the nearest other robots: centre q_j, radius radius[y] + radius[j].  The obstacle term of _set_obstacles charges them with
  * weight[y].  Every position of a tick is the pose at the start of that tick, before its advance (the own one too): a
- * neighbour's disc stands where that robot was one tick ago, and the caller covers its motion of one period with the radius.
+ * neighbour's disc stands where that robot was one tick ago, and the caller covers its motion of one period with the radius --
+ * or turns on ccv_mppi_batch_set_fleet_prediction (ccv_mppi.h), with which the disc moves over the horizon at the velocity the
+ * robot had over its last tick.
  * Selection, all in fp64 without FMA: dx = q_j[0] - q_y[0], dy = q_j[1] - q_y[1], d2 = dx*dx + dy*dy; robot j != y is a
  * candidate iff d2 <= range*range (the product rounded once; a NaN fails); the candidates in (d2, j) order, the first M_y taken
  * and written in that order.  The lists are formed on the device in the prologue of the tick, with no host data and no
