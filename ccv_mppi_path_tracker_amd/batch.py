@@ -235,6 +235,45 @@ class BatchController:
                                                           capi.MAX_OBSTACLES, capi.dptr(w)))
         return [xyr[b, :n[b]].copy() for b in range(self.B)], w
 
+    def set_grids(self, maps, map_of=None, weight=0.0):
+        """maps: a list of (cells[ny][nx] float32, (origin_x, origin_y), resolution, outside), or None: the term off and the
+        kernels that ran before; map_of: [B] index of the instance's map, -1 for none; weight: one value or [B], >= 0.  Every
+        state the path term covers reads the cell it lies in (cells[int(fy)][int(fx)], f = (p - origin) * (1 / resolution);
+        `outside` where there is none) and the cost gains weight_b * their sum.  Flushes a pending resident update; warm
+        starts, paths, poses, per-instance parameters and discs stay."""
+        if maps is None or len(maps) == 0:
+            self._check(self.lib.ccv_mppi_batch_set_grids(self._h, None, 0, None, None))
+            return
+        rows = (capi.Grid * len(maps))()
+        keep = []
+        for m, (cells, origin, resolution, outside) in enumerate(maps):
+            cells = np.ascontiguousarray(cells, dtype=np.float32)
+            if cells.ndim != 2:
+                raise ValueError("map %d: cells must be [ny][nx]" % m)
+            keep.append(cells)
+            rows[m] = capi.Grid(float(origin[0]), float(origin[1]), float(resolution), float(outside), cells.shape[1], cells.shape[0],
+                                cells.ctypes.data_as(C.POINTER(C.c_float)))
+        mo = np.ascontiguousarray(np.broadcast_to(np.asarray(map_of, dtype=np.int32), (self.B,)))
+        w = capi.as_f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), (self.B,)))
+        self._check(self.lib.ccv_mppi_batch_set_grids(self._h, rows, len(maps), mo.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(w)))
+
+    def get_grids(self):
+        """(maps, map_of [B], weight [B]) as the library holds them, maps a list of (cells[ny][nx] float32, (origin_x, origin_y),
+        resolution, outside) with the cells read back from the device; ([], all -1, zeros) while the term is off."""
+        n = C.c_int32(0)
+        mo = np.zeros(self.B, dtype=np.int32)
+        w = np.zeros(self.B)
+        self._check(self.lib.ccv_mppi_batch_get_grids(self._h, None, 0, C.byref(n), mo.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(w)))
+        rows = (capi.Grid * max(n.value, 1))()
+        self._check(self.lib.ccv_mppi_batch_get_grids(self._h, rows, n.value, None, None, None))
+        maps = []
+        for m in range(n.value):
+            g = rows[m]
+            cells = np.empty((g.ny, g.nx), dtype=np.float32)
+            self._check(self.lib.ccv_mppi_batch_read_grid_cells(self._h, m, cells.ctypes.data_as(C.POINTER(C.c_float))))
+            maps.append((cells, (g.origin_x, g.origin_y), g.resolution, g.outside))
+        return maps, mo, w
+
     # ---- warm starts [B][H-1][u_dim] ----
     def set_nominal(self, u):
         u = capi.as_f64(u, (self.B, self.H - 1, self.udim))

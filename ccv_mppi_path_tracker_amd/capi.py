@@ -29,6 +29,7 @@ BATCH_KERNEL_VARIED = 32
 BATCH_KERNEL_SHIFT = 64
 BATCH_KERNEL_OBST = 128
 BATCH_KERNEL_MOVING = 256
+BATCH_KERNEL_GRID = 512
 MAX_OBSTACLES = 32
 BATCH_TRACE_ROWS = 1024
 
@@ -51,6 +52,14 @@ class Stats(C.Structure):
         ("sum_w", C.c_double), ("min_cost", C.c_double), ("max_cost", C.c_double),
         ("n_zero_weight", C.c_int64), ("nonfinite", C.c_int32), ("reserved", C.c_int32),
         ("device_us", C.c_float), ("rollout_us", C.c_float),
+    ]
+
+
+class Grid(C.Structure):
+    """struct ccv_mppi_grid"""
+    _fields_ = [
+        ("origin_x", C.c_double), ("origin_y", C.c_double), ("resolution", C.c_double),
+        ("outside", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("cells", C.POINTER(C.c_float)),
     ]
 
 
@@ -119,6 +128,9 @@ SIGNATURES = {
     "ccv_mppi_batch_set_fleet_prediction": (C.c_int, [_H, C.c_int32]),
     "ccv_mppi_batch_get_fleet_prediction": (C.c_int, [_H]),
     "ccv_mppi_batch_read_fleet_velocities": (C.c_int, [_H, _dp]),
+    "ccv_mppi_batch_set_grids": (C.c_int, [_H, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32), _dp]),
+    "ccv_mppi_batch_get_grids": (C.c_int, [_H, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
+    "ccv_mppi_batch_read_grid_cells": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_float)]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),

@@ -16,12 +16,12 @@ int batch_kernel_code(const RolloutPlan& p) {
                                                            : CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
     return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0) |
            (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0) | (p.obst ? CCV_MPPI_BATCH_KERNEL_OBST : 0) |
-           (p.moving ? CCV_MPPI_BATCH_KERNEL_MOVING : 0);
+           (p.moving ? CCV_MPPI_BATCH_KERNEL_MOVING : 0) | (p.grid ? CCV_MPPI_BATCH_KERNEL_GRID : 0);
 }
 
 // whether the kernels read the parameter table: per-instance parameters, or shifted weights or obstacles (B copies of cfg in
-// the table then), or the fleet term
-bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift || bh->obst || bh->fleet; }
+// the table then), or the fleet term, or occupancy grids
+bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift || bh->obst || bh->fleet || bh->grid; }
 
 // whether the obstacle kernels run: static discs (ccv_mppi_batch_set_obstacles) or the fleet term (_resident_set_fleet); the
 // obst_* vectors and d_obst exist then
@@ -59,6 +59,13 @@ int fleet_zero_velocities(ccv_mppi_batch* bh) {
 // flushed and synchronised: a queued rollout or prologue may still read the old table.
 int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     const int B = bh->B;
+    // occupancy grids run the MOVING kernels: discs that have no velocities of their own (no static ones, no prediction) get a
+    // table of zeros, over which the moving term equals the static one bit for bit.  Every setter ends here, so the table
+    // follows every change of the discs, the fleet term and prediction.
+    const bool grid_moving = bh->grid && obst_on(bh) && !moving_on(bh);
+    if (grid_moving) {
+        if (int rc = upload_velocities(bh)) return rc;
+    }
     std::vector<BatchParams> rows((size_t)B);
     for (int b = 0; b < B; ++b) {
         RolloutArgs A;
@@ -86,8 +93,10 @@ int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
             P.n_obst = bh->obst_n[(size_t)b];
             P.obst = bh->d_obst + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 3;
             P.w_obs = bh->obst_w[(size_t)b];
-            if (moving_on(bh)) P.obst_v = bh->d_obst_v + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 2;
+            if (moving_on(bh) || grid_moving) P.obst_v = bh->d_obst_v + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 2;
         }
+        // (without discs a GRID kernel sees n_obst = 0 and reads neither table)
+        if (bh->grid && bh->grid_map_of[(size_t)b] >= 0) P.grid = bh->d_grid_rows + b;
     }
     if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
     HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
@@ -159,7 +168,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // of the fused kernels waits in bh->fin for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
-    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, obst_on(bh), moving_on(bh));
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, obst_on(bh), moving_on(bh), bh->grid);
     const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -310,7 +319,8 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
         if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
     }
     void* bufs[] = {bh->d_rec,  bh->d_rframe, bh->d_inst,     bh->d_rpath,        bh->d_rtrace,       bh->d_params,
-                    bh->d_cmin, bh->d_obst,   bh->d_fleet_xy, bh->d_fleet_radius, bh->d_fleet_nstatic, bh->d_obst_v, bh->d_fleet_v};
+                    bh->d_cmin, bh->d_obst,   bh->d_fleet_xy, bh->d_fleet_radius, bh->d_fleet_nstatic, bh->d_obst_v, bh->d_fleet_v,
+                    bh->d_grid_rows, bh->d_grid_cells};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete bh;
@@ -360,7 +370,7 @@ int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     const int B = bh->B;
     if (!cfgs) {   // back to the creation configuration; the shared kernels, or in shifted-weight mode B copies in the table
         if (int rc = batch_flush(bh)) return rc;
-        if (bh->min_shift || obst_on(bh)) {
+        if (bh->min_shift || obst_on(bh) || bh->grid) {
             HIP_TRY(bh, hipStreamSynchronize(bh->stream));
             if (int rc = upload_params(bh, nullptr)) return rc;
         }
@@ -489,6 +499,124 @@ int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* bh, double* xyr, int32_t* n, in
             if (nb > 0) std::memcpy(xyr + (size_t)b * max_n * 3, &bh->obst_xyr[(size_t)b * M * 3], (size_t)nb * 3 * sizeof(double));
         }
     }
+    return CCV_MPPI_OK;
+}
+
+// ---- occupancy grids ------------------------------------------------------------------------------------------------------
+
+int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int32_t n_maps, const int32_t* map_of, const double* weight) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int B = bh->B;
+    const bool off = !maps || n_maps == 0;
+    // every check comes before anything changes
+    size_t total = 0;
+    if (!off) {
+        if (n_maps < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: n_maps < 0");
+        if (!map_of || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+        for (int m = 0; m < n_maps; ++m) {
+            const ccv_mppi_grid& g = maps[m];
+            if (!g.cells) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a map has no cells");
+            if (g.nx < 1 || g.nx > CCV_MPPI_GRID_MAX_DIM || g.ny < 1 || g.ny > CCV_MPPI_GRID_MAX_DIM ||
+                (int64_t)g.nx * g.ny > CCV_MPPI_GRID_MAX_CELLS)
+                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: nx, ny outside [1, 32768] or nx * ny above 2^26");
+            if (!(g.resolution > 0.0) || !std::isfinite(g.resolution) || !std::isfinite(1.0 / g.resolution))
+                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a resolution is not positive and finite");
+            if (!std::isfinite(g.origin_x) || !std::isfinite(g.origin_y)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: an origin is not finite");
+            if (!std::isfinite(g.outside)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: an outside value is not finite");
+            const size_t n = (size_t)g.nx * (size_t)g.ny;
+            for (size_t i = 0; i < n; ++i)
+                if (!std::isfinite(g.cells[i])) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a cell is not finite");
+            total += n;
+        }
+        for (int b = 0; b < B; ++b) {
+            if (!(weight[b] >= 0.0) || !std::isfinite(weight[b]))
+                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a weight is negative or not finite");
+            if (map_of[b] < -1 || map_of[b] >= n_maps) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: map_of outside [-1, n_maps)");
+        }
+    }
+    if (off && !bh->grid) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    if (int rc = batch_flush(bh)) return rc;
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table, rows and cells)
+    if (off) {
+        if (bh->d_grid_cells) HIP_TRY(bh, hipFree(bh->d_grid_cells));
+        bh->d_grid_cells = nullptr;
+        bh->grid = false;
+        bh->grid_maps.clear();
+        bh->grid_offset.clear();
+        bh->grid_map_of.clear();
+        bh->grid_w.clear();
+        if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (null in every row)
+        return CCV_MPPI_OK;
+    }
+    // the cells of all maps are one allocation, sized by the maps: a new set is a new allocation, the old one goes when the new
+    // one is filled
+    float* cells = nullptr;
+    HIP_TRY(bh, hipMalloc(&cells, total * sizeof(float)));
+    if (!bh->d_grid_rows) HIP_TRY(bh, hipMalloc(&bh->d_grid_rows, (size_t)B * sizeof(GridRow)));
+    std::vector<size_t> offset((size_t)n_maps);
+    size_t at = 0;
+    for (int m = 0; m < n_maps; ++m) {
+        const size_t n = (size_t)maps[m].nx * (size_t)maps[m].ny;
+        const hipError_t e = hipMemcpy(cells + at, maps[m].cells, n * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(cells);
+            return fail(bh, CCV_MPPI_ERR_HIP, "set_grids: copying the cells", e);
+        }
+        offset[(size_t)m] = at;
+        at += n;
+    }
+    std::vector<GridRow> rows((size_t)B);
+    std::memset(rows.data(), 0, rows.size() * sizeof(GridRow));
+    for (int b = 0; b < B; ++b) {
+        if (map_of[b] < 0) continue;
+        const ccv_mppi_grid& g = maps[map_of[b]];
+        GridRow& r = rows[(size_t)b];
+        r.origin_x = g.origin_x;
+        r.origin_y = g.origin_y;
+        r.inv = 1.0 / g.resolution;
+        r.w = weight[b];
+        r.cells = cells + offset[(size_t)map_of[b]];
+        r.nx = g.nx;
+        r.ny = g.ny;
+        r.outside = g.outside;
+    }
+    HIP_TRY(bh, hipMemcpy(bh->d_grid_rows, rows.data(), rows.size() * sizeof(GridRow), hipMemcpyHostToDevice));
+    if (bh->d_grid_cells) (void)hipFree(bh->d_grid_cells);
+    bh->d_grid_cells = cells;
+    bh->grid_maps.assign(maps, maps + n_maps);
+    for (ccv_mppi_grid& g : bh->grid_maps) g.cells = nullptr;
+    bh->grid_offset.swap(offset);
+    bh->grid_map_of.assign(map_of, map_of + B);
+    bh->grid_w.assign(weight, weight + B);
+    bh->grid = true;
+    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+}
+
+int ccv_mppi_batch_get_grids(ccv_mppi_batch* bh, ccv_mppi_grid* maps, int32_t max_maps, int32_t* n_maps, int32_t* map_of, double* weight) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int n = bh->grid ? (int)bh->grid_maps.size() : 0;
+    if (maps && (max_maps < 0 || max_maps < n)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_grids: max_maps below the number of maps");
+    if (n_maps) *n_maps = n;
+    for (int m = 0; m < n && maps; ++m) maps[m] = bh->grid_maps[(size_t)m];
+    for (int b = 0; b < bh->B; ++b) {
+        if (map_of) map_of[b] = bh->grid ? bh->grid_map_of[(size_t)b] : -1;
+        if (weight) weight[b] = bh->grid ? bh->grid_w[(size_t)b] : 0.0;
+    }
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* bh, int32_t map, float* cells_out) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!cells_out) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->grid) return fail(bh, CCV_MPPI_ERR_STATE, "read_grid_cells: no maps are set (ccv_mppi_batch_set_grids)");
+    if (map < 0 || map >= (int32_t)bh->grid_maps.size()) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "read_grid_cells: map out of range");
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
+    HIP_TRY(bh, hipMemcpy(cells_out, bh->d_grid_cells + bh->grid_offset[(size_t)map], (size_t)g.nx * (size_t)g.ny * sizeof(float),
+                          hipMemcpyDeviceToHost));
     return CCV_MPPI_OK;
 }
 

@@ -224,6 +224,15 @@ struct ccv_mppi_batch : Core {
     bool moving = false;
     double* d_obst_v = nullptr;             // [B][CCV_MPPI_MAX_OBSTACLES][2], allocated at the first velocities, freed at destroy
     std::vector<double> obst_vxy;           // [B][CCV_MPPI_MAX_OBSTACLES][2] host copy while moving
+    // occupancy grids (ccv_mppi_batch_set_grids): the GRID rollout kernels while `grid`.  A grid plan is a moving plan: without
+    // discs the kernels see n_obst = 0 and read neither disc nor velocity rows; with discs and no velocities, d_obst_v is zero.
+    bool grid = false;
+    GridRow* d_grid_rows = nullptr;         // [B], a row per instance (BatchParams::grid points at it, or is null)
+    float* d_grid_cells = nullptr;          // the cells of all maps, one allocation
+    std::vector<ccv_mppi_grid> grid_maps;   // host copy of the maps' geometry (cells: null)
+    std::vector<size_t> grid_offset;        // [n_maps] first cell of map m in d_grid_cells
+    std::vector<int32_t> grid_map_of;       // [B]
+    std::vector<double> grid_w;             // [B]
     bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
     // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
     // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
@@ -304,12 +313,15 @@ inline bool has_wide_form(const KernelChoice& k, const int mode) {
 // The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
 // (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
 // shift (a batch in shifted-weight mode), obst (a batch with obstacles): always with the per-instance-parameter kernels.
-// moving (a batch whose discs have velocities): always an obstacle plan.
+// moving (a batch whose discs have velocities): always an obstacle plan.  grid (a batch with occupancy grids): always a moving plan.
 inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied,
-                             const bool shift = false, const bool obst = false, const bool moving = false) {
-    const KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
-    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift || obst || moving, shift,
-                       obst || moving, moving, k.lds_window != 0};
+                             const bool shift = false, const bool obst = false, const bool moving = false, const bool grid = false) {
+    KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
+    // (the one-wave full-body kernel has no grid form -- it has no register left, DESIGN.md section 10h: the four-wave kernel
+    //  runs such a plan, at any number of workgroups)
+    if (grid && model == CCV_MPPI_FULL_BODY && f == KernelFamily::OneWave) f = KernelFamily::FourWave;
+    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift || obst || moving || grid, shift,
+                       obst || moving || grid, moving || grid, grid, k.lds_window != 0};
 }
 
 RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);   // a single handle's

@@ -95,6 +95,8 @@ struct BatchHead {
 // table, and the weight of their penalty; null / 0 / 0 without obstacles.
 // obst_v (ccv_mppi_batch_set_obstacle_velocities; MOVING kernels only): the discs' velocities, rows (vx, vy) of a device table
 // [B][32][2] beside the discs'; null while no velocities are set.  Every row of a non-null table is defined: zero unless given.
+// grid (ccv_mppi_batch_set_grids; GRID kernels only): the instance's row of the occupancy-grid table; null without a map.
+struct GridRow;
 struct alignas(64) BatchParams {
     double sigma, lambda, v_ref;
     double umin[5], umax[5];
@@ -103,8 +105,19 @@ struct alignas(64) BatchParams {
     const double* obst;
     double w_obs;
     const double* obst_v;
+    const GridRow* grid;
 };
 static_assert(sizeof(BatchParams) == 192, "three 64-byte lines per instance");
+// One instance's occupancy grid (GRID kernels): a 64-byte row of a device table [B].  The map is nx x ny
+// cells of float, row-major with x fastest, its corner at (origin_x, origin_y) in world coordinates; inv = RN(1 / resolution),
+// formed on the host; `outside` is the value of everything that is not in a cell.  nx, ny in [1, 32 768], nx * ny <= 2^26.
+struct alignas(64) GridRow {
+    double origin_x, origin_y, inv, w;
+    const float* cells;
+    int32_t nx, ny;
+    float outside;
+};
+static_assert(sizeof(GridRow) == 64, "one 64-byte line per instance");
 constexpr int kBatchHeadDoubles = 16;
 __host__ __device__ constexpr int batch_record_doubles(int H) { return kBatchHeadDoubles + ((3 * H + 7) & ~7); }
 
@@ -480,6 +493,66 @@ __device__ __forceinline__ void obst_term_moving(const RolloutArgs& A, const Obs
     }
 }
 
+// ---- occupancy grid (GRID kernels, on MOVING) ------------------------------------------------------
+// State (x, y) AS STORED (absolute, the doubles of ccv_mppi_batch_read_candidates) reads one cell:
+//   fx = (x - origin_x) * inv, fy = (y - origin_y) * inv      (one subtraction, one multiplication each, no FMA)
+//   in = fx >= 0 && fx < nx && fy >= 0 && fy < ny             (fp64 compares: false for NaN, so a NaN state reads `outside`)
+//   v  = in ? cells[(int)fy * nx + (int)fx] : outside
+// G = the fp64 sum of (double)v over the states the path term covers, in state order from 0.0; cost = fma(w, G, cost) is the
+// LAST thing added to a sample's cost.  The row is read wave-uniformly through the constant address space (as obst_row).
+typedef const GridRow __attribute__((address_space(4))) * ConstGridRow;
+__device__ __forceinline__ ConstGridRow grid_row(const RolloutArgs& A) {
+    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
+    typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
+    return (ConstGridRow)(const void*)(*(ConstParams)(const void*)((ConstHead)(const void*)A.frame)->params).grid;
+}
+// the gather of one state: ONE unconditional load whose address is the cell's, or that of the row's own `outside` field when the
+// state is in no cell -- so a block's gathers are in flight together with no branch between them, and nothing but the loaded
+// float is alive until it is summed (held beside the gathers, eight `in` masks cost the four-wave kernels sixteen scalar
+// registers, which they spill into vector lanes)
+struct GridTap {
+    float v;
+};
+__device__ __forceinline__ GridTap grid_tap(const ConstGridRow g, const double x, const double y) {
+    typedef const float __attribute__((address_space(1))) * GlobalF32;
+    const double fx = (x - g->origin_x) * g->inv;
+    const double fy = (y - g->origin_y) * g->inv;
+    const int nx = g->nx;
+    const bool in = fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)g->ny;
+    const int ix = (int)(in ? fx : 0.0), iy = (int)(in ? fy : 0.0);   // (in: 0 <= fx < 32 768 -- truncation is exact)
+    const uint64_t cell = (uint64_t)(uintptr_t)g->cells + (uint64_t)(uint32_t)(iy * nx + ix) * 4u;   // (nx ny <= 2^26)
+    const uint64_t outside = (uint64_t)(uintptr_t)(const void*)g + offsetof(GridRow, outside);
+    return GridTap{*(GlobalF32)(uintptr_t)(in ? cell : outside)};
+}
+__device__ __forceinline__ double grid_value(const GridTap& t) { return (double)t.v; }
+// the per-lane accumulator of a wave that meets every state of its sample (null row: the instance has no map).  slot: the sum
+// lives in LDS instead of in G (the plain kernel)
+struct GridAcc {
+    ConstGridRow row;
+    double G;
+    int nstates;   // states that reach the path cost
+    double* slot;
+};
+// states t0 .. t0+NV-1 held in registers: all gathers first (grid_issue), then the sum in state order (grid_sum); states at or
+// past nstates do not count
+template <int NV>
+__device__ __forceinline__ void grid_issue(const GridAcc& ga, const double (&xv)[NV], const double (&yv)[NV], GridTap (&tap)[NV]) {
+    if (!ga.row) return;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) tap[i] = grid_tap(ga.row, xv[i], yv[i]);
+}
+template <int NV>
+__device__ __forceinline__ void grid_sum(GridAcc& ga, const GridTap (&tap)[NV], const int t0) {
+    if (!ga.row) return;
+    double G = ga.slot ? *ga.slot : ga.G;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if (t0 + i < ga.nstates) G += grid_value(tap[i]);
+    if (ga.slot) *ga.slot = G;
+    else ga.G = G;
+}
+__device__ __forceinline__ double grid_total(const GridAcc& ga) { return ga.slot ? *ga.slot : ga.G; }
+
 // min over the H window points of (a_j*px + b_j*py + c_j) for NV trajectory points held in registers.
 // 2 FMA + 1 MIN per (point, window point): the O(K*H^2) core (calc_MinDistance, dd:183-192).
 template <int NV, bool LDSWIN>
@@ -506,13 +579,16 @@ __device__ __forceinline__ void window_min(const double (&px)[kTU], const double
 }
 
 // BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters;
-// OBST (on VARIED): with the instance's disc obstacles (obst_term); MOVING (on OBST): the discs move (obst_term_moving)
-template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false, bool OBST = false, bool MOVING = false>
+// OBST (on VARIED): with the instance's disc obstacles (obst_term); MOVING (on OBST): the discs move (obst_term_moving);
+// GRID (on MOVING): the instance's occupancy grid, read in the state loop where x and y are stored (grid_tap)
+template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false, bool OBST = false, bool MOVING = false,
+          bool GRID = false>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
     static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
     static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
+    static_assert(!GRID || MOVING, "the grid forms are built on the moving-disc kernels");
     constexpr int UD = udim_of(MODEL);
     __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
     __shared__ double s_c[LDSWIN ? kMaxH : 1];
@@ -565,6 +641,14 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, c
     const double fb_mgz = A.fb_mass * A.fb_gz;    // (mass*gravity_).z
     const double fb_den = A.fb_mass * A.fb_gz;    // mass*(gravity_-accel).dot(z); accel.z == 0 (fb:475,601)
 
+    GridAcc grid_acc{};
+    if constexpr (GRID) {
+        // the lane's running sum lives in LDS (2 KB): in two registers it took the diff-drive and steering forms from 127 to 131
+        // and a workgroup per CU away; for the same reason every gather is summed at once -- this is the fallback family
+        __shared__ double s_grid[kBlock];
+        s_grid[threadIdx.x] = 0.0;
+        grid_acc = GridAcc{grid_row(A), 0.0, MODEL == CCV_MPPI_FULL_BODY ? H - 2 : H, &s_grid[threadIdx.x]};
+    }
     for (int t0 = 0; t0 < H; t0 += kTU) {
         double px[kTU], py[kTU];
         float zq[4] = {0.f, 0.f, 0.f, 0.f};
@@ -573,6 +657,9 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, c
             const int t = t0 + tt;
             px[tt] = x - A.x0[0];
             py[tt] = y - A.x0[1];
+            if constexpr (GRID) {
+                if (grid_acc.row && t < grid_acc.nstates) *grid_acc.slot += grid_value(grid_tap(grid_acc.row, x, y));
+            }
             if (t < H) {
                 if (A.store_xy && live) {
                     A.xs[(size_t)t * pitch + k] = x;
@@ -688,6 +775,11 @@ __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, c
                 if constexpr (MOVING) obst_term_moving<kTU, kTU, true>(A, *obst_mov, px, py, m, cost, t0, nv);
                 else if constexpr (OBST) obst_term<kTU, kTU, true>(A, *obst_lds, px, py, m, cost, nv);
             }
+        }
+    }
+    if constexpr (GRID) {
+        if (grid_acc.row) {
+            cost = fma(grid_acc.row->w, grid_total(grid_acc), cost);   // the last term (section 10h)
         }
     }
     if (A.do_cost && live) {

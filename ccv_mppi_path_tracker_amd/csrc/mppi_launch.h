@@ -1,6 +1,6 @@
 // Launching a rollout kernel.  Which kernel a launch runs is a value, RolloutPlan; launch_rollout() (mppi_launch.hip) is a
 // switch over it.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip, k_r4_fb.hip, k_pc_fb.hip,
-// k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip, k_batch_shift.hip, k_batch_obst.hip, k_batch_obst_shift.hip, k_batch_moving.hip, k_batch_moving_shift.hip: batch forms): hipcc spends over a minute on all
+// k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip, k_batch_shift.hip, k_batch_obst.hip, k_batch_obst_shift.hip, k_batch_moving.hip, k_batch_moving_shift.hip, k_batch_grid.hip, k_batch_grid_shift.hip: batch forms): hipcc spends over a minute on all
 // instantiations in one file, the units compile side by side (build.py), and an instantiation placed beside others can change
 // the code generated for those.  The C ABI picks the family at create (select_kernels(), ccv_mppi_capi.hip) and makes the plan
 // of each launch from it (make_plan(), capi_internal.h).
@@ -33,6 +33,7 @@ struct RolloutPlan {
     bool shift;        // batch, varied: shifted weights (ccv_mppi_batch_set_min_shift; the four- and one-wave kernels' SHIFT forms)
     bool obst;         // batch, varied: the disc-obstacle term (ccv_mppi_batch_set_obstacles; the OBST forms of all three families)
     bool moving;       // batch, obst: the discs move (ccv_mppi_batch_set_obstacle_velocities; the MOVING forms of all three families)
+    bool grid;         // batch, moving: the occupancy-grid term (ccv_mppi_batch_set_grids; the GRID forms of all three families)
     bool lds_window;   // Plain: the window from LDS (false: CCV_MPPI_WINDOW=scalar)
 };
 

@@ -20,10 +20,12 @@ void launch_batch_varied(const RolloutPlan& p, bool tail, const LaunchAt& at, co
 void launch_batch_shift(const RolloutPlan& p, bool tail, const LaunchAt& at, const RolloutArgs& A, const Window& W);    // k_batch_shift.hip: four-, one-wave
 void launch_batch_obst(const RolloutPlan& p, bool tail, const LaunchAt& at, const RolloutArgs& A, const Window& W);     // k_batch_obst.hip, k_batch_obst_shift.hip: all
 void launch_batch_moving(const RolloutPlan& p, bool tail, const LaunchAt& at, const RolloutArgs& A, const Window& W);   // k_batch_moving.hip, k_batch_moving_shift.hip: all
+void launch_batch_grid(const RolloutPlan& p, bool tail, const LaunchAt& at, const RolloutArgs& A, const Window& W);     // k_batch_grid.hip, k_batch_grid_shift.hip: all
 
 void launch_rollout(const RolloutPlan& p, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
     const bool fb = p.model == CCV_MPPI_FULL_BODY;
     const bool tail = (A.H - 1) % kTU >= kPartialMin;
+    if (p.batch && p.obst && p.moving && p.grid) return launch_batch_grid(p, tail, at, A, W);   // (a grid plan is a moving plan)
     if (p.batch && p.obst && p.moving) return launch_batch_moving(p, tail, at, A, W);   // (a moving plan is an obstacle plan)
     if (p.batch && p.obst) return launch_batch_obst(p, tail, at, A, W);   // (with or without shifted weights)
     // (shifted weights: the plain family keeps the varied kernel -- the host re-forms its weights, k_reweight_batch)

@@ -206,10 +206,12 @@ __device__ __forceinline__ void pc_barrier_lds() { asm volatile("s_waitcnt lgkmc
 // producer: steps t0 .. t0+7 of one sample (sampling + predict_NextState + control costs).  FULL: every step of the
 // block carries controls (t0 + 8 <= H - 1), so the body is branch-free.
 // ---------------------------------------------------------------------------------------------------------------
-template <int MODEL, int MODE, bool FULL, class SH>
+// GRID (the one-wave kernel's grid forms): every state of the block is looked up in the instance's occupancy grid as it is
+// stored (grid_tap, mppi_kernels.h) and summed into *ga at once -- this is the rare path
+template <int MODEL, int MODE, bool FULL, bool GRID = false, class SH>
 __device__ __forceinline__ void pc_produce(const RolloutArgs& A, SH& sh, PcState<MODEL>& S, double& cost,
                                            const int b, const int lane, const int k, const int kk, const bool live,
-                                           const uint32_t kg) {
+                                           const uint32_t kg, GridAcc* ga = nullptr) {
     constexpr int UD = udim_of(MODEL);
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
@@ -228,6 +230,12 @@ __device__ __forceinline__ void pc_produce(const RolloutArgs& A, SH& sh, PcState
         } else {
             sh.p[b & (SH::kPBuf - 1)][tt][0][lane] = S.x - A.x0[0];
             sh.p[b & (SH::kPBuf - 1)][tt][1][lane] = S.y - A.x0[1];
+        }
+        if constexpr (GRID) {
+            const double gx[1] = {S.x}, gy[1] = {S.y};
+            GridTap tap[1];
+            grid_issue(*ga, gx, gy, tap);
+            grid_sum(*ga, tap, t);
         }
         if (FULL || t < H) {
             if constexpr (MODE != MODE_COST && !SH::kStage) {
@@ -397,13 +405,16 @@ constexpr int kPartialMin = 4;
 // NCTL > 0 (with PARTIAL): the number of control steps is known at compile time -- every mask folds, and what the masked steps
 // would have computed falls away as dead code (the reference's default horizon H = 15 leaves a last block of six: a quarter of
 // the batch).  The steps that remain are computed as before, bit for bit.
+// GRID (the one-wave kernel's grid forms; 0: none): the block's eight states are looked up in the instance's occupancy grid
+// where they are stored, all gathers issued together; 1: summed into *ga here; 2: left in *tap for the caller to sum after the
+// distance phase (grid_sum), so that the gathers' latency passes under it
 template <int MODEL, int MODE, class SH, bool ZLDS = false, bool FASTCLAMP = false, bool WIDE = false, bool PARTIAL = false,
-          int NCTL = 0>
+          int NCTL = 0, int GRID = 0>
 __device__ __forceinline__ bool pc_produce_batched(const RolloutArgs& A, SH& sh, PcState<MODEL>& S, double& cost,
                                                    const int b, const int lane, const int k, const int kk, const bool live,
                                                    const uint32_t kg,
                                                    const float (*ahead)[kPcSamples] = nullptr,   // pc_noise_ahead's slot
-                                                   const int nctl_in = kTU) {
+                                                   const int nctl_in = kTU, GridAcc* ga = nullptr, GridTap (*tap)[kTU] = nullptr) {
     static_assert(NCTL == 0 || (PARTIAL && NCTL < kTU), "a compile-time step count is a partial block's");
     const int nctl = NCTL > 0 ? NCTL : (PARTIAL ? nctl_in : kTU);   // steps of this block that carry controls (wave-uniform)
     constexpr int UD = udim_of(MODEL);
@@ -682,6 +693,13 @@ __device__ __forceinline__ bool pc_produce_batched(const RolloutArgs& A, SH& sh,
                 }
             }
         }
+    }
+    if constexpr (GRID == 1) {
+        GridTap here[kTU];
+        grid_issue(*ga, xv, yv, here);
+        grid_sum(*ga, here, t0);
+    } else if constexpr (GRID == 2) {
+        grid_issue(*ga, xv, yv, *tap);
     }
     if constexpr (NCTL > 0) return true;   // (the horizon's last block: the state is not carried any further)
     S.x = x;

@@ -239,8 +239,13 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // pose the kernel holds; their term in the distance wave (pc_consume, obst_term)
 // MOVING (on OBST): the discs move with a constant velocity over the horizon (obst_stage_moving, obst_term_moving); the distance
 // wave takes whole blocks of kTU states whatever the dynamics wave's tail form, so state i of block b is step b * kTU + i
+// GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_kernels.h) -- in the store wave, which has every absolute state
+// in registers on its way from LDS to HBM whether or not the states are stored, and issue slots to spare.  A block's eight
+// gathers are issued before its stores and summed after them, so their latency passes under the issue of the block's 32 to 56
+// stores.  The lane's sum reaches the epilogue in sh.cost[3], the store wave's slot of the cost parts, which is 0.0 otherwise:
+// the GRID epilogue adds a literal 0.0 in its place (the same bits) and then the grid term, one FMA, last.  No new LDS.
 template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false,
-          bool OBST = false, bool MOVING = false>
+          bool OBST = false, bool MOVING = false, bool GRID = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
@@ -252,6 +257,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
     static_assert(!OBST || (VARIED && MODE == MODE_FUSED), "the obstacle term is built on the per-instance-parameter kernels");
     static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
+    static_assert(!GRID || MOVING, "the grid forms are built on the moving-disc kernels");
     __shared__ R4Shared<MODEL> sh;
     ObstLds* obst_lds = nullptr;   // (an array of its own: R4Shared, and with it every other kernel's LDS, stays as it is)
     ObstMovLds* obst_mov = nullptr;
@@ -470,6 +476,8 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         const R4Lane L = r4_lane(A);
         const int lane = L.lane;
         const uint32_t koff4 = (uint32_t)L.k * 4u, koff8 = (uint32_t)L.k * 8u;
+        GridAcc grid_acc{};
+        if constexpr (GRID) grid_acc = GridAcc{grid_row(A), 0.0, nstates, nullptr};
         for (int b = 0; b < nblocks; ++b) {
             r4_rotate_priority(A, b, 3);
             pc_wait_for(seq_ready, b + 1);
@@ -489,6 +497,10 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             pc_publish(seq_store, b + 1);
+            GridTap tap[kTU];
+            if constexpr (GRID) {   // the block's gathers, ahead of its stores (vector-memory operations complete in order)
+                grid_issue(grid_acc, xv, yv, tap);
+            }
             // (the row pitch in bytes stays below 4 GB by construction: 32-bit lane offsets)
             if constexpr (MODE == MODE_FUSED) {
                 const int nrows = min(kTU, H - 1 - t0) * UD;   // control steps t < H-1
@@ -513,6 +525,9 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
                     }
                 }
             }
+            if constexpr (GRID) {   // ... summed in state order once the stores are issued (states past nstates: not counted)
+                grid_sum(grid_acc, tap, t0);
+            }
             if constexpr (MODE == MODE_FUSED) {
                 // all stores of the blocks before this one are acknowledged once no more than this block's own are
                 // outstanding (vector-memory operations complete in order); a partial block waits for everything
@@ -527,7 +542,8 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         // the other waves re-read the rows of normals in the epilogue: all of this wave's stores are acknowledged before the
         // barrier below
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (COST) sh.cost[3][lane] = 0.0;
+        if constexpr (GRID) sh.cost[3][lane] = grid_acc.G;   // (read as the grid sum, not as a cost part: the epilogue)
+        else if constexpr (COST) sh.cost[3][lane] = 0.0;
     }
     // (the epilogue at equal priorities: youngest-first there, as in the prologue, was measured 1.4 us SLOWER -- the epilogue is
     //  bound by LDS bandwidth, and strict priorities only serialise it)
@@ -560,7 +576,16 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             }
         }
         if (!from_lds && (MODE != MODE_FUSED || wv >= 2 || nb_early == 0) && mcount > 0) r4_fetch0(A, upd, rows, kk);
-        const double total = ((sh.cost[0][lane] + sh.cost[1][lane]) + sh.cost[2][lane]) + sh.cost[3][lane];
+        double total_;
+        if constexpr (GRID) {
+            // the store wave's cost part is 0.0 in every other form: the same sum, then the grid term last
+            total_ = ((sh.cost[0][lane] + sh.cost[1][lane]) + sh.cost[2][lane]) + 0.0;
+            const ConstGridRow g = grid_row(A);
+            if (g) total_ = fma(g->w, sh.cost[3][lane], total_);
+        } else {
+            total_ = ((sh.cost[0][lane] + sh.cost[1][lane]) + sh.cost[2][lane]) + sh.cost[3][lane];
+        }
+        const double total = total_;
         double wgt_;
         if constexpr (SHIFT) wgt_ = pc_shifted_weight(A, total, live);   // (every wave: the same 64 totals, the same minimum)
         else wgt_ = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)

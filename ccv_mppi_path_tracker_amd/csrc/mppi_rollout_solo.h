@@ -27,15 +27,21 @@ struct SoloShared {
 // WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h);
 // VARIED: with the batch's per-instance parameters; SHIFT (on VARIED): block-relative weights (pc_shifted_weight);
 // OBST (on VARIED): the instance's disc obstacles (obst_stage, obst_term); MOVING (on OBST): the discs move (obst_stage_moving,
-// obst_term_moving)
+// obst_term_moving); GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_kernels.h), looked up by the producer where
+// it stores the block's absolute states; the block's gathers are summed after its distance phase, under which their latency
+// passes.  The grid term is the last added to the cost.  Diff drive and steering only.
 template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false, bool OBST = false,
-          bool MOVING = false>
+          bool MOVING = false, bool GRID = false>
 __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArgs Ak, const Window Wk) {
     static_assert(MODE == MODE_FUSED, "the stage-wise modes use k_rollout_pc");
     static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
     static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
     static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
+    static_assert(!GRID || MOVING, "the grid forms are built on the moving-disc kernels");
+    // (the MOVING parent uses all 256 registers without a spill; with the term it spilled two or three whether the sum was held
+    //  in registers or in LDS -- DESIGN.md section 10h -- so full-body grid plans run the four-wave form, make_plan)
+    static_assert(!GRID || MODEL != CCV_MPPI_FULL_BODY, "the one-wave full-body kernel has no grid form");
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     __shared__ SoloShared<MODEL> sh;
     ObstLds* obst_lds = nullptr;   // (an array of its own: SoloShared stays as it is)
@@ -78,6 +84,9 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
     S.p_v = S.p_rv = S.p_sdir = S.p_c2 = S.p_c3 = S.p_ac = 0.0;
     S.p_cdir = 1.0;
     fast_sincos(A.x0[2], S.sn, S.cs);
+    constexpr int GM = GRID ? 2 : 0;   // (pc_produce_batched's GRID)
+    GridAcc grid_acc{};
+    if constexpr (GRID) grid_acc = GridAcc{grid_row(A), 0.0, nstates, nullptr};
     __syncthreads();   // (one wave: the staged window and warm start are visible to all its lanes)
     // Wave priorities: two (or more) of these waves share a SIMD and run the same code in step; left alone they contend for
     // the same pipe at the same time.  Level (-rank - b) mod 4 -- the workgroup's dispatch rank on its CU, rotating with the
@@ -89,21 +98,22 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
         if (A.prio_rotate) pc_set_priority((-prio_rank - b) & 3);
         // ---------------- states and controls of steps 8b .. 8b+7
         bool done = false;
+        GridTap tap[kTU];
         const int nctl = min(kTU, H - 1 - b * kTU);   // steps of this block that carry controls
         if (nctl == kTU) {
             if (fast_clamp)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, true, WIDE>(A, sh, S, cost, b, lane, k, kk, live, kg);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, true, WIDE, false, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, kTU, &grid_acc, &tap);
             else if constexpr (!FB)   // (a second instantiation, so that a NaN in the warm start gives the multi-wave kernels'
                                       //  bits; full body has no registers for it -- its NaN case takes pc_produce below, whose
                                       //  sin / cos differ from the block path's in the last place)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, false, WIDE>(A, sh, S, cost, b, lane, k, kk, live, kg);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, false, WIDE, false, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, kTU, &grid_acc, &tap);
         } else if (nctl >= kPartialMin) {   // the horizon's last block, partly filled (C4: 7 of its 8 steps)
             if (fast_clamp)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, true, WIDE, true>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, true, WIDE, true, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl, &grid_acc, &tap);
             else if constexpr (!FB)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, false, WIDE, true>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, false, WIDE, true, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl, &grid_acc, &tap);
         }
-        if (!done) pc_produce<MODEL, MODE, false>(A, sh, S, cost, b, lane, k, kk, live, kg);
+        if (!done) pc_produce<MODEL, MODE, false, GRID>(A, sh, S, cost, b, lane, k, kk, live, kg, &grid_acc);
         // ---------------- their distance to the window
         const int nv = min(kTU, nstates - b * kTU);
         switch (nv) {
@@ -117,6 +127,12 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
             case 1: pc_consume<1, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
             default: break;
         }
+        if constexpr (GM == 2) {
+            if (done) grid_sum(grid_acc, tap, b * kTU);
+        }
+    }
+    if constexpr (GRID) {
+        if (grid_acc.row) cost = fma(grid_acc.row->w, grid_total(grid_acc), cost);   // the last term (section 10h)
     }
     if (A.prio_rotate) __builtin_amdgcn_s_setprio(0);
     // ---------------- weights and this wave's share of the update (dd:216-237)

@@ -253,7 +253,10 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_BATCH_KERNEL_SHIFT 64   /* ORed into ccv_mppi_batch_last_kernel(): the shifted-weight kernels ran */
 #define CCV_MPPI_BATCH_KERNEL_OBST 128   /* ORed in: the kernels with the disc-obstacle term ran (ccv_mppi_batch_set_obstacles) */
 #define CCV_MPPI_BATCH_KERNEL_MOVING 256 /* ORed in (with OBST): the kernels with moving discs ran (ccv_mppi_batch_set_obstacle_velocities) */
+#define CCV_MPPI_BATCH_KERNEL_GRID 512   /* ORed in (with MOVING | OBST): the kernels with the occupancy-grid term ran (ccv_mppi_batch_set_grids) */
 #define CCV_MPPI_MAX_OBSTACLES 32        /* discs per instance */
+#define CCV_MPPI_GRID_MAX_DIM 32768      /* cells per axis of an occupancy grid */
+#define CCV_MPPI_GRID_MAX_CELLS (1 << 26) /* cells per occupancy grid */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
 
@@ -352,6 +355,39 @@ int ccv_mppi_batch_get_obstacle_velocities(ccv_mppi_batch* b, double* vxy, int32
 int ccv_mppi_batch_set_fleet_prediction(ccv_mppi_batch* b, int32_t on);
 int ccv_mppi_batch_get_fleet_prediction(const ccv_mppi_batch* b);
 int ccv_mppi_batch_read_fleet_velocities(ccv_mppi_batch* b, double* vxy);
+/* Occupancy grids (NOT reference behaviour; off by default; batch handles only).  The handle holds n_maps >= 1 maps.  Map m is
+ * nx x ny cells of float, row-major with x fastest (cell (ix, iy) at cells[iy * nx + ix]), its corner (origin_x, origin_y) in
+ * world coordinates, resolution > 0 the side of a cell, and `outside` the value of everything that is not in a cell.  Instance b
+ * uses map map_of[b] (-1: none) with weight[b] >= 0.  For every state the path term is taken over (the same states and step
+ * ranges as the disc term: all H for diff drive and steering, the first H - 2 for full body), in state order k = 0, 1, ..., with
+ * (x, y) the state AS STORED, the doubles ccv_mppi_batch_read_candidates returns:
+ *     inv = 1.0 / resolution                                  (rounded once, on the host)
+ *     fx  = (x - origin_x) * inv,  fy = (y - origin_y) * inv    (one subtraction, one multiplication, no FMA)
+ *     in  = fx >= 0 && fx < nx && fy >= 0 && fy < ny           (fp64 compares: false for NaN)
+ *     v_k = in ? cells[(int)fy * nx + (int)fx] : outside
+ *     G   = ((double)v_0 + (double)v_1) + ...                  (fp64, in state order, from 0.0)
+ *     cost = fma(weight[b], G, cost_rest)
+ * with cost_rest the sample's complete cost without the term: the grid term is added last, as one FMA, before the weight is
+ * formed.  A NaN state reads `outside`: that is the one rule for states that are not numbers.  The term touches the cost only:
+ * noise, controls and states keep their bits, an instance with map_of[b] = -1 or weight[b] = 0 keeps every bit of its result
+ * (G finite), and no map, map_of or weight of one instance changes a bit of another.  Nearest cell only: no interpolation, no
+ * integer cells, no rotated maps, no partial updates -- a new map is a new _set_grids.
+ * The term always runs the moving-disc kernels' GRID forms (_last_kernel: GRID | MOVING | OBST | VARIED | family, | SHIFT,
+ * | WIDE): a handle without discs runs them over an empty disc list, a handle with static discs over a zero velocity table, whose
+ * disc term equals the static one bit for bit.  nx, ny in [1, CCV_MPPI_GRID_MAX_DIM], nx * ny <= CCV_MPPI_GRID_MAX_CELLS.
+ * _set_grids: maps [n_maps], map_of [B], weight [B]; the cells are copied.  NULL cells, a size out of range, a non-finite or
+ * non-positive resolution, a non-finite origin, outside, weight or cell, a negative weight, map_of[b] outside [-1, n_maps):
+ * CCV_MPPI_ERR_INVALID_ARG, nothing changes.  maps == NULL or n_maps == 0 turns the term off and returns to the kernels, and the
+ * bits, that ran before.  Flushes a pending resident update and synchronises, like _set_obstacles; the resident loop sees the
+ * maps from the next step on; _set_params, _set_obstacles, _set_obstacle_velocities, _set_min_shift and the fleet setters keep
+ * them.
+ * _get_grids: maps [max_maps] (cells returned NULL), *n_maps, map_of [B] (-1 while off), weight [B] (0 while off); any may be
+ * NULL; max_maps below the number of maps with maps != NULL: CCV_MPPI_ERR_INVALID_ARG.
+ * _read_grid_cells: cells_out [ny * nx] of map `map`, read back from the device. */
+typedef struct ccv_mppi_grid { double origin_x, origin_y, resolution; float outside; int32_t nx, ny; const float* cells; } ccv_mppi_grid;
+int ccv_mppi_batch_set_grids(ccv_mppi_batch* b, const ccv_mppi_grid* maps, int32_t n_maps, const int32_t* map_of, const double* weight);
+int ccv_mppi_batch_get_grids(ccv_mppi_batch* b, ccv_mppi_grid* maps, int32_t max_maps, int32_t* n_maps, int32_t* map_of, double* weight);
+int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* b, int32_t map, float* cells_out);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
