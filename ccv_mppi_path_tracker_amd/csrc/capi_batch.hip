@@ -9,27 +9,36 @@ namespace {
 // instance b's configuration: its own under per-instance parameters, the creation configuration otherwise
 const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->cfg; }
 
-// CCV_MPPI_BATCH_KERNEL_* of a launch (ccv_mppi_batch_last_kernel)
+// whether the obstacle kernels run (BatchForm::Obst and up): static discs (ccv_mppi_batch_set_obstacles) or the fleet term
+// (_resident_set_fleet); the obst_* vectors and d_obst exist then
+bool obst_on(const ccv_mppi_batch* bh) { return bh->obst || bh->fleet; }
+
+// whether the discs have velocities of their own (BatchForm::Moving without a grid): static ones
+// (ccv_mppi_batch_set_obstacle_velocities) or fleet prediction; d_obst_v exists then and every row of it is defined
+bool moving_on(const ccv_mppi_batch* bh) { return obst_on(bh) && (bh->moving || bh->fleet_pred); }
+
+// the rung of the kernels the handle's next launch runs (BatchForm, mppi_kernels.h): the highest one whose addition is on.  Shifted
+// weights alone need the parameter table, B copies of the creation configuration.
+BatchForm batch_form(const ccv_mppi_batch* bh) {
+    return bh->grid                      ? BatchForm::Grid
+           : moving_on(bh)               ? BatchForm::Moving
+           : obst_on(bh)                 ? BatchForm::Obst
+           : bh->varied || bh->min_shift ? BatchForm::Varied
+                                         : BatchForm::Batch;
+}
+
+// whether the kernels read the parameter table
+bool uses_table(const ccv_mppi_batch* bh) { return batch_form(bh) >= BatchForm::Varied; }
+
+// CCV_MPPI_BATCH_KERNEL_* of a launch (ccv_mppi_batch_last_kernel): every rung up to the plan's sets its bit
 int batch_kernel_code(const RolloutPlan& p) {
     const int family = p.family == KernelFamily::Plain     ? CCV_MPPI_BATCH_KERNEL_PLAIN
                        : p.family == KernelFamily::OneWave ? CCV_MPPI_BATCH_KERNEL_ONE_WAVE
                                                            : CCV_MPPI_BATCH_KERNEL_FOUR_WAVE;
-    return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0) |
-           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0) | (p.obst ? CCV_MPPI_BATCH_KERNEL_OBST : 0) |
-           (p.moving ? CCV_MPPI_BATCH_KERNEL_MOVING : 0) | (p.grid ? CCV_MPPI_BATCH_KERNEL_GRID : 0);
+    return family | (p.wide ? CCV_MPPI_BATCH_KERNEL_WIDE : 0) | (p.form >= BatchForm::Varied ? CCV_MPPI_BATCH_KERNEL_VARIED : 0) |
+           (p.shift ? CCV_MPPI_BATCH_KERNEL_SHIFT : 0) | (p.form >= BatchForm::Obst ? CCV_MPPI_BATCH_KERNEL_OBST : 0) |
+           (p.form >= BatchForm::Moving ? CCV_MPPI_BATCH_KERNEL_MOVING : 0) | (p.form >= BatchForm::Grid ? CCV_MPPI_BATCH_KERNEL_GRID : 0);
 }
-
-// whether the kernels read the parameter table: per-instance parameters, or shifted weights or obstacles (B copies of cfg in
-// the table then), or the fleet term, or occupancy grids
-bool uses_table(const ccv_mppi_batch* bh) { return bh->varied || bh->min_shift || bh->obst || bh->fleet || bh->grid; }
-
-// whether the obstacle kernels run: static discs (ccv_mppi_batch_set_obstacles) or the fleet term (_resident_set_fleet); the
-// obst_* vectors and d_obst exist then
-bool obst_on(const ccv_mppi_batch* bh) { return bh->obst || bh->fleet; }
-
-// whether the MOVING kernels run: static velocities (ccv_mppi_batch_set_obstacle_velocities) or fleet prediction; d_obst_v exists
-// then and every row of it is defined
-bool moving_on(const ccv_mppi_batch* bh) { return obst_on(bh) && (bh->moving || bh->fleet_pred); }
 
 // the velocity table [B][32][2] on the device: the static rows from the host copy (zeros without one), every other row zero (the
 // fleet's rows are the prologue's to write, every tick).  The caller has flushed and synchronised.
@@ -103,6 +112,9 @@ int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
     return CCV_MPPI_OK;
 }
 
+// the table again from the handle's present state: every setter but set_params and set_min_shift ends here
+int refresh_params(ccv_mppi_batch* bh) { return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr); }
+
 int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
                      const double* yaw_ref0, const uint64_t* seed) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
@@ -168,7 +180,7 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
 // of the fused kernels waits in bh->fin for the next tick's prologue (k_finalize_advance_batch) or for batch_flush
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool defer) {
     const int B = bh->B;
-    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, bh->varied, bh->min_shift, obst_on(bh), moving_on(bh), bh->grid);
+    const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, batch_form(bh), bh->min_shift);
     const bool plain = plan.family == KernelFamily::Plain;
     A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
@@ -464,7 +476,7 @@ int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const in
         bh->obst_xyr.clear();
         bh->obst_n.clear();
         bh->obst_w.clear();
-        if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (null / 0 / 0 in every row)
+        if (uses_table(bh)) return refresh_params(bh);   // (null / 0 / 0 in every row)
         return CCV_MPPI_OK;
     }
     // (off under the fleet term: the static discs go; table, weights and fleet stay)
@@ -479,7 +491,7 @@ int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const in
     if (!off) bh->obst_w.assign(weight, weight + B);
     bh->obst = !off;
     if (bh->fleet) HIP_TRY(bh, hipMemcpy(bh->d_fleet_nstatic, bh->obst_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
-    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+    return refresh_params(bh);
 }
 
 int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* bh, double* xyr, int32_t* n, int32_t max_n, double* weight) {
@@ -547,7 +559,7 @@ int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int3
         bh->grid_offset.clear();
         bh->grid_map_of.clear();
         bh->grid_w.clear();
-        if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (null in every row)
+        if (uses_table(bh)) return refresh_params(bh);   // (null in every row)
         return CCV_MPPI_OK;
     }
     // the cells of all maps are one allocation, sized by the maps: a new set is a new allocation, the old one goes when the new
@@ -591,7 +603,7 @@ int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int3
     bh->grid_map_of.assign(map_of, map_of + B);
     bh->grid_w.assign(weight, weight + B);
     bh->grid = true;
-    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+    return refresh_params(bh);
 }
 
 int ccv_mppi_batch_get_grids(ccv_mppi_batch* bh, ccv_mppi_grid* maps, int32_t max_maps, int32_t* n_maps, int32_t* map_of, double* weight) {
@@ -649,7 +661,7 @@ int ccv_mppi_batch_set_obstacle_velocities(ccv_mppi_batch* bh, const double* vxy
         if (bh->fleet_pred) {
             if (int rc = upload_velocities(bh)) return rc;
         }
-        return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+        return refresh_params(bh);
     }
     // rows at or past an instance's count (the fleet term's rows among them) are zero
     std::vector<double> rows((size_t)B * M * 2, 0.0);
@@ -659,7 +671,7 @@ int ccv_mppi_batch_set_obstacle_velocities(ccv_mppi_batch* bh, const double* vxy
     bh->obst_vxy.swap(rows);
     bh->moving = true;
     if (int rc = upload_velocities(bh)) return rc;
-    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+    return refresh_params(bh);
 }
 
 int ccv_mppi_batch_get_obstacle_velocities(ccv_mppi_batch* bh, double* vxy, int32_t max_n) {
@@ -991,7 +1003,7 @@ int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, 
             bh->obst_n.clear();
             bh->obst_w.clear();
         }
-        if (uses_table(bh)) return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);   // (the static counts again)
+        if (uses_table(bh)) return refresh_params(bh);   // (the static counts again)
         return CCV_MPPI_OK;
     }
     if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, (size_t)B * M * 3 * sizeof(double)));
@@ -1021,7 +1033,7 @@ int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, 
     bh->fleet_range = range;
     bh->fleet_maxn = max_neighbours;
     bh->fleet = true;
-    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+    return refresh_params(bh);
 }
 
 int ccv_mppi_batch_resident_get_fleet(ccv_mppi_batch* bh, double* radius, double* range, int32_t* max_neighbours) {
@@ -1070,7 +1082,7 @@ int ccv_mppi_batch_set_fleet_prediction(ccv_mppi_batch* bh, int32_t on) {
         if (int rc = upload_velocities(bh)) return rc;       // every row defined: the static rows, zero elsewhere
         if (int rc = fleet_zero_velocities(bh)) return rc;   // no robot has moved yet
     } else if (int rc = clear_fleet_velocity_rows(bh)) return rc;
-    return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr);
+    return refresh_params(bh);
 }
 
 int ccv_mppi_batch_get_fleet_prediction(const ccv_mppi_batch* bh) { return bh ? (bh->fleet_pred ? 1 : 0) : CCV_MPPI_ERR_INVALID_ARG; }

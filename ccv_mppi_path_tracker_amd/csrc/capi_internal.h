@@ -312,16 +312,14 @@ inline bool has_wide_form(const KernelChoice& k, const int mode) {
 }
 // The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
 // (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
-// shift (a batch in shifted-weight mode), obst (a batch with obstacles): always with the per-instance-parameter kernels.
-// moving (a batch whose discs have velocities): always an obstacle plan.  grid (a batch with occupancy grids): always a moving plan.
-inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const bool varied,
-                             const bool shift = false, const bool obst = false, const bool moving = false, const bool grid = false) {
+// form: what the launch serves (BatchForm, mppi_kernels.h; a batch handle's: batch_form(), capi_batch.hip); shift (a batch in
+// shifted-weight mode): with a form from Varied up.
+inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const BatchForm form,
+                             const bool shift) {
     KernelFamily f = trig == kTrigUnsafe ? KernelFamily::Plain : family_of(k, mode);
-    // (the one-wave full-body kernel has no grid form -- it has no register left, DESIGN.md section 10h: the four-wave kernel
-    //  runs such a plan, at any number of workgroups)
-    if (grid && model == CCV_MPPI_FULL_BODY && f == KernelFamily::OneWave) f = KernelFamily::FourWave;
-    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, varied || shift || obst || moving || grid, shift,
-                       obst || moving || grid, moving || grid, grid, k.lds_window != 0};
+    // (the four-wave kernel runs a plan whose form the one-wave kernel lacks, at any number of workgroups)
+    if (f == KernelFamily::OneWave && !has_one_wave_form(model, form)) f = KernelFamily::FourWave;
+    return RolloutPlan{f, model, mode, f != KernelFamily::Plain && trig == kTrigWide, batch, form, shift, k.lds_window != 0};
 }
 
 RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, int mode);   // a single handle's

@@ -219,7 +219,7 @@ int fast_trig_safe(const Core* h, const ccv_mppi_config& c, const RolloutArgs& A
 
 // the plan of a single handle's launch
 RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, const int mode) {
-    return make_plan(*h, h->cfg.model, mode, fast_trig_safe(h, h->cfg, A, mode, has_wide_form(*h, mode)), 0, false);
+    return make_plan(*h, h->cfg.model, mode, fast_trig_safe(h, h->cfg, A, mode, has_wide_form(*h, mode)), 0, BatchForm::Single, false);
 }
 
 // mode: MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h).  A timed fused launch carries its events on the dispatch

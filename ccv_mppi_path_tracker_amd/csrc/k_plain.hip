@@ -7,7 +7,7 @@ namespace ccv {
 template <int MODEL>
 static void launch_plain_model(const RolloutPlan& p, const LaunchAt& at, const RolloutArgs& A, const Window& W) {
     const dim3 grid = blocks_plain(A, p.batch), block(kBlock);
-    if (p.batch) launch_at(k_rollout_cost<MODEL, SRC_PHILOX, true, true>, grid, block, at, A, W);
+    if (p.batch) launch_at(k_rollout_cost<MODEL, SRC_PHILOX, true, BatchForm::Batch>, grid, block, at, A, W);
     else if (p.mode == MODE_FUSED) {   // device noise; the stage-wise modes read the controls from the buffer
         if (p.lds_window) launch_at(k_rollout_cost<MODEL, SRC_PHILOX, true>, grid, block, at, A, W);
         else launch_at(k_rollout_cost<MODEL, SRC_PHILOX, false>, grid, block, at, A, W);

@@ -12,13 +12,13 @@ static void launch_r4_model(const RolloutPlan& p, bool tail, const LaunchAt& at,
     if (p.batch) {
         if constexpr (MODEL == CCV_MPPI_DIFF_DRIVE) {
             if (p.wide) {
-                if (tail) launch_at(k_rollout_r4<MODEL, MODE_FUSED, true, true, true>, grid, block, at, A, W);
-                else launch_at(k_rollout_r4<MODEL, MODE_FUSED, true, false, true>, grid, block, at, A, W);
+                if (tail) launch_at(k_rollout_r4<MODEL, MODE_FUSED, true, true, BatchForm::Batch>, grid, block, at, A, W);
+                else launch_at(k_rollout_r4<MODEL, MODE_FUSED, true, false, BatchForm::Batch>, grid, block, at, A, W);
                 return;
             }
         }
-        if (tail) launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, true, true>, grid, block, at, A, W);
-        else launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, false, true>, grid, block, at, A, W);
+        if (tail) launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, true, BatchForm::Batch>, grid, block, at, A, W);
+        else launch_at(k_rollout_r4<MODEL, MODE_FUSED, false, false, BatchForm::Batch>, grid, block, at, A, W);
         return;
     }
     if constexpr (MODEL == CCV_MPPI_DIFF_DRIVE) {

@@ -118,6 +118,17 @@ struct alignas(64) GridRow {
     float outside;
 };
 static_assert(sizeof(GridRow) == 64, "one 64-byte line per instance");
+// What a rollout kernel serves, as one ordered value: every rung is the one before it plus one thing, so a kernel (template
+// parameter FORM of k_rollout_r4, k_rollout_solo, k_rollout_cost), a launch (RolloutPlan::form, mppi_launch.h) and a handle
+// (batch_form(), capi_batch.hip) each name a rung, and "has X" is FORM >= X.
+//   Single  a single handle: no records
+//   Batch   + the instances' records (BatchHead, batch_view below)
+//   Varied  + the per-instance parameter table (BatchParams above)
+//   Obst    + the instance's disc obstacles (obst_stage, obst_term below)
+//   Moving  + the discs' velocities (obst_stage_moving, obst_term_moving below)
+//   Grid    + the instance's occupancy grid (GridRow above, grid_tap below)
+// The shifted weights (SHIFT, pc_shifted_weight in mppi_rollout_pc.h) are the one independent bit: on any rung from Varied up.
+enum class BatchForm : int { Single, Batch, Varied, Obst, Moving, Grid };
 constexpr int kBatchHeadDoubles = 16;
 __host__ __device__ constexpr int batch_record_doubles(int H) { return kBatchHeadDoubles + ((3 * H + 7) & ~7); }
 
@@ -581,14 +592,11 @@ __device__ __forceinline__ void window_min(const double (&px)[kTU], const double
 // BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters;
 // OBST (on VARIED): with the instance's disc obstacles (obst_term); MOVING (on OBST): the discs move (obst_term_moving);
 // GRID (on MOVING): the instance's occupancy grid, read in the state loop where x and y are stored (grid_tap)
-template <int MODEL, int SRC, bool LDSWIN, bool BATCH = false, bool VARIED = false, bool OBST = false, bool MOVING = false,
-          bool GRID = false>
+template <int MODEL, int SRC, bool LDSWIN, BatchForm FORM = BatchForm::Single>
 __global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
+    constexpr bool BATCH = FORM >= BatchForm::Batch, VARIED = FORM >= BatchForm::Varied, OBST = FORM >= BatchForm::Obst,
+                   MOVING = FORM >= BatchForm::Moving, GRID = FORM >= BatchForm::Grid;
     static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
-    static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
-    static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
-    static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
-    static_assert(!GRID || MOVING, "the grid forms are built on the moving-disc kernels");
     constexpr int UD = udim_of(MODEL);
     __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
     __shared__ double s_c[LDSWIN ? kMaxH : 1];

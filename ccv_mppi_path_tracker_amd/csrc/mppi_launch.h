@@ -1,9 +1,11 @@
 // Launching a rollout kernel.  Which kernel a launch runs is a value, RolloutPlan; launch_rollout() (mppi_launch.hip) is a
 // switch over it.  Every family is a translation unit of its own (k_r4.hip, k_r3.hip, k_pc.hip, k_r4_fb.hip, k_pc_fb.hip,
-// k_solo.hip, k_solo_fb.hip, k_plain.hip; k_batch.hip, k_batch_varied.hip, k_batch_shift.hip, k_batch_obst.hip, k_batch_obst_shift.hip, k_batch_moving.hip, k_batch_moving_shift.hip, k_batch_grid.hip, k_batch_grid_shift.hip: batch forms): hipcc spends over a minute on all
-// instantiations in one file, the units compile side by side (build.py), and an instantiation placed beside others can change
-// the code generated for those.  The C ABI picks the family at create (select_kernels(), ccv_mppi_capi.hip) and makes the plan
-// of each launch from it (make_plan(), capi_internal.h).
+// k_solo.hip, k_solo_fb.hip, k_plain.hip), and so is every rung of the batch handles' BatchForm (mppi_kernels.h) with and without
+// shifted weights (k_batch.hip; k_batch_varied.hip, k_batch_shift.hip; k_batch_obst.hip, k_batch_obst_shift.hip;
+// k_batch_moving.hip, k_batch_moving_shift.hip; k_batch_grid.hip, k_batch_grid_shift.hip -- one launcher, k_batch_form.h, which
+// each of them names once): hipcc spends over a minute on all instantiations in one file, the units compile side by side
+// (build.py), and an instantiation placed beside others can change the code generated for those.  The C ABI picks the family at
+// create (select_kernels(), ccv_mppi_capi.hip) and makes the plan of each launch from it (make_plan(), capi_internal.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -29,13 +31,14 @@ struct RolloutPlan {
     int mode;          // MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h)
     bool wide;         // diff drive, fused, four- or one-wave: a turn per step beyond pi/4 -> sin / cos of every heading in full
     int batch;         // instances of a batch handle's launch (A.frame = their records, batch_view); 0 = a single handle
-    bool varied;       // batch: per-instance parameters (the records' heads point at the parameter table)
-    bool shift;        // batch, varied: shifted weights (ccv_mppi_batch_set_min_shift; the four- and one-wave kernels' SHIFT forms)
-    bool obst;         // batch, varied: the disc-obstacle term (ccv_mppi_batch_set_obstacles; the OBST forms of all three families)
-    bool moving;       // batch, obst: the discs move (ccv_mppi_batch_set_obstacle_velocities; the MOVING forms of all three families)
-    bool grid;         // batch, moving: the occupancy-grid term (ccv_mppi_batch_set_grids; the GRID forms of all three families)
+    BatchForm form;    // what the kernel serves (mppi_kernels.h): Single if and only if batch == 0
+    bool shift;        // form >= Varied: shifted weights (ccv_mppi_batch_set_min_shift; the four- and one-wave kernels' SHIFT forms)
     bool lds_window;   // Plain: the window from LDS (false: CCV_MPPI_WINDOW=scalar)
 };
+
+// whether the one-wave kernel of a model has the form: the full-body kernel has no register left for the grid term (DESIGN.md
+// section 10h; the kernel's own assert, mppi_rollout_solo.h).  make_plan() sends such a plan to the four-wave kernel.
+constexpr bool has_one_wave_form(const int model, const BatchForm form) { return !(model == CCV_MPPI_FULL_BODY && form >= BatchForm::Grid); }
 
 // K, H, ... come from the arguments themselves.  Plain: device noise in the fused iteration, else the controls of the buffer.
 // Built: batches -- Plain, FourWave, OneWave, fused; ThreeWave -- not full body; OneWave -- fused.

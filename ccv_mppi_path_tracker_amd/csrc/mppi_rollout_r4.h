@@ -244,20 +244,19 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // gathers are issued before its stores and summed after them, so their latency passes under the issue of the block's 32 to 56
 // stores.  The lane's sum reaches the epilogue in sh.cost[3], the store wave's slot of the cost parts, which is 0.0 otherwise:
 // the GRID epilogue adds a literal 0.0 in its place (the same bits) and then the grid term, one FMA, last.  No new LDS.
-template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false,
-          bool OBST = false, bool MOVING = false, bool GRID = false>
+// FORM (BatchForm, mppi_kernels.h) names the rung; BATCH .. GRID below are "FORM is at least that rung".
+template <int MODEL, int MODE, bool WIDE = false, bool TAIL = false, BatchForm FORM = BatchForm::Single, bool SHIFT = false>
 __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4) void k_rollout_r4(const RolloutArgs Ak, const Window Wk) {
+    constexpr bool BATCH = FORM >= BatchForm::Batch, VARIED = FORM >= BatchForm::Varied, OBST = FORM >= BatchForm::Obst,
+                   MOVING = FORM >= BatchForm::Moving, GRID = FORM >= BatchForm::Grid;
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
     constexpr int UD = udim_of(MODEL);
     static_assert(!WIDE || (MODEL == CCV_MPPI_DIFF_DRIVE && MODE == MODE_FUSED), "the wide-turn form exists for the fused diff-drive iteration");
     static_assert(!TAIL || MODE == MODE_FUSED, "the stage-wise modes carry the masked producer anyway");
     static_assert(!BATCH || MODE == MODE_FUSED, "batch handles run the fused iteration only");
-    static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
-    static_assert(!OBST || (VARIED && MODE == MODE_FUSED), "the obstacle term is built on the per-instance-parameter kernels");
-    static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
-    static_assert(!GRID || MOVING, "the grid forms are built on the moving-disc kernels");
+    static_assert(!OBST || MODE == MODE_FUSED, "the obstacle term is the fused iteration's");
     __shared__ R4Shared<MODEL> sh;
     ObstLds* obst_lds = nullptr;   // (an array of its own: R4Shared, and with it every other kernel's LDS, stays as it is)
     ObstMovLds* obst_mov = nullptr;

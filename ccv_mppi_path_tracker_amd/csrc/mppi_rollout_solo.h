@@ -30,15 +30,13 @@ struct SoloShared {
 // obst_term_moving); GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_kernels.h), looked up by the producer where
 // it stores the block's absolute states; the block's gathers are summed after its distance phase, under which their latency
 // passes.  The grid term is the last added to the cost.  Diff drive and steering only.
-template <int MODEL, int MODE, bool WIDE = false, bool BATCH = false, bool VARIED = false, bool SHIFT = false, bool OBST = false,
-          bool MOVING = false, bool GRID = false>
+// FORM (BatchForm, mppi_kernels.h) names the rung; BATCH .. GRID below are "FORM is at least that rung".
+template <int MODEL, int MODE, bool WIDE = false, BatchForm FORM = BatchForm::Single, bool SHIFT = false>
 __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArgs Ak, const Window Wk) {
+    constexpr bool BATCH = FORM >= BatchForm::Batch, VARIED = FORM >= BatchForm::Varied, OBST = FORM >= BatchForm::Obst,
+                   MOVING = FORM >= BatchForm::Moving, GRID = FORM >= BatchForm::Grid;
     static_assert(MODE == MODE_FUSED, "the stage-wise modes use k_rollout_pc");
-    static_assert(!VARIED || BATCH, "per-instance parameters are a batch handle's");
     static_assert(!SHIFT || VARIED, "the shifted weights are built on the per-instance-parameter kernels");
-    static_assert(!OBST || VARIED, "the obstacle term is built on the per-instance-parameter kernels");
-    static_assert(!MOVING || OBST, "moving discs are a form of the obstacle term");
-    static_assert(!GRID || MOVING, "the grid forms are built on the moving-disc kernels");
     // (the MOVING parent uses all 256 registers without a spill; with the term it spilled two or three whether the sum was held
     //  in registers or in LDS -- DESIGN.md section 10h -- so full-body grid plans run the four-wave form, make_plan)
     static_assert(!GRID || MODEL != CCV_MPPI_FULL_BODY, "the one-wave full-body kernel has no grid form");
