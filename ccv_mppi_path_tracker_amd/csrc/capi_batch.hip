@@ -1,34 +1,11 @@
-// C ABI, batch handles: B independent problems in one launch (ccv_mppi_batch_*; struct ccv_mppi_batch: capi_internal.h),
-// their device-resident closed loop included.  The plumbing is the single handle's (ccv_mppi_capi.hip), on the core.
+// C ABI, batch handles: B independent problems in one launch (ccv_mppi_batch_*; struct ccv_mppi_batch: capi_internal.h) -- what
+// a tick runs and what reads its results, the device-resident closed loop included; what configures the next launch is in
+// capi_batch_config.hip.  The plumbing is the single handle's (ccv_mppi_capi.hip), on the core.
 #include <new>
 
 #include "capi_internal.h"
 
 namespace {
-
-// instance b's configuration: its own under per-instance parameters, the creation configuration otherwise
-const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->cfg; }
-
-// whether the obstacle kernels run (BatchForm::Obst and up): static discs (ccv_mppi_batch_set_obstacles) or the fleet term
-// (_resident_set_fleet); the obst_* vectors and d_obst exist then
-bool obst_on(const ccv_mppi_batch* bh) { return bh->obst || bh->fleet; }
-
-// whether the discs have velocities of their own (BatchForm::Moving without a grid): static ones
-// (ccv_mppi_batch_set_obstacle_velocities) or fleet prediction; d_obst_v exists then and every row of it is defined
-bool moving_on(const ccv_mppi_batch* bh) { return obst_on(bh) && (bh->moving || bh->fleet_pred); }
-
-// the rung of the kernels the handle's next launch runs (BatchForm, mppi_kernels.h): the highest one whose addition is on.  Shifted
-// weights alone need the parameter table, B copies of the creation configuration.
-BatchForm batch_form(const ccv_mppi_batch* bh) {
-    return bh->grid                      ? BatchForm::Grid
-           : moving_on(bh)               ? BatchForm::Moving
-           : obst_on(bh)                 ? BatchForm::Obst
-           : bh->varied || bh->min_shift ? BatchForm::Varied
-                                         : BatchForm::Batch;
-}
-
-// whether the kernels read the parameter table
-bool uses_table(const ccv_mppi_batch* bh) { return batch_form(bh) >= BatchForm::Varied; }
 
 // CCV_MPPI_BATCH_KERNEL_* of a launch (ccv_mppi_batch_last_kernel): every rung up to the plan's sets its bit
 int batch_kernel_code(const RolloutPlan& p) {
@@ -40,81 +17,6 @@ int batch_kernel_code(const RolloutPlan& p) {
            (p.form >= BatchForm::Moving ? CCV_MPPI_BATCH_KERNEL_MOVING : 0) | (p.form >= BatchForm::Grid ? CCV_MPPI_BATCH_KERNEL_GRID : 0);
 }
 
-// the velocity table [B][32][2] on the device: the static rows from the host copy (zeros without one), every other row zero (the
-// fleet's rows are the prologue's to write, every tick).  The caller has flushed and synchronised.
-int upload_velocities(ccv_mppi_batch* bh) {
-    const size_t count = (size_t)bh->B * CCV_MPPI_MAX_OBSTACLES * 2;
-    const std::vector<double> zeros(bh->moving ? 0 : count, 0.0);
-    if (!bh->d_obst_v) HIP_TRY(bh, hipMalloc(&bh->d_obst_v, count * sizeof(double)));
-    HIP_TRY(bh, hipMemcpy(bh->d_obst_v, bh->moving ? bh->obst_vxy.data() : zeros.data(), count * sizeof(double), hipMemcpyHostToDevice));
-    return CCV_MPPI_OK;
-}
-
-// prediction has just gone off: the fleet's rows of the velocity table still hold what the last prologue with prediction wrote.
-// With static velocities the MOVING kernels go on reading them, beside disc rows the prologue now writes without a velocity, so
-// the table is written again (the static rows, zero elsewhere).  Without static velocities nothing reads the table until
-// upload_velocities writes all of it.  The caller has flushed and synchronised.
-int clear_fleet_velocity_rows(ccv_mppi_batch* bh) { return bh->moving ? upload_velocities(bh) : CCV_MPPI_OK; }
-
-// both halves of the fleet's velocity snapshot zero: no robot has moved yet
-int fleet_zero_velocities(ccv_mppi_batch* bh) {
-    const size_t bytes = (size_t)bh->B * 4 * sizeof(double);
-    if (!bh->d_fleet_v) HIP_TRY(bh, hipMalloc(&bh->d_fleet_v, bytes));
-    HIP_TRY(bh, hipMemset(bh->d_fleet_v, 0, bytes));
-    return CCV_MPPI_OK;
-}
-
-// the parameter table [B] on the device from B configurations (null: B copies of the creation configuration).  The caller has
-// flushed and synchronised: a queued rollout or prologue may still read the old table.
-int upload_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
-    const int B = bh->B;
-    // occupancy grids run the MOVING kernels: discs that have no velocities of their own (no static ones, no prediction) get a
-    // table of zeros, over which the moving term equals the static one bit for bit.  Every setter ends here, so the table
-    // follows every change of the discs, the fleet term and prediction.
-    const bool grid_moving = bh->grid && obst_on(bh) && !moving_on(bh);
-    if (grid_moving) {
-        if (int rc = upload_velocities(bh)) return rc;
-    }
-    std::vector<BatchParams> rows((size_t)B);
-    for (int b = 0; b < B; ++b) {
-        RolloutArgs A;
-        std::memset(&A, 0, sizeof(A));
-        fill_params(cfgs ? cfgs[b] : bh->cfg, bh->fast_clamp_allowed, A);   // (per instance: the clamp form of its own sigma and bounds)
-        BatchParams& P = rows[(size_t)b];
-        std::memset(&P, 0, sizeof(P));
-        P.sigma = A.sigma;
-        P.lambda = A.lambda;
-        P.v_ref = A.v_ref;
-        for (int d = 0; d < 5; ++d) {
-            P.umin[d] = A.umin[d];
-            P.umax[d] = A.umax[d];
-        }
-        P.w_path = A.w_path;
-        P.w_v = A.w_v;
-        P.w_zmp = A.w_zmp;
-        P.w_rollv = A.w_rollv;
-        P.w_back = A.w_back;
-        P.w_yaw = A.w_yaw;
-        P.fast_clamp = A.fast_clamp;
-        // (every upload keeps the obstacle fields: ccv_mppi_batch_set_obstacles; under the fleet term n_obst is the static count
-        // until the next resident tick's prologue writes the tick's own)
-        if (obst_on(bh)) {
-            P.n_obst = bh->obst_n[(size_t)b];
-            P.obst = bh->d_obst + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 3;
-            P.w_obs = bh->obst_w[(size_t)b];
-            if (moving_on(bh) || grid_moving) P.obst_v = bh->d_obst_v + (size_t)b * CCV_MPPI_MAX_OBSTACLES * 2;
-        }
-        // (without discs a GRID kernel sees n_obst = 0 and reads neither table)
-        if (bh->grid && bh->grid_map_of[(size_t)b] >= 0) P.grid = bh->d_grid_rows + b;
-    }
-    if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
-    HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
-    return CCV_MPPI_OK;
-}
-
-// the table again from the handle's present state: every setter but set_params and set_min_shift ends here
-int refresh_params(ccv_mppi_batch* bh) { return upload_params(bh, bh->varied ? bh->cfgs.data() : nullptr); }
-
 int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
                      const double* yaw_ref0, const uint64_t* seed) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
@@ -125,9 +27,6 @@ int batch_check_args(ccv_mppi_batch* bh, const double* x0, const double* dt, con
 }
 
 int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, int trig, bool defer);
-
-// a deferred resident update (batch_launch) is launched now
-int batch_flush(ccv_mppi_batch* bh) { return flush_finalize(bh); }
 
 // fast_trig_safe of instance b (its own clamp bounds), folded into the batch's: the worst instance decides
 int batch_trig(const ccv_mppi_batch* bh, const int b, const RolloutArgs& A, const int trig) {
@@ -263,13 +162,6 @@ int batch_check_read(ccv_mppi_batch* bh, int32_t instance, const void* out) {
     if (!bh->have_result) return fail(bh, CCV_MPPI_ERR_STATE, "no iteration yet");
     return batch_flush(bh);
 }
-
-// both halves of the fleet's position table from xy [B][2] (the stream is idle: the caller has synchronised)
-int fleet_write_positions(ccv_mppi_batch* bh, const std::vector<double>& xy) {
-    const size_t half = (size_t)bh->B * 2;
-    for (int h = 0; h < 2; ++h) HIP_TRY(bh, hipMemcpy(bh->d_fleet_xy + h * half, xy.data(), half * sizeof(double), hipMemcpyHostToDevice));
-    return CCV_MPPI_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -326,15 +218,12 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     (void)hipSetDevice(bh->cfg.device);
     if (bh->stream) (void)batch_flush(bh);
     release_buffers(bh);
-    for (int s = 0; s < ccv_mppi_batch::kRecSlots; ++s) {
-        if (bh->rec_ev[s]) (void)hipEventDestroy(bh->rec_ev[s]);
-        if (bh->h_rec[s]) (void)hipHostFree(bh->h_rec[s]);
-    }
-    void* bufs[] = {bh->d_rec,  bh->d_rframe, bh->d_inst,     bh->d_rpath,        bh->d_rtrace,       bh->d_params,
-                    bh->d_cmin, bh->d_obst,   bh->d_fleet_xy, bh->d_fleet_radius, bh->d_fleet_nstatic, bh->d_obst_v, bh->d_fleet_v,
-                    bh->d_grid_rows, bh->d_grid_cells};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
+    bh->BatchRecords::release();
+    bh->BatchResident::release();
+    bh->ParamTable::release();
+    bh->Discs::release();
+    bh->Grids::release();
+    bh->Fleet::release();
     delete bh;
     return CCV_MPPI_OK;
 }
@@ -372,326 +261,6 @@ int ccv_mppi_batch_get_nominal(ccv_mppi_batch* bh, double* u) {
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(bh, hipMemcpyAsync(u, bh->d_nominal, (size_t)bh->B * bh->R * sizeof(double), hipMemcpyDeviceToHost, bh->stream));
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));
-    return CCV_MPPI_OK;
-}
-
-// ---- per-instance parameters ------------------------------------------------------------------------------------------
-
-int ccv_mppi_batch_set_params(ccv_mppi_batch* bh, const ccv_mppi_config* cfgs) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
-    if (!cfgs) {   // back to the creation configuration; the shared kernels, or in shifted-weight mode B copies in the table
-        if (int rc = batch_flush(bh)) return rc;
-        if (bh->min_shift || obst_on(bh) || bh->grid) {
-            HIP_TRY(bh, hipStreamSynchronize(bh->stream));
-            if (int rc = upload_params(bh, nullptr)) return rc;
-        }
-        bh->varied = false;
-        bh->cfgs.clear();
-        return CCV_MPPI_OK;
-    }
-    // the fields that fix the layout, the kernel family and the compile-time shape stay the creation configuration's; every
-    // check comes before anything changes
-    const ccv_mppi_config& c0 = bh->cfg;
-    for (int b = 0; b < B; ++b) {
-        const ccv_mppi_config& c = cfgs[b];
-        const char* field = c.abi_version != c0.abi_version       ? "abi_version"
-                            : c.model != c0.model                 ? "model"
-                            : c.num_samples != c0.num_samples     ? "num_samples"
-                            : c.horizon != c0.horizon             ? "horizon"
-                            : c.sample_offset != c0.sample_offset ? "sample_offset"
-                            : c.device != c0.device               ? "device"
-                            : c.flags != c0.flags                 ? "flags"
-                                                                  : nullptr;
-        if (field) {
-            char msg[128];
-            std::snprintf(msg, sizeof(msg), "set_params: instance %d: %s differs from the creation configuration", b, field);
-            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, msg);
-        }
-    }
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the old table)
-    if (int rc = upload_params(bh, cfgs)) return rc;
-    bh->cfgs.assign(cfgs, cfgs + B);
-    bh->varied = true;
-    return CCV_MPPI_OK;
-}
-
-// ---- shifted weights -----------------------------------------------------------------------------------------------------
-
-int ccv_mppi_batch_set_min_shift(ccv_mppi_batch* bh, int32_t on) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const bool want = on != 0;
-    if (want == bh->min_shift) return CCV_MPPI_OK;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;   // (the pending update is the old mode's)
-    if (want && !uses_table(bh)) {             // the SHIFT kernels read the table: B copies of the creation configuration
-        HIP_TRY(bh, hipStreamSynchronize(bh->stream));
-        if (int rc = upload_params(bh, nullptr)) return rc;
-    }
-    bh->min_shift = want;
-    return CCV_MPPI_OK;
-}
-
-int ccv_mppi_batch_get_min_shift(const ccv_mppi_batch* bh) { return bh ? (bh->min_shift ? 1 : 0) : CCV_MPPI_ERR_INVALID_ARG; }
-
-// ---- disc obstacles -------------------------------------------------------------------------------------------------------
-
-int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const int32_t* n, int32_t max_n, const double* weight) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    const bool off = !xyr || max_n == 0;
-    // every check comes before anything changes
-    if (!off) {
-        if (max_n < 0 || max_n > M) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: max_n outside [0, CCV_MPPI_MAX_OBSTACLES]");
-        if (!n || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-        for (int b = 0; b < B; ++b) {
-            if (!(weight[b] >= 0.0) || !std::isfinite(weight[b]))
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a weight is negative or not finite");
-            if (n[b] < 0 || n[b] > max_n) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a count outside [0, max_n]");
-            for (int j = 0; j < n[b]; ++j) {
-                const double* o = xyr + ((size_t)b * max_n + j) * 3;
-                if (!std::isfinite(o[0]) || !std::isfinite(o[1]))
-                    return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a centre is not finite");
-                if (!(o[2] >= 0.0) || !std::isfinite(o[2]))
-                    return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacles: a radius is negative or not finite");
-            }
-        }
-    }
-    if (off && !bh->obst) return CCV_MPPI_OK;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table and discs)
-    // (a new list has no velocities until it is given some; without a list there are none)
-    bh->moving = false;
-    bh->obst_vxy.clear();
-    if (bh->fleet_pred) {   // (the static rows stand still again)
-        if (int rc = upload_velocities(bh)) return rc;
-    }
-    if (off && !bh->fleet) {
-        bh->obst = false;
-        bh->obst_xyr.clear();
-        bh->obst_n.clear();
-        bh->obst_w.clear();
-        if (uses_table(bh)) return refresh_params(bh);   // (null / 0 / 0 in every row)
-        return CCV_MPPI_OK;
-    }
-    // (off under the fleet term: the static discs go; table, weights and fleet stay)
-    std::vector<double> rows((size_t)B * M * 3, 0.0);
-    for (int b = 0; b < B && !off; ++b)
-        for (int j = 0; j < n[b]; ++j) std::memcpy(&rows[((size_t)b * M + j) * 3], xyr + ((size_t)b * max_n + j) * 3, 3 * sizeof(double));
-    if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, rows.size() * sizeof(double)));
-    HIP_TRY(bh, hipMemcpy(bh->d_obst, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    bh->obst_xyr.swap(rows);
-    if (off) bh->obst_n.assign((size_t)B, 0);
-    else bh->obst_n.assign(n, n + B);
-    if (!off) bh->obst_w.assign(weight, weight + B);
-    bh->obst = !off;
-    if (bh->fleet) HIP_TRY(bh, hipMemcpy(bh->d_fleet_nstatic, bh->obst_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
-    return refresh_params(bh);
-}
-
-int ccv_mppi_batch_get_obstacles(ccv_mppi_batch* bh, double* xyr, int32_t* n, int32_t max_n, double* weight) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    if (max_n < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacles: max_n < 0");
-    const bool on = obst_on(bh);   // (under the fleet term alone: no discs, the fleet's weights)
-    for (int b = 0; b < B && on; ++b)
-        if (xyr && bh->obst_n[(size_t)b] > max_n) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacles: max_n below an instance's count");
-    for (int b = 0; b < B; ++b) {
-        const int nb = on ? bh->obst_n[(size_t)b] : 0;
-        if (n) n[b] = nb;
-        if (weight) weight[b] = on ? bh->obst_w[(size_t)b] : 0.0;
-        if (xyr) {
-            std::memset(xyr + (size_t)b * max_n * 3, 0, (size_t)max_n * 3 * sizeof(double));
-            if (nb > 0) std::memcpy(xyr + (size_t)b * max_n * 3, &bh->obst_xyr[(size_t)b * M * 3], (size_t)nb * 3 * sizeof(double));
-        }
-    }
-    return CCV_MPPI_OK;
-}
-
-// ---- occupancy grids ------------------------------------------------------------------------------------------------------
-
-int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int32_t n_maps, const int32_t* map_of, const double* weight) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
-    const bool off = !maps || n_maps == 0;
-    // every check comes before anything changes
-    size_t total = 0;
-    if (!off) {
-        if (n_maps < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: n_maps < 0");
-        if (!map_of || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-        for (int m = 0; m < n_maps; ++m) {
-            const ccv_mppi_grid& g = maps[m];
-            if (!g.cells) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a map has no cells");
-            if (g.nx < 1 || g.nx > CCV_MPPI_GRID_MAX_DIM || g.ny < 1 || g.ny > CCV_MPPI_GRID_MAX_DIM ||
-                (int64_t)g.nx * g.ny > CCV_MPPI_GRID_MAX_CELLS)
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: nx, ny outside [1, 32768] or nx * ny above 2^26");
-            if (!(g.resolution > 0.0) || !std::isfinite(g.resolution) || !std::isfinite(1.0 / g.resolution))
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a resolution is not positive and finite");
-            if (!std::isfinite(g.origin_x) || !std::isfinite(g.origin_y)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: an origin is not finite");
-            if (!std::isfinite(g.outside)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: an outside value is not finite");
-            const size_t n = (size_t)g.nx * (size_t)g.ny;
-            for (size_t i = 0; i < n; ++i)
-                if (!std::isfinite(g.cells[i])) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a cell is not finite");
-            total += n;
-        }
-        for (int b = 0; b < B; ++b) {
-            if (!(weight[b] >= 0.0) || !std::isfinite(weight[b]))
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a weight is negative or not finite");
-            if (map_of[b] < -1 || map_of[b] >= n_maps) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: map_of outside [-1, n_maps)");
-        }
-    }
-    if (off && !bh->grid) return CCV_MPPI_OK;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table, rows and cells)
-    if (off) {
-        if (bh->d_grid_cells) HIP_TRY(bh, hipFree(bh->d_grid_cells));
-        bh->d_grid_cells = nullptr;
-        bh->grid = false;
-        bh->grid_maps.clear();
-        bh->grid_offset.clear();
-        bh->grid_map_of.clear();
-        bh->grid_w.clear();
-        if (uses_table(bh)) return refresh_params(bh);   // (null in every row)
-        return CCV_MPPI_OK;
-    }
-    // the cells of all maps are one allocation, sized by the maps: a new set is a new allocation, the old one goes when the new
-    // one is filled
-    float* cells = nullptr;
-    HIP_TRY(bh, hipMalloc(&cells, total * sizeof(float)));
-    if (!bh->d_grid_rows) HIP_TRY(bh, hipMalloc(&bh->d_grid_rows, (size_t)B * sizeof(GridRow)));
-    std::vector<size_t> offset((size_t)n_maps);
-    size_t at = 0;
-    for (int m = 0; m < n_maps; ++m) {
-        const size_t n = (size_t)maps[m].nx * (size_t)maps[m].ny;
-        const hipError_t e = hipMemcpy(cells + at, maps[m].cells, n * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(cells);
-            return fail(bh, CCV_MPPI_ERR_HIP, "set_grids: copying the cells", e);
-        }
-        offset[(size_t)m] = at;
-        at += n;
-    }
-    std::vector<GridRow> rows((size_t)B);
-    std::memset(rows.data(), 0, rows.size() * sizeof(GridRow));
-    for (int b = 0; b < B; ++b) {
-        if (map_of[b] < 0) continue;
-        const ccv_mppi_grid& g = maps[map_of[b]];
-        GridRow& r = rows[(size_t)b];
-        r.origin_x = g.origin_x;
-        r.origin_y = g.origin_y;
-        r.inv = 1.0 / g.resolution;
-        r.w = weight[b];
-        r.cells = cells + offset[(size_t)map_of[b]];
-        r.nx = g.nx;
-        r.ny = g.ny;
-        r.outside = g.outside;
-    }
-    HIP_TRY(bh, hipMemcpy(bh->d_grid_rows, rows.data(), rows.size() * sizeof(GridRow), hipMemcpyHostToDevice));
-    if (bh->d_grid_cells) (void)hipFree(bh->d_grid_cells);
-    bh->d_grid_cells = cells;
-    bh->grid_maps.assign(maps, maps + n_maps);
-    for (ccv_mppi_grid& g : bh->grid_maps) g.cells = nullptr;
-    bh->grid_offset.swap(offset);
-    bh->grid_map_of.assign(map_of, map_of + B);
-    bh->grid_w.assign(weight, weight + B);
-    bh->grid = true;
-    return refresh_params(bh);
-}
-
-int ccv_mppi_batch_get_grids(ccv_mppi_batch* bh, ccv_mppi_grid* maps, int32_t max_maps, int32_t* n_maps, int32_t* map_of, double* weight) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int n = bh->grid ? (int)bh->grid_maps.size() : 0;
-    if (maps && (max_maps < 0 || max_maps < n)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_grids: max_maps below the number of maps");
-    if (n_maps) *n_maps = n;
-    for (int m = 0; m < n && maps; ++m) maps[m] = bh->grid_maps[(size_t)m];
-    for (int b = 0; b < bh->B; ++b) {
-        if (map_of) map_of[b] = bh->grid ? bh->grid_map_of[(size_t)b] : -1;
-        if (weight) weight[b] = bh->grid ? bh->grid_w[(size_t)b] : 0.0;
-    }
-    return CCV_MPPI_OK;
-}
-
-int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* bh, int32_t map, float* cells_out) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    if (!cells_out) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-    if (!bh->grid) return fail(bh, CCV_MPPI_ERR_STATE, "read_grid_cells: no maps are set (ccv_mppi_batch_set_grids)");
-    if (map < 0 || map >= (int32_t)bh->grid_maps.size()) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "read_grid_cells: map out of range");
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
-    HIP_TRY(bh, hipMemcpy(cells_out, bh->d_grid_cells + bh->grid_offset[(size_t)map], (size_t)g.nx * (size_t)g.ny * sizeof(float),
-                          hipMemcpyDeviceToHost));
-    return CCV_MPPI_OK;
-}
-
-// ---- moving discs ---------------------------------------------------------------------------------------------------------
-
-int ccv_mppi_batch_set_obstacle_velocities(ccv_mppi_batch* bh, const double* vxy, int32_t max_n) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    // every check comes before anything changes
-    if (!bh->obst) return fail(bh, CCV_MPPI_ERR_STATE, "set_obstacle_velocities: no discs are set (ccv_mppi_batch_set_obstacles)");
-    if (vxy) {
-        if (max_n < 0 || max_n > M)
-            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacle_velocities: max_n outside [0, CCV_MPPI_MAX_OBSTACLES]");
-        for (int b = 0; b < B; ++b)
-            for (int j = 0; j < bh->obst_n[(size_t)b] && j < max_n; ++j) {
-                const double* v = vxy + ((size_t)b * max_n + j) * 2;
-                if (!std::isfinite(v[0]) || !std::isfinite(v[1]))
-                    return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_obstacle_velocities: a velocity is not finite");
-            }
-    }
-    if (!vxy && !bh->moving) return CCV_MPPI_OK;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout may still read the old table and velocities)
-    if (!vxy) {   // back to the static kernels and their bits (under fleet prediction: the static rows stand still)
-        bh->moving = false;
-        bh->obst_vxy.clear();
-        if (bh->fleet_pred) {
-            if (int rc = upload_velocities(bh)) return rc;
-        }
-        return refresh_params(bh);
-    }
-    // rows at or past an instance's count (the fleet term's rows among them) are zero
-    std::vector<double> rows((size_t)B * M * 2, 0.0);
-    for (int b = 0; b < B; ++b)
-        for (int j = 0; j < bh->obst_n[(size_t)b] && j < max_n; ++j)
-            std::memcpy(&rows[((size_t)b * M + j) * 2], vxy + ((size_t)b * max_n + j) * 2, 2 * sizeof(double));
-    bh->obst_vxy.swap(rows);
-    bh->moving = true;
-    if (int rc = upload_velocities(bh)) return rc;
-    return refresh_params(bh);
-}
-
-int ccv_mppi_batch_get_obstacle_velocities(ccv_mppi_batch* bh, double* vxy, int32_t max_n) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    if (!vxy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    if (max_n < 0 || max_n > M) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_obstacle_velocities: max_n outside [0, CCV_MPPI_MAX_OBSTACLES]");
-    std::memset(vxy, 0, (size_t)B * max_n * 2 * sizeof(double));
-    if (!bh->moving) return CCV_MPPI_OK;
-    for (int b = 0; b < B; ++b) {
-        const int nb = bh->obst_n[(size_t)b] < max_n ? bh->obst_n[(size_t)b] : max_n;
-        if (nb > 0) std::memcpy(vxy + (size_t)b * max_n * 2, &bh->obst_vxy[(size_t)b * M * 2], (size_t)nb * 2 * sizeof(double));
-    }
-    return CCV_MPPI_OK;
-}
-
-int ccv_mppi_batch_get_params(ccv_mppi_batch* bh, ccv_mppi_config* out) {
-    if (!bh || !out) return CCV_MPPI_ERR_INVALID_ARG;
-    for (int b = 0; b < bh->B; ++b) out[b] = batch_cfg(bh, b);
     return CCV_MPPI_OK;
 }
 
@@ -831,10 +400,7 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
     if (bh->fleet) {
         std::vector<double> xy((size_t)B * 2);
         for (int b = 0; b < B; ++b) std::memcpy(&xy[(size_t)b * 2], heads[b].x0, 2 * sizeof(double));
-        if (int rc = fleet_write_positions(bh, xy)) return rc;
-        if (bh->fleet_pred) {
-            if (int rc = fleet_zero_velocities(bh)) return rc;
-        }
+        if (int rc = fleet_restart(bh, xy.data())) return rc;
     }
     bh->res_angle_abs.swap(angles);
     bh->res_steps = 0;
@@ -960,151 +526,6 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* bh, int32_t instance, int
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     const int64_t cap = CCV_MPPI_BATCH_TRACE_ROWS;
     HIP_TRY(bh, read_trace_ring(bh->d_rtrace + (size_t)instance * cap * 6, cap, bh->res_steps, max_rows, rows, n_rows));
-    return CCV_MPPI_OK;
-}
-
-// ---- fleet term: the robots of one resident batch keep clear of each other (mppi_fleet.h) ---------------------------------
-
-int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, double range, int32_t max_neighbours, const double* weight) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    const bool off = !radius && max_neighbours == 0;
-    // every check comes before anything changes
-    if (!off) {
-        if (!radius || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-        if (max_neighbours < 1 || max_neighbours > M)
-            return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: max_neighbours outside [1, CCV_MPPI_MAX_OBSTACLES]");
-        if (!(range >= 0.0) || !std::isfinite(range)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: range is negative or not finite");
-        if (B > kFleetMaxBatch) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: more than 1024 instances");
-        for (int b = 0; b < B; ++b) {
-            if (!(radius[b] >= 0.0) || !std::isfinite(radius[b]))
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: a radius is negative or not finite");
-            if (!(weight[b] >= 0.0) || !std::isfinite(weight[b]))
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_fleet: a weight is negative or not finite");
-        }
-    }
-    if (off && !bh->fleet) return CCV_MPPI_OK;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the tables)
-    if (off) {
-        bh->fleet = false;
-        if (bh->fleet_pred) {   // (prediction is the fleet term's)
-            bh->fleet_pred = false;
-            if (int rc = clear_fleet_velocity_rows(bh)) return rc;
-        }
-        bh->fleet_radius.clear();
-        bh->fleet_range = 0.0;
-        bh->fleet_maxn = 0;
-        if (!bh->obst) {   // no static discs either: back to the kernels that ran before
-            bh->obst_xyr.clear();
-            bh->obst_n.clear();
-            bh->obst_w.clear();
-        }
-        if (uses_table(bh)) return refresh_params(bh);   // (the static counts again)
-        return CCV_MPPI_OK;
-    }
-    if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, (size_t)B * M * 3 * sizeof(double)));
-    if (!obst_on(bh)) {   // no static discs: empty lists
-        bh->obst_xyr.assign((size_t)B * M * 3, 0.0);
-        bh->obst_n.assign((size_t)B, 0);
-        HIP_TRY(bh, hipMemcpy(bh->d_obst, bh->obst_xyr.data(), bh->obst_xyr.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (!bh->d_fleet_xy) {
-        HIP_TRY(bh, hipMalloc(&bh->d_fleet_xy, (size_t)B * 4 * sizeof(double)));
-        HIP_TRY(bh, hipMalloc(&bh->d_fleet_radius, (size_t)B * sizeof(double)));
-        HIP_TRY(bh, hipMalloc(&bh->d_fleet_nstatic, (size_t)B * sizeof(int32_t)));
-    }
-    HIP_TRY(bh, hipMemcpy(bh->d_fleet_radius, radius, (size_t)B * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(bh, hipMemcpy(bh->d_fleet_nstatic, bh->obst_n.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
-    // the position table from the current frames (zeros before the first _set_poses, which writes it again)
-    std::vector<double> xy((size_t)B * 2, 0.0);
-    if (bh->have_poses)
-        HIP_TRY(bh, hipMemcpy2D(xy.data(), 2 * sizeof(double), bh->d_rframe, sizeof(ResidentFrame), 2 * sizeof(double), (size_t)B,
-                               hipMemcpyDeviceToHost));
-    if (int rc = fleet_write_positions(bh, xy)) return rc;
-    if (bh->fleet_pred) {
-        if (int rc = fleet_zero_velocities(bh)) return rc;
-    }
-    bh->obst_w.assign(weight, weight + B);
-    bh->fleet_radius.assign(radius, radius + B);
-    bh->fleet_range = range;
-    bh->fleet_maxn = max_neighbours;
-    bh->fleet = true;
-    return refresh_params(bh);
-}
-
-int ccv_mppi_batch_resident_get_fleet(ccv_mppi_batch* bh, double* radius, double* range, int32_t* max_neighbours) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    for (int b = 0; b < bh->B && radius; ++b) radius[b] = bh->fleet ? bh->fleet_radius[(size_t)b] : 0.0;
-    if (range) *range = bh->fleet_range;
-    if (max_neighbours) *max_neighbours = bh->fleet_maxn;
-    return CCV_MPPI_OK;
-}
-
-int ccv_mppi_batch_resident_read_fleet(ccv_mppi_batch* bh, int32_t* n_static, int32_t* n_total, double* xyr) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    if (!bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_fleet first");
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
-    std::vector<int32_t> total((size_t)B);
-    HIP_TRY(bh, hipMemcpy2D(total.data(), sizeof(int32_t), reinterpret_cast<const char*>(bh->d_params) + offsetof(BatchParams, n_obst),
-                           sizeof(BatchParams), sizeof(int32_t), (size_t)B, hipMemcpyDeviceToHost));
-    if (xyr) {
-        HIP_TRY(bh, hipMemcpy(xyr, bh->d_obst, (size_t)B * M * 3 * sizeof(double), hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; ++b)   // (rows past the count: whatever an earlier tick left there)
-            for (int j = total[(size_t)b]; j < M; ++j) std::memset(xyr + ((size_t)b * M + j) * 3, 0, 3 * sizeof(double));
-    }
-    for (int b = 0; b < B; ++b) {
-        if (n_static) n_static[b] = bh->obst_n[(size_t)b];
-        if (n_total) n_total[b] = total[(size_t)b];
-    }
-    return CCV_MPPI_OK;
-}
-
-// ---- fleet prediction: a neighbour's disc moves with the velocity its robot had over the last tick -------------------------
-
-int ccv_mppi_batch_set_fleet_prediction(ccv_mppi_batch* bh, int32_t on) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    if (!bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, "set_fleet_prediction: the fleet term is off (ccv_mppi_batch_resident_set_fleet)");
-    const bool want = on != 0;
-    if (want == bh->fleet_pred) return CCV_MPPI_OK;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued rollout or prologue may still read the tables)
-    bh->fleet_pred = want;
-    if (want) {
-        if (int rc = upload_velocities(bh)) return rc;       // every row defined: the static rows, zero elsewhere
-        if (int rc = fleet_zero_velocities(bh)) return rc;   // no robot has moved yet
-    } else if (int rc = clear_fleet_velocity_rows(bh)) return rc;
-    return refresh_params(bh);
-}
-
-int ccv_mppi_batch_get_fleet_prediction(const ccv_mppi_batch* bh) { return bh ? (bh->fleet_pred ? 1 : 0) : CCV_MPPI_ERR_INVALID_ARG; }
-
-int ccv_mppi_batch_read_fleet_velocities(ccv_mppi_batch* bh, double* vxy) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    if (!vxy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
-    if (!bh->fleet) return fail(bh, CCV_MPPI_ERR_STATE, "ccv_mppi_batch_resident_set_fleet first");
-    const int B = bh->B;
-    constexpr int M = CCV_MPPI_MAX_OBSTACLES;
-    const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    if (int rc = batch_flush(bh)) return rc;
-    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
-    std::memset(vxy, 0, (size_t)B * M * 2 * sizeof(double));
-    if (!moving_on(bh)) return CCV_MPPI_OK;   // (the static kernels ran: every disc stood still)
-    std::vector<int32_t> total((size_t)B);
-    HIP_TRY(bh, hipMemcpy2D(total.data(), sizeof(int32_t), reinterpret_cast<const char*>(bh->d_params) + offsetof(BatchParams, n_obst),
-                           sizeof(BatchParams), sizeof(int32_t), (size_t)B, hipMemcpyDeviceToHost));
-    HIP_TRY(bh, hipMemcpy(vxy, bh->d_obst_v, (size_t)B * M * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b)   // (rows past the count: whatever an earlier tick left there)
-        for (int j = total[(size_t)b] < 0 ? 0 : total[(size_t)b]; j < M; ++j) std::memset(vxy + ((size_t)b * M + j) * 2, 0, 2 * sizeof(double));
     return CCV_MPPI_OK;
 }
 

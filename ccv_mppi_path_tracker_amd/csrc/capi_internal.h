@@ -3,7 +3,8 @@
 //   capi_exchange.hip    direct exchange of the partial vectors between the devices of a node
 //   capi_resident.hip    device-resident closed loop of a single handle
 //   capi_stage.hip       stage-wise calls, read-back, timing
-//   capi_batch.hip       batch handles (ccv_mppi_batch_*), their resident loop and its fleet term included
+//   capi_batch.hip       batch handles (ccv_mppi_batch_*): what a tick runs and what reads its results, the resident loop included
+//   capi_batch_config.hip  batch handles: what configures the next launch (parameters, shifted weights, discs, grids, fleet term)
 // A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".
@@ -17,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -178,22 +180,35 @@ struct ccv_mppi_handle : Core, StageState, ResidentLoop, Exchange {
     const double* pending_vec = nullptr;
 };
 
-// One configuration, B instances on one sample axis of B * Kpad columns (Kpad = K rounded up to 64; mppi_kernels.h,
-// batch_view): the core of a single handle, whose K is the instance's and whose
-// pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
-// one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
-struct ccv_mppi_batch : Core {
-    int B = 0, kpad = 0, rec_doubles = 0;
+// ---- a batch handle only (ccv_mppi_batch_*) -----------------------------------------------------------------------------
+namespace ccv {
+
+// a part's release(): its device allocations go (a null pointer: one it never made)
+inline void free_device(std::initializer_list<void*> ptrs) {
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+}
+
+// the instances' records: per call, poses, dt, windows and noise keys go to the device as one block
+struct BatchRecords {
+    int rec_doubles = 0;
     double* d_rec = nullptr;                        // [B][rec_doubles]: BatchHead + window a[H], b[H], c[H] per instance
     static constexpr int kRecSlots = 4;             // pinned staging of the records, in rotation: a slot is refilled only
     double* h_rec[kRecSlots] = {nullptr, nullptr, nullptr, nullptr};   // after the copy that read it has run
     hipEvent_t rec_ev[kRecSlots] = {nullptr, nullptr, nullptr, nullptr};
     bool rec_used[kRecSlots] = {false, false, false, false};
     int rec_next = 0;
-    int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
-    bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
-    bool have_result = false;
-    // device-resident closed loop of every instance (ccv_mppi_batch_resident_*, mppi_resident.h)
+    void release() {
+        for (hipEvent_t e : rec_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (double* h : h_rec)
+            if (h) (void)hipHostFree(h);
+        free_device({d_rec});
+    }
+};
+
+// device-resident closed loop of every instance (ccv_mppi_batch_resident_*, mppi_resident.h)
+struct BatchResident {
     ResidentFrame* d_rframe = nullptr;      // [B]
     BatchInstance* d_inst = nullptr;        // [B]
     double* d_rpath = nullptr;              // [2][n_total]
@@ -203,29 +218,42 @@ struct ccv_mppi_batch : Core {
     std::vector<double> res_angle_abs;      // [B][3]: bounds on |yaw|, |roll|, |pitch| of every resident pose
     bool have_paths = false, have_poses = false;
     int64_t res_steps = 0;                  // resident ticks since the poses were set (every instance's step count)
-    // per-instance parameters (ccv_mppi_batch_set_params): the VARIED kernels read instance b's row of d_params through the
-    // pointer in its record's head; without them (varied = false) every instance has cfg and the shared kernels run
+    void release() { free_device({d_rframe, d_inst, d_rpath, d_rtrace}); }
+};
+
+// per-instance parameters (ccv_mppi_batch_set_params): the VARIED kernels read instance b's row of d_params through the
+// pointer in its record's head; without them (varied = false) every instance has cfg and the shared kernels run.
+// Shifted weights (ccv_mppi_batch_set_min_shift): the SHIFT rollout kernels and the _shift update kernels, always over the
+// parameter table -- B copies of cfg in it while `varied` is false
+struct ParamTable {
     bool varied = false;
     std::vector<ccv_mppi_config> cfgs;      // [B] the instances' configurations while varied
-    BatchParams* d_params = nullptr;        // [B], allocated at the first _set_params or _set_min_shift(1), freed at destroy
-    // shifted weights (ccv_mppi_batch_set_min_shift): the SHIFT rollout kernels and the _shift update kernels, always over the
-    // parameter table -- B copies of cfg in it while `varied` is false
+    BatchParams* d_params = nullptr;        // [B], allocated when a form from Varied up first needs it (sync_tables), freed at destroy
     bool min_shift = false;
     double* d_cmin = nullptr;               // [B]: the plain family's exact instance minima (k_min_cost_batch)
-    // disc obstacles (ccv_mppi_batch_set_obstacles): the OBST rollout kernels, always over the parameter table too; the rows of
-    // the table point into d_obst
+    bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
+    void release() { free_device({d_params, d_cmin}); }
+};
+
+// disc obstacles (ccv_mppi_batch_set_obstacles): the OBST rollout kernels, always over the parameter table too; the rows of
+// the table point into d_obst.  Moving discs (ccv_mppi_batch_set_obstacle_velocities): the MOVING rollout kernels while
+// `moving`; the rows of the table point into d_obst_v.  Every row of d_obst_v is defined from its allocation on: zero unless
+// the caller gave a velocity (a neighbour's disc under fleet prediction: what the prologue wrote this tick).
+struct Discs {
     bool obst = false;
     double* d_obst = nullptr;               // [B][CCV_MPPI_MAX_OBSTACLES][3], allocated at the first _set_obstacles, freed at destroy
     std::vector<double> obst_xyr;           // [B][CCV_MPPI_MAX_OBSTACLES][3] host copy while obst
     std::vector<int32_t> obst_n;            // [B]
     std::vector<double> obst_w;             // [B]
-    // moving discs (ccv_mppi_batch_set_obstacle_velocities): the MOVING rollout kernels while `moving`; the rows of the table
-    // point into d_obst_v.  Every row of d_obst_v is defined from its allocation on: zero unless the caller gave a velocity.
     bool moving = false;
-    double* d_obst_v = nullptr;             // [B][CCV_MPPI_MAX_OBSTACLES][2], allocated at the first velocities, freed at destroy
+    double* d_obst_v = nullptr;             // [B][CCV_MPPI_MAX_OBSTACLES][2], allocated when first needed (sync_tables), freed at destroy
     std::vector<double> obst_vxy;           // [B][CCV_MPPI_MAX_OBSTACLES][2] host copy while moving
-    // occupancy grids (ccv_mppi_batch_set_grids): the GRID rollout kernels while `grid`.  A grid plan is a moving plan: without
-    // discs the kernels see n_obst = 0 and read neither disc nor velocity rows; with discs and no velocities, d_obst_v is zero.
+    void release() { free_device({d_obst, d_obst_v}); }
+};
+
+// occupancy grids (ccv_mppi_batch_set_grids): the GRID rollout kernels while `grid`.  A grid plan is a moving plan: without
+// discs the kernels see n_obst = 0 and read neither disc nor velocity rows; with discs and no velocities, d_obst_v is zero.
+struct Grids {
     bool grid = false;
     GridRow* d_grid_rows = nullptr;         // [B], a row per instance (BatchParams::grid points at it, or is null)
     float* d_grid_cells = nullptr;          // the cells of all maps, one allocation
@@ -233,22 +261,39 @@ struct ccv_mppi_batch : Core {
     std::vector<size_t> grid_offset;        // [n_maps] first cell of map m in d_grid_cells
     std::vector<int32_t> grid_map_of;       // [B]
     std::vector<double> grid_w;             // [B]
-    bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
-    // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
-    // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
-    // the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance)
+    void release() { free_device({d_grid_rows, d_grid_cells}); }
+};
+
+// fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
+// robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
+// the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance).
+// Fleet prediction (ccv_mppi_batch_set_fleet_prediction): the velocities travel with the positions, a neighbour's disc moves
+// with the velocity its robot had over the last tick, and the MOVING kernels run (over d_obst_v: the static rows the host's,
+// zero without ccv_mppi_batch_set_obstacle_velocities; the fleet's rows written by the prologue every tick)
+struct Fleet {
     bool fleet = false;
     double* d_fleet_xy = nullptr;           // [2][B][2]: tick n reads half n & 1 and writes the other (n = res_steps)
     double* d_fleet_radius = nullptr;       // [B]
-    int32_t* d_fleet_nstatic = nullptr;     // [B]: obst_n on the device, for the prologue
+    int32_t* d_fleet_nstatic = nullptr;     // [B]: obst_n on the device, for the prologue (sync_tables)
     std::vector<double> fleet_radius;       // [B]
     double fleet_range = 0.0;
     int32_t fleet_maxn = 0;
-    // fleet prediction (ccv_mppi_batch_set_fleet_prediction): the velocities travel with the positions, a neighbour's disc moves
-    // with the velocity its robot had over the last tick, and the MOVING kernels run (over d_obst_v: the static rows the host's,
-    // zero without ccv_mppi_batch_set_obstacle_velocities; the fleet's rows written by the prologue every tick)
     bool fleet_pred = false;
     double* d_fleet_v = nullptr;            // [2][B][2]: tick n reads half n & 1 and writes the other, like d_fleet_xy
+    void release() { free_device({d_fleet_xy, d_fleet_radius, d_fleet_nstatic, d_fleet_v}); }
+};
+
+}  // namespace ccv
+
+// One configuration, B instances on one sample axis of B * Kpad columns (Kpad = K rounded up to 64; mppi_kernels.h,
+// batch_view): the core of a single handle, whose K is the instance's and whose
+// pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
+// one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
+struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Fleet {
+    int B = 0, kpad = 0;
+    int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
+    bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
+    bool have_result = false;
 };
 
 namespace ccv {
@@ -312,7 +357,7 @@ inline bool has_wide_form(const KernelChoice& k, const int mode) {
 }
 // The kernel of one launch: the family chosen at create, demoted to the plain kernel when the headings are unbounded
 // (trig = fast_trig_safe of the launch; a batch: of its worst instance), the wide-turn form when trig says so.
-// form: what the launch serves (BatchForm, mppi_kernels.h; a batch handle's: batch_form(), capi_batch.hip); shift (a batch in
+// form: what the launch serves (BatchForm, mppi_kernels.h; a batch handle's: batch_form(), capi_batch_config.hip); shift (a batch in
 // shifted-weight mode): with a form from Varied up.
 inline RolloutPlan make_plan(const KernelChoice& k, const int model, const int mode, const int trig, const int batch, const BatchForm form,
                              const bool shift) {
@@ -382,5 +427,20 @@ struct ResidentBounds {
 };
 ResidentBounds resident_bounds(const DeviceBuffers& d, const ccv_mppi_config& c, const double* angle_abs, double dt, int32_t advance);
 hipError_t read_trace_ring(const double* d_ring, int64_t cap, int64_t steps, int32_t max_rows, double* rows, int32_t* n_rows);
+
+// ---- batch handles: what the tick path (capi_batch.hip) and the setters (capi_batch_config.hip) share ----------------------
+// instance b's configuration: its own under per-instance parameters, the creation configuration otherwise
+inline const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->cfg; }
+// the rung of the kernels the handle's next launch runs (BatchForm, mppi_kernels.h): the highest one whose addition is on
+BatchForm batch_form(const ccv_mppi_batch* bh);
+// whether the kernels read the parameter table
+inline bool uses_table(const ccv_mppi_batch* bh) { return batch_form(bh) >= BatchForm::Varied; }
+// a deferred resident update (batch_launch) is launched now
+inline int batch_flush(ccv_mppi_batch* bh) { return flush_finalize(bh); }
+// the handle's device current, no update deferred, the stream idle: nothing queued reads a table or writes a result any more
+int quiesce(ccv_mppi_batch* bh);
+// the fleet's snapshots start over (the caller has quiesced): both halves of the position table from xy [B][2] (null: as they are)
+// and, under prediction, both halves of the velocity snapshot zero -- no robot has moved yet
+int fleet_restart(ccv_mppi_batch* bh, const double* xy);
 
 }  // namespace ccv
