@@ -62,8 +62,10 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
         if (threadIdx.x < kMaxObst) obst_stage(A, *obst_lds, (int)threadIdx.x);
     }
     // two-instruction clamps (clampd_fast, mppi_kernels.h): the host has checked sigma and the bounds, this wave the warm start;
-    // a NaN anywhere takes every block through the compare-and-select instantiation
-    const bool fast_clamp = A.fast_clamp && __builtin_amdgcn_ballot_w64(pc_stage_nominal<MODEL>(A, sh, kPcSamples)) == 0ull;
+    // a NaN anywhere takes every block through the compare-and-select instantiation.  (The staging is not an operand of the
+    // `&&`: with A.fast_clamp off it would be skipped, and the kernel would read a warm start nobody put into LDS.)
+    const bool nan_nominal = __builtin_amdgcn_ballot_w64(pc_stage_nominal<MODEL>(A, sh, kPcSamples)) != 0ull;
+    const bool fast_clamp = A.fast_clamp && !nan_nominal;
     const int k = blockIdx.x * kPcSamples + lane;
     const bool live = k < A.K;
     const int kk = live ? k : A.K - 1;

@@ -162,6 +162,30 @@ def map_ahead(pose, v_ref, dt, horizon, salt=0, ahead=0.5, backwards=False):
     return Grid(cells, (lo_x, lo_y), res, -2.5 - salt)
 
 
+def map_over(P, salt=0):
+    """A map placed from the rollouts themselves: P [K][n][2], the covered states of one instance (the oracle's).  The box
+    between the 10 % and the 90 % quantile of the states per axis -- so a share of the fan lies inside and a share outside
+    whatever the horizon, the model and the way the warm start drives -- cells of a (36 + salt)-th of its longer side; as
+    map_ahead: nx != ny, neither a power of two, every cell a distinct small integer, `outside` a value no cell has.  One map
+    per instance: the horizon sweeps (tests/test_gpu_horizon_sweep_batch.py) use it where map_ahead's fixed reach misses the
+    conditions on the inputs at short or odd horizons."""
+    P = np.asarray(P, dtype=np.float64)
+    lo_x, hi_x = (float(q) for q in np.quantile(P[..., 0], (0.1, 0.9)))
+    lo_y, hi_y = (float(q) for q in np.quantile(P[..., 1], (0.1, 0.9)))
+    res = max(hi_x - lo_x, hi_y - lo_y) / (36.0 + salt)
+    nx, ny = max(1, int(math.ceil((hi_x - lo_x) / res))), max(1, int(math.ceil((hi_y - lo_y) / res)))
+
+    def pow2(n):
+        return n & (n - 1) == 0
+
+    while pow2(nx):
+        nx += 1
+    while pow2(ny) or ny == nx:
+        ny += 1
+    cells = (1.0 + np.arange(nx * ny, dtype=np.float64)).reshape(ny, nx).astype(np.float32)
+    return Grid(cells, (lo_x, lo_y), res, -2.5 - salt)
+
+
 def coverage(g, P):
     """(share of the states in bounds, share out of bounds, distinct cells hit) over states P [K][n][2]"""
     _, inside, idx = lookup(g, P[..., 0], P[..., 1])
