@@ -88,6 +88,36 @@ def pack_velocities(velocities, batch, counts=None):
     return vxy, max_n
 
 
+def inflation_profile(radius_m, resolution, kind="linear", lethal=1.0, inscribed=None, inscribed_m=0.0, free_value=0.0, scaling=10.0):
+    """(R, profile float32 [R * R + 1], free_value) for BatchController.set_occupancy: the cost of a cell by the squared distance
+    D2, in cells, from its centre to the centre of the nearest occupied cell, built on the host -- the device only looks it up.
+    R = ceil(radius_m / resolution) cells.  With d = sqrt(D2) * resolution: d = 0 -> lethal; d <= inscribed_m -> inscribed
+    (default: lethal); inscribed_m < d <= radius_m -> by `kind`: "step": inscribed; "linear": from inscribed at inscribed_m down to
+    free_value at radius_m; "exponential": inscribed * exp(-scaling * (d - inscribed_m)) (nav2's inflation layer, scaling in
+    1 / m); d > radius_m -> free_value.  ValueError for an unknown kind, a radius of more than capi.INFLATE_MAX_RADIUS cells or
+    an inscribed_m above radius_m."""
+    radius_m, resolution, inscribed_m = float(radius_m), float(resolution), float(inscribed_m)
+    if not (resolution > 0.0 and radius_m >= 0.0 and 0.0 <= inscribed_m <= radius_m):
+        raise ValueError("inflation_profile: need resolution > 0 and 0 <= inscribed_m <= radius_m")
+    R = int(np.ceil(radius_m / resolution - 1e-9))
+    if R > capi.INFLATE_MAX_RADIUS:
+        raise ValueError("inflation_profile: %d cells, at most %d" % (R, capi.INFLATE_MAX_RADIUS))
+    inscribed = float(lethal if inscribed is None else inscribed)
+    d = np.sqrt(np.arange(R * R + 1, dtype=np.float64)) * resolution
+    if kind == "step":
+        f = np.full_like(d, inscribed)
+    elif kind == "linear":
+        f = inscribed + (free_value - inscribed) * (d - inscribed_m) / max(radius_m - inscribed_m, np.finfo(float).tiny)
+    elif kind == "exponential":
+        f = inscribed * np.exp(-float(scaling) * (d - inscribed_m))
+    else:
+        raise ValueError("inflation_profile: kind must be 'step', 'linear' or 'exponential', not %r" % (kind,))
+    f = np.where(d <= inscribed_m, inscribed, f)
+    f = np.where(d > radius_m, float(free_value), f)
+    f[0] = float(lethal)
+    return R, np.ascontiguousarray(f, dtype=np.float32), float(free_value)
+
+
 class BatchController:
     """`batch` controllers on one device: one MPPIParams shared by all, or a sequence of `batch` MPPIParams that agree in
     SHARED_FIELDS (per-instance sigma, lambda, v_ref, bounds and weights; K = num_samples per instance).  min_shift: the
@@ -273,6 +303,68 @@ class BatchController:
             self._check(self.lib.ccv_mppi_batch_read_grid_cells(self._h, m, cells.ctypes.data_as(C.POINTER(C.c_float))))
             maps.append((cells, (g.origin_x, g.origin_y), g.resolution, g.outside))
         return maps, mo, w
+
+    # ---- costmaps inflated on the device (ccv_mppi_batch_set_occupancy) ----
+    def set_occupancy(self, maps, inflation=None, map_of=None, weight=0.0):
+        """maps: a list of (cells[ny][nx] uint8, (origin_x, origin_y), resolution, outside, threshold), or None: the grid term off;
+        inflation: one (R, profile[R * R + 1], free_value) per map (inflation_profile), or one for all; map_of, weight: as
+        set_grids.  The float cells the grid term reads are derived on the device: a cell whose nearest occupied cell
+        (cells >= threshold) is at squared distance D2 <= R * R costs profile[D2], every other cell free_value.  Takes the place
+        of set_grids' maps (and a later set_grids takes the place of these); get_grids returns the derived cells.  Flushes a
+        pending resident update."""
+        if maps is None or len(maps) == 0:
+            self._check(self.lib.ccv_mppi_batch_set_occupancy(self._h, None, None, 0, None, None))
+            return
+        if len(inflation) == 3 and np.isscalar(inflation[0]):
+            inflation = [inflation] * len(maps)
+        if len(inflation) != len(maps):
+            raise ValueError("inflation: expected one (R, profile, free_value) or %d, got %d" % (len(maps), len(inflation)))
+        rows, infl, keep = (capi.Occupancy * len(maps))(), (capi.Inflation * len(maps))(), []
+        for m, ((cells, origin, resolution, outside, threshold), (R, profile, free_value)) in enumerate(zip(maps, inflation)):
+            cells = np.ascontiguousarray(cells, dtype=np.uint8)
+            profile = np.ascontiguousarray(profile, dtype=np.float32)
+            if cells.ndim != 2:
+                raise ValueError("map %d: cells must be [ny][nx]" % m)
+            if profile.shape != (int(R) * int(R) + 1,):
+                raise ValueError("map %d: profile must have R * R + 1 = %d entries, got %s" % (m, int(R) * int(R) + 1, profile.shape))
+            keep += [cells, profile]
+            rows[m] = capi.Occupancy(float(origin[0]), float(origin[1]), float(resolution), float(outside), cells.shape[1], cells.shape[0],
+                                     int(threshold), cells.ctypes.data_as(C.POINTER(C.c_uint8)))
+            infl[m] = capi.Inflation(int(R), float(free_value), profile.ctypes.data_as(C.POINTER(C.c_float)))
+        mo = np.ascontiguousarray(np.broadcast_to(np.asarray(map_of, dtype=np.int32), (self.B,)))
+        w = capi.as_f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), (self.B,)))
+        self._check(self.lib.ccv_mppi_batch_set_occupancy(self._h, rows, infl, len(maps), mo.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(w)))
+
+    def update_occupancy(self, map, x0, y0, patch2d):
+        """Map `map`'s occupancy cells [y0 : y0 + h, x0 : x0 + w] become patch2d [h][w] uint8, and the float cells within R of them
+        are derived again, in stream order: a step enqueued before this call reads the old map, every step enqueued after it
+        the new one.  No synchronisation; patch2d may be reused as soon as the call returns.  At most
+        capi.OCC_PATCH_MAX_CELLS cells."""
+        patch = np.ascontiguousarray(patch2d, dtype=np.uint8)
+        if patch.ndim != 2:
+            raise ValueError("patch2d must be [h][w]")
+        self._check(self.lib.ccv_mppi_batch_update_occupancy_enqueue(self._h, int(map), int(x0), int(y0), patch.shape[1], patch.shape[0],
+                                                                      patch.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def get_occupancy(self):
+        """A list of ((origin_x, origin_y), resolution, outside, nx, ny, threshold, R, free_value) per map as the library holds
+        them; [] unless occupancy is set.  (map_of and weight: get_grids.)"""
+        n = C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_get_occupancy(self._h, None, None, 0, C.byref(n)))
+        rows, infl = (capi.Occupancy * max(n.value, 1))(), (capi.Inflation * max(n.value, 1))()
+        self._check(self.lib.ccv_mppi_batch_get_occupancy(self._h, rows, infl, n.value, None))
+        return [((g.origin_x, g.origin_y), g.resolution, g.outside, g.nx, g.ny, g.threshold, f.radius, f.free_value)
+                for g, f in zip(rows[:n.value], infl[:n.value])]
+
+    def read_occupancy(self, map):
+        """cells[ny][nx] uint8 of map `map`, read back from the device; synchronises."""
+        geo = self.get_occupancy()
+        if not 0 <= int(map) < max(len(geo), 1):
+            raise ValueError("map %d out of range" % int(map))
+        ny, nx = (geo[int(map)][4], geo[int(map)][3]) if geo else (1, 1)   # (no occupancy: the library refuses)
+        out = np.empty((ny, nx), dtype=np.uint8)
+        self._check(self.lib.ccv_mppi_batch_read_occupancy(self._h, int(map), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
 
     # ---- warm starts [B][H-1][u_dim] ----
     def set_nominal(self, u):

@@ -31,6 +31,9 @@ BATCH_KERNEL_OBST = 128
 BATCH_KERNEL_MOVING = 256
 BATCH_KERNEL_GRID = 512
 MAX_OBSTACLES = 32
+INFLATE_MAX_RADIUS = 64
+OCC_PATCH_MAX_CELLS = 1 << 20
+OCC_PATCH_SLOTS = 4
 BATCH_TRACE_ROWS = 1024
 
 
@@ -61,6 +64,19 @@ class Grid(C.Structure):
         ("origin_x", C.c_double), ("origin_y", C.c_double), ("resolution", C.c_double),
         ("outside", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("cells", C.POINTER(C.c_float)),
     ]
+
+
+class Occupancy(C.Structure):
+    """struct ccv_mppi_occupancy"""
+    _fields_ = [
+        ("origin_x", C.c_double), ("origin_y", C.c_double), ("resolution", C.c_double),
+        ("outside", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("threshold", C.c_int32), ("cells", C.POINTER(C.c_uint8)),
+    ]
+
+
+class Inflation(C.Structure):
+    """struct ccv_mppi_inflation"""
+    _fields_ = [("radius", C.c_int32), ("free_value", C.c_float), ("profile", C.POINTER(C.c_float))]
 
 
 _dp = C.POINTER(C.c_double)
@@ -131,6 +147,10 @@ SIGNATURES = {
     "ccv_mppi_batch_set_grids": (C.c_int, [_H, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32), _dp]),
     "ccv_mppi_batch_get_grids": (C.c_int, [_H, C.POINTER(Grid), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
     "ccv_mppi_batch_read_grid_cells": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_float)]),
+    "ccv_mppi_batch_set_occupancy": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(Inflation), C.c_int32, C.POINTER(C.c_int32), _dp]),
+    "ccv_mppi_batch_update_occupancy_enqueue": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "ccv_mppi_batch_get_occupancy": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(Inflation), C.c_int32, C.POINTER(C.c_int32)]),
+    "ccv_mppi_batch_read_occupancy": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint8)]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),

@@ -1,5 +1,5 @@
 // C ABI, batch handles: what configures the next launch -- per-instance parameters, shifted weights, disc obstacles and their
-// velocities, occupancy grids, the fleet term and its prediction (struct ccv_mppi_batch and its parts: capi_internal.h; what a
+// velocities, occupancy grids and the occupancy layers they can be derived from, the fleet term and its prediction (struct ccv_mppi_batch and its parts: capi_internal.h; what a
 // tick runs: capi_batch.hip).  Every setter has one shape: validate (every check before anything changes), quiesce, commit the
 // host-side state, sync_tables.  The device tables the kernels read are a function of that state and are written in one place.
 #include "capi_internal.h"
@@ -74,6 +74,86 @@ int sync_tables(ccv_mppi_batch* bh) {
     if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
     HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
     return CCV_MPPI_OK;
+}
+
+// what is wrong with a map's geometry (the checks _set_grids and _set_occupancy share, in this order), or null
+const char* geometry_fault(const int32_t nx, const int32_t ny, const double resolution, const double origin_x, const double origin_y,
+                           const float outside) {
+    if (nx < 1 || nx > CCV_MPPI_GRID_MAX_DIM || ny < 1 || ny > CCV_MPPI_GRID_MAX_DIM || (int64_t)nx * ny > CCV_MPPI_GRID_MAX_CELLS)
+        return "nx, ny outside [1, 32768] or nx * ny above 2^26";
+    if (!(resolution > 0.0) || !std::isfinite(resolution) || !std::isfinite(1.0 / resolution)) return "a resolution is not positive and finite";
+    if (!std::isfinite(origin_x) || !std::isfinite(origin_y)) return "an origin is not finite";
+    if (!std::isfinite(outside)) return "an outside value is not finite";
+    return nullptr;
+}
+
+int refuse(ccv_mppi_batch* bh, const char* who, const char* what) { return fail(bh, CCV_MPPI_ERR_INVALID_ARG, (std::string(who) + what).c_str()); }
+
+// map_of and weight of _set_grids / _set_occupancy
+int check_map_roles(ccv_mppi_batch* bh, const char* who, const int32_t n_maps, const int32_t* map_of, const double* weight) {
+    for (int b = 0; b < bh->B; ++b) {
+        if (!valid_weight(weight[b])) return refuse(bh, who, "a weight is negative or not finite");
+        if (map_of[b] < -1 || map_of[b] >= n_maps) return refuse(bh, who, "map_of outside [-1, n_maps)");
+    }
+    return CCV_MPPI_OK;
+}
+
+// the grid term off (the caller has quiesced): cells, layers and host copies go, null in every row of the table
+int maps_off(ccv_mppi_batch* bh) {
+    if (bh->d_grid_cells) HIP_TRY(bh, hipFree(bh->d_grid_cells));
+    bh->d_grid_cells = nullptr;
+    bh->drop_layers();
+    bh->grid = false;
+    bh->grid_maps.clear();
+    bh->grid_offset.clear();
+    bh->grid_map_of.clear();
+    bh->grid_w.clear();
+    return sync_tables(bh);
+}
+
+// A new set of maps takes the place of the old one (the caller has quiesced and filled `cells`, which the handle owns from here
+// on, at `offset`): the grid rows, the host copies, the old cells freed.  geo: the maps' geometry, cells null.
+int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, float* cells, std::vector<size_t>& offset, const int32_t* map_of,
+                 const double* weight) {
+    const int B = bh->B;
+    std::vector<GridRow> rows((size_t)B);
+    std::memset(rows.data(), 0, rows.size() * sizeof(GridRow));
+    for (int b = 0; b < B; ++b) {
+        if (map_of[b] < 0) continue;
+        const ccv_mppi_grid& g = geo[(size_t)map_of[b]];
+        GridRow& r = rows[(size_t)b];
+        r.origin_x = g.origin_x;
+        r.origin_y = g.origin_y;
+        r.inv = 1.0 / g.resolution;
+        r.w = weight[b];
+        r.cells = cells + offset[(size_t)map_of[b]];
+        r.nx = g.nx;
+        r.ny = g.ny;
+        r.outside = g.outside;
+    }
+    hipError_t e = bh->d_grid_rows ? hipSuccess : hipMalloc(&bh->d_grid_rows, (size_t)B * sizeof(GridRow));
+    if (e == hipSuccess) e = hipMemcpy(bh->d_grid_rows, rows.data(), rows.size() * sizeof(GridRow), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(cells);
+        return fail(bh, CCV_MPPI_ERR_HIP, "the grid rows", e);
+    }
+    if (bh->d_grid_cells) (void)hipFree(bh->d_grid_cells);
+    bh->d_grid_cells = cells;
+    bh->grid_maps.swap(geo);
+    bh->grid_offset.swap(offset);
+    bh->grid_map_of.assign(map_of, map_of + B);
+    bh->grid_w.assign(weight, weight + B);
+    bh->grid = true;
+    return CCV_MPPI_OK;
+}
+
+// the float cells of the rectangle (x0, y0, w, h) of map m from its layer, on the handle's stream
+void inflate(ccv_mppi_batch* bh, const int m, const int32_t x0, const int32_t y0, const int32_t w, const int32_t h) {
+    const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+    const size_t at = bh->grid_offset[(size_t)m];
+    launch_inflate(InflateArgs{bh->d_occ + at, bh->d_grid_cells + at, bh->d_profile + bh->profile_offset[(size_t)m], bh->occ_free[(size_t)m], g.nx,
+                               g.ny, bh->occ_threshold[(size_t)m], bh->occ_radius[(size_t)m], x0, y0, w, h},
+                   bh->stream);
 }
 
 // the instances' present disc counts, BatchParams::n_obst as the last prologue left it (the static counts after a setter)
@@ -293,51 +373,32 @@ int ccv_mppi_batch_get_obstacle_velocities(ccv_mppi_batch* bh, double* vxy, int3
 
 int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int32_t n_maps, const int32_t* map_of, const double* weight) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    const int B = bh->B;
+    static const char who[] = "set_grids: ";
     const bool off = !maps || n_maps == 0;
     // every check comes before anything changes
     size_t total = 0;
     if (!off) {
-        if (n_maps < 0) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: n_maps < 0");
+        if (n_maps < 0) return refuse(bh, who, "n_maps < 0");
         if (!map_of || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
         for (int m = 0; m < n_maps; ++m) {
             const ccv_mppi_grid& g = maps[m];
-            if (!g.cells) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a map has no cells");
-            if (g.nx < 1 || g.nx > CCV_MPPI_GRID_MAX_DIM || g.ny < 1 || g.ny > CCV_MPPI_GRID_MAX_DIM ||
-                (int64_t)g.nx * g.ny > CCV_MPPI_GRID_MAX_CELLS)
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: nx, ny outside [1, 32768] or nx * ny above 2^26");
-            if (!(g.resolution > 0.0) || !std::isfinite(g.resolution) || !std::isfinite(1.0 / g.resolution))
-                return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a resolution is not positive and finite");
-            if (!std::isfinite(g.origin_x) || !std::isfinite(g.origin_y)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: an origin is not finite");
-            if (!std::isfinite(g.outside)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: an outside value is not finite");
+            if (!g.cells) return refuse(bh, who, "a map has no cells");
+            if (const char* f = geometry_fault(g.nx, g.ny, g.resolution, g.origin_x, g.origin_y, g.outside)) return refuse(bh, who, f);
             const size_t n = (size_t)g.nx * (size_t)g.ny;
             for (size_t i = 0; i < n; ++i)
-                if (!std::isfinite(g.cells[i])) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a cell is not finite");
+                if (!std::isfinite(g.cells[i])) return refuse(bh, who, "a cell is not finite");
             total += n;
         }
-        for (int b = 0; b < B; ++b) {
-            if (!valid_weight(weight[b])) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: a weight is negative or not finite");
-            if (map_of[b] < -1 || map_of[b] >= n_maps) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "set_grids: map_of outside [-1, n_maps)");
-        }
+        if (int rc = check_map_roles(bh, who, n_maps, map_of, weight)) return rc;
     }
     if (off && !bh->grid) return CCV_MPPI_OK;
     const DeviceGuard guard(bh->cfg.device);
     if (int rc = quiesce(bh)) return rc;   // (a queued rollout may still read the old table, rows and cells)
-    if (off) {
-        if (bh->d_grid_cells) HIP_TRY(bh, hipFree(bh->d_grid_cells));
-        bh->d_grid_cells = nullptr;
-        bh->grid = false;
-        bh->grid_maps.clear();
-        bh->grid_offset.clear();
-        bh->grid_map_of.clear();
-        bh->grid_w.clear();
-        return sync_tables(bh);   // (null in every row)
-    }
+    if (off) return maps_off(bh);
     // the cells of all maps are one allocation, sized by the maps: a new set is a new allocation, the old one goes when the new
     // one is filled
     float* cells = nullptr;
     HIP_TRY(bh, hipMalloc(&cells, total * sizeof(float)));
-    if (!bh->d_grid_rows) HIP_TRY(bh, hipMalloc(&bh->d_grid_rows, (size_t)B * sizeof(GridRow)));
     std::vector<size_t> offset((size_t)n_maps);
     size_t at = 0;
     for (int m = 0; m < n_maps; ++m) {
@@ -350,30 +411,10 @@ int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int3
         offset[(size_t)m] = at;
         at += n;
     }
-    std::vector<GridRow> rows((size_t)B);
-    std::memset(rows.data(), 0, rows.size() * sizeof(GridRow));
-    for (int b = 0; b < B; ++b) {
-        if (map_of[b] < 0) continue;
-        const ccv_mppi_grid& g = maps[map_of[b]];
-        GridRow& r = rows[(size_t)b];
-        r.origin_x = g.origin_x;
-        r.origin_y = g.origin_y;
-        r.inv = 1.0 / g.resolution;
-        r.w = weight[b];
-        r.cells = cells + offset[(size_t)map_of[b]];
-        r.nx = g.nx;
-        r.ny = g.ny;
-        r.outside = g.outside;
-    }
-    HIP_TRY(bh, hipMemcpy(bh->d_grid_rows, rows.data(), rows.size() * sizeof(GridRow), hipMemcpyHostToDevice));
-    if (bh->d_grid_cells) (void)hipFree(bh->d_grid_cells);
-    bh->d_grid_cells = cells;
-    bh->grid_maps.assign(maps, maps + n_maps);
-    for (ccv_mppi_grid& g : bh->grid_maps) g.cells = nullptr;
-    bh->grid_offset.swap(offset);
-    bh->grid_map_of.assign(map_of, map_of + B);
-    bh->grid_w.assign(weight, weight + B);
-    bh->grid = true;
+    std::vector<ccv_mppi_grid> geo(maps, maps + n_maps);
+    for (ccv_mppi_grid& g : geo) g.cells = nullptr;
+    if (int rc = install_maps(bh, geo, cells, offset, map_of, weight)) return rc;
+    bh->drop_layers();   // (the cells are the caller's now)
     return sync_tables(bh);
 }
 
@@ -396,10 +437,152 @@ int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* bh, int32_t map, float* cells
     if (!bh->grid) return fail(bh, CCV_MPPI_ERR_STATE, "read_grid_cells: no maps are set (ccv_mppi_batch_set_grids)");
     if (map < 0 || map >= (int32_t)bh->grid_maps.size()) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "read_grid_cells: map out of range");
     const DeviceGuard guard(bh->cfg.device);
-    HIP_TRY(bh, hipSetDevice(bh->cfg.device));   // (no kernel writes the cells: nothing to wait for)
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    // (a caller's cells: no kernel writes them, nothing to wait for; derived cells: k_inflate does, in stream order)
+    if (bh->occ) HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
     HIP_TRY(bh, hipMemcpy(cells_out, bh->d_grid_cells + bh->grid_offset[(size_t)map], (size_t)g.nx * (size_t)g.ny * sizeof(float),
                           hipMemcpyDeviceToHost));
+    return CCV_MPPI_OK;
+}
+
+// ---- costmaps inflated on the device: occupancy layers behind the maps of the grid term (mppi_costmap.h) --------------------
+
+int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* bh, const ccv_mppi_occupancy* maps, const ccv_mppi_inflation* inflation, int32_t n_maps,
+                                 const int32_t* map_of, const double* weight) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "set_occupancy: ";
+    const bool off = !maps || n_maps == 0;
+    // every check comes before anything changes
+    size_t total = 0, n_profile = 0;
+    if (!off) {
+        if (n_maps < 0) return refuse(bh, who, "n_maps < 0");
+        if (!inflation || !map_of || !weight) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+        for (int m = 0; m < n_maps; ++m) {
+            const ccv_mppi_occupancy& g = maps[m];
+            const ccv_mppi_inflation& f = inflation[m];
+            if (!g.cells) return refuse(bh, who, "a map has no cells");
+            if (const char* fault = geometry_fault(g.nx, g.ny, g.resolution, g.origin_x, g.origin_y, g.outside)) return refuse(bh, who, fault);
+            if (g.threshold < 0 || g.threshold > 255) return refuse(bh, who, "a threshold outside [0, 255]");
+            if (f.radius < 0 || f.radius > CCV_MPPI_INFLATE_MAX_RADIUS) return refuse(bh, who, "a radius outside [0, CCV_MPPI_INFLATE_MAX_RADIUS]");
+            if (!f.profile) return refuse(bh, who, "an inflation has no profile");
+            if (!std::isfinite(f.free_value)) return refuse(bh, who, "a free_value is not finite");
+            const size_t np = (size_t)f.radius * (size_t)f.radius + 1;
+            for (size_t i = 0; i < np; ++i)
+                if (!std::isfinite(f.profile[i])) return refuse(bh, who, "a profile entry is not finite");
+            total += (size_t)g.nx * (size_t)g.ny;
+            n_profile += np;
+        }
+        if (int rc = check_map_roles(bh, who, n_maps, map_of, weight)) return rc;
+    }
+    if (off && !bh->grid) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    if (int rc = quiesce(bh)) return rc;   // (a queued rollout may still read the old table, rows and cells)
+    if (off) return maps_off(bh);
+    // the staging ring of the patches, at the first call (kept until destroy)
+    if (!bh->h_patch) {
+        HIP_TRY(bh, hipHostMalloc(&bh->h_patch, (size_t)Costmap::kPatchSlots * CCV_MPPI_OCC_PATCH_MAX_CELLS, hipHostMallocDefault));
+        HIP_TRY(bh, hipHostGetDevicePointer(reinterpret_cast<void**>(&bh->d_patch), bh->h_patch, 0));
+        for (hipEvent_t& e : bh->patch_ev) HIP_TRY(bh, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    // cells, layers and profile tables of all maps: three allocations sized by the maps, filled before the old ones go
+    float* cells = nullptr;
+    uint8_t* layers = nullptr;
+    float* profiles = nullptr;
+    std::vector<size_t> offset((size_t)n_maps), poffset((size_t)n_maps);
+    hipError_t e = hipMalloc(&cells, total * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&layers, total);
+    if (e == hipSuccess) e = hipMalloc(&profiles, n_profile * sizeof(float));
+    size_t at = 0, pat = 0;
+    for (int m = 0; m < n_maps && e == hipSuccess; ++m) {
+        const size_t n = (size_t)maps[m].nx * (size_t)maps[m].ny, np = (size_t)inflation[m].radius * (size_t)inflation[m].radius + 1;
+        e = hipMemcpy(layers + at, maps[m].cells, n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(profiles + pat, inflation[m].profile, np * sizeof(float), hipMemcpyHostToDevice);
+        offset[(size_t)m] = at;
+        poffset[(size_t)m] = pat;
+        at += n;
+        pat += np;
+    }
+    if (e != hipSuccess) {
+        free_device({cells, layers, profiles});
+        return fail(bh, CCV_MPPI_ERR_HIP, "set_occupancy: allocating or copying the layers", e);
+    }
+    std::vector<ccv_mppi_grid> geo((size_t)n_maps);
+    for (int m = 0; m < n_maps; ++m)
+        geo[(size_t)m] = ccv_mppi_grid{maps[m].origin_x, maps[m].origin_y, maps[m].resolution, maps[m].outside, maps[m].nx, maps[m].ny, nullptr};
+    if (int rc = install_maps(bh, geo, cells, offset, map_of, weight)) {
+        free_device({layers, profiles});
+        return rc;
+    }
+    bh->drop_layers();
+    bh->d_occ = layers;
+    bh->d_profile = profiles;
+    bh->profile_offset.swap(poffset);
+    for (int m = 0; m < n_maps; ++m) {
+        bh->occ_threshold.push_back(maps[m].threshold);
+        bh->occ_radius.push_back(inflation[m].radius);
+        bh->occ_free.push_back(inflation[m].free_value);
+    }
+    bh->occ = true;
+    // one full inflation per map; the stream is idle again before the tables point at the cells
+    for (int m = 0; m < n_maps; ++m) inflate(bh, m, 0, 0, maps[m].nx, maps[m].ny);
+    HIP_TRY(bh, hipGetLastError());
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));
+    return sync_tables(bh);
+}
+
+// Stream-ordered: the deferred resident update is not flushed (it reads no map), nothing is allocated, and the only wait is for
+// the writer that last read the staging slot about to be refilled.
+int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* bh, int32_t map, int32_t x0, int32_t y0, int32_t w, int32_t h, const uint8_t* patch) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "update_occupancy: ";
+    if (!bh->occ) return fail(bh, CCV_MPPI_ERR_STATE, "update_occupancy: no occupancy is set (ccv_mppi_batch_set_occupancy)");
+    if (!patch) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (map < 0 || map >= (int32_t)bh->grid_maps.size()) return refuse(bh, who, "map out of range");
+    const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
+    if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > g.nx - x0 || h > g.ny - y0) return refuse(bh, who, "the rectangle is not inside the map");
+    if ((int64_t)w * h > CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "more than CCV_MPPI_OCC_PATCH_MAX_CELLS cells");
+    const int slot = bh->patch_next;
+    bh->patch_next = (slot + 1) % Costmap::kPatchSlots;
+    if (bh->patch_used[slot]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[slot]));
+    const size_t at = (size_t)slot * CCV_MPPI_OCC_PATCH_MAX_CELLS;
+    std::memcpy(bh->h_patch + at, patch, (size_t)w * (size_t)h);
+    launch_occupancy_patch(bh->d_occ + bh->grid_offset[(size_t)map], g.nx, bh->d_patch + at, x0, y0, w, h, bh->stream);
+    HIP_TRY(bh, hipEventRecord(bh->patch_ev[slot], bh->stream));
+    bh->patch_used[slot] = true;
+    // A changed cell moves the cost of cells up to R away: the patch grown by R, clipped to the map, is derived again (from layer
+    // cells up to 2R from the patch).  A second launch: no workgroup of it reads a layer cell another is writing.
+    const int R = bh->occ_radius[(size_t)map];
+    const int32_t rx0 = x0 - R < 0 ? 0 : x0 - R, ry0 = y0 - R < 0 ? 0 : y0 - R;
+    const int32_t rx1 = x0 + w + R > g.nx ? g.nx : x0 + w + R, ry1 = y0 + h + R > g.ny ? g.ny : y0 + h + R;
+    inflate(bh, map, rx0, ry0, rx1 - rx0, ry1 - ry0);
+    HIP_TRY(bh, hipGetLastError());
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* bh, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    const int n = bh->occ ? (int)bh->grid_maps.size() : 0;
+    if ((maps || inflation) && (max_maps < 0 || max_maps < n)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_occupancy: max_maps below the number of maps");
+    if (n_maps) *n_maps = n;
+    for (int m = 0; m < n; ++m) {
+        const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+        if (maps) maps[m] = ccv_mppi_occupancy{g.origin_x, g.origin_y, g.resolution, g.outside, g.nx, g.ny, bh->occ_threshold[(size_t)m], nullptr};
+        if (inflation) inflation[m] = ccv_mppi_inflation{bh->occ_radius[(size_t)m], bh->occ_free[(size_t)m], nullptr};
+    }
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_read_occupancy(ccv_mppi_batch* bh, int32_t map, uint8_t* out) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!out) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->occ) return fail(bh, CCV_MPPI_ERR_STATE, "read_occupancy: no occupancy is set (ccv_mppi_batch_set_occupancy)");
+    if (map < 0 || map >= (int32_t)bh->grid_maps.size()) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "read_occupancy: map out of range");
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (queued patch writers)
+    const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
+    HIP_TRY(bh, hipMemcpy(out, bh->d_occ + bh->grid_offset[(size_t)map], (size_t)g.nx * (size_t)g.ny, hipMemcpyDeviceToHost));
     return CCV_MPPI_OK;
 }
 

@@ -4,7 +4,8 @@
 //   capi_resident.hip    device-resident closed loop of a single handle
 //   capi_stage.hip       stage-wise calls, read-back, timing
 //   capi_batch.hip       batch handles (ccv_mppi_batch_*): what a tick runs and what reads its results, the resident loop included
-//   capi_batch_config.hip  batch handles: what configures the next launch (parameters, shifted weights, discs, grids, fleet term)
+//   capi_batch_config.hip  batch handles: what configures the next launch (parameters, shifted weights, discs, grids and their
+//                          occupancy layers, fleet term)
 // A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".
@@ -28,6 +29,7 @@
 #include "mppi_update.h"
 #include "mppi_resident.h"
 #include "mppi_fleet.h"
+#include "mppi_costmap.h"
 
 namespace ccv {
 
@@ -264,6 +266,43 @@ struct Grids {
     void release() { free_device({d_grid_rows, d_grid_cells}); }
 };
 
+// occupancy layers (ccv_mppi_batch_set_occupancy, mppi_costmap.h): while `occ`, the cells of Grids are not a caller's but derived
+// on the device from a uint8 layer per map (same geometry, same offsets: layer m starts at d_occ + grid_offset[m]) and the map's
+// inflation; a patch of a layer is enqueued on the stream (ccv_mppi_batch_update_occupancy_enqueue) through the staging ring.
+// The ring is allocated at the first _set_occupancy and kept until destroy.
+struct Costmap {
+    bool occ = false;
+    uint8_t* d_occ = nullptr;                // the layers of all maps, one allocation
+    float* d_profile = nullptr;              // the profile tables of all maps, one allocation
+    std::vector<size_t> profile_offset;      // [n_maps] first entry of map m's table in d_profile
+    std::vector<int32_t> occ_threshold;      // [n_maps]
+    std::vector<int32_t> occ_radius;         // [n_maps] R, in cells
+    std::vector<float> occ_free;             // [n_maps] free_value
+    static constexpr int kPatchSlots = CCV_MPPI_OCC_PATCH_SLOTS;   // pinned staging of the patches, in rotation: a slot is refilled
+    uint8_t* h_patch = nullptr;              // only after the writer that read it has run; [kPatchSlots][CCV_MPPI_OCC_PATCH_MAX_CELLS]
+    uint8_t* d_patch = nullptr;              // its device address (the patch writer reads the slots in place)
+    hipEvent_t patch_ev[kPatchSlots] = {};
+    bool patch_used[kPatchSlots] = {};
+    int patch_next = 0;
+    // the layers and tables go (the maps become a caller's, or none); the ring stays
+    void drop_layers() {
+        free_device({d_occ, d_profile});
+        d_occ = nullptr;
+        d_profile = nullptr;
+        occ = false;
+        profile_offset.clear();
+        occ_threshold.clear();
+        occ_radius.clear();
+        occ_free.clear();
+    }
+    void release() {
+        for (hipEvent_t e : patch_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (h_patch) (void)hipHostFree(h_patch);
+        free_device({d_occ, d_profile});
+    }
+};
+
 // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
 // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
 // the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance).
@@ -289,7 +328,7 @@ struct Fleet {
 // batch_view): the core of a single handle, whose K is the instance's and whose
 // pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
 // one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
-struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Fleet {
+struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, Fleet {
     int B = 0, kpad = 0;
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)

@@ -257,6 +257,9 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_MAX_OBSTACLES 32        /* discs per instance */
 #define CCV_MPPI_GRID_MAX_DIM 32768      /* cells per axis of an occupancy grid */
 #define CCV_MPPI_GRID_MAX_CELLS (1 << 26) /* cells per occupancy grid */
+#define CCV_MPPI_INFLATE_MAX_RADIUS 64    /* cells: the largest inflation radius of ccv_mppi_batch_set_occupancy */
+#define CCV_MPPI_OCC_PATCH_MAX_CELLS (1 << 20) /* cells of one patch of ccv_mppi_batch_update_occupancy_enqueue */
+#define CCV_MPPI_OCC_PATCH_SLOTS 4        /* patches whose staging can be in flight before _update_occupancy_enqueue waits */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
 
@@ -371,7 +374,8 @@ int ccv_mppi_batch_read_fleet_velocities(ccv_mppi_batch* b, double* vxy);
  * formed.  A NaN state reads `outside`: that is the one rule for states that are not numbers.  The term touches the cost only:
  * noise, controls and states keep their bits, an instance with map_of[b] = -1 or weight[b] = 0 keeps every bit of its result
  * (G finite), and no map, map_of or weight of one instance changes a bit of another.  Nearest cell only: no interpolation, no
- * integer cells, no rotated maps, no partial updates -- a new map is a new _set_grids.
+ * integer cells, no rotated maps, no partial updates of a caller's float map -- a new map is a new _set_grids (a map kept as
+ * occupancy can be patched in stream order: ccv_mppi_batch_set_occupancy, _update_occupancy_enqueue below).
  * The term always runs the moving-disc kernels' GRID forms (_last_kernel: GRID | MOVING | OBST | VARIED | family, | SHIFT,
  * | WIDE): a handle without discs runs them over an empty disc list, a handle with static discs over a zero velocity table, whose
  * disc term equals the static one bit for bit.  nx, ny in [1, CCV_MPPI_GRID_MAX_DIM], nx * ny <= CCV_MPPI_GRID_MAX_CELLS.
@@ -388,6 +392,41 @@ typedef struct ccv_mppi_grid { double origin_x, origin_y, resolution; float outs
 int ccv_mppi_batch_set_grids(ccv_mppi_batch* b, const ccv_mppi_grid* maps, int32_t n_maps, const int32_t* map_of, const double* weight);
 int ccv_mppi_batch_get_grids(ccv_mppi_batch* b, ccv_mppi_grid* maps, int32_t max_maps, int32_t* n_maps, int32_t* map_of, double* weight);
 int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* b, int32_t map, float* cells_out);
+/* Costmaps inflated on the device (NOT reference behaviour; off by default; batch handles only).  A second source for the
+ * maps of the grid term above: instead of float cells the caller gives occupancy, and the device derives the float cells.  Map m
+ * has the geometry of ccv_mppi_grid (origin, resolution, nx, ny, outside), uint8 cells (row-major, x fastest), a threshold in
+ * [0, 255] and an inflation (radius R in cells, 0 <= R <= CCV_MPPI_INFLATE_MAX_RADIUS; profile [R * R + 1]; free_value):
+ *     occ(ix, iy)  = cells[iy * nx + ix] >= threshold               (a cell outside the map is not occupied)
+ *     D2(ix, iy)   = min over occupied (jx, jy) of (jx - ix)^2 + (jy - iy)^2      (int32; +inf if there is none)
+ *     cost(ix, iy) = D2 <= R * R ? profile[D2] : free_value
+ * -- an exact truncated Euclidean distance transform and a table the caller fills (a linear ramp, an exponential decay, a
+ * step): the device evaluates no function of the distance, so cost is defined in every bit.  cost is the float cell the GRID
+ * kernels read; everything the grid term's comment says holds with these cells, _get_grids and _read_grid_cells included.
+ * _set_occupancy: maps [n_maps], inflation [n_maps], map_of [B], weight [B]; cells and profiles are copied.  What _set_grids
+ * refuses, a threshold outside [0, 255], a radius outside [0, CCV_MPPI_INFLATE_MAX_RADIUS], a NULL profile, a non-finite profile
+ * entry or free_value: CCV_MPPI_ERR_INVALID_ARG, nothing changes.  maps == NULL or n_maps == 0 turns the term off, as
+ * _set_grids(NULL) does.  Flushes a pending resident update and synchronises, like _set_grids.  The two sources replace each
+ * other: a later _set_grids (maps or NULL) drops the occupancy layers.  _set_params, _set_obstacles, _set_obstacle_velocities,
+ * _set_min_shift and the fleet setters keep them.
+ * _update_occupancy_enqueue: the w x h rectangle at cell (x0, y0) of map `map` becomes `patch` (row-major, tightly packed,
+ * w * h <= CCV_MPPI_OCC_PATCH_MAX_CELLS), and the float cells the change can reach -- the rectangle grown by R, clipped to the
+ * map -- are derived again.  Stream-ordered: no synchronisation, no allocation, no flush of a pending resident update; the patch
+ * is copied out of the caller's buffer before the call returns; with CCV_MPPI_OCC_PATCH_SLOTS patches in flight the call waits
+ * for the oldest one's writer and nothing else.  A rollout enqueued before the call reads the old cells, every rollout enqueued
+ * after it the new ones; the call may come between _resident_step_enqueue calls and between _iterate_enqueue calls.  A
+ * rectangle not inside the map, w or h < 1, a patch of more cells than the limit (split it, or call _set_occupancy), a NULL
+ * patch, map out of range: CCV_MPPI_ERR_INVALID_ARG; no occupancy set: CCV_MPPI_ERR_STATE; nothing changes either way.
+ * _get_occupancy: maps [max_maps] (cells NULL) and inflation [max_maps] (profile NULL), *n_maps (0 unless occupancy is set); any
+ * may be NULL; max_maps below the number of maps with maps or inflation != NULL: CCV_MPPI_ERR_INVALID_ARG.
+ * _read_occupancy: out [ny * nx], the layer of map `map` read back from the device; synchronises (so does _read_grid_cells while
+ * occupancy is set); CCV_MPPI_ERR_STATE while no occupancy is set. */
+typedef struct ccv_mppi_occupancy { double origin_x, origin_y, resolution; float outside; int32_t nx, ny, threshold; const uint8_t* cells; } ccv_mppi_occupancy;
+typedef struct ccv_mppi_inflation { int32_t radius; float free_value; const float* profile; } ccv_mppi_inflation;
+int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* b, const ccv_mppi_occupancy* maps, const ccv_mppi_inflation* inflation, int32_t n_maps,
+                                 const int32_t* map_of, const double* weight);
+int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* b, int32_t map, int32_t x0, int32_t y0, int32_t w, int32_t h, const uint8_t* patch);
+int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* b, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps);
+int ccv_mppi_batch_read_occupancy(ccv_mppi_batch* b, int32_t map, uint8_t* out);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
