@@ -45,9 +45,9 @@ struct KernelChoice {
     KernelFamily stagewise = KernelFamily::FourWave;   // family of MODE_ROLLOUT / MODE_COST launches
     KernelFamily fused = KernelFamily::FourWave;       // family of the fused iteration: the same, or OneWave
     int lds_window = 1;                // CCV_MPPI_WINDOW=scalar -> 0: the plain kernel's scalar-load window variant (experiments)
-    bool fast_clamp_allowed = true;    // clampd_fast (mppi_kernels.h) unless CCV_MPPI_FAST_CLAMP=0
-    int prio_rotate = 0;               // pc_rotate_priority (mppi_rollout_pc.h)
-    int prune = 0;                     // pc_prune_window (mppi_rollout_pc.h)
+    bool fast_clamp_allowed = true;    // clampd_fast (mppi_device_util.h) unless CCV_MPPI_FAST_CLAMP=0
+    int prio_rotate = 0;               // pc_rotate_priority (mppi_handoff.h)
+    int prune = 0;                     // pc_prune_window (mppi_consume.h)
 };
 
 struct DeviceBuffers {
@@ -154,7 +154,7 @@ struct ResidentLoop {
     double res_angle_abs[3] = {0, 0, 0};   // conservative bounds on |yaw|, |roll|, |pitch| of the resident pose (fast_trig_safe)
 };
 
-// direct exchange of the partial vectors between the devices of a node (k_finalize_exchange, mppi_kernels.h)
+// direct exchange of the partial vectors between the devices of a node (k_finalize_exchange, mppi_update.h)
 struct Exchange {
     ExchangeBox* d_box = nullptr;                   // this device's box (peers write into it)
     ExchangeBox* box_peer[kMaxRanks] = {nullptr};   // every rank's box as mapped here ([xchg_rank] = d_box)

@@ -1,4 +1,5 @@
-// C ABI (include/ccv_mppi.h) over the gfx950 kernels of mppi_kernels.h.
+// C ABI (include/ccv_mppi.h) over the gfx950 rollout kernels (mppi_rollout_*.h, launched through mppi_launch.h; their shared
+// vocabulary: mppi_kernels.h).
 // Host side only orchestrates: allocate once, build the window coefficients, launch, copy u* back.
 // There is deliberately no CPU fallback: every entry point fails with CCV_MPPI_ERR_NO_DEVICE / _HIP.
 // The other host units (capi_internal.h lists them) call the plumbing defined here.
@@ -31,7 +32,7 @@ void fill_params(const ccv_mppi_config& c, const bool fast_clamp_allowed, Rollou
         A.umin[d] = c.u_min[d];
         A.umax[d] = c.u_max[d];
     }
-    // two-instruction clamps (clampd_fast, mppi_kernels.h) give the reference's values when no control is NaN and no pair of
+    // two-instruction clamps (clampd_fast, mppi_device_util.h) give the reference's values when no control is NaN and no pair of
     // bounds is out of order; the kernel adds its own test of the warm start
     A.fast_clamp = std::isfinite(c.control_noise) ? 1 : 0;
     for (int d = 0; d < udim_of(c.model); ++d)
@@ -210,7 +211,7 @@ int fast_trig_safe(const Core* h, const ccv_mppi_config& c, const RolloutArgs& A
         if (!(umax[1] * std::fabs(A.dt) <= kSmallTurnLimit) || !(umax[3] * std::fabs(A.dt) <= kSmallTurnLimit) ||
             !(umax[4] * std::fabs(A.dt) <= kSmallTurnLimit) || !(umax[2] <= kSmallTurnLimit))
             return kTrigUnsafe;
-        // ... and divides by dt through its reciprocal (div_uniform, mppi_kernels.h): nothing may overflow or vanish on the way
+        // ... and divides by dt through its reciprocal (div_uniform, mppi_device_util.h): nothing may overflow or vanish on the way
         if (!(std::fabs(A.dt) >= 1.0e-100 && std::fabs(A.dt) <= 1.0e100) || !(umax[0] <= 1.0e100) || !(umax[3] <= 1.0e100)) return kTrigUnsafe;
     }
     if (!(bound <= kFastTrigLimit)) return kTrigUnsafe;   // (also for NaN)
@@ -222,7 +223,7 @@ RolloutPlan plan_of(const ccv_mppi_handle* h, const RolloutArgs& A, const int mo
     return make_plan(*h, h->cfg.model, mode, fast_trig_safe(h, h->cfg, A, mode, has_wide_form(*h, mode)), 0, BatchForm::Single, false);
 }
 
-// mode: MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h).  A timed fused launch carries its events on the dispatch
+// mode: MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_kernels.h).  A timed fused launch carries its events on the dispatch
 // itself (timing_rollout_at).
 int launch_rollout(ccv_mppi_handle* h, const RolloutArgs& A_in, const Window& W, int mode) {
     RolloutArgs A = A_in;
@@ -546,7 +547,7 @@ int fetch_result(ccv_mppi_handle* h, double* u_opt_out, ccv_mppi_stats* stats) {
 }
 
 // the four-wave kernel's wave priorities: (rank + level[role] + b) mod 4 with the roles' levels per model -- noise / dynamics /
-// distance / store (r4_rotate_priority, mppi_rollout_pc.h: where the numbers are)
+// distance / store (r4_rotate_priority, mppi_handoff.h: where the numbers are)
 static int r4_prio_levels(int model) {
     auto levels = [](int noise, int dynamics, int distance, int store) { return 16 + (noise | dynamics << 2 | distance << 4 | store << 6); };
     return model == CCV_MPPI_DIFF_DRIVE ? levels(3, 2, 1, 0) : model == CCV_MPPI_STEERING_DIFF_DRIVE ? levels(2, 3, 1, 0) : levels(0, 1, 2, 3);

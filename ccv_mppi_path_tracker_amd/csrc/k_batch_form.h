@@ -4,6 +4,7 @@
 // (mppi_launch.hip) sends no such plan here.
 #pragma once
 #include "mppi_launch.h"
+#include "mppi_rollout_plain.h"
 #include "mppi_rollout_r4.h"
 #include "mppi_rollout_solo.h"
 

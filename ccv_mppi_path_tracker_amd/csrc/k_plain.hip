@@ -1,6 +1,7 @@
 // translation unit: the plain one-sample-per-lane kernel (k_rollout_cost, OCML sincos: the path of unbounded headings and the
 // experiment baseline CCV_MPPI_KERNEL=v1) and the stand-alone sampling() kernel
 #include "mppi_launch.h"
+#include "mppi_rollout_plain.h"
 
 namespace ccv {
 

@@ -1,10 +1,14 @@
-// HIP kernels of the MPPI hot path for gfx950 (MI355X).  Hand-written, wave64, one sample per lane.
+// The shared vocabulary of the MPPI rollout kernels for gfx950 (MI355X) and of the host code that launches them: constants,
+// the MODE_* / SRC_* enums, the argument structs (Window, ResidentFrame, BatchHead / BatchParams / GridRow, BatchForm,
+// RolloutArgs) and a workgroup's view of them (batch_view, rollout_view, stage_window).  No kernel and no cost arithmetic.
+// Hand-written HIP, wave64, one sample per lane; the kernels over these types:
 //
 //   k_rollout_cost   sampling() + predict_States() + calc_Cost()/calc_MinDistance() + exp   (dd:81-124,183-221;
-//                    sd:97-140,199-237; fb:394-424,445-520)
+//                    sd:97-140,199-237; fb:394-424,445-520)  -- the plain family, mppi_rollout_plain.h; the cooperative
+//                    families: mppi_rollout_r4.h, mppi_rollout_r3.h, mppi_rollout_pc.h, mppi_rollout_solo.h
 //   k_update_partials / k_finalize / k_apply_partials    calc_Weights() normalisation + determine_OptimalSolution()
 //                    (dd:216-237, sd:232-255, fb:437-326)  -- in mppi_update.h
-//   k_sample         stand-alone sampling() for the stage-wise ABI
+//   k_sample         stand-alone sampling() for the stage-wise ABI  -- mppi_rollout_plain.h
 //   k_gather_xy      strided read-back feeding publish_CandidatePath() (dd:265-294)
 //
 // Data layout in HBM (all fp64, k fastest => every store/load of a wave is one contiguous 512-byte run):
@@ -23,11 +27,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <type_traits>
-#include <utility>
-
 #include "../../include/ccv_mppi.h"
-#include "noise_spec.h"
 
 #if defined(CCV_DIAG)
 #include "mppi_diag.h"   // in-kernel time stamps of the diagnostic builds (tools/ablate.py, tools/stamps_r4.py)
@@ -43,6 +43,9 @@ constexpr int kTU = 8;        // time steps per register block (kTU*u_dim is a m
 constexpr int kBlock = 256;   // 4 waves: one per SIMD of a CU
 constexpr int kChunk = 2048;  // samples per k_update_partials block
 constexpr int kPcSamples = 64;   // samples per block of the cooperative kernels: one per lane (mppi_rollout_*.h)
+constexpr int kPartialMin = 4;   // fewest control steps of a horizon's last block that is made as a masked batch (pc_produce_batched,
+                                 // PARTIAL, mppi_produce.h: why 4); the launcher picks the four-wave kernel's TAIL form by it
+constexpr int kMaxObst = CCV_MPPI_MAX_OBSTACLES;   // discs per instance (mppi_cost_terms.h)
 
 enum : int { MODE_FUSED = 0, MODE_ROLLOUT = 1, MODE_COST = 2 };
 //   MODE_FUSED    device Philox noise, controls + states stored, cost + weight   (ccv_mppi_iterate*)
@@ -61,7 +64,7 @@ struct Window {
     double c[kMaxH];
 };
 
-// Device-resident closed loop (k_advance below): the pose, the window built from it and its distance coefficients stay
+// Device-resident closed loop (k_advance, mppi_resident.h): the pose, the window built from it and its distance coefficients stay
 // in HBM; a rollout launched with RolloutArgs::frame set takes x0, yaw_ref0 and the window from here instead of from its
 // kernel arguments.
 struct ResidentFrame {
@@ -124,10 +127,10 @@ static_assert(sizeof(GridRow) == 64, "one 64-byte line per instance");
 //   Single  a single handle: no records
 //   Batch   + the instances' records (BatchHead, batch_view below)
 //   Varied  + the per-instance parameter table (BatchParams above)
-//   Obst    + the instance's disc obstacles (obst_stage, obst_term below)
-//   Moving  + the discs' velocities (obst_stage_moving, obst_term_moving below)
-//   Grid    + the instance's occupancy grid (GridRow above, grid_tap below)
-// The shifted weights (SHIFT, pc_shifted_weight in mppi_rollout_pc.h) are the one independent bit: on any rung from Varied up.
+//   Obst    + the instance's disc obstacles (obst_stage, obst_term: mppi_cost_terms.h)
+//   Moving  + the discs' velocities (obst_stage_moving, obst_term_moving: mppi_cost_terms.h)
+//   Grid    + the instance's occupancy grid (GridRow above, grid_tap: mppi_cost_terms.h)
+// The shifted weights (SHIFT, pc_shifted_weight in mppi_epilogue.h) are the one independent bit: on any rung from Varied up.
 enum class BatchForm : int { Single, Batch, Varied, Obst, Moving, Grid };
 constexpr int kBatchHeadDoubles = 16;
 __host__ __device__ constexpr int batch_record_doubles(int H) { return kBatchHeadDoubles + ((3 * H + 7) & ~7); }
@@ -140,7 +143,7 @@ struct RolloutArgs {
     double umin[5], umax[5];
     double w_path, w_v, w_zmp, w_rollv, w_back, w_yaw;
     double fb_mass, fb_L, fb_Ixx, fb_gz;  // fb.h:212-216, fb:86-91, fb.h:30
-    double inv_dt;                        // 1 / dt, correctly rounded on the host: div_uniform() below
+    double inv_dt;                        // 1 / dt, correctly rounded on the host: div_uniform(), mppi_device_util.h
     uint32_t seed_lo, seed_hi, iter_lo, iter_hi;
     int32_t K, pitch, H, k_offset;
     int32_t steer_off, store_u, store_xy, do_cost;
@@ -272,619 +275,5 @@ __device__ __forceinline__ void stage_window(const RolloutArgs& A, const Window&
         }
     }
 }
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl<N>(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
-// x / d for a wave-uniform divisor d whose reciprocal r = RN(1 / d) was formed once: q = RN(x r), the exact remainder
-// x - q d by FMA, one correction -- the correctly rounded quotient (Markstein's theorem for a faithful q and a correctly
-// rounded r), in 3 instructions instead of the ~10 of an fp64 division.  The full-body ZMP term divides by dt twice per
-// sample-step (fb:469, fb:479-481).  (Its third division, by mass * gravity_.z (fb:601), stays a division: one more pair of
-// kernel-argument registers pushes the one-wave full-body kernel from 232 to 256 VGPRs with 17 spilled -- SGPR spills live
-// in VGPR lanes -- and costs more than the division: C4 287 -> 294 us, measured.)  Valid while nothing overflows or
-// vanishes on the way (the host admits the kernels that use it only for 1e-100 <= |dt| <= 1e100 and control bounds below
-// 1e100, fast_trig_safe(); anything else runs the plain kernel with true divisions); a zero quotient may lose its sign.
-__device__ __forceinline__ double div_uniform(const double x, const double d, const double r) {
-    const double q = x * r;
-    return fma(fma(-q, d, x), r, q);
-}
-
-// dd:62-67
-__device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// The same value in two instructions instead of six (two compares, four selects) -- for every v that is not NaN and bounds
-// with lo <= hi (NaN bounds pass v through in both forms).  The reference's clamp passes a NaN control through (dd:98-99: both
-// comparisons are false), min / max would replace it by a bound: the kernels use this form only where the host has checked
-// sigma and the bounds and the kernel itself has found no NaN in the warm start (RolloutArgs::fast_clamp; a control is
-// double(z) * sigma + u* with a finite z).  (-0 against a bound of +0 comes out as +0 here and -0 there: equal values.)
-__device__ __forceinline__ double clampd_fast(double v, double lo, double hi) { return __builtin_fmin(__builtin_fmax(v, lo), hi); }
-template <bool FAST>
-__device__ __forceinline__ double clampd_as(double v, double lo, double hi) {
-    if constexpr (FAST) return clampd_fast(v, lo, hi);
-    else return clampd(v, lo, hi);
-}
-
-// ---- per-instance disc obstacles of a batch handle (OBST kernels) -----------------------------
-// The power of a point p with respect to disc j, |p - o_j|^2 - r_j^2, is |p|^2 + a_j px + b_j py + c_j in pose-relative
-// coordinates -- the window distance's form with c_j = |o_j - x0|^2 - r_j^2 -- so the deepest penetration over the discs is
-// a second minimum of the same kind over a second, short coefficient list.
-constexpr int kMaxObst = CCV_MPPI_MAX_OBSTACLES;
-struct ObstLds {
-    double2 ab[kMaxObst];
-    double c[kMaxObst];
-};
-// the instance's obstacle fields, from the row of the parameter table its record's head points at (A.frame: batch_view);
-// wave-uniform, read through the constant address space
-struct ObstRow {
-    const double* xyr;
-    double w;
-    int n;
-};
-__device__ __forceinline__ ObstRow obst_row(const RolloutArgs& A) {
-    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
-    typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
-    const auto& P = *(ConstParams)(const void*)((ConstHead)(const void*)A.frame)->params;
-    const int n = P.n_obst;
-    return ObstRow{P.obst, P.w_obs, n < 0 ? 0 : (n > kMaxObst ? kMaxObst : n)};
-}
-// staging, once per workgroup: thread j = 0 .. kMaxObst-1 writes disc j's coefficients relative to the pose the kernel holds,
-// or the padding a = b = 0, c = +inf (never the minimum) past the instance's count
-__device__ __forceinline__ void obst_stage(const RolloutArgs& A, ObstLds& ob, const int j) {
-    const ObstRow o = obst_row(A);
-    double a = 0.0, b = 0.0, c = INFINITY;
-    if (j < o.n) {
-        const double ox = o.xyr[3 * j], oy = o.xyr[3 * j + 1], r = o.xyr[3 * j + 2];
-        const double dx = ox - A.x0[0], dy = oy - A.x0[1];
-        a = -2.0 * dx;
-        b = -2.0 * dy;
-        c = fma(dx, dx, dy * dy) - r * r;
-    }
-    ob.ab[j] = make_double2(a, b);
-    ob.c[j] = c;
-}
-// cost += w_obs * max(max_j(r_j^2 - |p - o_j|^2), 0) for states i < nv of the NV held in registers (p relative to the pose).
-// m: registers for the running minima (the window loop's, dead by now).  Four discs per iteration over the padded list; a NaN
-// position gives s = NaN and v_max_f64(-NaN, 0) = 0.
-template <int NV, int NM, bool MASK = false>   // MASK: only the first nv of the NV states count (the plain kernel's blocks)
-__device__ __forceinline__ void obst_term(const RolloutArgs& A, const ObstLds& ob, const double (&px)[NM], const double (&py)[NM],
-                                          double (&m)[NM], double& cost, const int nv = NV) {
-    const ObstRow o = obst_row(A);
-    const int n4 = (o.n + 3) & ~3;
-    if (n4 == 0) return;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) m[i] = INFINITY;
-    if constexpr (MASK) {
-        // the plain kernel: one disc per iteration, as window_min -- four at a time cost it 21 registers and a wave per SIMD
-#pragma unroll 1
-        for (int j = 0; j < n4; ++j) {
-            const double2 ab = ob.ab[j];
-            const double c = ob.c[j];
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const double t = fma(ab.x, px[i], fma(ab.y, py[i], c));
-                asm("v_min_f64 %0, %1, %2" : "=v"(m[i]) : "v"(m[i]), "v"(t));
-            }
-        }
-    } else {
-        for (int j = 0; j < n4; j += 4) {
-            double2 ab[4];
-            double c[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                ab[jj] = ob.ab[j + jj];
-                c[jj] = ob.c[j + jj];
-            }
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const double f0 = fma(ab[0].x, px[i], fma(ab[0].y, py[i], c[0]));
-                const double f1 = fma(ab[1].x, px[i], fma(ab[1].y, py[i], c[1]));
-                const double f2 = fma(ab[2].x, px[i], fma(ab[2].y, py[i], c[2]));
-                const double f3 = fma(ab[3].x, px[i], fma(ab[3].y, py[i], c[3]));
-                const double t = fmin(fmin(f0, f1), fmin(f2, f3));
-                asm("v_min_f64 %0, %1, %2" : "=v"(m[i]) : "v"(m[i]), "v"(t));   // (two quiet operands: pc_consume)
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const double s = m[i] + fma(px[i], px[i], py[i] * py[i]);
-        double g;
-        asm("v_max_f64 %0, -%1, 0" : "=v"(g) : "v"(s));
-        if (!MASK || i < nv) cost = fma(o.w, g, cost);
-    }
-}
-
-// ---- moving discs (MOVING kernels, on OBST) -----------------------------------------------------
-// Disc j has a constant velocity v_j over the horizon: state k (k dynamics steps after the pose) is charged against the disc at
-// o_j + v_j tau_k, tau_k = k dt.  The power of the point stays linear in (px, py); its coefficients become polynomials in tau:
-//   a_j(tau) = a_j - 2 vx_j tau,  b_j(tau) = b_j - 2 vy_j tau,  c_j(tau) = c_j + 2 (d_j . v_j) tau + |v_j|^2 tau^2.
-// Seven doubles per disc are staged once per workgroup; the coefficients of a (disc, state) pair are formed per lane, 4 FMA,
-// from tau_k held wave-uniform.
-struct ObstMovLds {
-    double2 ab[kMaxObst];    // a, b
-    double2 vab[kMaxObst];   // -2 vx, -2 vy
-    double c[kMaxObst], c1[kMaxObst], c2[kMaxObst];   // c, 2 (d . v), |v|^2
-};
-__device__ __forceinline__ const double* obst_velocity_rows(const RolloutArgs& A) {
-    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
-    typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
-    return (*(ConstParams)(const void*)((ConstHead)(const void*)A.frame)->params).obst_v;
-}
-// staging: obst_stage's a, b, c, and the velocity's four coefficients; the padding has zero velocity
-__device__ __forceinline__ void obst_stage_moving(const RolloutArgs& A, ObstMovLds& ob, const int j) {
-    const ObstRow o = obst_row(A);
-    const double* vrows = obst_velocity_rows(A);
-    double a = 0.0, b = 0.0, c = INFINITY, va = 0.0, vb = 0.0, c1 = 0.0, c2 = 0.0;
-    if (j < o.n) {
-        const double ox = o.xyr[3 * j], oy = o.xyr[3 * j + 1], r = o.xyr[3 * j + 2];
-        const double vx = vrows[2 * j], vy = vrows[2 * j + 1];
-        const double dx = ox - A.x0[0], dy = oy - A.x0[1];
-        a = -2.0 * dx;
-        b = -2.0 * dy;
-        c = fma(dx, dx, dy * dy) - r * r;
-        va = -2.0 * vx;
-        vb = -2.0 * vy;
-        c1 = 2.0 * fma(dx, vx, dy * vy);
-        c2 = fma(vx, vx, vy * vy);
-    }
-    ob.ab[j] = make_double2(a, b);
-    ob.vab[j] = make_double2(va, vb);
-    ob.c[j] = c;
-    ob.c1[j] = c1;
-    ob.c2[j] = c2;
-}
-// a wave-uniform double into scalar registers (the compiler cannot see that a converted integer is uniform)
-__device__ __forceinline__ double uniform_f64(const double v) {
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-// obst_term with the discs where they are at each state's own time: state i of the NV held in registers is global step
-// k0 + i (k0: the block's first step, wave-uniform), tau = double(k0 + i) * dt, one rounding.  One disc per iteration over the
-// instance's own count; per (disc, state): at = fma(va, tau, a), bt = fma(vb, tau, b), ct = fma(fma(c2, tau, c1), tau, c),
-// f = fma(at, px, fma(bt, py, ct)).  The rest is obst_term's.  With v = 0 every at, bt, ct is a, b, c exactly (tau finite).
-template <int NV, int NM, bool MASK = false>
-__device__ __forceinline__ void obst_term_moving(const RolloutArgs& A, const ObstMovLds& ob, const double (&px)[NM], const double (&py)[NM],
-                                                 double (&m)[NM], double& cost, const int k0, const int nv = NV) {
-    const ObstRow o = obst_row(A);
-    if (o.n == 0) return;
-    double tau[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        tau[i] = uniform_f64((double)(k0 + i) * A.dt);
-        if constexpr (!MASK) m[i] = INFINITY;
-    }
-    if constexpr (MASK) {
-        // the plain kernel: state by state, one running minimum alive at a time -- the same pairs, hence the same minima; with
-        // all eight alive beside a disc's seven coefficients it needed 139 registers and lost a wave per SIMD
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            double mi = INFINITY;
-#pragma unroll 1
-            for (int j = 0; j < o.n; ++j) {
-                const double2 ab = ob.ab[j], vab = ob.vab[j];
-                const double c = ob.c[j], c1 = ob.c1[j], c2 = ob.c2[j];
-                const double at = fma(vab.x, tau[i], ab.x);
-                const double bt = fma(vab.y, tau[i], ab.y);
-                const double ct = fma(fma(c2, tau[i], c1), tau[i], c);
-                const double t = fma(at, px[i], fma(bt, py[i], ct));
-                asm("v_min_f64 %0, %1, %2" : "=v"(mi) : "v"(mi), "v"(t));
-            }
-            const double s = mi + fma(px[i], px[i], py[i] * py[i]);
-            double g;
-            asm("v_max_f64 %0, -%1, 0" : "=v"(g) : "v"(s));
-            if (i < nv) cost = fma(o.w, g, cost);
-        }
-    } else {
-        // the cooperative kernels: disc by disc, all NV running minima alive, every state counted
-#pragma unroll 1
-        for (int j = 0; j < o.n; ++j) {
-            const double2 ab = ob.ab[j], vab = ob.vab[j];
-            const double c = ob.c[j], c1 = ob.c1[j], c2 = ob.c2[j];
-#pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const double at = fma(vab.x, tau[i], ab.x);
-                const double bt = fma(vab.y, tau[i], ab.y);
-                const double ct = fma(fma(c2, tau[i], c1), tau[i], c);
-                const double t = fma(at, px[i], fma(bt, py[i], ct));
-                asm("v_min_f64 %0, %1, %2" : "=v"(m[i]) : "v"(m[i]), "v"(t));
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const double s = m[i] + fma(px[i], px[i], py[i] * py[i]);
-            double g;
-            asm("v_max_f64 %0, -%1, 0" : "=v"(g) : "v"(s));
-            cost = fma(o.w, g, cost);
-        }
-    }
-}
-
-// ---- occupancy grid (GRID kernels, on MOVING) ------------------------------------------------------
-// State (x, y) AS STORED (absolute, the doubles of ccv_mppi_batch_read_candidates) reads one cell:
-//   fx = (x - origin_x) * inv, fy = (y - origin_y) * inv      (one subtraction, one multiplication each, no FMA)
-//   in = fx >= 0 && fx < nx && fy >= 0 && fy < ny             (fp64 compares: false for NaN, so a NaN state reads `outside`)
-//   v  = in ? cells[(int)fy * nx + (int)fx] : outside
-// G = the fp64 sum of (double)v over the states the path term covers, in state order from 0.0; cost = fma(w, G, cost) is the
-// LAST thing added to a sample's cost.  The row is read wave-uniformly through the constant address space (as obst_row).
-typedef const GridRow __attribute__((address_space(4))) * ConstGridRow;
-__device__ __forceinline__ ConstGridRow grid_row(const RolloutArgs& A) {
-    typedef const BatchHead __attribute__((address_space(4))) * ConstHead;
-    typedef const BatchParams __attribute__((address_space(4))) * ConstParams;
-    return (ConstGridRow)(const void*)(*(ConstParams)(const void*)((ConstHead)(const void*)A.frame)->params).grid;
-}
-// the gather of one state: ONE unconditional load whose address is the cell's, or that of the row's own `outside` field when the
-// state is in no cell -- so a block's gathers are in flight together with no branch between them, and nothing but the loaded
-// float is alive until it is summed (held beside the gathers, eight `in` masks cost the four-wave kernels sixteen scalar
-// registers, which they spill into vector lanes)
-struct GridTap {
-    float v;
-};
-__device__ __forceinline__ GridTap grid_tap(const ConstGridRow g, const double x, const double y) {
-    typedef const float __attribute__((address_space(1))) * GlobalF32;
-    const double fx = (x - g->origin_x) * g->inv;
-    const double fy = (y - g->origin_y) * g->inv;
-    const int nx = g->nx;
-    const bool in = fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)g->ny;
-    const int ix = (int)(in ? fx : 0.0), iy = (int)(in ? fy : 0.0);   // (in: 0 <= fx < 32 768 -- truncation is exact)
-    const uint64_t cell = (uint64_t)(uintptr_t)g->cells + (uint64_t)(uint32_t)(iy * nx + ix) * 4u;   // (nx ny <= 2^26)
-    const uint64_t outside = (uint64_t)(uintptr_t)(const void*)g + offsetof(GridRow, outside);
-    return GridTap{*(GlobalF32)(uintptr_t)(in ? cell : outside)};
-}
-__device__ __forceinline__ double grid_value(const GridTap& t) { return (double)t.v; }
-// the per-lane accumulator of a wave that meets every state of its sample (null row: the instance has no map).  slot: the sum
-// lives in LDS instead of in G (the plain kernel)
-struct GridAcc {
-    ConstGridRow row;
-    double G;
-    int nstates;   // states that reach the path cost
-    double* slot;
-};
-// states t0 .. t0+NV-1 held in registers: all gathers first (grid_issue), then the sum in state order (grid_sum); states at or
-// past nstates do not count
-template <int NV>
-__device__ __forceinline__ void grid_issue(const GridAcc& ga, const double (&xv)[NV], const double (&yv)[NV], GridTap (&tap)[NV]) {
-    if (!ga.row) return;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) tap[i] = grid_tap(ga.row, xv[i], yv[i]);
-}
-template <int NV>
-__device__ __forceinline__ void grid_sum(GridAcc& ga, const GridTap (&tap)[NV], const int t0) {
-    if (!ga.row) return;
-    double G = ga.slot ? *ga.slot : ga.G;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-        if (t0 + i < ga.nstates) G += grid_value(tap[i]);
-    if (ga.slot) *ga.slot = G;
-    else ga.G = G;
-}
-__device__ __forceinline__ double grid_total(const GridAcc& ga) { return ga.slot ? *ga.slot : ga.G; }
-
-// min over the H window points of (a_j*px + b_j*py + c_j) for NV trajectory points held in registers.
-// 2 FMA + 1 MIN per (point, window point): the O(K*H^2) core (calc_MinDistance, dd:183-192).
-template <int NV, bool LDSWIN>
-__device__ __forceinline__ void window_min(const double (&px)[kTU], const double (&py)[kTU], double (&m)[kTU], int H,
-                                           const Window& W, const double2* s_ab, const double* s_c) {
-#pragma unroll 2
-    for (int j = 0; j < H; ++j) {
-        double a, b, c;
-        if constexpr (LDSWIN) {
-            const double2 ab = s_ab[j];
-            a = ab.x;
-            b = ab.y;
-            c = s_c[j];
-        } else {
-            a = W.a[j];
-            b = W.b[j];
-            c = W.c[j];
-        }
-        static_for<NV>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            m[i] = fmin(m[i], fma(a, px[i], fma(b, py[i], c)));
-        });
-    }
-}
-
-// BATCH: grid (workgroups per instance, B), instance = blockIdx.y (batch_view); VARIED: with per-instance parameters;
-// OBST (on VARIED): with the instance's disc obstacles (obst_term); MOVING (on OBST): the discs move (obst_term_moving);
-// GRID (on MOVING): the instance's occupancy grid, read in the state loop where x and y are stored (grid_tap)
-template <int MODEL, int SRC, bool LDSWIN, BatchForm FORM = BatchForm::Single>
-__global__ __launch_bounds__(kBlock) void k_rollout_cost(const RolloutArgs Ak, const Window W) {
-    constexpr bool BATCH = FORM >= BatchForm::Batch, VARIED = FORM >= BatchForm::Varied, OBST = FORM >= BatchForm::Obst,
-                   MOVING = FORM >= BatchForm::Moving, GRID = FORM >= BatchForm::Grid;
-    static_assert(!BATCH || (LDSWIN && SRC == SRC_PHILOX), "the batch runs the fused iteration with the LDS window");
-    constexpr int UD = udim_of(MODEL);
-    __shared__ double2 s_ab[LDSWIN ? kMaxH : 1];
-    __shared__ double s_c[LDSWIN ? kMaxH : 1];
-    const RolloutArgs A = BATCH ? batch_view<VARIED>(Ak, (int)blockIdx.y) : Ak;
-    const int H = A.H;
-    ObstLds* obst_lds = nullptr;
-    ObstMovLds* obst_mov = nullptr;
-    if constexpr (MOVING) {
-        __shared__ ObstMovLds s_obst_mov;
-        obst_mov = &s_obst_mov;
-    } else if constexpr (OBST) {
-        __shared__ ObstLds s_obst;
-        obst_lds = &s_obst;
-    }
-    if constexpr (BATCH) {
-        const double* win = reinterpret_cast<const double*>(A.frame) + kBatchHeadDoubles;
-        for (int j = threadIdx.x; j < H; j += kBlock) {
-            s_ab[j] = make_double2(win[j], win[H + j]);
-            s_c[j] = win[2 * H + j];
-        }
-        if constexpr (MOVING) {
-            if (threadIdx.x < kMaxObst) obst_stage_moving(A, *obst_mov, (int)threadIdx.x);
-        } else if constexpr (OBST) {
-            if (threadIdx.x < kMaxObst) obst_stage(A, *obst_lds, (int)threadIdx.x);
-        }
-        __syncthreads();
-    } else if constexpr (LDSWIN) {
-        for (int j = threadIdx.x; j < H; j += kBlock) {
-            s_ab[j] = make_double2(W.a[j], W.b[j]);
-            s_c[j] = W.c[j];
-        }
-        __syncthreads();
-    }
-    const int k = blockIdx.x * kBlock + threadIdx.x + (BATCH ? (int)blockIdx.y * ((Ak.K + 63) & ~63) : 0);
-    const bool live = k < A.K;
-    const int kk = live ? k : A.K - 1;
-    const size_t pitch = (size_t)A.pitch;
-    const double dt = A.dt;
-    const uint32_t kg = (uint32_t)(A.k_offset + kk);
-
-    double x = A.x0[0], y = A.x0[1], yaw = A.x0[2];
-    double roll = A.x0[3], pitchang = A.x0[4];
-    double cost = 0.0;
-    if constexpr (MODEL == CCV_MPPI_FULL_BODY) {
-        // fb:408 -- identical for every sample
-        cost += A.w_yaw * (yaw - A.yaw_ref0) * (yaw - A.yaw_ref0);
-    }
-    // full-body carry from step t-1 (the ZMP term of index t-1 needs controls t-1 and t, fb:468-486)
-    double p_v = 0.0, p_rv = 0.0, p_sdir = 0.0, p_cdir = 1.0, p_c2 = 0.0, p_c3 = 0.0, p_ac = 0.0;
-    const double fb_mgz = A.fb_mass * A.fb_gz;    // (mass*gravity_).z
-    const double fb_den = A.fb_mass * A.fb_gz;    // mass*(gravity_-accel).dot(z); accel.z == 0 (fb:475,601)
-
-    GridAcc grid_acc{};
-    if constexpr (GRID) {
-        // the lane's running sum lives in LDS (2 KB): in two registers it took the diff-drive and steering forms from 127 to 131
-        // and a workgroup per CU away; for the same reason every gather is summed at once -- this is the fallback family
-        __shared__ double s_grid[kBlock];
-        s_grid[threadIdx.x] = 0.0;
-        grid_acc = GridAcc{grid_row(A), 0.0, MODEL == CCV_MPPI_FULL_BODY ? H - 2 : H, &s_grid[threadIdx.x]};
-    }
-    for (int t0 = 0; t0 < H; t0 += kTU) {
-        double px[kTU], py[kTU];
-        float zq[4] = {0.f, 0.f, 0.f, 0.f};
-        static_for<kTU>([&](auto TT) {
-            constexpr int tt = decltype(TT)::value;
-            const int t = t0 + tt;
-            px[tt] = x - A.x0[0];
-            py[tt] = y - A.x0[1];
-            if constexpr (GRID) {
-                if (grid_acc.row && t < grid_acc.nstates) *grid_acc.slot += grid_value(grid_tap(grid_acc.row, x, y));
-            }
-            if (t < H) {
-                if (A.store_xy && live) {
-                    A.xs[(size_t)t * pitch + k] = x;
-                    A.ys[(size_t)t * pitch + k] = y;
-                }
-                if (t < H - 1) {
-                    double u[UD];
-                    static_for<UD>([&](auto D) {
-                        constexpr int d = decltype(D)::value;
-                        constexpr int nloc = tt * UD + d;
-                        const size_t row = (size_t)(t * UD + d);
-                        if constexpr (SRC == SRC_PHILOX) {
-                            if constexpr ((nloc & 3) == 0) {
-                                const Philox4 r = philox4x32_10(kg, (uint32_t)((t0 * UD + nloc) >> 2), A.iter_lo,
-                                                                A.iter_hi, A.seed_lo, A.seed_hi);
-                                box_muller_f32(r.x, r.y, zq[0], zq[1]);
-                                box_muller_f32(r.z, r.w, zq[2], zq[3]);
-                            }
-                            // libstdc++ normal_distribution: ret * stddev + mean (dd:96-97), then clamp (dd:98-99)
-                            double v = (double)zq[nloc & 3] * A.sigma + A.nominal[row];
-                            v = clampd(v, A.umin[d], A.umax[d]);
-                            if constexpr (MODEL == CCV_MPPI_FULL_BODY && d == 2) {
-                                if (A.steer_off) v = 0.0;  // fb:517
-                            }
-                            u[d] = v;
-                            if (A.store_u && live) A.u[row * pitch + k] = v;
-                        } else {
-                            u[d] = A.u[row * pitch + kk];
-                        }
-                    });
-                    // ---- cost terms that do not need the window ----
-                    if (A.do_cost) {
-                        if constexpr (MODEL != CCV_MPPI_FULL_BODY) {
-                            cost += A.w_v * ((u[0] - A.v_ref) * (u[0] - A.v_ref));  // dd:204-206
-                        } else {
-                            if (t < H - 2) {  // fb:409
-                                cost += A.w_v * (u[0] - A.v_ref) * (u[0] - A.v_ref);          // fb:413
-                                if (u[0] < 0.0) cost += A.w_back * u[0] * u[0];               // fb:420
-                            }
-                            if (t >= 1) {  // finish index t-1 <= H-3: ZMP (fb:468-485, 597-603) and roll-rate terms
-                                const double drive_accel = (u[0] - p_v) / dt;                  // fb:469
-                                const double ay = drive_accel * p_sdir + p_ac * p_cdir;        // fb:473
-                                const double hgdot_x = (A.fb_Ixx * u[3] - A.fb_Ixx * p_rv) / dt;  // fb:479-481
-                                const double mo_x = (p_c2 * fb_mgz + p_c3 * (A.fb_mass * ay)) - hgdot_x;  // fb:600
-                                const double zmp_y = mo_x / fb_den;                            // fb:601
-                                cost += A.w_zmp * zmp_y * zmp_y;                               // fb:416
-                                cost += A.w_rollv * (u[3] - p_rv) * (u[3] - p_rv);             // fb:418
-                            }
-                        }
-                    }
-                    // ---- dynamics: explicit Euler (dd:104-109, sd:120-125, fb:445-452) ----
-                    double hd = yaw;
-                    if constexpr (MODEL != CCV_MPPI_DIFF_DRIVE) hd = yaw + u[2];
-                    double sn, cs;
-                    sincos(hd, &sn, &cs);
-                    if constexpr (MODEL == CCV_MPPI_FULL_BODY) {
-                        if (A.do_cost) {
-                            double sd_, cd_, sr_, cr_;
-                            sincos(u[2], &sd_, &cd_);
-                            sincos(roll, &sr_, &cr_);
-                            p_sdir = sd_;
-                            p_cdir = cd_;
-                            p_c2 = -A.fb_L * sr_;                      // CoM.y (fb:482)
-                            p_c3 = A.fb_L * cos(pitchang) * cr_;       // CoM.z
-                            p_ac = u[0] * u[1];                        // fb:471
-                            p_v = u[0];
-                            p_rv = u[3];
-                        }
-                    }
-                    x = x + u[0] * cs * dt;
-                    y = y + u[0] * sn * dt;
-                    yaw = yaw + u[1] * dt;
-                    if constexpr (MODEL == CCV_MPPI_FULL_BODY) {
-                        roll = roll + u[3] * dt;
-                        pitchang = pitchang + u[4] * dt;
-                    }
-                } else {
-                    if constexpr (MODEL != CCV_MPPI_FULL_BODY) {
-                        // t == H-1: the reference reads control index H-1, one past the end (dd:199,204); defined
-                        // semantics: that element is 0.0
-                        if (A.do_cost) cost += A.w_v * ((0.0 - A.v_ref) * (0.0 - A.v_ref));
-                    }
-                }
-            }
-        });
-        if (A.do_cost) {
-            // states that reach the path cost: all H for dd/sd (dd:199), the first H-2 for fb (fb:409)
-            const int nstates = (MODEL == CCV_MPPI_FULL_BODY) ? H - 2 : H;
-            const int nv = min(kTU, nstates - t0);
-            if (nv > 0) {
-                double m[kTU];
-#pragma unroll
-                for (int i = 0; i < kTU; ++i) m[i] = INFINITY;
-                switch (nv) {
-                    case 8: window_min<8, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    case 7: window_min<7, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    case 6: window_min<6, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    case 5: window_min<5, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    case 4: window_min<4, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    case 3: window_min<3, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    case 2: window_min<2, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                    default: window_min<1, LDSWIN>(px, py, m, H, W, s_ab, s_c); break;
-                }
-#pragma unroll
-                for (int i = 0; i < kTU; ++i) {
-                    if (i < nv) {
-                        // d^2 = |p|^2 + min_j(...), gate d <= 100 (dd:185), cost += path_weight*d*d (dd:206)
-                        double d2 = m[i] + fma(px[i], px[i], py[i] * py[i]);
-                        d2 = d2 < 1.0e4 ? fmax(d2, 0.0) : 1.0e4;   // NaN -> gate value, as `distance < min_distance` (dd:189) is false for NaN
-                        cost += A.w_path * d2;
-                    }
-                }
-                if constexpr (MOVING) obst_term_moving<kTU, kTU, true>(A, *obst_mov, px, py, m, cost, t0, nv);
-                else if constexpr (OBST) obst_term<kTU, kTU, true>(A, *obst_lds, px, py, m, cost, nv);
-            }
-        }
-    }
-    if constexpr (GRID) {
-        if (grid_acc.row) {
-            cost = fma(grid_acc.row->w, grid_total(grid_acc), cost);   // the last term (section 10h)
-        }
-    }
-    if (A.do_cost && live) {
-        A.cost[k] = cost;
-        A.w[k] = exp(-cost / A.lambda);  // dd:219 (no min-cost shift)
-    }
-}
-
-// stand-alone sampling(): one thread per (sample, Philox call) -> 4 consecutive rows of u.
-template <int MODEL>
-__global__ __launch_bounds__(kBlock) void k_sample(const RolloutArgs A) {
-    constexpr int UD = udim_of(MODEL);
-    const int k = blockIdx.x * kBlock + threadIdx.x;
-    const int call = blockIdx.y;
-    if (k >= A.K) return;
-    const int ntot = (A.H - 1) * UD;
-    const Philox4 r = philox4x32_10((uint32_t)(A.k_offset + k), (uint32_t)call, A.iter_lo, A.iter_hi, A.seed_lo, A.seed_hi);
-    float z[4];
-    box_muller_f32(r.x, r.y, z[0], z[1]);
-    box_muller_f32(r.z, r.w, z[2], z[3]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = call * 4 + i;
-        if (n < ntot) {
-            const int d = n % UD;
-            double v = (double)z[i] * A.sigma + A.nominal[n];
-            v = clampd(v, A.umin[d], A.umax[d]);
-            if (MODEL == CCV_MPPI_FULL_BODY && d == 2 && A.steer_off) v = 0.0;
-            A.u[(size_t)n * A.pitch + k] = v;
-        }
-    }
-}
-
-// ---- cross-lane reductions (DPP) ---------------------------------------------------------------------------------
-
-// Cross-lane moves of an fp64 value as two DPP moves (ALU latency) instead of ds_bpermute (an LDS round trip, ~250
-// cycles per butterfly step with its wait): a 64-lane reduction drops from ~1500 to ~150 cycles.
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(const double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-constexpr int kDppXor1 = 0xB1;          // quad_perm [1,0,3,2]: lane ^ 1
-constexpr int kDppXor2 = 0x4E;          // quad_perm [2,3,0,1]: lane ^ 2
-constexpr int kDppHalfMirror = 0x141;   // row_half_mirror: lane i <-> 7 - i within 8
-constexpr int kDppMirror = 0x140;       // row_mirror: lane i <-> 15 - i within 16
-
-__device__ __forceinline__ double lane_value(const double v, const int lane) {   // wave-uniform result
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
-// Fixed-shape reductions over the 64 lanes (every lane of a 16-lane row ends with the row's result; the four rows are
-// combined as (r0 op r1) op (r2 op r3)); the result is wave-uniform.
-#define CCV_WAVE_REDUCE(name, OP)                                                         \
-    __device__ __forceinline__ double name(double v) {                                    \
-        v = OP(v, dpp_move<kDppXor1>(v));                                                 \
-        v = OP(v, dpp_move<kDppXor2>(v));                                                 \
-        v = OP(v, dpp_move<kDppHalfMirror>(v));                                           \
-        v = OP(v, dpp_move<kDppMirror>(v));                                               \
-        return OP(OP(lane_value(v, 0), lane_value(v, 16)), OP(lane_value(v, 32), lane_value(v, 48))); \
-    }
-__device__ __forceinline__ double op_add(const double a, const double b) { return a + b; }
-__device__ __forceinline__ double op_min(const double a, const double b) { return fmin(a, b); }
-__device__ __forceinline__ double op_max(const double a, const double b) { return fmax(a, b); }
-CCV_WAVE_REDUCE(wave_sum, op_add)
-CCV_WAVE_REDUCE(wave_min, op_min)
-CCV_WAVE_REDUCE(wave_max, op_max)
-#undef CCV_WAVE_REDUCE
-
-// Four 64-lane fp32 reductions at once, each one DPP-modified VALU instruction per step (the compiler does not fold a DPP
-// move into v_min / v_max and puts a canonicalising v_max in front of every fminf): 24 instructions + 4 v_readlane for
-// four results, against ~25 per fp64 reduction above.  The four chains are interleaved, so a step's DPP read of a register
-// is four instructions behind its write (the DPP hazard needs two wait states; the leading s_nop covers the producer of
-// the inputs, which the compiler's hazard recogniser cannot see into from outside the asm).  row_bcast:15 / :31 carry a
-// row's result into the next row(s); lane 63 ends with the result of all 64 lanes.  NaN operands are ignored (IEEE
-// minNum / maxNum); all 64 lanes must be active.
-#define CCV_RED4_STEP(O0, O1, O2, O3, CTRL)                                                           \
-    O0 " %0, %0, %0 " CTRL "\n\t" O1 " %1, %1, %1 " CTRL "\n\t" O2 " %2, %2, %2 " CTRL "\n\t" O3 " %3, %3, %3 " CTRL "\n\t"
-#define CCV_RED4(NAME, O0, O1, O2, O3)                                                                \
-    __device__ __forceinline__ void NAME(float& a, float& b, float& c, float& d) {                    \
-        asm volatile("s_nop 1\n\t"                                                                    \
-                     CCV_RED4_STEP(O0, O1, O2, O3, "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")  \
-                     CCV_RED4_STEP(O0, O1, O2, O3, "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")  \
-                     CCV_RED4_STEP(O0, O1, O2, O3, "row_half_mirror row_mask:0xf bank_mask:0xf")      \
-                     CCV_RED4_STEP(O0, O1, O2, O3, "row_mirror row_mask:0xf bank_mask:0xf")           \
-                     CCV_RED4_STEP(O0, O1, O2, O3, "row_bcast:15 row_mask:0xa bank_mask:0xf")         \
-                     CCV_RED4_STEP(O0, O1, O2, O3, "row_bcast:31 row_mask:0xc bank_mask:0xf")         \
-                     : "+v"(a), "+v"(b), "+v"(c), "+v"(d));                                           \
-        a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), 63));                         \
-        b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), 63));                         \
-        c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), 63));                         \
-        d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63));                         \
-    }
-CCV_RED4(wave_min_max_min_max_f32, "v_min_f32_dpp", "v_max_f32_dpp", "v_min_f32_dpp", "v_max_f32_dpp")
-CCV_RED4(wave_min4_f32, "v_min_f32_dpp", "v_min_f32_dpp", "v_min_f32_dpp", "v_min_f32_dpp")
-#undef CCV_RED4
-#undef CCV_RED4_STEP
 
 }  // namespace ccv

@@ -28,7 +28,7 @@ enum class KernelFamily : int { Plain, TwoWave, ThreeWave, FourWave, OneWave };
 struct RolloutPlan {
     KernelFamily family;
     int model;
-    int mode;          // MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_rollout_pc.h)
+    int mode;          // MODE_FUSED / MODE_ROLLOUT / MODE_COST (mppi_kernels.h)
     bool wide;         // diff drive, fused, four- or one-wave: a turn per step beyond pi/4 -> sin / cos of every heading in full
     int batch;         // instances of a batch handle's launch (A.frame = their records, batch_view); 0 = a single handle
     BatchForm form;    // what the kernel serves (mppi_kernels.h): Single if and only if batch == 0

@@ -1,7 +1,6 @@
 // launch_rollout(): from a RolloutPlan to the translation unit that holds the kernel (mppi_launch.h: why the units).  Host code
 // only; no kernel is instantiated here.
 #include "mppi_launch.h"
-#include "mppi_rollout_pc.h"
 
 namespace ccv {
 

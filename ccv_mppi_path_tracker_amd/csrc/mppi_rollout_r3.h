@@ -20,14 +20,14 @@
 // summation order inside a row are those of k_rollout_pc; only the per-sample cost is the sum of the producer's and the
 // distance wave's parts.
 #pragma once
-#include "mppi_rollout_pc.h"
+#include "mppi_consume.h"
+#include "mppi_epilogue.h"
+#include "mppi_handoff.h"
+#include "mppi_produce.h"
 
 namespace ccv {
 
 constexpr int kR3Waves = 3;
-// states of a block whose distance the distance wave computes; the store wave would take the rest.  8: measured best
-// (6 + 2 is 4 us slower at K = 65 536: with eight waves per CU storing, the store wave is busy most of a block time)
-constexpr int kR3CStates = 8;
 constexpr int kR3RB = 12;   // rows per LDS transpose batch in the epilogue: 3 waves x 12 x 65 doubles fit p + ab + c
 
 // What the producer stages for the store wave besides the positions: the fp32 normals of the block (2 x 4 KB at u_dim = 2,
@@ -48,7 +48,7 @@ struct R3Shared {
     int seq[4];
 };
 
-// first part of the hand-off: see pc_publish / pc_wait_for in mppi_rollout_pc.h
+// first part of the hand-off: see pc_publish / pc_wait_for in mppi_handoff.h
 
 // First chunk of the epilogue's re-read for this kernel's row dealing (units of kR3RB rows, wave w owns units w, w+3, ...):
 // with the row of load i a compile-time distance from the wave's first row, an address costs one scalar multiply and
@@ -94,16 +94,9 @@ __global__ __launch_bounds__(kR3Waves * 64, 3) void k_rollout_r3(const RolloutAr
     int* const seq_store = &sh.seq[2];
     if (wv == 0) {
         // ---------------- producer: all time blocks, state in registers
-        if constexpr (FB && COST) cost += A.w_yaw * (A.x0[2] - A.yaw_ref0) * (A.x0[2] - A.yaw_ref0);   // fb:408
+        cost += pc_initial_cost<MODEL, MODE>(A);
         PcState<MODEL> S;
-        S.x = A.x0[0];
-        S.y = A.x0[1];
-        S.yaw = A.x0[2];
-        S.roll = A.x0[3];
-        S.pitch = A.x0[4];
-        S.p_v = S.p_rv = S.p_sdir = S.p_c2 = S.p_c3 = S.p_ac = 0.0;
-        S.p_cdir = 1.0;
-        fast_sincos(A.x0[2], S.sn, S.cs);
+        pc_initial_state<MODEL>(A, S);
         for (int b = 0; b < nblocks; ++b) {
             pc_rotate_priority(A, b);
             if (b >= 2) {   // the buffers of block b last held block b-2: both readers must have taken it
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(kR3Waves * 64, 3) void k_rollout_r3(const RolloutAr
             }
             const int nctl = min(kTU, H - 1 - b * kTU);   // steps of this block that carry controls
             if (nctl == kTU) pc_produce_batched<MODEL, MODE>(A, sh, S, cost, b, lane, k, kk, live, kg);
-            else if (nctl >= kPartialMin) pc_produce_batched<MODEL, MODE, R3Shared<MODEL>, false, false, false, true>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+            else if (nctl >= kPartialMin) pc_produce_batched<MODEL, MODE, R3Shared<MODEL>, kPartialBlock>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
             else pc_produce<MODEL, MODE, false>(A, sh, S, cost, b, lane, k, kk, live, kg);   // (a short tail, or the final state only)
             pc_publish(seq_ready, b + 1);
         }
@@ -124,19 +117,9 @@ __global__ __launch_bounds__(kR3Waves * 64, 3) void k_rollout_r3(const RolloutAr
             pc_wait_for(seq_ready, b + 1);
             bool taken = false;
             if constexpr (COST) {
-                const int nv = min(kR3CStates, nstates - b * kTU);
+                const int nv = min(kConsumeStates, nstates - b * kTU);
                 taken = nv > 0;
-                switch (nv) {
-                    case 8: pc_consume<8, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 7: pc_consume<7, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 6: pc_consume<6, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 5: pc_consume<5, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 4: pc_consume<4, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 3: pc_consume<3, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 2: pc_consume<2, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    case 1: pc_consume<1, MODEL>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1); break;
-                    default: break;
-                }
+                pc_consume_states<MODEL, R3Shared<MODEL>>(nv, A, sh, cost, b, lane, &prune_on, kNoDiscs, kNoDiscs, seq_dist, b + 1);
             }
             if (!taken) pc_publish(seq_dist, b + 1);   // (nothing of this block reaches the path cost)
         }
@@ -204,7 +187,7 @@ __global__ __launch_bounds__(kR3Waves * 64, 3) void k_rollout_r3(const RolloutAr
         // the re-read of this wave's share of the controls is issued before anything else (see pc_update_fetch)
         if (mcount > 0) r3_update_fetch0(A, upd, wv, mcount, kk);
         const double total = (sh.cost[0][lane] + sh.cost[1][lane]) + sh.cost[2][lane];
-        const double wgt = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)
+        const double wgt = pc_weight<false>(A, total, live);
         if (wv == 0 && live) {
             A.cost[k] = total;
             A.w[k] = wgt;

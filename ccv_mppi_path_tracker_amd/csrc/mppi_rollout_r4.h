@@ -16,10 +16,13 @@
 // that depends on the dispatch, and the steering workload ran at 52 or 61 us by process; and (2) the noise and the dynamics
 // wave are through their loops early, which lets the epilogue's re-read start before the kernel's barrier, and the noise
 // wave needs nothing that is staged, which lets block 0's normals be made beside the staging.
-// Hand-offs are LDS sequence numbers as in the three-wave kernel.  Arithmetic, noise and the summation order inside a row
+// Hand-offs are LDS sequence numbers as in the three-wave kernel (mppi_handoff.h).  Arithmetic, noise and the summation order inside a row
 // are those of k_rollout_pc / k_rollout_r3: the results are bit-identical.
 #pragma once
-#include "mppi_rollout_r3.h"
+#include "mppi_consume.h"
+#include "mppi_epilogue.h"
+#include "mppi_handoff.h"
+#include "mppi_produce.h"
 
 namespace ccv {
 
@@ -95,30 +98,17 @@ struct R4Shared {
     int nan_seen[kR4Waves];   // per wave: a thread of it staged a NaN of the warm start (see clampd_fast)
 };
 
-// The normals of time block b -> LDS (noise wave).  The same grouping of the Philox calls as pc_produce_batched (4 | 3 + 3):
-// a normal does not depend on it.
+// The normals of time block b -> LDS (noise wave).  The same grouping of the Philox calls as pc_produce_batched (4 | 3 + 3,
+// pc_for_call_groups): a normal does not depend on it.
 template <int MODEL, class SH>
 __device__ __forceinline__ void r4_noise_block(const RolloutArgs& A, SH& sh, const int b, const int lane, const uint32_t kg) {
-    constexpr int UD = udim_of(MODEL), NCALL = kTU * UD / 4;
-    auto group = [&](auto C0_, auto CN_) {
+    pc_for_call_groups<MODEL>([&](auto C0_, auto CN_) {
         constexpr int C0 = decltype(C0_)::value, CN = decltype(CN_)::value;
         float z[4 * CN];
         pc_block_normals<MODEL, C0, CN>(A, b, kg, z);
 #pragma unroll
         for (int i = 0; i < 4 * CN; ++i) sh.zs[b & 1][4 * C0 + i][lane] = z[i];
-    };
-    using std::integral_constant;
-    if constexpr (NCALL == 4) {
-        group(integral_constant<int, 0>{}, integral_constant<int, 4>{});
-    } else if constexpr (NCALL == 6) {
-        group(integral_constant<int, 0>{}, integral_constant<int, 3>{});
-        group(integral_constant<int, 3>{}, integral_constant<int, 3>{});
-    } else {
-        static_assert(NCALL == 10, "full body: 4 + 3 + 3 Philox calls");
-        group(integral_constant<int, 0>{}, integral_constant<int, 4>{});
-        group(integral_constant<int, 4>{}, integral_constant<int, 3>{});
-        group(integral_constant<int, 7>{}, integral_constant<int, 3>{});
-    }
+    });
 }
 
 // One Philox call's four normals of time block b -> LDS (the prologue: block 0's calls are dealt to all four waves, which have
@@ -239,7 +229,7 @@ __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
 // pose the kernel holds; their term in the distance wave (pc_consume, obst_term)
 // MOVING (on OBST): the discs move with a constant velocity over the horizon (obst_stage_moving, obst_term_moving); the distance
 // wave takes whole blocks of kTU states whatever the dynamics wave's tail form, so state i of block b is step b * kTU + i
-// GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_kernels.h) -- in the store wave, which has every absolute state
+// GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_cost_terms.h) -- in the store wave, which has every absolute state
 // in registers on its way from LDS to HBM whether or not the states are stored, and issue slots to spare.  A block's eight
 // gathers are issued before its stores and summed after them, so their latency passes under the issue of the block's 32 to 56
 // stores.  The lane's sum reaches the epilogue in sh.cost[3], the store wave's slot of the cost parts, which is 0.0 otherwise:
@@ -303,39 +293,20 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         }
         if (wv == 0) CCV_DIAG_STAMP(A, 3);
         if (wv == 1) {
-            S.x = A.x0[0];
-            S.y = A.x0[1];
-            S.yaw = A.x0[2];
-            S.roll = A.x0[3];
-            S.pitch = A.x0[4];
-            S.p_v = S.p_rv = S.p_sdir = S.p_c2 = S.p_c3 = S.p_ac = 0.0;
-            S.p_cdir = 1.0;
-            fast_sincos(A.x0[2], S.sn, S.cs);
+            pc_initial_state<MODEL>(A, S);
             CCV_DIAG_STAMP(A, 1);
         }
         bad_nominal = r4_stage_commit<MODEL>(A, sh, (int)threadIdx.x, staged);
-        if constexpr (MOVING) {
-            const int j = (int)threadIdx.x - 2 * 64;
-            if (j >= 0 && j < kMaxObst) obst_stage_moving(A, *obst_mov, j);
-        } else if constexpr (OBST) {
-            const int j = (int)threadIdx.x - 2 * 64;
-            if (j >= 0 && j < kMaxObst) obst_stage(A, *obst_lds, j);
+        if constexpr (OBST) {
+            const int j = (int)threadIdx.x - 2 * 64;   // (the distance wave's first lanes)
+            if (j >= 0 && j < kMaxObst) obst_stage_form<FORM>(A, obst_lds, obst_mov, j);
         }
         // a NaN in the warm start: every wave says what its threads saw, every wave reads all four words after the barrier
         const bool wave_bad = __builtin_amdgcn_ballot_w64(bad_nominal) != 0ull;
         if (r4_lane(A).lane == 0) sh.nan_seen[wv] = wave_bad ? 1 : 0;
     } else {
         if constexpr (COST) stage_window(A, Wk, sh, kR4Waves * 64);
-        if (wv == 1) {
-            S.x = A.x0[0];
-            S.y = A.x0[1];
-            S.yaw = A.x0[2];
-            S.roll = A.x0[3];
-            S.pitch = A.x0[4];
-            S.p_v = S.p_rv = S.p_sdir = S.p_c2 = S.p_c3 = S.p_ac = 0.0;
-            S.p_cdir = 1.0;
-            fast_sincos(A.x0[2], S.sn, S.cs);
-        }
+        if (wv == 1) pc_initial_state<MODEL>(A, S);
     }
     __syncthreads();
     if (wv == 1) CCV_DIAG_STAMP(A, 2);
@@ -359,7 +330,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     // with -mtgsplit / amdgpu-tgsplit.  hipcc's default is off, and the build (build.py) does not set it.
     // Controls are re-derived from the normals with the clamp form of the launch (fast_clamp: v_max / v_min); the rows of a
     // step-by-step tail (pc_produce: compare-and-select) can differ from that in ONE way -- the sign of a zero at a bound of
-    // +-0 -- which no sum, cost or comparison can see (clampd_fast, mppi_kernels.h).
+    // +-0 -- which no sum, cost or comparison can see (clampd_fast, mppi_device_util.h).
     auto early_fetch = [&]() {
         if constexpr (MODE == MODE_FUSED) {   // (stage-wise cost call: fp64 controls, 120 registers -- fetched after the barrier)
             if (rows.n > 0 && nb_early > 0) {   // (nb_early == 0: every wave reads its rows after the barrier)
@@ -395,7 +366,8 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         const bool live = L.live;
         const uint32_t kg = L.kg;
         double cost = 0.0;
-        if constexpr (FB && COST) cost += A.w_yaw * (A.x0[2] - A.yaw_ref0) * (A.x0[2] - A.yaw_ref0);   // fb:408
+        cost += pc_initial_cost<MODEL, MODE>(A);
+        constexpr unsigned LDSZ = kNormalsInLds | (WIDE ? kWideTurn : 0u);   // (the noise wave's blocks: every form below has these)
         for (int b = 0; b < nblocks; ++b) {
             r4_rotate_priority(A, b, 1);
             if (b >= 2) {   // the buffers of block b last held block b-2: both readers must have taken it
@@ -409,24 +381,24 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
                 // (two instantiations each: a NaN in the warm start is rare, but its results are to be the other kernels' bits too)
                 if (!TAIL || nctl == kTU) {
                     if (fast_clamp)
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, true, true, WIDE>(A, sh, S, cost, b, lane, k, kk, live, kg);
+                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kFastClamp>(A, sh, S, cost, b, lane, k, kk, live, kg);
                     else
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, true, false, WIDE>(A, sh, S, cost, b, lane, k, kk, live, kg);
+                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ>(A, sh, S, cost, b, lane, k, kk, live, kg);
                 } else if constexpr (TAIL) {
                     // (six steps -- the reference's default horizon, H = 15 -- as an instantiation of their own: the masked batch
                     //  computes all eight and drops two; same box, kernel: full body K = 10 000 17.8 -> 17.3 us, steering
                     //  K = 1 000 14.3 -> 13.9 us per iteration, diff drive unchanged)
                     if (fast_clamp && nctl == 6)
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, true, true, WIDE, true, 6>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kPartialBlock | kFastClamp, 6>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
                     else if (fast_clamp)
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, true, true, WIDE, true>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kPartialBlock | kFastClamp>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
                     else
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, true, false, WIDE, true>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kPartialBlock>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
                 }
             } else if (MODE != MODE_FUSED && nctl == kTU) {
                 pc_produce_batched<MODEL, MODE>(A, sh, S, cost, b, lane, k, kk, live, kg);
             } else if (MODE != MODE_FUSED && nctl >= kPartialMin) {
-                pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, false, false, false, true>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl);
+                pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, kPartialBlock>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
             } else {
                 pc_produce<MODEL, MODE, false>(A, sh, S, cost, b, lane, k, kk, live, kg);   // (a short tail, or the final state only)
             }
@@ -449,19 +421,9 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             pc_wait_for(seq_ready, b + 1);
             bool taken = false;
             if constexpr (COST) {
-                const int nv = min(kR3CStates, nstates - b * kTU);
+                const int nv = min(kConsumeStates, nstates - b * kTU);
                 taken = nv > 0;
-                switch (nv) {
-                    case 8: pc_consume<8, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 7: pc_consume<7, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 6: pc_consume<6, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 5: pc_consume<5, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 4: pc_consume<4, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 3: pc_consume<3, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 2: pc_consume<2, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    case 1: pc_consume<1, MODEL, R4Shared<MODEL>, true, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, seq_dist, b + 1, obst_lds, obst_mov); break;
-                    default: break;
-                }
+                pc_consume_states<MODEL, R4Shared<MODEL>, kLeanRegisters | consume_discs(FORM)>(nv, A, sh, cost, b, lane, &prune_on, obst_lds, obst_mov, seq_dist, b + 1);
             }
             if (!taken) pc_publish(seq_dist, b + 1);   // (nothing of this block reaches the path cost)
             if (b == 0) CCV_DIAG_STAMP(A, 14);
@@ -585,6 +547,8 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             total_ = ((sh.cost[0][lane] + sh.cost[1][lane]) + sh.cost[2][lane]) + sh.cost[3][lane];
         }
         const double total = total_;
+        // (not pc_weight<SHIFT>: with the unshifted exp behind the helper, the two stage-wise full-body instantiations of this
+        //  kernel, k_rollout_r4<2, MODE_ROLLOUT> and <2, MODE_COST>, compiled to other instructions)
         double wgt_;
         if constexpr (SHIFT) wgt_ = pc_shifted_weight(A, total, live);   // (every wave: the same 64 totals, the same minimum)
         else wgt_ = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)

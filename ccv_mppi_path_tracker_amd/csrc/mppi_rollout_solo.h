@@ -6,11 +6,15 @@
 // each other whenever a neighbour on their SIMD delays one of them (full body, K = 131 072: 29 % of the wave cycles are
 // barrier waits).  Once K provides two or more blocks of 64 samples per SIMD the SIMD is kept busy by independent waves
 // anyway, and the hand-off is pure loss: this kernel runs the same building blocks -- the batched branch-free producer
-// (pc_produce_batched), the software-pipelined distance loop (pc_consume), the fused update epilogue -- in ONE wave per 64
+// (pc_produce_batched, mppi_produce.h), the software-pipelined distance loop (pc_consume, mppi_consume.h), the fused update
+// epilogue (mppi_epilogue.h) -- in ONE wave per 64
 // samples, producer and distance phase alternating in program order, the state in registers, no barrier in the time loop.
 // The full-body model is the one that profits (its 230 VGPRs allow two waves per SIMD whatever the kernel shape).
 #pragma once
-#include "mppi_rollout_pc.h"
+#include "mppi_consume.h"
+#include "mppi_epilogue.h"
+#include "mppi_handoff.h"
+#include "mppi_produce.h"
 
 namespace ccv {
 
@@ -27,7 +31,7 @@ struct SoloShared {
 // WIDE: see pc_produce_batched (diff drive beyond |w|max dt = pi/4); BATCH: a batch handle's launch (batch_view, mppi_kernels.h);
 // VARIED: with the batch's per-instance parameters; SHIFT (on VARIED): block-relative weights (pc_shifted_weight);
 // OBST (on VARIED): the instance's disc obstacles (obst_stage, obst_term); MOVING (on OBST): the discs move (obst_stage_moving,
-// obst_term_moving); GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_kernels.h), looked up by the producer where
+// obst_term_moving); GRID (on MOVING): the instance's occupancy grid (grid_tap, mppi_cost_terms.h), looked up by the producer where
 // it stores the block's absolute states; the block's gathers are summed after its distance phase, under which their latency
 // passes.  The grid term is the last added to the cost.  Diff drive and steering only.
 // FORM (BatchForm, mppi_kernels.h) names the rung; BATCH .. GRID below are "FORM is at least that rung".
@@ -56,12 +60,8 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
     const int H = A.H;
     const int lane = threadIdx.x;
     stage_window<BATCH>(A, Wk, sh, kPcSamples);
-    if constexpr (MOVING) {
-        if (threadIdx.x < kMaxObst) obst_stage_moving(A, *obst_mov, (int)threadIdx.x);
-    } else if constexpr (OBST) {
-        if (threadIdx.x < kMaxObst) obst_stage(A, *obst_lds, (int)threadIdx.x);
-    }
-    // two-instruction clamps (clampd_fast, mppi_kernels.h): the host has checked sigma and the bounds, this wave the warm start;
+    if (threadIdx.x < kMaxObst) obst_stage_form<FORM>(A, obst_lds, obst_mov, (int)threadIdx.x);
+    // two-instruction clamps (clampd_fast, mppi_device_util.h): the host has checked sigma and the bounds, this wave the warm start;
     // a NaN anywhere takes every block through the compare-and-select instantiation.  (The staging is not an operand of the
     // `&&`: with A.fast_clamp off it would be skipped, and the kernel would read a warm start nobody put into LDS.)
     const bool nan_nominal = __builtin_amdgcn_ballot_w64(pc_stage_nominal<MODEL>(A, sh, kPcSamples)) != 0ull;
@@ -71,20 +71,14 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
     const int kk = live ? k : A.K - 1;
     const uint32_t kg = (uint32_t)(A.k_offset + kk);
     double cost = 0.0;
-    if constexpr (FB) cost += A.w_yaw * (A.x0[2] - A.yaw_ref0) * (A.x0[2] - A.yaw_ref0);   // fb:408
+    cost += pc_initial_cost<MODEL, MODE>(A);
     const int nblocks = (H + kTU - 1) / kTU;
     const int nstates = FB ? H - 2 : H;   // states that reach the path cost (dd:199 / fb:409)
     int prune_on = 1;
     PcState<MODEL> S;
-    S.x = A.x0[0];
-    S.y = A.x0[1];
-    S.yaw = A.x0[2];
-    S.roll = A.x0[3];
-    S.pitch = A.x0[4];
-    S.p_v = S.p_rv = S.p_sdir = S.p_c2 = S.p_c3 = S.p_ac = 0.0;
-    S.p_cdir = 1.0;
-    fast_sincos(A.x0[2], S.sn, S.cs);
-    constexpr int GM = GRID ? 2 : 0;   // (pc_produce_batched's GRID)
+    pc_initial_state<MODEL>(A, S);
+    // (pc_produce_batched's flags of every block here: the wide-turn form, and a grid's gathers left for after the distance phase)
+    constexpr unsigned WG = (WIDE ? kWideTurn : 0u) | (GRID ? kGridTaps : 0u);
     GridAcc grid_acc{};
     if constexpr (GRID) grid_acc = GridAcc{grid_row(A), 0.0, nstates, nullptr};
     __syncthreads();   // (one wave: the staged window and warm start are visible to all its lanes)
@@ -102,32 +96,22 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
         const int nctl = min(kTU, H - 1 - b * kTU);   // steps of this block that carry controls
         if (nctl == kTU) {
             if (fast_clamp)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, true, WIDE, false, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, kTU, &grid_acc, &tap);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, kFastClamp | WG>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, kTU, &grid_acc, &tap);
             else if constexpr (!FB)   // (a second instantiation, so that a NaN in the warm start gives the multi-wave kernels'
                                       //  bits; full body has no registers for it -- its NaN case takes pc_produce below, whose
                                       //  sin / cos differ from the block path's in the last place)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, false, WIDE, false, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, kTU, &grid_acc, &tap);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, WG>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, kTU, &grid_acc, &tap);
         } else if (nctl >= kPartialMin) {   // the horizon's last block, partly filled (C4: 7 of its 8 steps)
             if (fast_clamp)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, true, WIDE, true, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl, &grid_acc, &tap);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, kPartialBlock | kFastClamp | WG>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl, &grid_acc, &tap);
             else if constexpr (!FB)
-                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, false, false, WIDE, true, 0, GM>(A, sh, S, cost, b, lane, k, kk, live, kg, nullptr, nctl, &grid_acc, &tap);
+                done = pc_produce_batched<MODEL, MODE, SoloShared<MODEL>, kPartialBlock | WG>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl, &grid_acc, &tap);
         }
         if (!done) pc_produce<MODEL, MODE, false, GRID>(A, sh, S, cost, b, lane, k, kk, live, kg, &grid_acc);
         // ---------------- their distance to the window
         const int nv = min(kTU, nstates - b * kTU);
-        switch (nv) {
-            case 8: pc_consume<8, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 7: pc_consume<7, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 6: pc_consume<6, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 5: pc_consume<5, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 4: pc_consume<4, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 3: pc_consume<3, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 2: pc_consume<2, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            case 1: pc_consume<1, MODEL, SoloShared<MODEL>, false, OBST, MOVING>(A, sh, cost, b, lane, 0, &prune_on, nullptr, 0, obst_lds, obst_mov); break;
-            default: break;
-        }
-        if constexpr (GM == 2) {
+        pc_consume_states<MODEL, SoloShared<MODEL>, consume_discs(FORM)>(nv, A, sh, cost, b, lane, &prune_on, obst_lds, obst_mov);
+        if constexpr (GRID) {
             if (done) grid_sum(grid_acc, tap, b * kTU);
         }
     }
@@ -143,10 +127,7 @@ __global__ __launch_bounds__(kPcSamples, 2) void k_rollout_solo(const RolloutArg
     const int mcount = A.fuse_update ? rows.count() : 0;
     if (mcount > 0) pc_update_fetch(A, upd, rows, 0, mcount, kk);   // (in flight during the exp below)
     const double total = cost;
-    double wgt_;
-    if constexpr (SHIFT) wgt_ = pc_shifted_weight(A, total, live);
-    else wgt_ = live ? exp(-total / A.lambda) : 0.0;   // dd:219 (no min-cost shift)
-    const double wgt = wgt_;
+    const double wgt = pc_weight<SHIFT>(A, total, live);
     if (live) {
         A.cost[k] = total;
         A.w[k] = wgt;

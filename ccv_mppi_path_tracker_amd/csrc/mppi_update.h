@@ -2,7 +2,7 @@
 // k_apply_partials), re-derivation of the controls from the stored normals, MIN_SHIFT re-weighting and the read-back
 // helpers.  No entry point is a template: every kernel is DEFINED in one translation unit, k_update.hip; this header has the argument
 // structs and the declarations through which the host units of the C ABI (capi_internal.h) launch them.  The rollout
-// kernels' translation units (k_*.hip) include mppi_kernels.h alone.
+// kernels' translation units (k_*.hip) include mppi_launch.h and their family's header (mppi_rollout_*.h), not this one.
 #pragma once
 #include "mppi_kernels.h"
 

@@ -5,6 +5,7 @@
 // k_fleet.hip the fleet forms of the batch prologue (mppi_fleet.h).  Everything here is __forceinline__: no unit exports it.
 #pragma once
 #include "fast_trig.h"
+#include "mppi_device_util.h"
 #include "mppi_resident.h"
 
 namespace ccv {

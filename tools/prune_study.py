@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How much of the reference window can an exact, wave-level pruning test discard?  (CPU study, numpy only.)
 
-pc_consume (csrc/mppi_rollout_pc.h) skips window points that cannot be the nearest one for any sample of a wave: bounds
+pc_consume (csrc/mppi_consume.h) skips window points that cannot be the nearest one for any sample of a wave: bounds
 of the linear form f_j(p) = a_j px + b_j py + c_j over a bounding box of positions, then the hull of the surviving
 indices.  This script replays a diff-drive MPPI loop on the C2 workload in numpy and reports, per time block of 8 steps,
 the fraction of (state, window point) pairs that remain when the box is taken over 8 / 4 / 2 / 1 consecutive states of
