@@ -426,6 +426,28 @@ class BatchController:
                                                             capi.dptr(out)))
         return out
 
+    # ---- what a node publishes per robot, for every instance at once (ccv_mppi_batch_read_best_candidates / _optimal_paths) ----
+    def read_best_candidates(self, count, with_paths=True):
+        """The `count` lowest-cost samples of every instance of the last tick: (idx int32 [B, count], cost [B, count],
+        xy [B, count, H, 2] or None without with_paths).  Costs ascend, ties go to the lower sample index, NaN costs come last:
+        the order of np.lexsort((np.arange(K), cost)).  Selected, ordered and gathered on the device; does not flush a pending
+        resident update.  count <= min(K, capi.BEST_MAX)."""
+        count = int(count)
+        n = max(count, 0)
+        idx = np.empty((self.B, n), dtype=np.int32)
+        cost = np.empty((self.B, n))
+        xy = np.empty((self.B, n, self.H, 2)) if with_paths else None
+        self._check(self.lib.ccv_mppi_batch_read_best_candidates(self._h, count, idx.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(cost),
+                                                                 capi.dptr(xy) if with_paths else None))
+        return idx, cost, xy
+
+    def read_optimal_paths(self):
+        """[B, H-1, 3]: the plant model rolled through every instance's u* from the pose and dt of the last tick, row i =
+        (x, y, yaw) before control step i -- plant_step() H-1 times, on the device.  Flushes a pending resident update."""
+        out = np.empty((self.B, self.H - 1, 3))
+        self._check(self.lib.ccv_mppi_batch_read_optimal_paths(self._h, capi.dptr(out)))
+        return out
+
     # ---- device-resident closed loop of every instance (ccv_mppi_batch_resident_*) ----
     def resident_set_paths(self, paths, resolution=None):
         """paths: B (path_x, path_y) pairs, or one pair for every instance; resolution: one value or [B] (default: each

@@ -34,6 +34,7 @@ MAX_OBSTACLES = 32
 INFLATE_MAX_RADIUS = 64
 OCC_PATCH_MAX_CELLS = 1 << 20
 OCC_PATCH_SLOTS = 4
+BEST_MAX = 1024
 BATCH_TRACE_ROWS = 1024
 
 
@@ -157,6 +158,8 @@ SIGNATURES = {
     "ccv_mppi_batch_read_costs": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "ccv_mppi_batch_read_weights": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "ccv_mppi_batch_read_candidates": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
+    "ccv_mppi_batch_read_best_candidates": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), _dp, _dp]),
+    "ccv_mppi_batch_read_optimal_paths": (C.c_int, [_H, _dp]),
     "ccv_mppi_batch_timing_enable": (C.c_int, [_H, C.c_int32]),
     "ccv_mppi_batch_timing_read": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int64), C.c_int32]),
     "ccv_mppi_batch_resident_set_paths": (C.c_int, [_H, _dp, _dp, C.POINTER(C.c_int32), _dp]),

@@ -6,6 +6,7 @@
 //   capi_batch.hip       batch handles (ccv_mppi_batch_*): what a tick runs and what reads its results, the resident loop included
 //   capi_batch_config.hip  batch handles: what configures the next launch (parameters, shifted weights, discs, grids and their
 //                          occupancy layers, fleet term)
+//   capi_batch_feed.hip  batch handles: best candidates and optimal paths of every instance (mppi_feed.h)
 // A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".

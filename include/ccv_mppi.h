@@ -439,6 +439,28 @@ int ccv_mppi_batch_read_costs(ccv_mppi_batch* b, int32_t instance, int32_t first
 int ccv_mppi_batch_read_weights(ccv_mppi_batch* b, int32_t instance, int32_t first, int32_t count, double* out);
 int ccv_mppi_batch_read_candidates(ccv_mppi_batch* b, int32_t instance, int32_t first, int32_t count, int32_t stride,
                                    double* xy_out);
+/* What a node publishes per robot (publish_CandidatePath(), publish_OptimalPath(); dd:265-312), for every instance at once.
+ * Selection, ordering, gather and the re-roll run on the device; each call takes one synchronisation and one device-to-host copy
+ * per output array, sorts nothing on the host and copies nothing to the device.
+ * _read_best_candidates: the `count` lowest-cost samples of EVERY instance of the last tick.  sample_out [B][count] (local sample
+ * index 0..K-1), cost_out [B][count] (may be NULL), xy_out [B][count][H][2] (may be NULL; layout per candidate as
+ * ccv_mppi_batch_read_candidates).  Selection is by cost, not by weight: the same order as descending weight wherever the weights
+ * are distinct and positive, and defined where they are not -- where weights underflow to 0, and under
+ * ccv_mppi_batch_set_min_shift, where the stored weights are relative to their workgroup.  Costs ascend, ties go to the lower
+ * sample index, NaN costs come last, by index among themselves: the order of one 64-bit key (every NaN 0xFFFFFFFFFFFFFFFF, -0.0
+ * as +0.0, otherwise bits ^ (sign ? ~0 : 1 << 63)) and then the index, i.e. of numpy's lexsort((arange(K), cost)).  cost_out
+ * holds the costs' own bits.  Only samples 0..K-1 take part.  The call reads costs and states only: it does not flush a pending
+ * resident update and runs in stream order after the rollout launch, so a resident tick keeps its two launches.  Works with every
+ * form of a batch and every kernel family.  count == 0 is OK and writes nothing.  A null handle or sample_out, count < 0,
+ * count > K or count > CCV_MPPI_BEST_MAX: CCV_MPPI_ERR_INVALID_ARG; before any tick, or xy_out with
+ * CCV_MPPI_FLAG_NO_STATE_STORE: CCV_MPPI_ERR_STATE (indices and costs still work with that flag).
+ * _read_optimal_paths: the plant model rolled through every instance's u* from the pose and dt of the last tick: xyyaw_out
+ * [B][H-1][3], row i = the state BEFORE control step i (dd:295-312, as MPPIBase::optimal_path()), bit for bit H-1 calls of
+ * ccv_mppi_plant_step().  Needs u*, so it flushes a pending resident update as ccv_mppi_batch_get_nominal does.  A null handle
+ * or xyyaw_out: CCV_MPPI_ERR_INVALID_ARG; before any tick: CCV_MPPI_ERR_STATE. */
+#define CCV_MPPI_BEST_MAX 1024   /* candidates per instance of one call */
+int ccv_mppi_batch_read_best_candidates(ccv_mppi_batch* b, int32_t count, int32_t* sample_out, double* cost_out, double* xy_out);
+int ccv_mppi_batch_read_optimal_paths(ccv_mppi_batch* b, double* xyyaw_out);
 /* as ccv_mppi_timing_enable / _read: the rollout kernel of the whole batch and the whole launch sequence */
 int ccv_mppi_batch_timing_enable(ccv_mppi_batch* b, int32_t on);
 int ccv_mppi_batch_timing_read(ccv_mppi_batch* b, double* rollout_us_sum, double* iter_us_sum, int64_t* n_iters, int32_t reset);
