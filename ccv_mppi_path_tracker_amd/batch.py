@@ -88,6 +88,30 @@ def pack_velocities(velocities, batch, counts=None):
     return vxy, max_n
 
 
+def pack_exposed(sizes, dx, dy, exposed, fill=0):
+    """The `exposed` buffer of ccv_mppi_batch_roll_occupancy_enqueue: per entry the row strip and then the column strip, tightly
+    packed.  sizes: (nx, ny) per entry; exposed: (row_strip [min(|dy|, ny)][nx], col_strip [ny - min(|dy|, ny)][min(|dx|, nx)])
+    per entry, each in ascending new-frame iy and ix (an empty strip may be None), or None for an entry whose exposed cells all
+    become `fill`."""
+    if len(exposed) != len(sizes):
+        raise ValueError("exposed: expected %d pairs of strips, got %d" % (len(sizes), len(exposed)))
+    parts = []
+    for i, ((nx, ny), pair) in enumerate(zip(sizes, exposed)):
+        ax, ay = min(abs(int(dx[i])), nx), min(abs(int(dy[i])), ny)
+        if pair is None:
+            parts.append(np.full(ay * nx + (ny - ay) * ax, int(fill), dtype=np.uint8))
+            continue
+        rows, cols = pair
+        for name, strip, shape in (("row", rows, (ay, nx)), ("column", cols, (ny - ay, ax))):
+            strip = np.zeros(shape, dtype=np.uint8) if strip is None and 0 in shape else np.ascontiguousarray(strip, dtype=np.uint8)
+            if strip.size == 0:
+                strip = strip.reshape(shape)
+            if strip.shape != shape:
+                raise ValueError("entry %d: the %s strip must be %s, got %s" % (i, name, shape, strip.shape))
+            parts.append(strip.reshape(-1))
+    return np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, dtype=np.uint8)
+
+
 def inflation_profile(radius_m, resolution, kind="linear", lethal=1.0, inscribed=None, inscribed_m=0.0, free_value=0.0, scaling=10.0):
     """(R, profile float32 [R * R + 1], free_value) for BatchController.set_occupancy: the cost of a cell by the squared distance
     D2, in cells, from its centre to the centre of the nearest occupied cell, built on the host -- the device only looks it up.
@@ -345,6 +369,29 @@ class BatchController:
             raise ValueError("patch2d must be [h][w]")
         self._check(self.lib.ccv_mppi_batch_update_occupancy_enqueue(self._h, int(map), int(x0), int(y0), patch.shape[1], patch.shape[0],
                                                                       patch.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def roll_occupancy(self, maps, dx, dy, exposed=None, fill=0):
+        """The windows of the maps `maps` (each at most once) move by (dx[i], dy[i]) whole cells, in stream order and in two launches
+        for all of them: new[iy][ix] = old[iy + dy][ix + dx] where that lies inside the map, the origin moves by (dx, dy) *
+        resolution (formed from the accumulated cell count, so it never drifts), and the float cells are what set_occupancy of
+        the new layer would derive.  exposed: None -- every exposed cell becomes `fill` -- or per map a pair (row_strip
+        [min(|dy|, ny)][nx], col_strip [ny - min(|dy|, ny)][min(|dx|, nx)]) of uint8 in the new frame, or None for a map whose
+        exposed cells become `fill` (pack_exposed).  No
+        synchronisation, except that the handle's first roll allocates the second set of layers and synchronises once (a roll by
+        zeros primes it); the arguments may be reused when the call returns."""
+        maps = np.ascontiguousarray(np.atleast_1d(maps), dtype=np.int32)
+        dx = np.ascontiguousarray(np.broadcast_to(np.asarray(dx, dtype=np.int32), maps.shape))
+        dy = np.ascontiguousarray(np.broadcast_to(np.asarray(dy, dtype=np.int32), maps.shape))
+        buf = None
+        if exposed is not None:
+            geo = self.get_occupancy()
+            if any(not 0 <= int(m) < len(geo) for m in maps):
+                raise ValueError("a map out of range")
+            buf = pack_exposed([(geo[int(m)][3], geo[int(m)][4]) for m in maps], dx, dy, exposed, fill)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ccv_mppi_batch_roll_occupancy_enqueue(
+            self._h, len(maps), maps.ctypes.data_as(ip), dx.ctypes.data_as(ip), dy.ctypes.data_as(ip),
+            buf.ctypes.data_as(C.POINTER(C.c_uint8)) if buf is not None else None, int(fill)))
 
     def get_occupancy(self):
         """A list of ((origin_x, origin_y), resolution, outside, nx, ny, threshold, R, free_value) per map as the library holds

@@ -150,6 +150,8 @@ SIGNATURES = {
     "ccv_mppi_batch_read_grid_cells": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_float)]),
     "ccv_mppi_batch_set_occupancy": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(Inflation), C.c_int32, C.POINTER(C.c_int32), _dp]),
     "ccv_mppi_batch_update_occupancy_enqueue": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "ccv_mppi_batch_roll_occupancy_enqueue": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                        C.POINTER(C.c_uint8), C.c_int32]),
     "ccv_mppi_batch_get_occupancy": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(Inflation), C.c_int32, C.POINTER(C.c_int32)]),
     "ccv_mppi_batch_read_occupancy": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint8)]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,

@@ -4,6 +4,8 @@
 // host-side state, sync_tables.  The device tables the kernels read are a function of that state and are written in one place.
 #include "capi_internal.h"
 
+#include <algorithm>
+
 namespace {
 
 // whether the obstacle kernels run (BatchForm::Obst and up): static discs (ccv_mppi_batch_set_obstacles) or the fleet term
@@ -147,13 +149,26 @@ int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, float* cel
     return CCV_MPPI_OK;
 }
 
+// the layer and the float cells that hold map m now: the second allocation after an odd number of rolls (Costmap::roll_front)
+uint8_t* layer_of(const ccv_mppi_batch* bh, const int m, const bool back = false) {
+    return ((bh->roll_front[(size_t)m] != 0) != back ? bh->d_occ_roll : bh->d_occ) + bh->grid_offset[(size_t)m];
+}
+float* cells_of(const ccv_mppi_batch* bh, const int m, const bool back = false) {
+    const bool second = bh->occ && ((bh->roll_front[(size_t)m] != 0) != back);
+    return (second ? bh->d_cells_roll : bh->d_grid_cells) + bh->grid_offset[(size_t)m];
+}
+
+// one inflation of the rectangle (x0, y0, w, h) of map m: the float cells from the layer, both the front ones or both the back ones
+InflateArgs inflate_args(const ccv_mppi_batch* bh, const int m, const int32_t x0, const int32_t y0, const int32_t w, const int32_t h,
+                         const bool back = false) {
+    const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+    return InflateArgs{layer_of(bh, m, back), cells_of(bh, m, back), bh->d_profile + bh->profile_offset[(size_t)m], bh->occ_free[(size_t)m], g.nx,
+                       g.ny, bh->occ_threshold[(size_t)m], bh->occ_radius[(size_t)m], x0, y0, w, h};
+}
+
 // the float cells of the rectangle (x0, y0, w, h) of map m from its layer, on the handle's stream
 void inflate(ccv_mppi_batch* bh, const int m, const int32_t x0, const int32_t y0, const int32_t w, const int32_t h) {
-    const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
-    const size_t at = bh->grid_offset[(size_t)m];
-    launch_inflate(InflateArgs{bh->d_occ + at, bh->d_grid_cells + at, bh->d_profile + bh->profile_offset[(size_t)m], bh->occ_free[(size_t)m], g.nx,
-                               g.ny, bh->occ_threshold[(size_t)m], bh->occ_radius[(size_t)m], x0, y0, w, h},
-                   bh->stream);
+    launch_inflate(inflate_args(bh, m, x0, y0, w, h), bh->stream);
 }
 
 // the instances' present disc counts, BatchParams::n_obst as the last prologue left it (the static counts after a setter)
@@ -438,11 +453,10 @@ int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* bh, int32_t map, float* cells
     if (map < 0 || map >= (int32_t)bh->grid_maps.size()) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "read_grid_cells: map out of range");
     const DeviceGuard guard(bh->cfg.device);
     HIP_TRY(bh, hipSetDevice(bh->cfg.device));
-    // (a caller's cells: no kernel writes them, nothing to wait for; derived cells: k_inflate does, in stream order)
+    // (a caller's cells: no kernel writes them, nothing to wait for; derived cells: k_inflate and the roll kernels do, in stream order)
     if (bh->occ) HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
-    HIP_TRY(bh, hipMemcpy(cells_out, bh->d_grid_cells + bh->grid_offset[(size_t)map], (size_t)g.nx * (size_t)g.ny * sizeof(float),
-                          hipMemcpyDeviceToHost));
+    HIP_TRY(bh, hipMemcpy(cells_out, cells_of(bh, map), (size_t)g.nx * (size_t)g.ny * sizeof(float), hipMemcpyDeviceToHost));
     return CCV_MPPI_OK;
 }
 
@@ -522,7 +536,13 @@ int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* bh, const ccv_mppi_occupancy* m
         bh->occ_threshold.push_back(maps[m].threshold);
         bh->occ_radius.push_back(inflation[m].radius);
         bh->occ_free.push_back(inflation[m].free_value);
+        bh->roll_ox0.push_back(maps[m].origin_x);
+        bh->roll_oy0.push_back(maps[m].origin_y);
     }
+    // (no roll yet: every map in the first allocation, no cell moved; the second allocation went with the old layers)
+    bh->roll_front.assign((size_t)n_maps, 0);
+    bh->roll_cx.assign((size_t)n_maps, 0);
+    bh->roll_cy.assign((size_t)n_maps, 0);
     bh->occ = true;
     // one full inflation per map; the stream is idle again before the tables point at the cells
     for (int m = 0; m < n_maps; ++m) inflate(bh, m, 0, 0, maps[m].nx, maps[m].ny);
@@ -547,7 +567,7 @@ int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* bh, int32_t map, int
     if (bh->patch_used[slot]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[slot]));
     const size_t at = (size_t)slot * CCV_MPPI_OCC_PATCH_MAX_CELLS;
     std::memcpy(bh->h_patch + at, patch, (size_t)w * (size_t)h);
-    launch_occupancy_patch(bh->d_occ + bh->grid_offset[(size_t)map], g.nx, bh->d_patch + at, x0, y0, w, h, bh->stream);
+    launch_occupancy_patch(layer_of(bh, map), g.nx, bh->d_patch + at, x0, y0, w, h, bh->stream);
     HIP_TRY(bh, hipEventRecord(bh->patch_ev[slot], bh->stream));
     bh->patch_used[slot] = true;
     // A changed cell moves the cost of cells up to R away: the patch grown by R, clipped to the map, is derived again (from layer
@@ -557,6 +577,125 @@ int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* bh, int32_t map, int
     const int32_t rx1 = x0 + w + R > g.nx ? g.nx : x0 + w + R, ry1 = y0 + h + R > g.ny ? g.ny : y0 + h + R;
     inflate(bh, map, rx0, ry0, rx1 - rx0, ry1 - ry0);
     HIP_TRY(bh, hipGetLastError());
+    return CCV_MPPI_OK;
+}
+
+// Stream-ordered like the patch above: after the handle's first roll (which allocates the second set of layers and cells, and
+// quiesces for it like a setter) the deferred resident update is not flushed, nothing is allocated, and the only wait is for the
+// launches that last read the staging slot about to be refilled.  Two launches however many maps roll.
+int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const int32_t* map, const int32_t* dx, const int32_t* dy,
+                                          const uint8_t* exposed, int32_t fill) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "roll_occupancy: ";
+    // every check comes before anything changes
+    if (!bh->occ) return fail(bh, CCV_MPPI_ERR_STATE, "roll_occupancy: no occupancy is set (ccv_mppi_batch_set_occupancy)");
+    if (!map || !dx || !dy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    const int n_maps = (int)bh->grid_maps.size();
+    if (n < 1 || n > n_maps) return refuse(bh, who, "n outside [1, the number of maps]");
+    if (!exposed && (fill < 0 || fill > 255)) return refuse(bh, who, "fill outside [0, 255]");
+    constexpr int64_t kMaxOffset = (int64_t)1 << 30;
+    std::vector<uint8_t> named((size_t)n_maps, 0);
+    std::vector<double> ox((size_t)n), oy((size_t)n);
+    size_t moved = 0, strip_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = map[i];
+        if (m < 0 || m >= n_maps) return refuse(bh, who, "map out of range");
+        if (named[(size_t)m]) return refuse(bh, who, "a map is named twice");
+        named[(size_t)m] = 1;
+        const int64_t ex = dx[i], ey = dy[i];
+        if (ex < -CCV_MPPI_GRID_MAX_DIM || ex > CCV_MPPI_GRID_MAX_DIM || ey < -CCV_MPPI_GRID_MAX_DIM || ey > CCV_MPPI_GRID_MAX_DIM)
+            return refuse(bh, who, "|dx| or |dy| above CCV_MPPI_GRID_MAX_DIM");
+        const int64_t cx = bh->roll_cx[(size_t)m] + ex, cy = bh->roll_cy[(size_t)m] + ey;
+        if (cx < -kMaxOffset || cx > kMaxOffset || cy < -kMaxOffset || cy > kMaxOffset)
+            return refuse(bh, who, "an accumulated offset beyond 2^30 cells");
+        const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+        // (from the accumulated cell count, one product and one sum: no drift, and a checker can restate it exactly)
+        ox[(size_t)i] = bh->roll_ox0[(size_t)m] + (double)cx * g.resolution;
+        oy[(size_t)i] = bh->roll_oy0[(size_t)m] + (double)cy * g.resolution;
+        if (!std::isfinite(ox[(size_t)i]) || !std::isfinite(oy[(size_t)i])) return refuse(bh, who, "a rolled origin is not finite");
+        if (ex == 0 && ey == 0) continue;
+        ++moved;
+        const size_t ax = (size_t)std::min<int64_t>(std::llabs(ex), g.nx), ay = (size_t)std::min<int64_t>(std::llabs(ey), g.ny);
+        if (exposed) strip_bytes += ay * (size_t)g.nx + ((size_t)g.ny - ay) * ax;
+    }
+    const size_t entry_bytes = moved * sizeof(RollEntry), rect_bytes = moved * kRollMaxRects * sizeof(InflateArgs);
+    if (entry_bytes + rect_bytes + strip_bytes > (size_t)CCV_MPPI_OCC_PATCH_MAX_CELLS)
+        return refuse(bh, who, "tables and strips above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
+    // the second set of layers and cells, at the handle's first roll since the layers were set (every cell of it that is read
+    // later is written first: the shift writes every layer cell, and the shift and the bands every float cell)
+    if (!bh->d_occ_roll) {
+        const DeviceGuard guard(bh->cfg.device);
+        if (int rc = quiesce(bh)) return rc;
+        const ccv_mppi_grid& last = bh->grid_maps.back();
+        const size_t total = bh->grid_offset.back() + (size_t)last.nx * (size_t)last.ny;
+        uint8_t* layers = nullptr;
+        float* cells = nullptr;
+        hipError_t e = hipMalloc(&layers, total);
+        if (e == hipSuccess) e = hipMalloc(&cells, total * sizeof(float));
+        if (e != hipSuccess) {
+            free_device({layers, cells});
+            return fail(bh, CCV_MPPI_ERR_HIP, "roll_occupancy: allocating the second set of layers and cells", e);
+        }
+        bh->d_occ_roll = layers;
+        bh->d_cells_roll = cells;
+    }
+    if (moved == 0) return CCV_MPPI_OK;   // (nothing moves: no launch, no bit changes)
+    const int slot = bh->patch_next;
+    bh->patch_next = (slot + 1) % Costmap::kPatchSlots;
+    if (bh->patch_used[slot]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[slot]));
+    // the slot: the entries, the rectangles, the strips (the kernels read all three in place)
+    const size_t at = (size_t)slot * CCV_MPPI_OCC_PATCH_MAX_CELLS;
+    RollEntry* entries = reinterpret_cast<RollEntry*>(bh->h_patch + at);
+    InflateArgs* rects = reinterpret_cast<InflateArgs*>(bh->h_patch + at + entry_bytes);
+    uint8_t* strips = bh->h_patch + at + entry_bytes + rect_bytes;
+    const uint8_t* d_strips = bh->d_patch + at + entry_bytes + rect_bytes;
+    size_t n_entries = 0, n_rects = 0, strip_at = 0;
+    int64_t max_cells = 0;
+    int32_t max_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = map[i], ex = dx[i], ey = dy[i];
+        if (ex == 0 && ey == 0) continue;
+        const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+        const int nx = g.nx, ny = g.ny, R = bh->occ_radius[(size_t)m];
+        const size_t ax = (size_t)std::min(std::abs(ex), nx), ay = (size_t)std::min(std::abs(ey), ny);
+        const size_t bytes = exposed ? ay * (size_t)nx + ((size_t)ny - ay) * ax : 0;
+        if (bytes) std::memcpy(strips + strip_at, exposed + strip_at, bytes);
+        entries[n_entries++] = RollEntry{layer_of(bh, m), layer_of(bh, m, true), cells_of(bh, m), cells_of(bh, m, true),
+                                         exposed ? d_strips + strip_at : nullptr, ox[(size_t)i], oy[(size_t)i], nx, ny, ex, ey, fill, 0};
+        strip_at += bytes;
+        max_cells = std::max<int64_t>(max_cells, (int64_t)nx * ny);
+        // The float cells to derive again: within R of an exposed cell (the leading band, |d| + R wide) or
+        // of a cell that left the map (the trailing band, R wide), per axis; every other float cell is the shift's copy.  The
+        // bands in y keep to the columns the bands in x leave: no cell is written twice.
+        const int lx = ex ? std::min(std::abs(ex) + R, nx) : 0, tx = ex ? std::min(R, nx - lx) : 0;
+        const int ly = ey ? std::min(std::abs(ey) + R, ny) : 0, ty = ey ? std::min(R, ny - ly) : 0;
+        const int xa = ex > 0 ? tx : lx, xb = ex > 0 ? nx - lx : nx - tx;   // the columns between the bands in x
+        const int32_t band[kRollMaxRects][4] = {{ex > 0 ? nx - lx : 0, 0, lx, ny},
+                                                {ex > 0 ? 0 : nx - tx, 0, tx, ny},
+                                                {xa, ey > 0 ? ny - ly : 0, xb - xa, ly},
+                                                {xa, ey > 0 ? 0 : ny - ty, xb - xa, ty}};
+        for (const auto& r : band) {
+            if (r[2] < 1 || r[3] < 1) continue;
+            rects[n_rects++] = inflate_args(bh, m, r[0], r[1], r[2], r[3], true);
+            max_tiles = std::max(max_tiles, ((r[2] + kInflateTile - 1) / kInflateTile) * ((r[3] + kInflateTile - 1) / kInflateTile));
+        }
+    }
+    launch_roll_shift(reinterpret_cast<const RollEntry*>(bh->d_patch + at), (int32_t)n_entries, max_cells, bh->d_grid_rows, bh->B, bh->stream);
+    launch_inflate_rects(reinterpret_cast<const InflateArgs*>(bh->d_patch + at + entry_bytes), (int32_t)n_rects, max_tiles, bh->stream);
+    const hipError_t launched = hipGetLastError();
+    // the host's view moves at call time: the front bits, the offsets, the origins _get_grids and _get_occupancy return
+    for (int i = 0; i < n; ++i) {
+        const size_t m = (size_t)map[i];
+        if (dx[i] == 0 && dy[i] == 0) continue;
+        bh->roll_front[m] ^= 1;
+        bh->roll_cx[m] += dx[i];
+        bh->roll_cy[m] += dy[i];
+        bh->grid_maps[m].origin_x = ox[(size_t)i];
+        bh->grid_maps[m].origin_y = oy[(size_t)i];
+    }
+    bh->patch_used[slot] = true;
+    HIP_TRY(bh, launched);
+    HIP_TRY(bh, hipEventRecord(bh->patch_ev[slot], bh->stream));   // (after the second launch: both read the slot)
     return CCV_MPPI_OK;
 }
 
@@ -582,7 +721,7 @@ int ccv_mppi_batch_read_occupancy(ccv_mppi_batch* bh, int32_t map, uint8_t* out)
     HIP_TRY(bh, hipSetDevice(bh->cfg.device));
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (queued patch writers)
     const ccv_mppi_grid& g = bh->grid_maps[(size_t)map];
-    HIP_TRY(bh, hipMemcpy(out, bh->d_occ + bh->grid_offset[(size_t)map], (size_t)g.nx * (size_t)g.ny, hipMemcpyDeviceToHost));
+    HIP_TRY(bh, hipMemcpy(out, layer_of(bh, map), (size_t)g.nx * (size_t)g.ny, hipMemcpyDeviceToHost));
     return CCV_MPPI_OK;
 }
 

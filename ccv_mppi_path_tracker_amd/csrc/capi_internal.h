@@ -31,6 +31,7 @@
 #include "mppi_resident.h"
 #include "mppi_fleet.h"
 #include "mppi_costmap.h"
+#include "mppi_costmap_roll.h"
 
 namespace ccv {
 
@@ -269,7 +270,8 @@ struct Grids {
 
 // occupancy layers (ccv_mppi_batch_set_occupancy, mppi_costmap.h): while `occ`, the cells of Grids are not a caller's but derived
 // on the device from a uint8 layer per map (same geometry, same offsets: layer m starts at d_occ + grid_offset[m]) and the map's
-// inflation; a patch of a layer is enqueued on the stream (ccv_mppi_batch_update_occupancy_enqueue) through the staging ring.
+// inflation; a patch of a layer is enqueued on the stream (ccv_mppi_batch_update_occupancy_enqueue) through the staging ring,
+// and so is a roll of the maps' windows (ccv_mppi_batch_roll_occupancy_enqueue).
 // The ring is allocated at the first _set_occupancy and kept until destroy.
 struct Costmap {
     bool occ = false;
@@ -285,11 +287,26 @@ struct Costmap {
     hipEvent_t patch_ev[kPatchSlots] = {};
     bool patch_used[kPatchSlots] = {};
     int patch_next = 0;
+    // rolling maps (ccv_mppi_batch_roll_occupancy_enqueue, mppi_costmap_roll.h): a second allocation of the layers and of the
+    // float cells, same sizes and offsets, made at the first roll and freed with the layers.  roll_front[m] says which of the
+    // two holds map m: 0 the first (d_occ, Grids::d_grid_cells), 1 the second.  A roll writes the other one and flips the bit.
+    uint8_t* d_occ_roll = nullptr;
+    float* d_cells_roll = nullptr;
+    std::vector<uint8_t> roll_front;         // [n_maps]
+    std::vector<int64_t> roll_cx, roll_cy;   // [n_maps] cells moved since _set_occupancy
+    std::vector<double> roll_ox0, roll_oy0;  // [n_maps] the origin _set_occupancy was given
     // the layers and tables go (the maps become a caller's, or none); the ring stays
     void drop_layers() {
-        free_device({d_occ, d_profile});
+        free_device({d_occ, d_profile, d_occ_roll, d_cells_roll});
         d_occ = nullptr;
         d_profile = nullptr;
+        d_occ_roll = nullptr;
+        d_cells_roll = nullptr;
+        roll_front.clear();
+        roll_cx.clear();
+        roll_cy.clear();
+        roll_ox0.clear();
+        roll_oy0.clear();
         occ = false;
         profile_offset.clear();
         occ_threshold.clear();
@@ -300,7 +317,7 @@ struct Costmap {
         for (hipEvent_t e : patch_ev)
             if (e) (void)hipEventDestroy(e);
         if (h_patch) (void)hipHostFree(h_patch);
-        free_device({d_occ, d_profile});
+        free_device({d_occ, d_profile, d_occ_roll, d_cells_roll});
     }
 };
 

@@ -419,12 +419,47 @@ int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* b, int32_t map, float* cells_
  * _get_occupancy: maps [max_maps] (cells NULL) and inflation [max_maps] (profile NULL), *n_maps (0 unless occupancy is set); any
  * may be NULL; max_maps below the number of maps with maps or inflation != NULL: CCV_MPPI_ERR_INVALID_ARG.
  * _read_occupancy: out [ny * nx], the layer of map `map` read back from the device; synchronises (so does _read_grid_cells while
- * occupancy is set); CCV_MPPI_ERR_STATE while no occupancy is set. */
+ * occupancy is set); CCV_MPPI_ERR_STATE while no occupancy is set.
+ * _roll_occupancy_enqueue: rolling maps.  The windows of n maps (map [n], each map at most once, 1 <= n <= the number of maps)
+ * move by whole cells, map[i] by (dx[i], dy[i]).  With `old` and `new` the layer before and after the call:
+ *     new(ix, iy) = old(ix + dx, iy + dy)        where (ix + dx, iy + dy) lies inside the map
+ *                 = the caller's cell, or fill   elsewhere (the exposed cells)
+ *     cx += dx, cy += dy                         (cells moved since _set_occupancy, int64)
+ *     origin_x = origin0_x + (double)cx * resolution,  origin_y = origin0_y + (double)cy * resolution
+ * with origin0 the origin _set_occupancy was given: the origin is formed from the accumulated cell count by one multiplication
+ * and one addition (no FMA), never by repeated addition, so it does not drift.  nx, ny, resolution, outside, threshold and
+ * inflation stay.  |dx| >= nx or |dy| >= ny is legal: every cell is exposed then.  After the call the float cells, the layer and
+ * the origin of the map are, in every bit, what a fresh _set_occupancy of `new` at the new origin would produce.
+ * exposed == NULL: every exposed cell becomes fill, which must be in [0, 255] (with exposed != NULL fill is not read).  Otherwise
+ * exposed holds, entry after entry and tightly packed, for each entry first the row strip and then the column strip:
+ *     row strip     the min(|dy|, ny) exposed rows over the full width nx, in ascending new-frame iy
+ *     column strip  of every remaining row, in ascending iy, its min(|dx|, nx) exposed cells in ascending ix
+ * (an entry with dx = dy = 0 has neither).  A 5 x 4 map (nx = 5, ny = 4) rolled by (dx, dy) = (2, -1): row iy = 0 is exposed
+ * (dy < 0: the low rows), and in the rows iy = 1, 2, 3 the columns ix = 3, 4 (dx > 0: the high columns), so the entry is
+ *     new(0,0) new(1,0) new(2,0) new(3,0) new(4,0)   new(3,1) new(4,1)   new(3,2) new(4,2)   new(3,3) new(4,3)
+ * -- 1 * 5 + 3 * 2 = 11 bytes; rolled by (-2, 1) it is row iy = 3 and then the columns ix = 0, 1 of the rows iy = 0, 1, 2.
+ * Stream-ordered like _update_occupancy_enqueue: no synchronisation, no flush of a pending resident update; exposed, map, dx
+ * and dy may be reused when the call returns.  A rollout enqueued before the call reads the old map at the old origin, every
+ * rollout enqueued after it the new one; the call may come between _resident_step_enqueue calls, between _iterate_enqueue calls
+ * and between patches, and is two kernel launches however many maps it rolls (none when every shift is zero).  A later
+ * _update_occupancy_enqueue addresses the rolled frame; _read_occupancy, _read_grid_cells, _get_grids and _get_occupancy show the
+ * rolled map and its origin (the origin from the moment the call returns).  The call stages its tables and strips in one slot of
+ * the patches' ring: with m the number of entries that move, 336 * m bytes plus the strips must not exceed
+ * CCV_MPPI_OCC_PATCH_MAX_CELLS bytes -- split a larger call by maps, or use _set_occupancy (64 maps of 200 x 200 rolled by
+ * (1, 1): 64 * (336 + 399) bytes).  The handle's first roll after a _set_occupancy allocates a second set of layers and float
+ * cells of the same size and, that once, flushes and synchronises like a setter: a roll with every dx = dy = 0 is the priming
+ * call, which changes no bit; no later roll allocates.  The second set is freed with the layers (_set_occupancy, _set_grids,
+ * destroy), and a new _set_occupancy starts again from its own origin with no cell moved.  No occupancy set: CCV_MPPI_ERR_STATE.
+ * n out of range, a map out of range or named twice, |dx| or |dy| above CCV_MPPI_GRID_MAX_DIM, an accumulated offset beyond
+ * +-2^30 cells, a rolled origin that is not finite, fill out of range, tables and strips above a slot, NULL map, dx or dy:
+ * CCV_MPPI_ERR_INVALID_ARG.  Nothing changes either way. */
 typedef struct ccv_mppi_occupancy { double origin_x, origin_y, resolution; float outside; int32_t nx, ny, threshold; const uint8_t* cells; } ccv_mppi_occupancy;
 typedef struct ccv_mppi_inflation { int32_t radius; float free_value; const float* profile; } ccv_mppi_inflation;
 int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* b, const ccv_mppi_occupancy* maps, const ccv_mppi_inflation* inflation, int32_t n_maps,
                                  const int32_t* map_of, const double* weight);
 int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* b, int32_t map, int32_t x0, int32_t y0, int32_t w, int32_t h, const uint8_t* patch);
+int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* b, int32_t n, const int32_t* map, const int32_t* dx, const int32_t* dy,
+                                          const uint8_t* exposed, int32_t fill);
 int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* b, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps);
 int ccv_mppi_batch_read_occupancy(ccv_mppi_batch* b, int32_t map, uint8_t* out);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
