@@ -112,6 +112,37 @@ def pack_exposed(sizes, dx, dy, exposed, fill=0):
     return np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, dtype=np.uint8)
 
 
+def scan_cells(geometry, sensor_xy, sensor_yaw, ranges, angle_min, angle_increment, range_min, range_max):
+    """One entry of BatchController.scan_occupancy from a planar range scan (a sensor_msgs/LaserScan): (sensor_cell (sx, sy),
+    ends int32 [n][2], hits uint8 [n]).  geometry: the map's entry of get_occupancy().  Beam k leaves the sensor at world
+    position sensor_xy under the angle sensor_yaw + angle_min + k * angle_increment.  Points go to cells by the grid term's
+    formula with floor in place of the truncation: cell = floor((p - origin) * (1.0 / resolution)), so a point left of or below
+    the map gets a negative cell.  A range that is NaN or below range_min drops the beam; a range >= range_max (+inf included)
+    is a miss: the ray ends at range_max with hit = 0; a ray of more than capi.SCAN_MAX_REACH cells is cut at its own cell
+    SCAN_MAX_REACH and becomes a miss.  The sensor's cell is returned as it is: the call refuses one outside the map."""
+    (ox, oy), resolution = geometry[0], geometry[1]
+    inv = 1.0 / float(resolution)
+    r = np.asarray(ranges, dtype=np.float64).reshape(-1)
+    ang = float(sensor_yaw) + float(angle_min) + np.arange(r.size, dtype=np.float64) * float(angle_increment)
+    with np.errstate(invalid="ignore"):
+        keep = ~np.isnan(r) & ~(r < float(range_min))
+        miss = r >= float(range_max)
+    r, ang, hits = np.where(miss, float(range_max), r)[keep], ang[keep], ~miss[keep]
+    sx, sy = int(np.floor((float(sensor_xy[0]) - ox) * inv)), int(np.floor((float(sensor_xy[1]) - oy) * inv))
+    ex = np.floor(((float(sensor_xy[0]) + r * np.cos(ang)) - ox) * inv).astype(np.int64)
+    ey = np.floor(((float(sensor_xy[1]) + r * np.sin(ang)) - oy) * inv).astype(np.int64)
+    # a ray beyond the reach ends in its own cell i = SCAN_MAX_REACH (the closed form of the call)
+    dx, dy = ex - sx, ey - sy
+    a, b = np.maximum(np.abs(dx), np.abs(dy)), np.minimum(np.abs(dx), np.abs(dy))
+    far = a > capi.SCAN_MAX_REACH
+    minor = (2 * capi.SCAN_MAX_REACH * b + a) // np.maximum(2 * a, 1)
+    xmajor = np.abs(dx) >= np.abs(dy)
+    ex = np.where(far, sx + np.sign(dx) * np.where(xmajor, capi.SCAN_MAX_REACH, minor), ex)
+    ey = np.where(far, sy + np.sign(dy) * np.where(xmajor, minor, capi.SCAN_MAX_REACH), ey)
+    ends = np.ascontiguousarray(np.stack([ex, ey], axis=1), dtype=np.int32).reshape(-1, 2)
+    return (sx, sy), ends, np.ascontiguousarray(hits & ~far, dtype=np.uint8)
+
+
 def inflation_profile(radius_m, resolution, kind="linear", lethal=1.0, inscribed=None, inscribed_m=0.0, free_value=0.0, scaling=10.0):
     """(R, profile float32 [R * R + 1], free_value) for BatchController.set_occupancy: the cost of a cell by the squared distance
     D2, in cells, from its centre to the centre of the nearest occupied cell, built on the host -- the device only looks it up.
@@ -392,6 +423,30 @@ class BatchController:
         self._check(self.lib.ccv_mppi_batch_roll_occupancy_enqueue(
             self._h, len(maps), maps.ctypes.data_as(ip), dx.ctypes.data_as(ip), dy.ctypes.data_as(ip),
             buf.ctypes.data_as(C.POINTER(C.c_uint8)) if buf is not None else None, int(fill)))
+
+    def scan_occupancy(self, maps, sensor_cells, ends, hits, clear=0, mark=255):
+        """Range scans traced into the maps `maps` (each at most once), in stream order and in two launches for all of them.  Per
+        entry: sensor_cells[i] = (sx, sy), the sensor's cell, inside the map; ends[i] int32 [n_i][2], the rays' end cells (they
+        may lie outside); hits[i] [n_i], non-zero where the ray ended on something (scan_cells makes all three from a
+        LaserScan).  Every cell a ray passes through, from the sensor's cell up to but not including the end cell, becomes
+        `clear`; then every hit's end cell becomes `mark` -- marks win over clears whatever the order of rays and entries --
+        and the float cells are what set_occupancy of the new layer would derive.  Cells are those of the map's current
+        (rolled) frame.  No synchronisation; the arguments may be reused when the call returns."""
+        maps = np.ascontiguousarray(np.atleast_1d(maps), dtype=np.int32)
+        if not (len(sensor_cells) == len(ends) == len(hits) == len(maps)):
+            raise ValueError("scan_occupancy: expected %d sensor cells, end arrays and hit arrays" % len(maps))
+        sensors = np.ascontiguousarray(np.asarray(sensor_cells, dtype=np.int32).reshape(len(maps), 2))
+        ends = [np.asarray(e, dtype=np.int32).reshape(-1, 2) for e in ends]
+        hits = [np.asarray(h).reshape(-1) != 0 for h in hits]
+        if any(len(e) != len(h) for e, h in zip(ends, hits)):
+            raise ValueError("scan_occupancy: an entry's ends and hits differ in length")
+        n_rays = np.ascontiguousarray([len(e) for e in ends], dtype=np.int32)
+        end_xy = np.ascontiguousarray(np.concatenate(ends + [np.zeros((0, 2), dtype=np.int32)]), dtype=np.int32)
+        hit = np.ascontiguousarray(np.concatenate(hits + [np.zeros(0, dtype=bool)]), dtype=np.uint8)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ccv_mppi_batch_scan_occupancy_enqueue(
+            self._h, len(maps), maps.ctypes.data_as(ip), sensors.ctypes.data_as(ip), n_rays.ctypes.data_as(ip), end_xy.ctypes.data_as(ip),
+            hit.ctypes.data_as(C.POINTER(C.c_uint8)), int(clear), int(mark)))
 
     def get_occupancy(self):
         """A list of ((origin_x, origin_y), resolution, outside, nx, ny, threshold, R, free_value) per map as the library holds

@@ -34,6 +34,8 @@ MAX_OBSTACLES = 32
 INFLATE_MAX_RADIUS = 64
 OCC_PATCH_MAX_CELLS = 1 << 20
 OCC_PATCH_SLOTS = 4
+SCAN_MAX_REACH = 4096
+SCAN_RAY_BYTES, SCAN_ENTRY_BYTES = 9, 128   # of a staging slot (OCC_PATCH_MAX_CELLS bytes) per ray, and per entry that has rays
 BEST_MAX = 1024
 BATCH_TRACE_ROWS = 1024
 
@@ -152,6 +154,8 @@ SIGNATURES = {
     "ccv_mppi_batch_update_occupancy_enqueue": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "ccv_mppi_batch_roll_occupancy_enqueue": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                         C.POINTER(C.c_uint8), C.c_int32]),
+    "ccv_mppi_batch_scan_occupancy_enqueue": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                        C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32, C.c_int32]),
     "ccv_mppi_batch_get_occupancy": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(Inflation), C.c_int32, C.POINTER(C.c_int32)]),
     "ccv_mppi_batch_read_occupancy": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint8)]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,

@@ -699,6 +699,97 @@ int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     return CCV_MPPI_OK;
 }
 
+// Stream-ordered like the patch and the roll above: the deferred resident update is not flushed, nothing is allocated on the
+// device or pinned, and the only wait is for the launches that last read the staging slot about to be refilled.  Two launches
+// however many maps are scanned; the front buffers are written in place (roll_front and the grid rows stay as they are).
+int ccv_mppi_batch_scan_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const int32_t* map, const int32_t* sensor_xy, const int32_t* n_rays,
+                                          const int32_t* end_xy, const uint8_t* hit, int32_t clear_value, int32_t mark_value) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "scan_occupancy: ";
+    // every check comes first, then the next slot of the ring
+    if (!bh->occ) return fail(bh, CCV_MPPI_ERR_STATE, "scan_occupancy: no occupancy is set (ccv_mppi_batch_set_occupancy)");
+    if (!map || !sensor_xy || !n_rays) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    const int n_maps = (int)bh->grid_maps.size();
+    if (n < 1 || n > n_maps) return refuse(bh, who, "n outside [1, the number of maps]");
+    if (clear_value < 0 || clear_value > 255 || mark_value < 0 || mark_value > 255) return refuse(bh, who, "clear_value or mark_value outside [0, 255]");
+    std::vector<uint8_t> named((size_t)n_maps, 0);
+    int64_t traced = 0, total = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = map[i];
+        if (m < 0 || m >= n_maps) return refuse(bh, who, "map out of range");
+        if (named[(size_t)m]) return refuse(bh, who, "a map is named twice");
+        named[(size_t)m] = 1;
+        const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+        const int32_t sx = sensor_xy[2 * (size_t)i], sy = sensor_xy[2 * (size_t)i + 1];
+        if (sx < 0 || sx >= g.nx || sy < 0 || sy >= g.ny) return refuse(bh, who, "a sensor cell outside its map");
+        if (n_rays[i] < 0) return refuse(bh, who, "a negative n_rays");
+        if (n_rays[i] == 0) continue;
+        ++traced;
+        total += n_rays[i];
+    }
+    if (total > 0 && (!end_xy || !hit)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    const size_t entry_bytes = (size_t)traced * sizeof(ScanEntry), rect_bytes = (size_t)traced * sizeof(InflateArgs);
+    if ((int64_t)(entry_bytes + rect_bytes) + total * kScanRayBytes > (int64_t)CCV_MPPI_OCC_PATCH_MAX_CELLS)
+        return refuse(bh, who, "tables and rays above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
+    // the reaches, and per entry the bounding box of the sensor cell and all end cells (every cell a ray touches lies in the box
+    // of its two ends)
+    std::vector<int64_t> box((size_t)n * 4);
+    size_t ray = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t sx = sensor_xy[2 * (size_t)i], sy = sensor_xy[2 * (size_t)i + 1];
+        int64_t* bb = &box[(size_t)i * 4];
+        bb[0] = bb[2] = sx;
+        bb[1] = bb[3] = sy;
+        for (int r = 0; r < n_rays[i]; ++r, ++ray) {
+            const int64_t ex = end_xy[2 * ray], ey = end_xy[2 * ray + 1];
+            if (std::llabs(ex - sx) > CCV_MPPI_SCAN_MAX_REACH || std::llabs(ey - sy) > CCV_MPPI_SCAN_MAX_REACH)
+                return refuse(bh, who, "a reach above CCV_MPPI_SCAN_MAX_REACH");
+            bb[0] = std::min(bb[0], ex);
+            bb[1] = std::min(bb[1], ey);
+            bb[2] = std::max(bb[2], ex);
+            bb[3] = std::max(bb[3], ey);
+        }
+    }
+    if (traced == 0) return CCV_MPPI_OK;   // (nothing is traced: no launch, no bit changes)
+    const int slot = bh->patch_next;
+    bh->patch_next = (slot + 1) % Costmap::kPatchSlots;
+    if (bh->patch_used[slot]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[slot]));
+    // the slot: the entries, the rectangles, the end cells, the hit bytes (the kernels read all four in place)
+    const size_t at = (size_t)slot * CCV_MPPI_OCC_PATCH_MAX_CELLS, end_at = at + entry_bytes + rect_bytes, hit_at = end_at + (size_t)total * 2 * sizeof(int32_t);
+    ScanEntry* entries = reinterpret_cast<ScanEntry*>(bh->h_patch + at);
+    InflateArgs* rects = reinterpret_cast<InflateArgs*>(bh->h_patch + at + entry_bytes);
+    std::memcpy(bh->h_patch + end_at, end_xy, (size_t)total * 2 * sizeof(int32_t));
+    std::memcpy(bh->h_patch + hit_at, hit, (size_t)total);
+    const int32_t* d_end = reinterpret_cast<const int32_t*>(bh->d_patch + end_at);
+    const uint8_t* d_hit = bh->d_patch + hit_at;
+    size_t k = 0;
+    int32_t max_tiles = 0;
+    ray = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_rays[i] == 0) continue;
+        const int m = map[i];
+        const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+        entries[k] = ScanEntry{layer_of(bh, m), d_end + 2 * ray, d_hit + ray, g.nx, g.ny, sensor_xy[2 * (size_t)i], sensor_xy[2 * (size_t)i + 1],
+                               n_rays[i], clear_value, mark_value, 0};
+        ray += (size_t)n_rays[i];
+        // The float cells to derive again: the box clipped to the map holds every cell the entry can
+        // change; grown by R and clipped again it holds every float cell whose value can (from layer cells up to 2R from the box).
+        const int64_t* bb = &box[(size_t)i * 4];
+        const int R = bh->occ_radius[(size_t)m];
+        const int32_t x0 = (int32_t)std::max<int64_t>(bb[0] - R, 0), y0 = (int32_t)std::max<int64_t>(bb[1] - R, 0);
+        const int32_t x1 = (int32_t)std::min<int64_t>(bb[2] + R + 1, g.nx), y1 = (int32_t)std::min<int64_t>(bb[3] + R + 1, g.ny);
+        rects[k++] = inflate_args(bh, m, x0, y0, x1 - x0, y1 - y0);
+        max_tiles = std::max(max_tiles, ((x1 - x0 + kInflateTile - 1) / kInflateTile) * ((y1 - y0 + kInflateTile - 1) / kInflateTile));
+    }
+    launch_scan_trace(reinterpret_cast<const ScanEntry*>(bh->d_patch + at), (int32_t)traced, bh->stream);
+    launch_inflate_rects(reinterpret_cast<const InflateArgs*>(bh->d_patch + at + entry_bytes), (int32_t)traced, max_tiles, bh->stream);
+    const hipError_t launched = hipGetLastError();
+    bh->patch_used[slot] = true;
+    HIP_TRY(bh, launched);
+    HIP_TRY(bh, hipEventRecord(bh->patch_ev[slot], bh->stream));   // (after the second launch: both read the slot)
+    return CCV_MPPI_OK;
+}
+
 int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* bh, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps) {
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     const int n = bh->occ ? (int)bh->grid_maps.size() : 0;

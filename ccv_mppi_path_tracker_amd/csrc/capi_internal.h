@@ -32,6 +32,7 @@
 #include "mppi_fleet.h"
 #include "mppi_costmap.h"
 #include "mppi_costmap_roll.h"
+#include "mppi_costmap_scan.h"
 
 namespace ccv {
 
@@ -271,7 +272,8 @@ struct Grids {
 // occupancy layers (ccv_mppi_batch_set_occupancy, mppi_costmap.h): while `occ`, the cells of Grids are not a caller's but derived
 // on the device from a uint8 layer per map (same geometry, same offsets: layer m starts at d_occ + grid_offset[m]) and the map's
 // inflation; a patch of a layer is enqueued on the stream (ccv_mppi_batch_update_occupancy_enqueue) through the staging ring,
-// and so is a roll of the maps' windows (ccv_mppi_batch_roll_occupancy_enqueue).
+// and so are a roll of the maps' windows (ccv_mppi_batch_roll_occupancy_enqueue) and the range scans traced into the layers
+// (ccv_mppi_batch_scan_occupancy_enqueue, mppi_costmap_scan.h).
 // The ring is allocated at the first _set_occupancy and kept until destroy.
 struct Costmap {
     bool occ = false;

@@ -260,6 +260,7 @@ int ccv_mppi_timing_read(ccv_mppi_handle* h, double* rollout_us_sum, double* ite
 #define CCV_MPPI_INFLATE_MAX_RADIUS 64    /* cells: the largest inflation radius of ccv_mppi_batch_set_occupancy */
 #define CCV_MPPI_OCC_PATCH_MAX_CELLS (1 << 20) /* cells of one patch of ccv_mppi_batch_update_occupancy_enqueue */
 #define CCV_MPPI_OCC_PATCH_SLOTS 4        /* patches whose staging can be in flight before _update_occupancy_enqueue waits */
+#define CCV_MPPI_SCAN_MAX_REACH 4096      /* cells: the largest max(|ex - sx|, |ey - sy|) of a ray of ccv_mppi_batch_scan_occupancy_enqueue */
 
 typedef struct ccv_mppi_batch ccv_mppi_batch;
 
@@ -452,6 +453,36 @@ int ccv_mppi_batch_read_grid_cells(ccv_mppi_batch* b, int32_t map, float* cells_
  * destroy), and a new _set_occupancy starts again from its own origin with no cell moved.  No occupancy set: CCV_MPPI_ERR_STATE.
  * n out of range, a map out of range or named twice, |dx| or |dy| above CCV_MPPI_GRID_MAX_DIM, an accumulated offset beyond
  * +-2^30 cells, a rolled origin that is not finite, fill out of range, tables and strips above a slot, NULL map, dx or dy:
+ * CCV_MPPI_ERR_INVALID_ARG.  Nothing changes either way.
+ * _scan_occupancy_enqueue: range scans traced into the layers.  Entry i of the n entries (1 <= n <= the number of maps) names a
+ * map map[i] (each map at most once), the sensor's cell (sensor_xy[i][0], sensor_xy[i][1]), which must lie inside the map, and
+ * n_rays[i] >= 0 rays; the rays of all entries follow each other, entry after entry, in end_xy [sum n_rays][2] (a ray's end
+ * cell, which may lie outside the map) and hit [sum n_rays] (non-zero: the ray ended on something).  All coordinates are int32
+ * cells of the map's current frame, the rolled one that _update_occupancy_enqueue addresses.  Integers only.  With (sx, sy) the
+ * sensor's cell and (ex, ey) a ray's end cell:
+ *     adx = |ex - sx|, ady = |ey - sy|;  the major axis is x if adx >= ady, else y;  a = major length, b = minor length
+ *     cell i, 0 <= i < a:  major = s_major + sign_major * i,  minor = s_minor + sign_minor * ((2 * i * b + a) div (2 * a))
+ * -- the integer error walk (e = a; per step e += 2b; if e >= 2a: e -= 2a, minor += 1) written per step.  Cell 0 is the
+ * sensor's cell; the end cell (i = a) is not part of the ray; a ray with a = 0 has no cells.  The reach a of a ray is at most
+ * CCV_MPPI_SCAN_MAX_REACH.  With `old` and `new` the layer before and after the call:
+ *     new = old
+ *     every ray cell inside the map                                  = clear_value
+ *     the end cell, where it lies inside the map, of a ray with hit  = mark_value     (after ALL clears of that map)
+ * so marks win over clears within a call, whatever the order of the rays and of the entries; cells outside the map are
+ * skipped, never wrapped; clear_value and mark_value, each in [0, 255], are the bytes stored (occupancy is still
+ * cells >= threshold).  After the call the layer and the float cells of the map are, in every bit, what a fresh _set_occupancy
+ * of `new` would produce: per entry the float cells of one rectangle are derived again -- the bounding box of the sensor cell
+ * and all end cells, clipped to the map, grown by R and clipped again.  Stream-ordered like _update_occupancy_enqueue and
+ * _roll_occupancy_enqueue: no synchronisation, no allocation, no flush of a pending resident update; every array may be reused
+ * when the call returns.  A rollout enqueued before the call reads the old cells, every rollout enqueued after it the new ones;
+ * the call may come between _resident_step_enqueue calls, between _iterate_enqueue calls, between patches and rolls, and is two
+ * kernel launches however many maps it scans.  An entry with n_rays = 0 takes no room and does no work; a call in which nothing
+ * is traced launches nothing.  The call stages its tables and rays in one slot of the patches' ring: 9 bytes per ray (the end
+ * cell and the hit byte) and 128 bytes per entry that has rays must not exceed CCV_MPPI_OCC_PATCH_MAX_CELLS bytes -- the largest
+ * call of one entry has 116 494 rays, 64 entries of 360 rays take 215 552 bytes; split a larger call by maps, or by rays into
+ * calls that all clear and a last one that also marks.  No occupancy set: CCV_MPPI_ERR_STATE.  n out of range, a map out of range
+ * or named twice, a sensor cell outside its map, a negative n_rays, a reach above the limit, clear_value or mark_value outside
+ * [0, 255], a call that does not fit one slot, NULL map, sensor_xy or n_rays, NULL end_xy or hit with a ray to read:
  * CCV_MPPI_ERR_INVALID_ARG.  Nothing changes either way. */
 typedef struct ccv_mppi_occupancy { double origin_x, origin_y, resolution; float outside; int32_t nx, ny, threshold; const uint8_t* cells; } ccv_mppi_occupancy;
 typedef struct ccv_mppi_inflation { int32_t radius; float free_value; const float* profile; } ccv_mppi_inflation;
@@ -460,6 +491,9 @@ int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* b, const ccv_mppi_occupancy* ma
 int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* b, int32_t map, int32_t x0, int32_t y0, int32_t w, int32_t h, const uint8_t* patch);
 int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* b, int32_t n, const int32_t* map, const int32_t* dx, const int32_t* dy,
                                           const uint8_t* exposed, int32_t fill);
+int ccv_mppi_batch_scan_occupancy_enqueue(ccv_mppi_batch* b, int32_t n, const int32_t* map, const int32_t* sensor_xy /*[n][2]*/,
+                                          const int32_t* n_rays /*[n]*/, const int32_t* end_xy /*[sum n_rays][2]*/, const uint8_t* hit /*[sum n_rays]*/,
+                                          int32_t clear_value, int32_t mark_value);
 int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* b, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps);
 int ccv_mppi_batch_read_occupancy(ccv_mppi_batch* b, int32_t map, uint8_t* out);
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
