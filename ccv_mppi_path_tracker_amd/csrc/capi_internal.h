@@ -4,8 +4,9 @@
 //   capi_resident.hip    device-resident closed loop of a single handle
 //   capi_stage.hip       stage-wise calls, read-back, timing
 //   capi_batch.hip       batch handles (ccv_mppi_batch_*): what a tick runs and what reads its results, the resident loop included
-//   capi_batch_config.hip  batch handles: what configures the next launch (parameters, shifted weights, discs, grids and their
-//                          occupancy layers, fleet term)
+//   capi_batch_config.hip  batch handles: what configures the next launch (parameters, shifted weights, discs, fleet term)
+//   capi_batch_maps.hip  batch handles: the maps of the grid term, a caller's cells or costmaps derived on the device, and the
+//                        stream-ordered patches, rolls and scans of those
 //   capi_batch_feed.hip  batch handles: best candidates and optimal paths of every instance (mppi_feed.h)
 // A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
@@ -30,9 +31,6 @@
 #include "mppi_update.h"
 #include "mppi_resident.h"
 #include "mppi_fleet.h"
-#include "mppi_costmap.h"
-#include "mppi_costmap_roll.h"
-#include "mppi_costmap_scan.h"
 
 namespace ccv {
 
@@ -271,49 +269,39 @@ struct Grids {
 
 // occupancy layers (ccv_mppi_batch_set_occupancy, mppi_costmap.h): while `occ`, the cells of Grids are not a caller's but derived
 // on the device from a uint8 layer per map (same geometry, same offsets: layer m starts at d_occ + grid_offset[m]) and the map's
-// inflation; a patch of a layer is enqueued on the stream (ccv_mppi_batch_update_occupancy_enqueue) through the staging ring,
-// and so are a roll of the maps' windows (ccv_mppi_batch_roll_occupancy_enqueue) and the range scans traced into the layers
-// (ccv_mppi_batch_scan_occupancy_enqueue, mppi_costmap_scan.h).
-// The ring is allocated at the first _set_occupancy and kept until destroy.
+// inflation; patches of a layer, rolls of the maps' windows and range scans traced into the layers are enqueued on the stream
+// (ccv_mppi_batch_update_ / _roll_ / _scan_occupancy_enqueue) through the staging ring, which is allocated at the first
+// _set_occupancy and kept until destroy (capi_batch_maps.hip: ring_create, slot_take, slot_seal).
 struct Costmap {
     bool occ = false;
     uint8_t* d_occ = nullptr;                // the layers of all maps, one allocation
     float* d_profile = nullptr;              // the profile tables of all maps, one allocation
-    std::vector<size_t> profile_offset;      // [n_maps] first entry of map m's table in d_profile
-    std::vector<int32_t> occ_threshold;      // [n_maps]
-    std::vector<int32_t> occ_radius;         // [n_maps] R, in cells
-    std::vector<float> occ_free;             // [n_maps] free_value
+    // rolling maps (mppi_costmap_roll.h): a second allocation of the layers and of the float cells, same sizes and offsets, made at
+    // the first roll and freed with the layers.  A roll writes the one that does not hold the map and flips Layer::front.
+    uint8_t* d_occ_roll = nullptr;
+    float* d_cells_roll = nullptr;
+    struct Layer {
+        size_t profile_offset;               // first entry of the map's table in d_profile
+        int32_t threshold, radius;           // radius: R, in cells
+        float free_value;
+        uint8_t front;                       // which allocation holds the map: 0 the first (d_occ, Grids::d_grid_cells), 1 the second
+        int64_t cx, cy;                      // cells moved since _set_occupancy
+        double ox0, oy0;                     // ... and the origin it was given
+    };
+    std::vector<Layer> layers;               // [n_maps]
     static constexpr int kPatchSlots = CCV_MPPI_OCC_PATCH_SLOTS;   // pinned staging of the patches, in rotation: a slot is refilled
     uint8_t* h_patch = nullptr;              // only after the writer that read it has run; [kPatchSlots][CCV_MPPI_OCC_PATCH_MAX_CELLS]
     uint8_t* d_patch = nullptr;              // its device address (the patch writer reads the slots in place)
     hipEvent_t patch_ev[kPatchSlots] = {};
     bool patch_used[kPatchSlots] = {};
     int patch_next = 0;
-    // rolling maps (ccv_mppi_batch_roll_occupancy_enqueue, mppi_costmap_roll.h): a second allocation of the layers and of the
-    // float cells, same sizes and offsets, made at the first roll and freed with the layers.  roll_front[m] says which of the
-    // two holds map m: 0 the first (d_occ, Grids::d_grid_cells), 1 the second.  A roll writes the other one and flips the bit.
-    uint8_t* d_occ_roll = nullptr;
-    float* d_cells_roll = nullptr;
-    std::vector<uint8_t> roll_front;         // [n_maps]
-    std::vector<int64_t> roll_cx, roll_cy;   // [n_maps] cells moved since _set_occupancy
-    std::vector<double> roll_ox0, roll_oy0;  // [n_maps] the origin _set_occupancy was given
     // the layers and tables go (the maps become a caller's, or none); the ring stays
     void drop_layers() {
         free_device({d_occ, d_profile, d_occ_roll, d_cells_roll});
-        d_occ = nullptr;
-        d_profile = nullptr;
-        d_occ_roll = nullptr;
-        d_cells_roll = nullptr;
-        roll_front.clear();
-        roll_cx.clear();
-        roll_cy.clear();
-        roll_ox0.clear();
-        roll_oy0.clear();
+        d_occ = d_occ_roll = nullptr;
+        d_profile = d_cells_roll = nullptr;
+        layers.clear();
         occ = false;
-        profile_offset.clear();
-        occ_threshold.clear();
-        occ_radius.clear();
-        occ_free.clear();
     }
     void release() {
         for (hipEvent_t e : patch_ev)
@@ -487,7 +475,7 @@ struct ResidentBounds {
 ResidentBounds resident_bounds(const DeviceBuffers& d, const ccv_mppi_config& c, const double* angle_abs, double dt, int32_t advance);
 hipError_t read_trace_ring(const double* d_ring, int64_t cap, int64_t steps, int32_t max_rows, double* rows, int32_t* n_rows);
 
-// ---- batch handles: what the tick path (capi_batch.hip) and the setters (capi_batch_config.hip) share ----------------------
+// ---- batch handles: what the tick path (capi_batch.hip) and the setters (capi_batch_config.hip, capi_batch_maps.hip) share ---
 // instance b's configuration: its own under per-instance parameters, the creation configuration otherwise
 inline const ccv_mppi_config& batch_cfg(const ccv_mppi_batch* bh, const int b) { return bh->varied ? bh->cfgs[(size_t)b] : bh->cfg; }
 // the rung of the kernels the handle's next launch runs (BatchForm, mppi_kernels.h): the highest one whose addition is on
@@ -498,6 +486,9 @@ inline bool uses_table(const ccv_mppi_batch* bh) { return batch_form(bh) >= Batc
 inline int batch_flush(ccv_mppi_batch* bh) { return flush_finalize(bh); }
 // the handle's device current, no update deferred, the stream idle: nothing queued reads a table or writes a result any more
 int quiesce(ccv_mppi_batch* bh);
+// the derived tables the next launch or prologue reads, from the handle's state (capi_batch_config.hip); the caller has quiesced
+int sync_tables(ccv_mppi_batch* bh);
+inline bool valid_weight(const double w) { return w >= 0.0 && std::isfinite(w); }
 // the fleet's snapshots start over (the caller has quiesced): both halves of the position table from xy [B][2] (null: as they are)
 // and, under prediction, both halves of the velocity snapshot zero -- no robot has moved yet
 int fleet_restart(ccv_mppi_batch* bh, const double* xy);

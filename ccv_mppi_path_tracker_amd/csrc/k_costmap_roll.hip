@@ -2,12 +2,12 @@
 // on the tick path of a handle that never rolls; no rollout, prologue or update kernel knows of them -- the GRID kernels read
 // the grid rows afresh at every launch and find the back cells and the new origin there.
 #include "mppi_costmap_roll.h"
+#include "mppi_costmap_device.h"
 
 namespace ccv {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kNone = 255;   // row pass: no occupied cell within R in this row (R <= 64 < 255)
+constexpr int kThreads = kInflateThreads;
 
 // blockIdx.y: the entry.  Out of place: the back layer and the back float cells from the front ones at the shifted index (a
 // float cell whose source lies outside the map is in a band and is k_inflate_rects' to write), the exposed layer cells from the
@@ -46,51 +46,15 @@ __global__ __launch_bounds__(kThreads) void k_roll_shift(const RollEntry* __rest
 }
 
 // blockIdx.y: the rectangle, blockIdx.x: its tile, row-major; the tiles past a rectangle's end exit.  The body is k_inflate's
-// (k_costmap.hip) for a kInflateTile x kInflateTile tile, restated here so that that unit stays as it is: the occupancy of the
-// tile plus a halo of R cells staged in LDS (cells outside the map: free), the row pass, the column pass, the table lookup and
-// one float store.  LDS: 192 * 192 + 192 * 64 bytes = 48 KiB whatever R is.
+// (inflate_tile, mppi_costmap_device.h).
 __global__ __launch_bounds__(kThreads) void k_inflate_rects(const InflateArgs* __restrict__ rects) {
     __shared__ uint8_t s_occ[kInflateSpan * kInflateSpan];
     __shared__ uint8_t s_g[kInflateSpan * kInflateTile];
     const InflateArgs a = rects[blockIdx.y];
-    const int tiles_x = (a.w + kInflateTile - 1) / kInflateTile, tiles_y = (a.h + kInflateTile - 1) / kInflateTile;
-    if ((int)blockIdx.x >= tiles_x * tiles_y) return;
+    const int tiles_x = inflate_tiles(a.w);
+    if ((int)blockIdx.x >= inflate_tiles(a.w, a.h)) return;
     const int by = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - by * tiles_x;
-    const int R = a.R, span = kInflateTile + 2 * R;
-    const int tx0 = a.x0 + bx * kInflateTile, ty0 = a.y0 + by * kInflateTile;
-    for (int i = threadIdx.x; i < span * span; i += kThreads) {
-        const int r = i / span, c = i - r * span;
-        const int gx = tx0 - R + c, gy = ty0 - R + r;
-        uint8_t o = 0;
-        if (gx >= 0 && gx < a.nx && gy >= 0 && gy < a.ny) o = (int)a.layer[(size_t)gy * a.nx + gx] >= a.threshold ? 1 : 0;
-        s_occ[i] = o;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < span * kInflateTile; i += kThreads) {
-        const int r = i / kInflateTile, x = i - r * kInflateTile;
-        const uint8_t* at = s_occ + r * span + x + R;   // (x + R - d >= 0 and x + R + d < span for d <= R)
-        int g = kNone;
-        for (int d = 0; d <= R; ++d)
-            if (at[-d] | at[d]) {
-                g = d;
-                break;
-            }
-        s_g[i] = (uint8_t)g;
-    }
-    __syncthreads();
-    const int x_end = a.x0 + a.w, y_end = a.y0 + a.h, R2 = R * R;
-    for (int i = threadIdx.x; i < kInflateTile * kInflateTile; i += kThreads) {
-        const int y = i / kInflateTile, x = i - y * kInflateTile;
-        const int gx = tx0 + x, gy = ty0 + y;
-        if (gx >= x_end || gy >= y_end) continue;
-        int best = R2 + 1;
-        for (int dy = -R; dy <= R; ++dy) {
-            const int g = s_g[(y + R + dy) * kInflateTile + x];
-            const int d2 = g * g + dy * dy;   // (kNone^2 > R^2 + 1: never the minimum that counts)
-            best = d2 < best ? d2 : best;
-        }
-        a.cells[(size_t)gy * a.nx + gx] = best <= R2 ? a.profile[best] : a.free_value;
-    }
+    inflate_tile(a, bx, by, s_occ, s_g);
 }
 
 }  // namespace
@@ -101,6 +65,7 @@ void launch_roll_shift(const RollEntry* entries, const int32_t n, const int64_t 
     hipLaunchKernelGGL(k_roll_shift, dim3((unsigned)(blocks < 2048 ? blocks : 2048), (unsigned)n), dim3(kThreads), 0, stream, entries, rows, B);
 }
 
+// (declared in mppi_costmap.h beside launch_inflate: the roll and the scan both launch it)
 void launch_inflate_rects(const InflateArgs* rects, const int32_t n_rects, const int32_t max_tiles, hipStream_t stream) {
     hipLaunchKernelGGL(k_inflate_rects, dim3((unsigned)max_tiles, (unsigned)n_rects), dim3(kThreads), 0, stream, rects);
 }

@@ -4,7 +4,7 @@
 //     occ(ix, iy)  = layer[iy * nx + ix] >= threshold             (a cell outside the map is not occupied)
 //     D2(ix, iy)   = min over occupied (jx, jy) of (jx - ix)^2 + (jy - iy)^2
 //     cost(ix, iy) = D2 <= R * R ? profile[D2] : free_value
-// The kernels are k_costmap.hip's; the host side (the Costmap part, capi_internal.h) calls the two launchers below.
+// The kernels are k_costmap.hip's (the tile body: mppi_costmap_device.h); the host side (capi_batch_maps.hip) calls the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,7 +26,13 @@ struct InflateArgs {
     int32_t nx, ny, threshold, R;
     int32_t x0, y0, w, h;
 };
+// the tiles of n cells of one axis, and of a w x h rectangle
+constexpr int inflate_tiles(const int32_t n) { return (n + kInflateTile - 1) / kInflateTile; }
+constexpr int inflate_tiles(const int32_t w, const int32_t h) { return inflate_tiles(w) * inflate_tiles(h); }
 void launch_inflate(const InflateArgs& a, hipStream_t stream);
+// The same over a table of n_rects rectangles of any maps in one launch (a roll's bands, a scan's boxes); max_tiles: inflate_tiles
+// of the largest.  The table is read in place, from pinned host memory or device memory.  Defined in k_costmap_roll.hip.
+void launch_inflate_rects(const InflateArgs* rects, int32_t n_rects, int32_t max_tiles, hipStream_t stream);
 
 // The patch writer: the w x h rectangle at (x0, y0) of the layer [..][nx] from `patch` (row-major, tightly packed; pinned
 // host memory or device memory).  The rectangle lies inside the map.

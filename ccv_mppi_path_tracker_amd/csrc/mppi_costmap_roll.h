@@ -4,8 +4,8 @@
 //                 = the caller's cell, or fill elsewhere (the exposed cells)
 // and the float cells are the transform of mppi_costmap.h over `new`, complete.  Two launches for all maps of a call:
 // k_roll_shift writes the back layer and the back float cells from the front ones and points the instances' grid rows at the
-// back cells and the new origin; k_inflate_rects derives again the float cells of the bands whose value the roll can change.
-// The kernels are k_costmap_roll.hip's; both tables live in the staging slot of the call (pinned host memory, read in place).
+// back cells and the new origin; launch_inflate_rects (mppi_costmap.h) derives again the float cells of the bands whose value the
+// roll can change.  The kernels are k_costmap_roll.hip's; both tables live in the staging slot of the call (pinned, read in place).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,8 +33,7 @@ static_assert(sizeof(RollEntry) == 80, "a table of the staging slot");
 // (the rectangles of k_inflate_rects are InflateArgs: the rectangle lies inside the map, layer and cells are the back ones)
 constexpr int kRollMaxRects = 4;   // per map: a leading and a trailing band in x and in y
 
-// Launch 1: n entries, the grid rows [B] of the handle.  Launch 2: n_rects rectangles, the largest of max_tiles tiles.
+// Launch 1: n entries, the grid rows [B] of the handle.  (Launch 2: launch_inflate_rects.)
 void launch_roll_shift(const RollEntry* entries, int32_t n, int64_t max_cells, GridRow* rows, int32_t B, hipStream_t stream);
-void launch_inflate_rects(const InflateArgs* rects, int32_t n_rects, int32_t max_tiles, hipStream_t stream);
 
 }  // namespace ccv

@@ -7,7 +7,7 @@
 // 2 * i * b + a < 2^26.  The layer after a call:
 //     every ray cell inside the map = clear_value;  then, after ALL clears of that map, every end cell inside the map of a ray
 //     with hit != 0 = mark_value
-// and the float cells are the transform of mppi_costmap.h over the new layer: k_inflate_rects (mppi_costmap_roll.h) over one
+// and the float cells are the transform of mppi_costmap.h over the new layer: launch_inflate_rects (mppi_costmap.h) over one
 // rectangle per entry.  The kernel is k_costmap_scan.hip's; the entry table and the rays live in the staging slot of the call
 // (pinned host memory, read in place).
 #pragma once

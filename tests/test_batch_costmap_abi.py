@@ -105,3 +105,4 @@ def test_the_python_side_offers_the_calls_and_the_build_has_the_units():
         assert callable(getattr(BatchController, name))
     assert callable(batch.inflation_profile)
     assert "k_costmap.hip" in build.KERNEL_UNITS and "mppi_costmap.h" in build.HEADERS
+    assert "capi_batch_maps.hip" in build.CAPI_UNITS and "mppi_costmap_device.h" in build.HEADERS

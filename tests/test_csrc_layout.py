@@ -66,3 +66,31 @@ def test_a_unit_sees_only_the_kernel_headers_of_the_families_it_launches():
     # the kernel headers build on the building blocks, not on each other
     for h in family_of:
         assert not {p for p in _reachable(h) if p in family_of}, os.path.basename(h)
+
+
+def _reaching(header):
+    """the sources (build.SOURCES) that reach csrc/<header>"""
+    return {unit for unit in build.SOURCES if _norm(header) in _reachable(_norm(unit))}
+
+
+def test_the_inflation_tile_body_is_seen_by_the_two_units_that_run_it():
+    assert os.path.exists(_norm("mppi_costmap_device.h"))
+    assert _reaching("mppi_costmap_device.h") == {"k_costmap.hip", "k_costmap_roll.hip"}
+
+
+def test_the_configuration_unit_sees_no_costmap_header():
+    assert "capi_batch_maps.hip" in build.CAPI_UNITS
+    reach = {os.path.basename(p) for p in _reachable(_norm("capi_batch_config.hip"))}
+    assert not {h for h in reach if h.startswith("mppi_costmap")}, sorted(reach)
+    assert {"mppi_costmap.h", "mppi_costmap_roll.h", "mppi_costmap_scan.h"} <= {os.path.basename(p) for p in _reachable(_norm("capi_batch_maps.hip"))}
+
+
+def test_the_row_pass_of_the_inflation_stands_in_one_file():
+    # (kNone is the row pass's "no occupied cell within R": where it is defined, the pass is written)
+    holders = []
+    for name in sorted(os.listdir(build.CSRC)):
+        path = os.path.join(build.CSRC, name)
+        if os.path.isfile(path):
+            with open(path) as f:
+                holders += [name] * len(re.findall(r"^\s*constexpr\s+int\s+kNone\b", f.read(), re.M))
+    assert holders == ["mppi_costmap_device.h"], holders
