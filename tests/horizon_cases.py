@@ -52,7 +52,7 @@ def producer_steps(H):
     return [min(K_TU, H - 1 - K_TU * b) for b in range(nblocks)]
 
 
-# The one case of the batch sweep whose inputs are not TP.instance_inputs(p, 5) with salt 0: steering H = 5 with salt 0 gives a
+# The one case of the batch sweep whose inputs are not BS.instance_inputs(p, 5) with salt 0: steering H = 5 with salt 0 gives a
 # moving-disc instance every sample of which carries a penalty (share 1.00; the condition is 10 % .. 90 %).
 BATCH_SALT = {("steering_diff_drive", 5): 1}
 

@@ -12,13 +12,12 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
 import fleet_crossing_cpu as FC  # noqa: E402
-import test_gpu_batch_fleet as TF  # noqa: E402
-import test_gpu_batch_moving as TM  # noqa: E402
+import fleet_support as FS  # noqa: E402
 
 
 def test_the_crossing_parameters_separate_predicted_from_snapshot_on_the_cpu_restatement():
-    c = TM.CROSSING
-    p = TF.params()
+    c = FS.CROSSING
+    p = FS.params()
     res = {m: FC.closest_approach(p, c["paths"], c["s0"], c["seeds"], c["ticks"], [c["radius"]] * 2, c["range"], c["weight"], m)
            for m in ("off", "snapshot", "predicted")}
     print("closest approach off / snapshot / predicted (CPU restatement): %.4f / %.4f / %.4f" % (res["off"], res["snapshot"], res["predicted"]))

@@ -9,12 +9,12 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
 import fleet_head_on_cpu as HO  # noqa: E402
-import test_gpu_batch_fleet as TF  # noqa: E402
+import fleet_support as FS  # noqa: E402
 
 
 def test_the_head_on_parameters_separate_on_from_off_on_the_cpu_restatement():
-    c = TF.HEAD_ON
-    p = TF.params()
+    c = FS.HEAD_ON
+    p = FS.params()
     off = HO.closest_approach(p, c["paths"], c["s0"], c["seeds"], c["ticks"], [c["radius"]] * 2, c["range"], None)
     on = HO.closest_approach(p, c["paths"], c["s0"], c["seeds"], c["ticks"], [c["radius"]] * 2, c["range"], c["weight"])
     print("closest approach off / on (CPU restatement): %.4f / %.4f" % (off, on))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import helpers
+from batch_support import MODEL_DEFAULTS, families, instance_seed
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIController, MPPIError
 from oracle import oracle_lib as O
@@ -16,27 +17,11 @@ pytestmark = pytest.mark.gpu
 
 TOL_U = 1e-5      # as test_gpu_parity.py
 TOL_COST = 1e-9
-MODEL_DEFAULTS = {"diff_drive": configs.diff_drive_defaults, "steering_diff_drive": configs.steering_defaults,
-                  "full_body": configs.full_body_defaults}
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def _cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def families(model, K, B):
-    """(single handle's kernel family, batch's) by the selection rule of ccv_mppi_create / ccv_mppi_batch_create"""
-    cus, nblk = _cus(), -(-K // 64)
-    if model == "full_body":
-        single = "r4" if nblk <= cus else ("pc" if nblk <= 4 * cus else "solo")
-        return single, ("r4" if B * nblk <= cus else "solo")
-    return ("r4" if nblk <= 5 * cus else "solo"), ("r4" if B * nblk <= 5 * cus else "solo")
 
 
 def instance_inputs(p, B, salt=0):
@@ -58,7 +43,7 @@ def instance_inputs(p, B, salt=0):
         dt[b] = p.dt * (1.0 + 0.05 * (b % 4))
         _, xr[b], yr[b], yaw = O.calc_ref_path(px, py, x0[b, 0], x0[b, 1], p.v_ref, dt[b], p.resolution, p.horizon)
         yaw0[b] = yaw[0]
-        seeds[b] = (0x9E3779B97F4A7C15 * (b + 1) + salt) & 0xFFFFFFFFFFFFFFFF
+        seeds[b] = instance_seed(b, salt)
     lo, hi = np.array(p.u_min), np.array(p.u_max)
     nom = np.clip(0.3 * (hi - lo) / 2 * rng.standard_normal((B, p.horizon - 1, p.udim)) + (hi + lo) / 2, lo, hi)
     return x0, dt, xr, yr, yaw0, seeds, nom

@@ -13,38 +13,26 @@ import sys
 import numpy as np
 import pytest
 
+import batch_support as BS
 import ccv_mppi_path_tracker_amd as amd
 import costmap_reference as CR
+import fleet_support as FS
 import grid_reference as GR
-import test_gpu_batch_fleet as TF
-import test_gpu_batch_obstacles as TO
-import test_gpu_batch_params as TP
+import obstacle_cases as OC
+from batch_support import GRID, SHIFT
 from ccv_mppi_path_tracker_amd import BatchController, batch, capi, configs
+from costmap_support import INFLATION, _rss_kb, cells_hit, derived, layer_like, occ_map, same, tick_bits
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import costmap_door_cpu as CD  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SHIFT = capi.BATCH_KERNEL_SHIFT
-GRID = capi.BATCH_KERNEL_GRID | capi.BATCH_KERNEL_MOVING | capi.BATCH_KERNEL_OBST | capi.BATCH_KERNEL_VARIED
 u8p = C.POINTER(C.c_uint8)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def occ_map(cells, threshold=128, origin=(0.0, 0.0), resolution=0.05, outside=CR.OUTSIDE):
-    return (cells, origin, resolution, outside, threshold)
-
-
-def derived(bat, m=0):
-    return bat.get_grids()[0][m][0]
-
-
-def same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 # 1. full inflation ------------------------------------------------------------------------------------------------------------
@@ -129,15 +117,6 @@ def test_a_clearing_patch_needs_both_margins(small_handle):
 
 
 # 3. same bits as a caller-made map ----------------------------------------------------------------------------------------------
-INFLATION = batch.inflation_profile(0.2, 0.05, kind="exponential", lethal=3.0, inscribed=2.0, inscribed_m=0.05, scaling=8.0, free_value=0.125)
-
-
-def layer_like(g, seed):
-    """an occupancy layer with the geometry of a grid_reference map: 6 % of the cells occupied"""
-    rng = np.random.default_rng(seed)
-    return np.where(rng.random((g.ny, g.nx)) < 0.06, 255, 0).astype(np.uint8)
-
-
 def twin_maps(geos, seed=0):
     """(the arguments of set_occupancy's maps, the checker's float maps as set_grids takes them)"""
     R, profile, free = INFLATION
@@ -149,46 +128,40 @@ def twin_maps(geos, seed=0):
     return occ, flt
 
 
-def tick_bits(bat):
-    B = bat.B
-    return [bat.get_nominal().tobytes()] + [bat.read_costs(b).tobytes() + bat.read_weights(b).tobytes() + bat.read_candidates(b).tobytes()
-                                            for b in range(B)]
-
-
 @pytest.mark.parametrize("discs", ["none", "static", "moving"])
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
 def test_derived_cells_give_the_bits_of_a_caller_made_map(shift, discs):
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
     occ, flt = twin_maps(geos)
-    d = TO.discs_for(p, inputs, ns=(32, 0, 3, 3, 32)) if discs != "none" else None
+    d = OC.discs_for(p, inputs, ns=(32, 0, 3, 3, 32)) if discs != "none" else None
     vels = [np.stack([0.3 * np.cos(np.arange(len(a)) + b), 0.2 * np.sin(np.arange(len(a)) - b)], axis=1).reshape(-1, 2)
             for b, a in enumerate(d)] if discs == "moving" else None
-    s0, rseeds = TP.start_poses(p, B)
+    s0, rseeds = BS.start_poses(p, B)
     rgeos = [GR.map_ahead(s0[b, :3], p.v_ref, p.dt, p.horizon, salt=b - 1, ahead=2.0) for b in (1, 2)]
     rocc, rflt = twin_maps(rgeos, seed=7)
     out = []
     for source in ("occupancy", "grids"):
         bat = BatchController(p, B, min_shift=shift)
         if d is not None:
-            bat.set_obstacles(d, TO.W_OBS, velocities=vels)
+            bat.set_obstacles(d, OC.W_OBS, velocities=vels)
         if source == "occupancy":
             bat.set_occupancy(occ, INFLATION, map_of, w)
         else:
             bat.set_grids(flt, map_of, w)
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        res = [TO.snapshot(bat, u, st), bat.last_kernel(), derived(bat, 0), derived(bat, 1)]
+        res = [BS.snapshot(bat, u, st), bat.last_kernel(), derived(bat, 0), derived(bat, 1)]
         # five resident ticks over maps placed from the start poses
         if source == "occupancy":
             bat.set_occupancy(rocc, INFLATION, map_of, w)
         else:
             bat.set_grids(rflt, map_of, w)
-        bat.resident_set_paths([TP.path_of(b) for b in range(B)])
+        bat.resident_set_paths([BS.path_of(b) for b in range(B)])
         bat.resident_set_poses(s0, rseeds)
         for it in range(5):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
@@ -199,22 +172,22 @@ def test_derived_cells_give_the_bits_of_a_caller_made_map(shift, discs):
     a, b = out
     assert a[1] == b[1] == a[-1] == b[-1] == capi.BATCH_KERNEL_FOUR_WAVE | GRID | (SHIFT if shift else 0)
     assert same(a[2], b[2]) and same(a[3], b[3]) and len(np.unique(a[2])) > 5
-    assert all(TO.same_bits(x, y) for x, y in zip(a[0], b[0]))
+    assert all(BS.same_bits(x, y) for x, y in zip(a[0], b[0]))
     for it in range(5):
         assert a[4 + it] == b[4 + it], it
 
 
 def test_derived_cells_give_the_bits_of_a_caller_made_map_beside_the_fleet_term():
-    p = TF.params("diff_drive", 1000, 15)
+    p = FS.params("diff_drive", 1000, 15)
     B = 5
-    s0, seeds, paths = TF.fleet_start(p, B)
+    s0, seeds, paths = FS.fleet_start(p, B)
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(s0[b, :3], p.v_ref, p.dt, p.horizon, salt=b - 1, ahead=2.0) for b in (1, 2)]
     occ, flt = twin_maps(geos, seed=3)
-    static = [TF.far_discs(b % 3, b) for b in range(B)]
+    static = [FS.far_discs(b % 3, b) for b in range(B)]
     out = []
     for source in ("occupancy", "grids"):
-        bat = TF.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
+        bat = FS.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
         bat.resident_set_fleet_prediction(True)
         if source == "occupancy":
             bat.set_occupancy(occ, INFLATION, map_of, w)
@@ -234,12 +207,6 @@ def test_derived_cells_give_the_bits_of_a_caller_made_map_beside_the_fleet_term(
 T_STREAM = 30
 
 
-def cells_hit(geo, P):
-    """the flat cell indices the covered states P [K][n][2] read"""
-    _, inside, idx = GR.lookup(geo, P[..., 0], P[..., 1])
-    return np.unique(idx[inside])
-
-
 @pytest.mark.parametrize("mode", ["resident", "iterate"])
 def test_patches_take_effect_in_stream_order(mode):
     """A: occupancy, one patch enqueued after every step and nothing else between the steps.  B: before every step the
@@ -249,8 +216,8 @@ def test_patches_take_effect_in_stream_order(mode):
     p = configs.diff_drive_defaults(128, 15)
     B, R = 2, 3
     profile, free = CR.distinct_profile(R) * np.float32(0.001), 0.0   # (1.000 .. 1.009: the ring costs about what a cell does)
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     geo = GR.map_ahead(s0[0, :3], p.v_ref, p.dt, p.horizon, ahead=3.0)
     map_of, w = np.array([0, -1], dtype=np.int32), np.array([0.5, 0.0])
     x0 = np.zeros((B, 3))
@@ -352,7 +319,7 @@ def test_a_door_closes():
 def test_refusals_change_nothing_and_the_setters_keep_the_layers():
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
@@ -367,7 +334,7 @@ def test_refusals_change_nothing_and_the_setters_keep_the_layers():
     assert lib.ccv_mppi_batch_read_occupancy(bat._h, 0, one.ctypes.data_as(u8p)) == capi.ERR_STATE
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-    before, k_before = TO.snapshot(bat, u, st, states=False), bat.last_kernel()
+    before, k_before = BS.snapshot(bat, u, st, states=False), bat.last_kernel()
     bat.set_occupancy(occ, INFLATION, map_of, w)
 
     def holds():
@@ -384,7 +351,7 @@ def test_refusals_change_nothing_and_the_setters_keep_the_layers():
     def tick():
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        return TO.snapshot(bat, u, st, states=False)
+        return BS.snapshot(bat, u, st, states=False)
 
     holds()
     want = tick()
@@ -438,12 +405,12 @@ def test_refusals_change_nothing_and_the_setters_keep_the_layers():
     assert lib.ccv_mppi_batch_read_occupancy(bat._h, 2, one.ctypes.data_as(u8p)) == capi.ERR_INVALID_ARG
     assert lib.ccv_mppi_batch_get_occupancy(bat._h, rows[0], rows[1], 1, None) == capi.ERR_INVALID_ARG   # two maps, room for one
     holds()
-    assert all(TO.same_bits(a, b, states=False) for a, b in zip(want, tick()))
+    assert all(BS.same_bits(a, b, states=False) for a, b in zip(want, tick()))
     # the other setters keep the layers
-    discs = TO.discs_for(p, inputs, ns=(0, 3, 0, 3, 0))
+    discs = OC.discs_for(p, inputs, ns=(0, 3, 0, 3, 0))
     bat.set_params([p] * B)
     bat.set_params(None)
-    bat.set_obstacles(discs, TO.W_OBS, velocities=[np.zeros((len(a), 2)) for a in discs])
+    bat.set_obstacles(discs, OC.W_OBS, velocities=[np.zeros((len(a), 2)) for a in discs])
     bat.set_obstacle_velocities(None)
     bat.set_obstacles(None)
     bat.set_min_shift(True)
@@ -452,22 +419,22 @@ def test_refusals_change_nothing_and_the_setters_keep_the_layers():
     bat.resident_set_fleet_prediction(True)
     bat.resident_set_fleet(None)
     holds()
-    assert all(TO.same_bits(a, b, states=False) for a, b in zip(want, tick()))
+    assert all(BS.same_bits(a, b, states=False) for a, b in zip(want, tick()))
     # _set_occupancy(NULL) restores the kernel and the bits that ran before, twice over
     for again in range(2):
         bat.set_occupancy(None)
         assert bat.get_occupancy() == [] and bat.get_grids()[0] == []
         assert lib.ccv_mppi_batch_read_occupancy(bat._h, 0, one.ctypes.data_as(u8p)) == capi.ERR_STATE
         back = tick()
-        assert bat.last_kernel() == k_before and all(TO.same_bits(a, b, states=False) for a, b in zip(before, back))
+        assert bat.last_kernel() == k_before and all(BS.same_bits(a, b, states=False) for a, b in zip(before, back))
         bat.set_occupancy(occ, INFLATION, map_of, w)
-        assert all(TO.same_bits(a, b, states=False) for a, b in zip(want, tick()))
+        assert all(BS.same_bits(a, b, states=False) for a, b in zip(want, tick()))
     # _set_grids drops the layers: the maps are the caller's
     bat.set_grids([(derived(bat, 0), occ[0][1], occ[0][2], occ[0][3]), (derived(bat, 1), occ[1][1], occ[1][2], occ[1][3])], map_of, w)
     assert bat.get_occupancy() == []
     assert lib.ccv_mppi_batch_read_occupancy(bat._h, 0, one.ctypes.data_as(u8p)) == capi.ERR_STATE
     assert lib.ccv_mppi_batch_update_occupancy_enqueue(bat._h, 0, 0, 0, 1, 1, one.ctypes.data_as(u8p)) == capi.ERR_STATE
-    assert all(TO.same_bits(a, b, states=False) for a, b in zip(want, tick()))
+    assert all(BS.same_bits(a, b, states=False) for a, b in zip(want, tick()))
     bat.close()
 
 
@@ -491,7 +458,7 @@ def test_the_patch_size_limit():
 def test_one_instances_map_or_patch_changes_no_bit_of_an_instance_on_another_map():
     p = configs.diff_drive_defaults(1000, 15)
     B, j = 5, 2   # (instance 2 is on map 1, with instance 4)
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 0], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.02, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
@@ -505,18 +472,18 @@ def test_one_instances_map_or_patch_changes_no_bit_of_an_instance_on_another_map
             bat.update_occupancy(1, 0, 0, np.full(occ[1][0].shape, 255, dtype=np.uint8))
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        snaps.append(TO.snapshot(bat, u, st))
+        snaps.append(BS.snapshot(bat, u, st))
         bat.close()
     for s in snaps[1:]:
         assert not np.array_equal(snaps[0][j]["c"], s[j]["c"])
-        assert all(TO.same_bits(snaps[0][b], s[b]) for b in range(B) if b != j)
+        assert all(BS.same_bits(snaps[0][b], s[b]) for b in range(B) if b != j)
 
 
 def test_costmap_returns_all_device_memory():
     import torch
     p = configs.diff_drive_defaults(1000, 15)
     B = 16
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     map_of, w = np.array([b % 2 for b in range(B)], dtype=np.int32), np.full(B, 0.01)
     big = (np.ones((700, 900), dtype=np.uint8), (0.0, 0.0), 0.05, 0.0, 1)      # (0.6 MiB of layer, 2.4 MiB of cells)
     small = (np.ones((3, 5), dtype=np.uint8), (0.0, 0.0), 0.05, 0.0, 1)
@@ -548,9 +515,3 @@ def test_costmap_returns_all_device_memory():
     # the staging ring is 4 MiB of pinned, hence resident, host memory per handle: 40 rings left behind would be 160 MiB
     assert rss1 - rss0 < 96 * 1024, "resident host memory grew by %d kB over 40 cycles" % (rss1 - rss0)
 
-
-def _rss_kb():
-    for line in open("/proc/self/status"):
-        if line.startswith("VmRSS:"):
-            return int(line.split()[1])
-    return 0

@@ -13,15 +13,13 @@ import pytest
 import ccv_mppi_path_tracker_amd as amd
 import select_probe
 import select_reference as R
+from batch_support import MODEL_DEFAULTS, instance_seed, path_of
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIError
 
 pytestmark = pytest.mark.gpu
 
-MODEL_DEFAULTS = {"diff_drive": configs.diff_drive_defaults, "steering_diff_drive": configs.steering_defaults,
-                  "full_body": configs.full_body_defaults}
 MODELS = ("diff_drive", "steering_diff_drive", "full_body")
-PATHS = {}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -31,13 +29,6 @@ def _need_gpu(gpu_required):
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def path_of(b):
-    kind = "sinusoid" if b % 2 == 0 else "dkan"
-    if kind not in PATHS:
-        PATHS[kind] = amd.make_path(kind)
-    return PATHS[kind]
 
 
 def tick_inputs(p, B, salt=0, yaw_offset=None):
@@ -56,7 +47,7 @@ def tick_inputs(p, B, salt=0, yaw_offset=None):
         dt[b] = p.dt * (1.0 + 0.05 * (b % 4))
         _, xr[b], yr[b], yaw = amd.calc_ref_path(px, py, x0[b, 0], x0[b, 1], p.v_ref, dt[b], p.resolution, p.horizon)
         yaw0[b] = yaw[0]
-        seeds[b] = (0x9E3779B97F4A7C15 * (b + 1) + salt) & 0xFFFFFFFFFFFFFFFF
+        seeds[b] = instance_seed(b, salt)
     lo, hi = np.array(p.u_min), np.array(p.u_max)
     rng = np.random.default_rng(99 + salt)
     nom = np.clip(0.3 * (hi - lo) / 2 * rng.standard_normal((B, p.horizon - 1, p.udim)) + (hi + lo) / 2, lo, hi)

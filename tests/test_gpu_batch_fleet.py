@@ -9,67 +9,19 @@ forms the lists with the reference, hands static + fleet discs to set_obstacles 
 import numpy as np
 import pytest
 
+import batch_support as BS
 import fleet_reference as FR
-import test_gpu_batch_params as TP
-from ccv_mppi_path_tracker_amd import BatchController, capi
+from batch_support import OV, SHIFT
+from ccv_mppi_path_tracker_amd import capi
 from ccv_mppi_path_tracker_amd.controller import MPPIError
+from fleet_support import HEAD_ON, bits, far_discs, fleet_start, make, params, robot_bits
 
 pytestmark = pytest.mark.gpu
-OV = capi.BATCH_KERNEL_OBST | capi.BATCH_KERNEL_VARIED
-SHIFT = capi.BATCH_KERNEL_SHIFT
-FAR = 40.0   # static discs this far from the paths never touch a rollout: they fill rows
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def params(model="diff_drive", K=128, H=15):
-    return TP.MODEL_DEFAULTS[model](K, H)
-
-
-def fleet_start(p, B, first=5, step=3):
-    """B robots on the sinusoid path, `step` path points (0.1 m each) apart, with small lateral offsets"""
-    px, py = TP.path_of(0)
-    s = np.zeros((B, p.nstate))
-    seeds = np.zeros(B, dtype=np.uint64)
-    for b in range(B):
-        i = first + step * b
-        s[b, 0], s[b, 1] = px[i], py[i] + 0.05 * ((b % 5) - 2)
-        s[b, 2] = np.arctan2(py[i + 1] - py[i], px[i + 1] - px[i]) + 0.1 * ((b % 3) - 1)
-        seeds[b] = (0x9E3779B97F4A7C15 * (b + 1)) & 0xFFFFFFFFFFFFFFFF
-    return s, seeds, [TP.path_of(0)] * B
-
-
-def far_discs(n, salt=0):
-    a = 0.7 * np.arange(n) + salt
-    return np.stack([FAR * np.cos(a) + 5.0, FAR * np.sin(a), 0.5 + 0.01 * np.arange(n)], axis=1).reshape(-1, 3)
-
-
-def bits(bat):
-    """everything a tick leaves, as bytes per field"""
-    st, idx, xr, yr, _, steps = bat.resident_read()
-    return dict(u=bat.get_nominal().tobytes(), st=st.tobytes(), idx=idx.tobytes(), xr=xr.tobytes(), yr=yr.tobytes(), steps=steps,
-                c=b"".join(bat.read_costs(b).tobytes() for b in range(bat.B)))
-
-
-def robot_bits(bat, b):
-    st, idx = bat.resident_read()[:2]
-    return (bat.get_nominal()[b].tobytes(), st[b].tobytes(), int(idx[b]), bat.read_costs(b).tobytes())
-
-
-def make(p, B, shift, static, weight, paths, s0, seeds, fleet=None, timed=False):
-    bat = BatchController(p, B, min_shift=shift)
-    if static is not None:
-        bat.set_obstacles(static, weight)
-    bat.resident_set_paths(paths)
-    bat.resident_set_poses(s0, seeds)
-    if fleet is not None:
-        bat.resident_set_fleet(*fleet)
-    if timed:
-        bat.timing_enable(True)
-    return bat
 
 
 def twin_run(p, B, shift, static, radius, rng, maxn, weight, paths, s0, seeds, ticks, timed=False):
@@ -155,11 +107,11 @@ def test_lists_of_300_robots_equal_the_reference():
     equal the reference on the poses read after the previous tick; a run that reads nothing in between ends on the same lists."""
     p = params("diff_drive", 64, 10)
     B, ticks, maxn, rng = 300, 20, 4, 0.6
-    px, py = TP.path_of(0)
+    px, py = BS.path_of(0)
     s0 = np.zeros((B, p.nstate))
     s0[:, 0] = 1.0 + 0.25 * (np.arange(B) % 20)      # (dyadic: the grid's distances are exact)
     s0[:, 1] = 0.25 * (np.arange(B) // 20) - 1.75
-    seeds = (np.arange(B, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+    seeds = np.array([BS.instance_seed(b) for b in range(B)], dtype=np.uint64)
     n_static = np.array([0, 30, 0, 32, 0, 0, 30] * 43, dtype=np.int32)[:B]
     static = [far_discs(int(n), b) for b, n in enumerate(n_static)]
     radius = 0.1 + 0.001 * np.arange(B)
@@ -196,7 +148,7 @@ def test_a_robot_out_of_range_changes_no_bit_of_lists_without_it():
     robot 4 drives differently, and its disc moves with it); it does change robots 2 and 3, which see robot 4."""
     p = params()
     B, ticks = 5, 10
-    px, py = TP.path_of(0)
+    px, py = BS.path_of(0)
     s0, seeds, paths = fleet_start(p, B)
     for b, i in enumerate((5, 8, 45, 48, 51)):
         s0[b, 0], s0[b, 1] = px[i], py[i] + 0.05 * ((b % 5) - 2)
@@ -353,7 +305,7 @@ def test_refusals_change_nothing():
 def test_more_than_1024_instances_are_refused_at_set():
     p = params("diff_drive", 64, 10)
     B = 1025
-    px, py = TP.path_of(0)
+    px, py = BS.path_of(0)
     s0 = np.zeros((B, p.nstate))
     s0[:, 0], s0[:, 1] = px[5] + 0.01 * np.arange(B), py[5]
     res = []
@@ -411,12 +363,6 @@ def test_fleet_returns_all_device_memory():
 
 
 # 7. behaviour ---------------------------------------------------------------------------------------------------------------
-_X = 0.1 * np.arange(61)
-# chosen on the CPU restatement of the closed loop (tools/fleet_head_on_cpu.py; tests/test_fleet_head_on_cpu.py)
-HEAD_ON = dict(paths=[(_X, np.zeros(61)), (_X[::-1].copy(), np.zeros(61))], s0=np.array([[1.5, 0.0, 0.0], [4.5, 0.0, np.pi]]),
-               seeds=np.array([11, 12], dtype=np.uint64), ticks=90, radius=0.3, range=3.0, weight=200.0)
-
-
 def test_two_robots_head_on_pass_at_a_larger_distance():
     """Two robots on the same straight 6 m path in opposite directions, 3 m apart at the start, shifted weights on, radii
     0.3 m + 0.3 m, range 3 m, weight 200, 90 ticks.  With the term off their closest approach (same tick) is below the 0.6 m of

@@ -11,7 +11,7 @@ the TAIL form); the one-wave family needs more than five blocks per CU and is wa
 import numpy as np
 import pytest
 
-import test_gpu_batch_params as TP
+import batch_support as BS
 from ccv_mppi_path_tracker_amd import BatchController, capi
 
 pytestmark = pytest.mark.gpu
@@ -27,9 +27,9 @@ def _need_gpu(gpu_required):
 
 @pytest.mark.parametrize("model,K,H", [("diff_drive", 128, 9), ("diff_drive", 128, 15), ("full_body", 64, 15)])
 def test_up_and_down_the_ladder(model, K, H):
-    p = TP.MODEL_DEFAULTS[model](K, H)
-    assert TP.families(model, K, B)[1] == "r4"
-    x0, dt, xr, yr, yaw0, seeds, nom = TP.instance_inputs(p, B)
+    p = BS.MODEL_DEFAULTS[model](K, H)
+    assert BS.families(model, K, B)[1] == "r4"
+    x0, dt, xr, yr, yaw0, seeds, nom = BS.instance_inputs(p, B)
     # discs over the start (whichever way the warm start drives, the first states lie inside; instance 1: a second one beside it),
     # moving away from it; a map of positive cells around the start
     discs = [np.array([[x0[0, 0], x0[0, 1], 0.3]]), np.array([[x0[1, 0], x0[1, 1], 0.25], [x0[1, 0] + 0.2, x0[1, 1], 0.2]])]
@@ -45,7 +45,7 @@ def test_up_and_down_the_ladder(model, K, H):
         return bat.last_kernel(), u.copy(), [bat.read_costs(b) for b in range(B)]
 
     # (what the rung adds to the bits of the one below, its setter, the setter that undoes it, whether it changes the costs)
-    rungs = [(VARIED, lambda: bat.set_params(TP.varied(p, B)), lambda: bat.set_params(None), True),
+    rungs = [(VARIED, lambda: bat.set_params(BS.varied(p, B)), lambda: bat.set_params(None), True),
              (SHIFT, lambda: bat.set_min_shift(True), lambda: bat.set_min_shift(False), False),
              (OBST, lambda: bat.set_obstacles(discs, 5.0), lambda: bat.set_obstacles(None), True),
              (MOVING, lambda: bat.set_obstacle_velocities(velocities), lambda: bat.set_obstacle_velocities(None), True),

@@ -11,73 +11,33 @@ Instances of a batch of five, in order: no map; map 0; map 1; map 0 with weight 
 stand near instances 1 and 2 (grid_inputs), whose poses place the maps (grid_reference.map_ahead).
 """
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
 
-import os
-import sys
-
+import batch_support as BS
 import ccv_mppi_path_tracker_amd as amd
+import fleet_support as FS
 import grid_reference as GR
 import helpers
+import obstacle_cases as OC
+import update_checks as UC
 import update_reference as R
-import test_gpu_batch_fleet as TF
-import test_gpu_batch_obstacles as TO
-import test_gpu_batch_params as TP
-import test_gpu_batch_shift as TS
-import test_gpu_update as TU
+from batch_support import GRID, MOV, OV, SHIFT
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
+from grid_cases import CASES, PLAIN_CASE, check_identity, grid_inputs, maps_for, roles
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import grid_wall_cpu as GW  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SHIFT = capi.BATCH_KERNEL_SHIFT
-OV = capi.BATCH_KERNEL_OBST | capi.BATCH_KERNEL_VARIED
-MOV = capi.BATCH_KERNEL_MOVING | OV
-GRID = capi.BATCH_KERNEL_GRID | MOV
-W_GRID = (0.0, 0.01, 0.01, 0.0, 0.025)   # (not dyadic: the products round)
-MAP_OF = (-1, 0, 1, 0, 1)
-CASES = TO.CASES
-PLAIN_CASE = ("diff_drive", 1000, 15, 5, {}, "plain")
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def roles(B):
-    """(map_of [B], weight [B]): the five roles dealt round; a batch of two: a map and none"""
-    if B == 2:
-        return np.array([0, -1], dtype=np.int32), np.array([W_GRID[1], 0.0])
-    return np.array([MAP_OF[b % 5] for b in range(B)], dtype=np.int32), np.array([W_GRID[b % 5] for b in range(B)])
-
-
-def grid_inputs(p, B, salt=0):
-    """TP.instance_inputs with instances 3 and 4 of every five moved beside instances 1 and 2 (pose, dt and window theirs, a
-    little to the side and turned; seeds and warm starts their own), so that one map serves both"""
-    x0, dt, xr, yr, yaw0, seeds, nom = TP.instance_inputs(p, B, salt)
-    for b in range(B):
-        if b % 5 in (3, 4) and B >= 5:
-            a = b - 2
-            x0[b], dt[b], xr[b], yr[b], yaw0[b] = x0[a], dt[a], xr[a], yr[a], yaw0[a]
-            x0[b, 1] += 0.03
-            x0[b, 2] += 0.05
-    return x0, dt, xr, yr, yaw0, seeds, nom
-
-
-def maps_for(p, inputs):
-    """(two maps, map_of, weight): map m placed from the pose of the first instance that uses it, on the side its warm start
-    drives to (the full-body warm starts of instance_inputs, drawn around the middle of the speed bounds, reverse)"""
-    x0, dt, nom = inputs[0], inputs[1], inputs[6]
-    map_of, w = roles(len(dt))
-    maps = []
-    for m in (0, 1):
-        b = int(np.argmax(map_of == m)) if np.any(map_of == m) else 0
-        maps.append(GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m, backwards=bool(np.mean(nom[b, :, 0]) < 0.0)))
-    return maps, map_of, w
 
 
 def set_maps(bat, maps, map_of, w):
@@ -92,36 +52,22 @@ def run_off_on(p, B, inputs, maps, map_of, w, shift, prepare=None, it=0):
         prepare(bat)
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, it)
-    off, k_off = TO.snapshot(bat, u, st), bat.last_kernel()
+    off, k_off = BS.snapshot(bat, u, st), bat.last_kernel()
     set_maps(bat, maps, map_of, w)
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, it)
-    return off, TO.snapshot(bat, u, st), k_off, bat.last_kernel(), bat
-
-
-def check_identity(what, p, g, w, off, on, conditions=True):
-    """states bit-equal; cost_on == fma(w, G_ref, cost_off) in every bit; the conditions on the inputs"""
-    assert on["xy"].tobytes() == off["xy"].tobytes(), what
-    P = on["xy"][:, :GR.n_covered(p.model, p.horizon)]
-    share_in, share_out, cells = GR.coverage(g, P)
-    G = GR.grid_sum(g, P)
-    want = GR.cost_on(off["c"], w, G)
-    bad = int(np.sum(want.view(np.uint64) != on["c"].view(np.uint64)))
-    print("[grid] %s: in %.2f out %.2f cells %d, G %.6g .. %.6g, costs that differ %d of %d" % (what, share_in, share_out, cells, G.min(), G.max(), bad, len(G)))
-    if conditions:
-        assert share_in >= 0.25 and share_out >= 0.05 and cells >= 50, (what, share_in, share_out, cells)
-    assert bad == 0, (what, bad)
+    return off, BS.snapshot(bat, u, st), k_off, bat.last_kernel(), bat
 
 
 def check_all(what0, p, inputs, maps, map_of, w, off, on):
     for b in range(len(map_of)):
         what = "%s b=%d map=%d w=%g" % (what0, b, map_of[b], w[b])
         if map_of[b] < 0:
-            assert TO.same_bits(off[b], on[b]), what
+            assert BS.same_bits(off[b], on[b]), what
             continue
         check_identity(what, p, maps[map_of[b]], w[b], off[b], on[b])
         if w[b] == 0.0:
-            assert TO.same_bits(off[b], on[b]), what
+            assert BS.same_bits(off[b], on[b]), what
         else:
             assert not np.array_equal(off[b]["c"], on[b]["c"]), what
 
@@ -130,11 +76,11 @@ def check_all(what0, p, inputs, maps, map_of, w, off, on):
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
 @pytest.mark.parametrize("model,K,H,B,over,fam", CASES)
 def test_grid_term_is_the_spec_bit_for_bit(model, K, H, B, over, fam, shift):
-    p = TP.MODEL_DEFAULTS[model](K, H)
+    p = BS.MODEL_DEFAULTS[model](K, H)
     if over:
         p = p.with_(**over)
     if fam == "solo":
-        assert TP.families(model, K, B)[1] == "solo"
+        assert BS.families(model, K, B)[1] == "solo"
     inputs = grid_inputs(p, B)
     maps, map_of, w = maps_for(p, inputs)
     off, on, k_off, k_on, bat = run_off_on(p, B, inputs, maps, map_of, w, shift)
@@ -149,15 +95,15 @@ def test_grid_term_is_the_spec_bit_for_bit(model, K, H, B, over, fam, shift):
         bat.set_grids(None)
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        back = TO.snapshot(bat, u, st)
+        back = BS.snapshot(bat, u, st)
         assert bat.last_kernel() == k_off
-        assert all(TO.same_bits(off[b], back[b]) for b in range(B))
+        assert all(BS.same_bits(off[b], back[b]) for b in range(B))
         if again == 0:
             set_maps(bat, maps, map_of, w)
             bat.set_nominal(nom)
             u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
             assert bat.last_kernel() == k_on
-            assert all(TO.same_bits(on[b], s) for b, s in enumerate(TO.snapshot(bat, u, st)))
+            assert all(BS.same_bits(on[b], s) for b, s in enumerate(BS.snapshot(bat, u, st)))
     bat.close()
 
 
@@ -165,7 +111,7 @@ def test_grid_term_is_the_spec_bit_for_bit(model, K, H, B, over, fam, shift):
 def test_plain_family_through_one_heading(shift):
     """one instance's heading outside the fast sin / cos range sends the batch through the plain kernel's GRID form"""
     model, K, H, B, _, _ = PLAIN_CASE
-    p = TP.MODEL_DEFAULTS[model](K, H)
+    p = BS.MODEL_DEFAULTS[model](K, H)
     inputs = grid_inputs(p, B)
     inputs[0][0, 2] += 2.0e5 * np.pi   # (instance 0 has no map: no map is placed from this heading)
     maps, map_of, w = maps_for(p, inputs)
@@ -181,8 +127,8 @@ def test_full_body_beyond_one_workgroup_per_cu_runs_the_four_wave_form():
     of bit for bit: cost_on against fma(w, G_ref, cost_off) with G_ref from the term-on run's own states."""
     K, H = 128, 15
     p = configs.full_body_defaults(K, H)
-    B = 5 * (TP._cus() // 10 + 1)   # (two workgroups per instance: more than one per CU)
-    assert TP.families(p.model, K, B)[1] == "solo"
+    B = 5 * (BS.cus() // 10 + 1)   # (two workgroups per instance: more than one per CU)
+    assert BS.families(p.model, K, B)[1] == "solo"
     inputs = grid_inputs(p, B)
     maps, map_of, w = maps_for(p, inputs)
     off, on, k_off, k_on, bat = run_off_on(p, B, inputs, maps, map_of, w, False)
@@ -192,7 +138,7 @@ def test_full_body_beyond_one_workgroup_per_cu_runs_the_four_wave_form():
             continue
         P = on[b]["xy"][:, :GR.n_covered(p.model, H)]
         want = GR.cost_on(off[b]["c"], w[b], GR.grid_sum(maps[map_of[b]], P))
-        assert np.max(np.abs(on[b]["c"] - want) / np.abs(want)) < TP.TOL_COST, b
+        assert np.max(np.abs(on[b]["c"] - want) / np.abs(want)) < BS.TOL_COST, b
     bat.close()
 
 
@@ -205,11 +151,11 @@ def test_identity_holds_beside_discs(shift, vel):
     B = 5
     inputs = grid_inputs(p, B)
     maps, map_of, w = maps_for(p, inputs)
-    discs = TO.discs_for(p, inputs, ns=(32, 0, 3, 3, 32))
+    discs = OC.discs_for(p, inputs, ns=(32, 0, 3, 3, 32))
     vels = [np.stack([0.3 * np.cos(np.arange(len(d)) + b), 0.2 * np.sin(np.arange(len(d)) - b)], axis=1).reshape(-1, 2) for b, d in enumerate(discs)]
 
     def prepare(bat):
-        bat.set_obstacles(discs, TO.W_OBS, velocities=vels if vel else None)
+        bat.set_obstacles(discs, OC.W_OBS, velocities=vels if vel else None)
 
     off, on, k_off, k_on, bat = run_off_on(p, B, inputs, maps, map_of, w, shift, prepare)
     assert k_off == capi.BATCH_KERNEL_FOUR_WAVE | (MOV if vel else OV) | (SHIFT if shift else 0)
@@ -218,7 +164,7 @@ def test_identity_holds_beside_discs(shift, vel):
     # the discs stay through _set_grids; the setters of the discs keep the maps
     got, _ = bat.get_obstacles()
     assert all(np.array_equal(a, b) for a, b in zip(got, discs))
-    bat.set_obstacles(discs, TO.W_OBS, velocities=vels if vel else None)
+    bat.set_obstacles(discs, OC.W_OBS, velocities=vels if vel else None)
     bat.set_min_shift(not shift)
     bat.set_min_shift(shift)
     bat.set_params([p] * B)
@@ -227,22 +173,22 @@ def test_identity_holds_beside_discs(shift, vel):
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
     assert bat.last_kernel() == k_on
-    assert all(TO.same_bits(on[b], s) for b, s in enumerate(TO.snapshot(bat, u, st)))
+    assert all(BS.same_bits(on[b], s) for b, s in enumerate(BS.snapshot(bat, u, st)))
     bat.close()
 
 
 @pytest.mark.parametrize("pred", [False, True], ids=["snapshot", "predicted"])
 def test_identity_holds_beside_the_fleet_term(pred):
     """two resident fleets run three ticks alike; then one gets the maps: its fourth tick's costs are the other's plus the term"""
-    p = TF.params("diff_drive", 1000, 15)
+    p = FS.params("diff_drive", 1000, 15)
     B = 5
-    s0, seeds, paths = TF.fleet_start(p, B)
+    s0, seeds, paths = FS.fleet_start(p, B)
     map_of, w = roles(B)
     maps = [GR.map_ahead(s0[1, :3], p.v_ref, p.dt, p.horizon, salt=0), GR.map_ahead(s0[2, :3], p.v_ref, p.dt, p.horizon, salt=1)]
-    static = [TF.far_discs(b % 3, b) for b in range(B)]
+    static = [FS.far_discs(b % 3, b) for b in range(B)]
     res = []
     for on in (False, True):
-        bat = TF.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
+        bat = FS.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
         if pred:
             bat.resident_set_fleet_prediction(True)
         for it in range(3):
@@ -279,13 +225,13 @@ def test_one_instances_map_changes_no_bit_of_another():
         set_maps(bat, m, mo, wt)
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        snaps.append(TO.snapshot(bat, u, st))
+        snaps.append(BS.snapshot(bat, u, st))
         bat.close()
     for s in snaps[1:]:
         assert not np.array_equal(snaps[0][j]["c"], s[j]["c"])
         for b in range(B):
             if b != j:
-                assert TO.same_bits(snaps[0][b], s[b])
+                assert BS.same_bits(snaps[0][b], s[b])
 
 
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
@@ -293,9 +239,9 @@ def test_four_wave_and_one_wave_agree(shift):
     K, H = 1000, 15
     p = configs.diff_drive_defaults(K, H)
     B4 = 5
-    reps = -(-(5 * TP._cus() + 1) // (16 * B4))
+    reps = -(-(5 * BS.cus() + 1) // (16 * B4))
     B1 = B4 * reps
-    assert TP.families(p.model, K, B4)[1] == "r4" and TP.families(p.model, K, B1)[1] == "solo"
+    assert BS.families(p.model, K, B4)[1] == "r4" and BS.families(p.model, K, B1)[1] == "solo"
     inp = grid_inputs(p, B4)
     maps, map_of, w = maps_for(p, inp)
     res = []
@@ -311,8 +257,8 @@ def test_four_wave_and_one_wave_agree(shift):
     assert k4 == capi.BATCH_KERNEL_FOUR_WAVE | GRID | (SHIFT if shift else 0)
     assert k1 == capi.BATCH_KERNEL_ONE_WAVE | GRID | (SHIFT if shift else 0)
     for b in range(B4):
-        assert helpers.rel_err(u4[b], u1[b]) < TP.TOL_U
-        assert np.max(np.abs(c4[b] - c1[b]) / c1[b]) < TP.TOL_COST
+        assert helpers.rel_err(u4[b], u1[b]) < BS.TOL_U
+        assert np.max(np.abs(c4[b] - c1[b]) / c1[b]) < BS.TOL_COST
 
 
 # 3. the update -------------------------------------------------------------------------------------------------------------
@@ -336,12 +282,12 @@ def test_update_from_the_term_on_costs(shift):
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
     assert bat.last_kernel() == capi.BATCH_KERNEL_FOUR_WAVE | GRID | (SHIFT if shift else 0)
     for b in range(B):
-        ctl = TU.host_controls(plist[b], nom[b], seeds[b], 0)
+        ctl = UC.host_controls(plist[b], nom[b], seeds[b], 0)
         what = "grid b=%d" % b
         if shift:
-            TS.check_shift(what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b], sens=False)
+            UC.check_shift(what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b], sens=False)
         else:
-            TU.check_update("batch grid", what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b],
+            UC.check_update("batch grid", what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b],
                             sens=False)
     bat.close()
 
@@ -351,13 +297,13 @@ def test_a_weight_that_underflows_needs_the_shift():
     that instance only; with shift on the same instance yields a finite u*"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 3
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     g = GR.Grid(1.0 + np.arange(35, dtype=np.float32).reshape(5, 7), (x0[1, 0] - 0.1, x0[1, 1] - 0.1), 0.05, 2.0)
     off, on, _, _, bat = run_off_on(p, B, inputs, [g], np.array([-1, 0, -1], dtype=np.int32), np.array([0.0, 1e6, 0.0]), False)
     assert np.all(on[1]["c"] > 1e6 * p.horizon)
     assert np.all(np.isnan(on[1]["u"])) and on[1]["st"][0] == 0.0 and on[1]["st"][4] == 1   # (sum_w, ..., nonfinite)
-    assert TO.same_bits(off[0], on[0]) and TO.same_bits(off[2], on[2])
+    assert BS.same_bits(off[0], on[0]) and BS.same_bits(off[2], on[2])
     bat.set_min_shift(True)
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
@@ -377,8 +323,8 @@ def test_resident_loop_with_maps_equals_the_host_prologue():
     (calc_ref_path, plant_step) driving ccv_mppi_batch_iterate with the same maps, bit for bit."""
     p = configs.diff_drive_defaults(1000, 15)
     B, ticks = 4, 41
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     maps, map_of, w = resident_maps(p, B, s0)
     host = BatchController(p, B, min_shift=True)
     set_maps(host, maps, map_of, w)
@@ -472,7 +418,7 @@ def test_refusals_change_nothing_and_get_round_trips():
     holds()
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-    want = TO.snapshot(bat, u, st, states=False)
+    want = BS.snapshot(bat, u, st, states=False)
 
     def refused(rows, n, mo, wt):
         mo, wt = np.ascontiguousarray(mo, dtype=np.int32), np.ascontiguousarray(wt, dtype=np.float64)
@@ -508,22 +454,22 @@ def test_refusals_change_nothing_and_get_round_trips():
     holds()
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-    assert all(TO.same_bits(a, b, states=False) for a, b in zip(want, TO.snapshot(bat, u, st, states=False)))
+    assert all(BS.same_bits(a, b, states=False) for a, b in zip(want, BS.snapshot(bat, u, st, states=False)))
     # _set_params and _set_params(NULL) keep the maps
     bat.set_params([p] * B)
     bat.set_params(None)
     holds()
     bat.set_nominal(nom)
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-    assert all(TO.same_bits(a, b, states=False) for a, b in zip(want, TO.snapshot(bat, u, st, states=False)))
+    assert all(BS.same_bits(a, b, states=False) for a, b in zip(want, BS.snapshot(bat, u, st, states=False)))
     bat.close()
 
 
 def test_set_grids_flushes_a_pending_resident_update():
     p = configs.diff_drive_defaults(1000, 15)
     B = 4
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     maps, map_of, w = resident_maps(p, B, s0)
 
     def run(sync):

@@ -13,84 +13,26 @@ the cases below; the device's shares are printed with -s)."""
 import numpy as np
 import pytest
 
+import batch_support as BS
 import ccv_mppi_path_tracker_amd as amd
+import fleet_reference as FR
+import fleet_support as FS
+import fleet_velocity_reference as FV
 import helpers
-import moving_obstacle_reference as MR
-import obstacle_reference as OR
+import obstacle_cases as OC
+import update_checks as UC
 import update_reference as R
-import test_gpu_batch_obstacles as TO
-import test_gpu_batch_params as TP
-import test_gpu_batch_shift as TS
-import test_gpu_update as TU
+from batch_support import MOV, OV, SHIFT, same_bits, snapshot
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
+from fleet_support import CROSSING
+from obstacle_cases import NS, W_OBS, check_moving, moving_discs_for
 
 pytestmark = pytest.mark.gpu
-LD = np.longdouble
-OV = capi.BATCH_KERNEL_OBST | capi.BATCH_KERNEL_VARIED
-MOV = capi.BATCH_KERNEL_MOVING | OV
-SHIFT = capi.BATCH_KERNEL_SHIFT
-NS = TO.NS
-W_OBS = TO.W_OBS
-nstates, snapshot, same_bits = TO.nstates, TO.snapshot, TO.same_bits
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def first_moving_disc(P, x0, dt, v_ref, cands):
-    """cands: (step j, centre at step j, unit normal of the path there).  The first whose disc -- at the centre at step j,
-    moving at v_ref along the normal, radius the median over the samples of the closest approach of the states k >= 1 to the
-    disc where it is at step k -- leaves the pose outside at step 0 and between 30 % and 70 % of the samples inside."""
-    ks = np.arange(P.shape[1])
-    for j, c, nrm in cands:
-        v = v_ref * np.asarray(nrm)
-        o = np.asarray(c) - v * (j * dt)
-        ctr = o[None, :] + v[None, :] * (ks * dt)[:, None]
-        dm = np.min(np.hypot(P[:, 1:, 0] - ctr[1:, 0], P[:, 1:, 1] - ctr[1:, 1]), axis=1)
-        r = float(np.median(dm))
-        if r < 0.95 * np.hypot(x0[0] - o[0], x0[1] - o[1]) and 0.3 <= np.mean(dm < r) <= 0.7:
-            return (o[0], o[1], r), (v[0], v[1])
-    raise AssertionError("no candidate gives a usable moving disc")
-
-
-def moving_discs_for(p, inputs, it=0, ns=NS):
-    """([B] arrays (n_b, 3), [B] arrays (n_b, 2)).  Disc 0: first_moving_disc over the window points nearest the middle of the
-    horizon, crossing to the left for even b and to the right for odd b (the fall-back, where the samples do not follow the
-    window -- full body here: a mid-horizon or end state of sample 0 or 1 in the window point's place).  Discs 1 and 3: 2 cm, on
-    the end states of samples 1 and 3 at the last step, drifting; the rest on a ring no sample reaches, drifting at 0.5 m/s
-    (they exercise the loop, the minimum and the polynomial)."""
-    x0, dt, xr, yr, yaw0, seeds, nom = inputs
-    discs, vels = [], []
-    for b in range(len(dt)):
-        n = ns[b % len(ns)]
-        d, v = np.zeros((n, 3)), np.zeros((n, 2))
-        if n:
-            P = TO.oracle_states(p, x0[b], dt[b], nom[b], seeds[b], it)
-            T = P.shape[1]
-            mid = p.horizon // 2
-            cands = []
-            for j in sorted(range(2, T - 1), key=lambda j: abs(j - mid)):
-                tx, ty = xr[b, j + 1] - xr[b, j - 1], yr[b, j + 1] - yr[b, j - 1]
-                s = (1.0 if b % 2 == 0 else -1.0) / np.hypot(tx, ty)
-                cands.append((j, (xr[b, j], yr[b, j]), (-ty * s, tx * s)))
-            for i, j in ((0, mid), (1, mid), (0, T - 1), (1, T - 1)):   # the fall-back: a state of a sample, at its own step
-                tx, ty = P[i, j] - P[i, j - 1]
-                s = (1.0 if b % 2 == 0 else -1.0) / max(np.hypot(tx, ty), 1e-12)
-                cands.append((j, tuple(P[i, j]), (-ty * s, tx * s)))
-            d[0], v[0] = first_moving_disc(P, x0[b], dt[b], p.v_ref, cands)
-            reach = 1.5 * max(abs(p.u_min[0]), abs(p.u_max[0])) * dt[b] * p.horizon + 2.0
-            for i in range(1, n):
-                if i in (1, 3) and np.hypot(*(P[i, -1] - x0[b, :2])) > 0.1:
-                    v[i] = (0.3, -0.2)
-                    d[i] = (P[i, -1, 0] - v[i, 0] * (T - 1) * dt[b], P[i, -1, 1] - v[i, 1] * (T - 1) * dt[b], 0.02)
-                else:
-                    d[i] = (x0[b, 0] + reach * np.cos(i), x0[b, 1] + reach * np.sin(i), 0.3 + 0.02 * i)
-                    v[i] = (-0.5 * np.sin(i), 0.5 * np.cos(i))
-        discs.append(d)
-        vels.append(v)
-    return discs, vels
 
 
 def run_all(p, B, inputs, discs, vels, weights, shift, it=0):
@@ -122,29 +64,6 @@ def run_all(p, B, inputs, discs, vels, weights, shift, it=0):
     return snaps, codes
 
 
-def check_moving(what, p, x0, dt, discs, vels, w, off, sta, mov):
-    """states bit-equal; cost_moving - cost_off within the checker's bound of the reference penalty of the read-back states; the
-    shares the docstring states"""
-    assert mov["xy"].tobytes() == off["xy"].tobytes() == sta["xy"].tobytes(), what
-    T = nstates(p)
-    P, ks = mov["xy"][:, :T], np.arange(T)
-    tot, bnd = MR.sample_penalty(P, x0[:2], ks, dt, discs, vels, w)
-    diff = mov["c"].astype(LD) - off["c"].astype(LD)
-    allowed = bnd + MR.bound_difference(mov["c"], off["c"], p.horizon)
-    miss = np.abs(diff - tot).astype(np.float64)
-    ratio = float(np.max(miss / np.maximum(allowed, 1e-300)))
-    frac = float(np.mean(tot > 0))
-    print("err/bound [moving] %s: %.3g  (share with a penalty %.2f, largest penalty %.3g)" % (what, ratio, frac, float(tot.max())))
-    assert np.all(miss <= allowed), (what, ratio)
-    if len(discs) and w > 0:
-        assert 0.10 <= frac <= 0.90, (what, frac)
-        stot, _ = OR.sample_penalty(P, x0[:2], discs, w)
-        hit = tot > 0
-        apart = float(np.mean(np.abs(tot - stot).astype(np.float64)[hit] > 10.0 * allowed[hit]))
-        print("    moving and static reference penalty more than 10 bounds apart: %.2f of the penalised samples" % apart)
-        assert apart >= 0.10, (what, apart)
-
-
 def check_case(p, B, inputs, discs, vels, weights, shift, family, what0):
     snaps, codes = run_all(p, B, inputs, discs, vels, weights, shift)
     off, sta, mov, zero, unmoved, back = snaps
@@ -166,14 +85,14 @@ def check_case(p, B, inputs, discs, vels, weights, shift, family, what0):
 
 # 1. - 3. the term touches only the cost; zero velocities; restoration ------------------------------------------------------
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
-@pytest.mark.parametrize("model,K,H,B,over,fam", TO.CASES)
+@pytest.mark.parametrize("model,K,H,B,over,fam", OC.CASES)
 def test_moving_term_touches_only_the_cost(model, K, H, B, over, fam, shift):
-    p = TP.MODEL_DEFAULTS[model](K, H)
+    p = BS.MODEL_DEFAULTS[model](K, H)
     if over:
         p = p.with_(**over)
     if fam == "solo":
-        assert TP.families(model, K, B)[1] == "solo"
-    inputs = TP.instance_inputs(p, B)
+        assert BS.families(model, K, B)[1] == "solo"
+    inputs = BS.instance_inputs(p, B)
     ns = NS if B >= len(NS) else (3, 32)
     discs, vels = moving_discs_for(p, inputs, ns=ns)
     weights = np.full(B, W_OBS)
@@ -188,7 +107,7 @@ def test_plain_family_through_one_heading(shift):
     """one instance's heading outside the fast sin / cos range sends the batch through the plain kernel's MOVING form"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     inputs[0][1, 2] += 2.0e5 * np.pi
     discs, vels = moving_discs_for(p, inputs)
     check_case(p, B, inputs, discs, vels, np.full(B, W_OBS), shift, capi.BATCH_KERNEL_PLAIN, "plain")
@@ -197,7 +116,7 @@ def test_plain_family_through_one_heading(shift):
 def test_one_instances_velocities_change_no_bit_of_another():
     p = configs.diff_drive_defaults(1000, 15)
     B, j = 5, 2
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs, vels = moving_discs_for(p, inputs)
     other = [v.copy() for v in vels]
@@ -222,10 +141,10 @@ def test_four_wave_and_one_wave_agree(shift):
     K, H = 1000, 15
     p = configs.diff_drive_defaults(K, H)
     B4 = 5
-    reps = -(-(5 * TP._cus() + 1) // (16 * B4))
+    reps = -(-(5 * BS.cus() + 1) // (16 * B4))
     B1 = B4 * reps
-    assert TP.families(p.model, K, B4)[1] == "r4" and TP.families(p.model, K, B1)[1] == "solo"
-    inp = TP.instance_inputs(p, B4)
+    assert BS.families(p.model, K, B4)[1] == "r4" and BS.families(p.model, K, B1)[1] == "solo"
+    inp = BS.instance_inputs(p, B4)
     discs, vels = moving_discs_for(p, inp)
     res = []
     for B, r in ((B4, 1), (B1, reps)):
@@ -240,8 +159,8 @@ def test_four_wave_and_one_wave_agree(shift):
     assert k4 == capi.BATCH_KERNEL_FOUR_WAVE | MOV | (SHIFT if shift else 0)
     assert k1 == capi.BATCH_KERNEL_ONE_WAVE | MOV | (SHIFT if shift else 0)
     for b in range(B4):
-        assert helpers.rel_err(u4[b], u1[b]) < TP.TOL_U
-        assert np.max(np.abs(c4[b] - c1[b]) / c1[b]) < TP.TOL_COST
+        assert helpers.rel_err(u4[b], u1[b]) < BS.TOL_U
+        assert np.max(np.abs(c4[b] - c1[b]) / c1[b]) < BS.TOL_COST
 
 
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
@@ -250,7 +169,7 @@ def test_update_from_the_moving_costs(shift):
     with shift on, as test_gpu_batch_obstacles)"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs, vels = moving_discs_for(p, inputs)
     probe = BatchController(p, B)
@@ -265,12 +184,12 @@ def test_update_from_the_moving_costs(shift):
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
     assert bat.last_kernel() == capi.BATCH_KERNEL_FOUR_WAVE | MOV | (SHIFT if shift else 0)
     for b in range(B):
-        ctl = TU.host_controls(plist[b], nom[b], seeds[b], 0)
+        ctl = UC.host_controls(plist[b], nom[b], seeds[b], 0)
         what = "moving b=%d n=%d" % (b, len(discs[b]))
         if shift:
-            TS.check_shift(what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b], sens=False)
+            UC.check_shift(what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b], sens=False)
         else:
-            TU.check_update("batch moving", what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b],
+            UC.check_update("batch moving", what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b],
                             sens=False)
     bat.close()
 
@@ -281,8 +200,8 @@ def test_resident_loop_with_moving_discs_equals_the_host_prologue():
     batch equal the host prologue driving ccv_mppi_batch_iterate with the same discs and velocities, bit for bit."""
     p = configs.diff_drive_defaults(1000, 15)
     B, ticks = 4, 41
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     discs, vels = [], []
     for b in range(B):
         i = (37 * b + 5) % (len(paths[b][0]) // 2) + 12 + 2 * b
@@ -325,7 +244,7 @@ def test_resident_loop_with_moving_discs_equals_the_host_prologue():
 def test_refusals_change_nothing_and_get_round_trips():
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs, vels = moving_discs_for(p, inputs)
     bat = BatchController(p, B)
@@ -385,8 +304,8 @@ def test_refusals_change_nothing_and_get_round_trips():
 def test_set_obstacle_velocities_flushes_a_pending_resident_update():
     p = configs.diff_drive_defaults(1000, 15)
     B = 4
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     discs = [np.array([[paths[b][0][60], paths[b][1][60] - 0.4, 0.4]]) for b in range(B)]
     vels = [np.array([[0.0, 0.5]]) for b in range(B)]
 
@@ -416,7 +335,7 @@ def test_velocities_return_all_device_memory():
     import torch
     p = configs.diff_drive_defaults(1000, 15)
     B = 16
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     discs = [np.array([[1.0, 2.0, 0.5]] * (b % 4)).reshape(-1, 3) for b in range(B)]
     vels = [np.array([[0.3, -0.2]] * (b % 4)).reshape(-1, 2) for b in range(B)]
 
@@ -449,17 +368,12 @@ def test_velocities_return_all_device_memory():
 
 
 # 6. fleet prediction against a twin handle ---------------------------------------------------------------------------------
-import fleet_reference as FR  # noqa: E402
-import fleet_velocity_reference as FV  # noqa: E402
-import test_gpu_batch_fleet as TF  # noqa: E402
-
-
 def pred_twin_run(p, B, shift, static, static_v, radius, rng, maxn, weight, paths, s0, seeds, ticks, dts, advances):
     """the fleet term off: before every tick the lists from the poses read (fleet_reference), the velocities from the poses
     before and after the previous tick (fleet_velocity_reference), through set_obstacles and set_obstacle_velocities -> per
     tick (bits, n_total, disc table, velocity table)"""
     n_static = np.array([len(d) for d in static], dtype=np.int32)
-    twin = TF.make(p, B, shift, None, weight, paths, s0, seeds)
+    twin = FS.make(p, B, shift, None, weight, paths, s0, seeds)
     out, v = [], np.zeros((B, 2))
     for it in range(ticks):
         q = twin.resident_read()[0][:, :2]
@@ -467,7 +381,7 @@ def pred_twin_run(p, B, shift, static, static_v, radius, rng, maxn, weight, path
         vrows = FV.velocity_rows(static_v, taken, v)
         twin.set_obstacles(FR.full_lists(static, rows), weight, velocities=vrows)
         twin.resident_step_enqueue(dts[it], it, advance=advances[it])
-        out.append((TF.bits(twin), n_total, FR.table(static, rows), FV.table(vrows)))
+        out.append((FS.bits(twin), n_total, FR.table(static, rows), FV.table(vrows)))
         v = FV.velocity(q, twin.resident_read()[0][:, :2], dts[it], advances[it])
     k = twin.last_kernel()
     twin.close()
@@ -483,10 +397,10 @@ def test_fleet_prediction_equals_a_twin_fed_with_velocities(model, H, shift):
     costs, poses, indices, windows, the _read_fleet rows and the _read_fleet_velocities rows equal the twin's on every tick, read
     after every tick and, in a second run, at ticks 0, 14 and 29 only.  Tick 7 does not advance and, for diff drive, tick 11 has
     dt = 0: the velocities the ticks after them are charged with are zero (asserted on the tables)."""
-    p = TF.params(model, 128, H)
+    p = FS.params(model, 128, H)
     B, ticks, maxn, rng, weight = 5, 30, 2, 1.5, 50.0
-    s0, seeds, paths = TF.fleet_start(p, B)
-    static = [np.zeros((0, 3)), TF.far_discs(3), np.zeros((0, 3)), TF.far_discs(31, 1), np.zeros((0, 3))]
+    s0, seeds, paths = FS.fleet_start(p, B)
+    static = [np.zeros((0, 3)), FS.far_discs(3), np.zeros((0, 3)), FS.far_discs(31, 1), np.zeros((0, 3))]
     static_v = [np.tile([0.3, -0.2], (len(d), 1)) for d in static]   # (static velocities beside the predicted ones)
     radius = np.array([0.15, 0.2, 0.1, 0.25, 0.3])
     dts = [p.dt] * ticks
@@ -500,7 +414,7 @@ def test_fleet_prediction_equals_a_twin_fed_with_velocities(model, H, shift):
     assert (want[5][3] != sv).any() and (want[20][3] != sv).any()  # ... and moving robots otherwise
     assert max(int((n - [0, 3, 0, 31, 0]).max()) for _, n, _, _ in want) == 2
     for every_tick in (True, False):
-        bat = TF.make(p, B, shift, static, weight, paths, s0, seeds, fleet=(radius, rng, maxn, weight))
+        bat = FS.make(p, B, shift, static, weight, paths, s0, seeds, fleet=(radius, rng, maxn, weight))
         bat.set_obstacle_velocities(static_v)
         assert not bat.resident_get_fleet_prediction()
         bat.resident_set_fleet_prediction(True)
@@ -508,7 +422,7 @@ def test_fleet_prediction_equals_a_twin_fed_with_velocities(model, H, shift):
         for it in range(ticks):
             bat.resident_step_enqueue(dts[it], it, advance=advances[it])
             if every_tick or it in (0, 14, ticks - 1):
-                got = TF.bits(bat)
+                got = FS.bits(bat)
                 ns, nt, xyr = bat.resident_read_fleet()
                 vxy = bat.resident_read_fleet_velocities()
                 wb, wn, wt, wv = want[it]
@@ -525,18 +439,18 @@ def test_fleet_velocities_of_300_robots_equal_the_rule():
     """test_gpu_batch_fleet's grid of 300 robots (K = 64, H = 10, exact ties, n_static from {0, 30, 32}) with prediction: the
     velocity rows of every tick equal the rule on the poses read before and after the previous tick, beside the reference's
     selection"""
-    p = TF.params("diff_drive", 64, 10)
+    p = FS.params("diff_drive", 64, 10)
     B, ticks, maxn, rng = 300, 8, 4, 0.6
-    px, py = TP.path_of(0)
+    px, py = BS.path_of(0)
     s0 = np.zeros((B, p.nstate))
     s0[:, 0] = 1.0 + 0.25 * (np.arange(B) % 20)
     s0[:, 1] = 0.25 * (np.arange(B) // 20) - 1.75
-    seeds = (np.arange(B, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+    seeds = np.array([BS.instance_seed(b) for b in range(B)], dtype=np.uint64)
     n_static = np.array([0, 30, 0, 32, 0, 0, 30] * 43, dtype=np.int32)[:B]
-    static = [TF.far_discs(int(n), b) for b, n in enumerate(n_static)]
+    static = [FS.far_discs(int(n), b) for b, n in enumerate(n_static)]
     static_v = [np.zeros((int(n), 2)) for n in n_static]
     radius = 0.1 + 0.001 * np.arange(B)
-    bat = TF.make(p, B, True, static, 20.0, (px, py), s0, seeds, fleet=(radius, rng, maxn, 20.0))
+    bat = FS.make(p, B, True, static, 20.0, (px, py), s0, seeds, fleet=(radius, rng, maxn, 20.0))
     bat.resident_set_fleet_prediction(True)
     q, v = s0[:, :2].copy(), np.zeros((B, 2))
     for it in range(ticks):
@@ -556,9 +470,9 @@ def test_fleet_velocities_of_300_robots_equal_the_rule():
 
 
 def test_prediction_off_after_on_restores_every_bit_and_refusals():
-    p = TF.params()
+    p = FS.params()
     B, ticks = 5, 8
-    s0, seeds, paths = TF.fleet_start(p, B)
+    s0, seeds, paths = FS.fleet_start(p, B)
     fleet = (0.2, 1.5, 2, 50.0)
 
     def run(bat):
@@ -567,10 +481,10 @@ def test_prediction_off_after_on_restores_every_bit_and_refusals():
         out = []
         for it in range(ticks):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
-            out.append(TF.bits(bat))
+            out.append(FS.bits(bat))
         return out, bat.last_kernel()
 
-    bat = TF.make(p, B, True, None, 50.0, paths, s0, seeds)
+    bat = FS.make(p, B, True, None, 50.0, paths, s0, seeds)
     # the fleet term off: the setter and the read are refused, nothing changes
     assert bat.lib.ccv_mppi_batch_set_fleet_prediction(bat._h, 1) == capi.ERR_STATE
     assert bat.lib.ccv_mppi_batch_read_fleet_velocities(bat._h, capi.dptr(np.zeros((B, 32, 2)))) == capi.ERR_STATE
@@ -600,12 +514,12 @@ def test_prediction_off_with_static_velocities_leaves_no_neighbour_velocity():
     term off and on: every run without prediction equals, bit for bit and in the _read_fleet_velocities rows of every tick, a
     handle that never had prediction -- the MOVING kernels go on running there (the static velocities), and the rows of the
     neighbours' discs have to be zero again, not what the last tick with prediction left."""
-    p = TF.params()
+    p = FS.params()
     B, ticks = 5, 8
-    s0, seeds, paths = TF.fleet_start(p, B)
+    s0, seeds, paths = FS.fleet_start(p, B)
     fleet = (0.2, 1.5, 2, 50.0)
     px, py = paths[0]
-    static = [np.zeros((0, 3)), TF.far_discs(3), np.array([[px[30], py[30] - 0.5, 0.3]]), TF.far_discs(5, 1), np.zeros((0, 3))]
+    static = [np.zeros((0, 3)), FS.far_discs(3), np.array([[px[30], py[30] - 0.5, 0.3]]), FS.far_discs(5, 1), np.zeros((0, 3))]
     static_v = [np.zeros((0, 2)), np.tile([0.3, -0.2], (3, 1)), np.array([[0.0, 0.7]]), np.tile([-0.4, 0.6], (5, 1)), np.zeros((0, 2))]
     sv = FV.table(static_v)
     assert sv.shape == (B, 32, 2) and sv.any()
@@ -616,11 +530,11 @@ def test_prediction_off_with_static_velocities_leaves_no_neighbour_velocity():
         out = []
         for it in range(ticks):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
-            out.append((TF.bits(bat), bat.resident_read_fleet()[1].tolist(), bat.resident_read_fleet_velocities().tobytes()))
+            out.append((FS.bits(bat), bat.resident_read_fleet()[1].tolist(), bat.resident_read_fleet_velocities().tobytes()))
         return out, bat.last_kernel()
 
     def make():
-        bat = TF.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=fleet)
+        bat = FS.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=fleet)
         bat.set_obstacle_velocities(static_v)
         return bat
 
@@ -651,27 +565,16 @@ def test_prediction_off_with_static_velocities_leaves_no_neighbour_velocity():
 
 
 # 7. behaviour: a crossing ----------------------------------------------------------------------------------------------------
-import os  # noqa: E402
-import sys  # noqa: E402
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-import fleet_crossing_cpu as FC  # noqa: E402
-
-# chosen on the CPU restatement of the closed loop (tools/fleet_crossing_cpu.py; tests/test_fleet_crossing_cpu.py)
-CROSSING = dict(paths=FC.PATHS, s0=FC.S0, seeds=np.array([11, 12], dtype=np.uint64), ticks=60, radius=0.1, range=3.0, weight=100.0,
-                margin=0.08)
-
-
 def test_two_robots_crossing_pass_at_a_larger_distance_with_prediction():
     """Two robots on perpendicular straight paths, each 1.5 m from the crossing and timed to reach it together, K = 128, shifted
     weights, radii 0.1 m + 0.1 m, range 3 m, weight 100, 60 ticks: the closest approach (same tick) with predicted discs is
     larger than with snapshot discs by the CPU test's margin.  (The figures are printed with -s)"""
-    p = TF.params()
+    p = FS.params()
     c = CROSSING
     B, ticks = 2, c["ticks"]
     closest = {}
     for mode in ("off", "snapshot", "predicted"):
-        bat = TF.make(p, B, True, None, 0.0, c["paths"], c["s0"], c["seeds"],
+        bat = FS.make(p, B, True, None, 0.0, c["paths"], c["s0"], c["seeds"],
                       fleet=(c["radius"], c["range"], 1, c["weight"]) if mode != "off" else None)
         if mode == "predicted":
             bat.resident_set_fleet_prediction(True)

@@ -12,85 +12,21 @@ instance with discs between 10 % and 90 % of the samples carry a non-zero refere
 import numpy as np
 import pytest
 
+import batch_support as BS
 import ccv_mppi_path_tracker_amd as amd
 import helpers
-import obstacle_reference as OR
+import update_checks as UC
 import update_reference as R
-import test_gpu_batch_params as TP
-import test_gpu_batch_shift as TS
-import test_gpu_update as TU
+from batch_support import OV, SHIFT, same_bits, snapshot
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
+from obstacle_cases import CASES, NS, W_OBS, check_penalty, discs_for
 
 pytestmark = pytest.mark.gpu
-LD = np.longdouble
-OV = capi.BATCH_KERNEL_OBST | capi.BATCH_KERNEL_VARIED
-SHIFT = capi.BATCH_KERNEL_SHIFT
-NS = (0, 1, 3, 4, 32)   # discs per instance, dealt round
-W_OBS = 5.0
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def nstates(p):
-    return p.horizon - 2 if p.model == "full_body" else p.horizon
-
-
-def oracle_states(p, x0, dt, nom, seed, it):
-    o = helpers.oracle_for(p)
-    o.set_nominal(nom)
-    o.sampling(int(seed), rng="philox", iteration=it)
-    o.predict_States(x0, dt)
-    return np.stack([o.states("x"), o.states("y")], axis=-1)[:, :nstates(p)]
-
-
-def first_disc(P, x0, cands):
-    """the first candidate centre whose tuned radius -- the median over the samples of the closest approach of the states
-    t >= 1 -- leaves the start outside and between 30 % and 70 % of the samples inside"""
-    for c in cands:
-        dm = np.min(np.hypot(P[:, 1:, 0] - c[0], P[:, 1:, 1] - c[1]), axis=1)
-        r = float(np.median(dm))
-        if r < 0.95 * np.hypot(x0[0] - c[0], x0[1] - c[1]) and 0.3 <= np.mean(dm < r) <= 0.7:
-            return (c[0], c[1], r)
-    raise AssertionError("no candidate centre gives a usable disc")
-
-
-def discs_for(p, inputs, it=0, ns=NS):
-    """[B] arrays (n_b, 3).  Disc 0 on a window point near the middle of the horizon (the nearest one that first_disc accepts;
-    the end state of a sample as the fall-back), radius tuned on the oracle's rollouts.  The others: discs 1 and 3 of 2 cm on
-    the end states of samples 1 and 3 (a few samples touch them), the rest on a ring around the start that no sample reaches
-    (they exercise the loop, the minimum and the padding)."""
-    x0, dt, xr, yr, yaw0, seeds, nom = inputs
-    out = []
-    for b in range(len(dt)):
-        n = ns[b % len(ns)]
-        d = np.zeros((n, 3))
-        if n:
-            P = oracle_states(p, x0[b], dt[b], nom[b], seeds[b], it)
-            mid = p.horizon // 2
-            order = sorted(range(1, p.horizon), key=lambda j: abs(j - mid))
-            d[0] = first_disc(P, x0[b], [(xr[b, j], yr[b, j]) for j in order] + [P[0, -1], P[1, -1]])
-            reach = 1.5 * max(abs(p.u_min[0]), abs(p.u_max[0])) * dt[b] * p.horizon + 2.0
-            for i in range(1, n):
-                if i in (1, 3) and np.hypot(*(P[i, -1] - x0[b, :2])) > 0.1:
-                    d[i] = (P[i, -1, 0], P[i, -1, 1], 0.02)
-                else:
-                    d[i] = (x0[b, 0] + reach * np.cos(i), x0[b, 1] + reach * np.sin(i), 0.3 + 0.02 * i)
-        out.append(d)
-    return out
-
-
-def snapshot(bat, u, st, states=True):
-    B = bat.B
-    return [dict(u=u[b].copy(), st=TP.stats_tuple(st[b]), c=bat.read_costs(b), w=bat.read_weights(b),
-                 xy=bat.read_candidates(b) if states else None) for b in range(B)]
-
-
-def same_bits(a, b, states=True):
-    keys = ("u", "c", "w") + (("xy",) if states else ())
-    return a["st"] == b["st"] and all(a[k].tobytes() == b[k].tobytes() for k in keys)
 
 
 def run_off_on(p, B, inputs, discs, weights, shift, it=0):
@@ -106,41 +42,16 @@ def run_off_on(p, B, inputs, discs, weights, shift, it=0):
     return off, snapshot(bat, u, st), k_off, bat.last_kernel(), bat
 
 
-def check_penalty(what, p, x0, discs, w, off, on, share=True):
-    """states bit-equal; cost_on - cost_off within the checker's bound of the reference penalty of the read-back states"""
-    assert on["xy"].tobytes() == off["xy"].tobytes(), what
-    P = on["xy"][:, :nstates(p)]
-    tot, bnd = OR.sample_penalty(P, x0[:2], discs, w)
-    diff = on["c"].astype(LD) - off["c"].astype(LD)
-    allowed = bnd + OR.bound_difference(on["c"], off["c"], p.horizon)
-    ratio = float(np.max(np.abs(diff - tot).astype(np.float64) / np.maximum(allowed, 1e-300)))
-    frac = float(np.mean(tot > 0))
-    print("err/bound [obstacles] %s: %.3g  (share with a penalty %.2f, largest penalty %.3g)" % (what, ratio, frac, float(tot.max())))
-    assert np.all(np.abs(diff - tot).astype(np.float64) <= allowed), (what, ratio)
-    if share and len(discs) and w > 0:
-        assert 0.10 <= frac <= 0.90, (what, frac)
-    return tot
-
-
 # 1. the term touches only the cost; nothing leaks; families --------------------------------------------------------------
-# (model, K, H, B, overrides, kernel, family): K = 1 000: 16 workgroups, 40 live lanes in the last; H = 15: the TAIL forms, six
-# steps in the last block; H = 10: one step in the last block, the step-by-step tail; the one-wave family through the workgroup
-# count; the wide form through dt; the plain family: below, through a heading
-CASES = [("diff_drive", 1000, 15, 5, {}, "r4"), ("diff_drive", 1000, 10, 5, {}, "r4"), ("diff_drive", 1000, 15, 5, {"dt": 0.4}, "r4w"),
-         ("steering_diff_drive", 1000, 15, 5, {}, "r4"), ("steering_diff_drive", 1000, 10, 5, {}, "r4"),
-         ("full_body", 128, 15, 5, {}, "r4"), ("full_body", 128, 10, 5, {}, "r4"),
-         ("diff_drive", 82048, 15, 2, {}, "solo")]
-
-
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
 @pytest.mark.parametrize("model,K,H,B,over,fam", CASES)
 def test_term_touches_only_the_cost(model, K, H, B, over, fam, shift):
-    p = TP.MODEL_DEFAULTS[model](K, H)
+    p = BS.MODEL_DEFAULTS[model](K, H)
     if over:
         p = p.with_(**over)
     if fam == "solo":
-        assert TP.families(model, K, B)[1] == "solo"
-    inputs = TP.instance_inputs(p, B)
+        assert BS.families(model, K, B)[1] == "solo"
+    inputs = BS.instance_inputs(p, B)
     ns = NS if B >= len(NS) else (3, 32)
     discs = discs_for(p, inputs, ns=ns)
     weights = np.full(B, W_OBS)
@@ -174,7 +85,7 @@ def test_plain_family_through_one_heading(shift):
     """one instance's heading outside the fast sin / cos range sends the batch through the plain kernel's OBST form"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     inputs[0][1, 2] += 2.0e5 * np.pi
     discs = discs_for(p, inputs)
     weights = np.full(B, W_OBS)
@@ -194,10 +105,10 @@ def test_four_wave_and_one_wave_agree(shift, monkeypatch):
     K, H = 1000, 15
     p = configs.diff_drive_defaults(K, H)
     B4 = 5
-    reps = -(-(5 * TP._cus() + 1) // (16 * B4))
+    reps = -(-(5 * BS.cus() + 1) // (16 * B4))
     B1 = B4 * reps
-    assert TP.families(p.model, K, B4)[1] == "r4" and TP.families(p.model, K, B1)[1] == "solo"
-    inp = TP.instance_inputs(p, B4)
+    assert BS.families(p.model, K, B4)[1] == "r4" and BS.families(p.model, K, B1)[1] == "solo"
+    inp = BS.instance_inputs(p, B4)
     discs = discs_for(p, inp)
     res = []
     for B, r in ((B4, 1), (B1, reps)):
@@ -212,14 +123,14 @@ def test_four_wave_and_one_wave_agree(shift, monkeypatch):
     assert k4 == capi.BATCH_KERNEL_FOUR_WAVE | OV | (SHIFT if shift else 0)
     assert k1 == capi.BATCH_KERNEL_ONE_WAVE | OV | (SHIFT if shift else 0)
     for b in range(B4):
-        assert helpers.rel_err(u4[b], u1[b]) < TP.TOL_U
-        assert np.max(np.abs(c4[b] - c1[b]) / c1[b]) < TP.TOL_COST
+        assert helpers.rel_err(u4[b], u1[b]) < BS.TOL_U
+        assert np.max(np.abs(c4[b] - c1[b]) / c1[b]) < BS.TOL_COST
 
 
 def test_one_instances_discs_change_no_bit_of_another():
     p = configs.diff_drive_defaults(1000, 15)
     B, j = 5, 2
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs = discs_for(p, inputs)
     other = [d.copy() for d in discs]
@@ -242,10 +153,10 @@ def test_one_instances_discs_change_no_bit_of_another():
 @pytest.mark.parametrize("shift", [False, True], ids=["plain_w", "shift"])
 def test_update_from_the_term_on_costs(shift):
     """u*, sum_w and n_zero_weight from the term-on costs inside update_reference's bounds: E_MAX with shift off (check_update
-    measures E and caps it), E_SHIFT = 9 with shift on (test_gpu_batch_shift.check_shift)"""
+    measures E and caps it), E_SHIFT = 9 with shift on (update_checks.check_shift)"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs = discs_for(p, inputs)
     probe = BatchController(p, B)
@@ -260,12 +171,12 @@ def test_update_from_the_term_on_costs(shift):
     u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
     assert bat.last_kernel() == capi.BATCH_KERNEL_FOUR_WAVE | OV | (SHIFT if shift else 0)
     for b in range(B):
-        ctl = TU.host_controls(plist[b], nom[b], seeds[b], 0)
+        ctl = UC.host_controls(plist[b], nom[b], seeds[b], 0)
         what = "obstacles b=%d n=%d" % (b, len(discs[b]))
         if shift:
-            TS.check_shift(what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b], sens=False)
+            UC.check_shift(what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b], sens=False)
         else:
-            TU.check_update("batch obstacles", what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b],
+            UC.check_update("batch obstacles", what, bat.read_costs(b), ctl, plist[b].lam, u[b], st[b].sum_w, bat.read_weights(b), st[b],
                             sens=False)
     bat.close()
 
@@ -275,7 +186,7 @@ def test_hard_penalty_needs_the_shift():
     underflows: sum_w = 0, u* = NaN, flagged, its neighbours untouched; with shift on the same instance yields a finite u*"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 3
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs = [np.zeros((0, 3)), np.array([[x0[1, 0], x0[1, 1], 50.0]]), np.zeros((0, 3))]
     off, on, _, _, bat = run_off_on(p, B, inputs, discs, [0.0, 1e6, 0.0], False)
@@ -295,8 +206,8 @@ def test_resident_loop_with_discs_equals_the_host_prologue():
     prologue (calc_ref_path, plant_step) driving ccv_mppi_batch_iterate with the same discs, bit for bit."""
     p = configs.diff_drive_defaults(1000, 15)
     B, ticks = 4, 41
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     discs = []
     for b in range(B):
         i = (37 * b + 5) % (len(paths[b][0]) // 2) + 12 + 2 * b   # a path point ahead, inside the rollouts' reach from tick 0 on
@@ -339,8 +250,8 @@ def test_resident_robot_keeps_away_from_a_disc_on_its_path():
     the term on than with it off (two runs compared; the size of the gap is the tool's to record)"""
     p = configs.diff_drive_defaults(1000, 15)
     B, ticks = 2, 60
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     discs = []
     for b in range(B):
         i = (37 * b + 5) % (len(paths[b][0]) // 2) + 15   # (the robots cover 2.4 m and 4.4 m of path in 60 ticks)
@@ -366,7 +277,7 @@ def test_resident_robot_keeps_away_from_a_disc_on_its_path():
 def test_refusals_change_nothing_and_get_round_trips():
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     discs = discs_for(p, inputs)
     weights = np.array([1.0, 2.0, 3.0, 4.0, 5.0])
@@ -417,8 +328,8 @@ def test_refusals_change_nothing_and_get_round_trips():
 def test_set_obstacles_flushes_a_pending_resident_update():
     p = configs.diff_drive_defaults(1000, 15)
     B = 4
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     discs = [np.array([[paths[b][0][60], paths[b][1][60], 0.4]]) for b in range(B)]
 
     def run(sync):
@@ -448,7 +359,7 @@ def test_obstacles_return_all_device_memory():
     import torch
     p = configs.diff_drive_defaults(1000, 15)
     B = 16
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     discs = [np.array([[1.0, 2.0, 0.5]] * (b % 4)).reshape(-1, 3) for b in range(B)]
 
     def cycle():

@@ -10,41 +10,17 @@ import numpy as np
 import pytest
 
 import ccv_mppi_path_tracker_amd as amd
+from batch_support import MODEL_DEFAULTS, families, instance_seed, path_of
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIController, MPPIError
+from resident_loops import host_batch_loop, resident_batch
 
 pytestmark = pytest.mark.gpu
-
-MODEL_DEFAULTS = {"diff_drive": configs.diff_drive_defaults, "steering_diff_drive": configs.steering_defaults,
-                  "full_body": configs.full_body_defaults}
-PATHS = {}
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def _cus():
-    import torch
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def families(model, K, B):
-    """(single handle's kernel family, batch's) by the selection rule of ccv_mppi_create / ccv_mppi_batch_create (the rule
-    test_gpu_batch.py states)"""
-    cus, nblk = _cus(), -(-K // 64)
-    if model == "full_body":
-        single = "r4" if nblk <= cus else ("pc" if nblk <= 4 * cus else "solo")
-        return single, ("r4" if B * nblk <= cus else "solo")
-    return ("r4" if nblk <= 5 * cus else "solo"), ("r4" if B * nblk <= 5 * cus else "solo")
-
-
-def path_of(b):
-    kind = "sinusoid" if b % 2 == 0 else "dkan"
-    if kind not in PATHS:
-        PATHS[kind] = amd.make_path(kind)
-    return PATHS[kind]
 
 
 def start_poses(p, B, salt=0):
@@ -59,35 +35,8 @@ def start_poses(p, B, salt=0):
         s[b, 2] = np.arctan2(py[i + 1] - py[i], px[i + 1] - px[i]) + 0.1 * ((b % 3) - 1)
         if p.nstate == 5:
             s[b, 3], s[b, 4] = 0.02 * ((b % 3) - 1), -0.01 * (b % 2)
-        seeds[b] = (0x9E3779B97F4A7C15 * (b + 1) + salt) & 0xFFFFFFFFFFFFFFFF
+        seeds[b] = instance_seed(b, salt)
     return s, seeds
-
-
-def host_batch_loop(p, B, K, s0, seeds, ticks, paths=None):
-    """The same closed loop with the prologue on the host: per instance plant + window, then BatchController.iterate."""
-    paths = paths or [path_of(b) for b in range(B)]
-    bat = BatchController(p, B, num_samples=K)
-    s = s0.copy()
-    out, u = [], None
-    for it in range(ticks):
-        if it > 0:
-            s = np.array([amd.plant_step(p.model, s[b], u[b][0], p.dt) for b in range(B)])
-        idx, xr, yr, yaw0 = np.zeros(B, dtype=np.int64), np.zeros((B, p.horizon)), np.zeros((B, p.horizon)), np.zeros(B)
-        for b in range(B):
-            idx[b], xr[b], yr[b], yaw = amd.calc_ref_path(paths[b][0], paths[b][1], s[b, 0], s[b, 1], p.v_ref, p.dt,
-                                                          p.resolution, p.horizon)
-            yaw0[b] = yaw[0]
-        u = bat.iterate(s, p.dt, xr, yr, yaw0, seeds, it, want_stats=False)
-        out.append((s.copy(), idx, xr, yr, yaw0, u.copy()))
-    bat.close()
-    return out
-
-
-def resident_batch(p, B, K, s0, seeds, paths=None):
-    bat = BatchController(p, B, num_samples=K)
-    bat.resident_set_paths(paths or [path_of(b) for b in range(B)])
-    bat.resident_set_poses(s0, seeds)
-    return bat
 
 
 def assert_ulp(a, b, n=4):

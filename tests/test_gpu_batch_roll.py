@@ -12,19 +12,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import batch_support as BS
 import costmap_reference as CR
+import costmap_support as CS
+import fleet_support as FS
 import grid_reference as GR
+import obstacle_cases as OC
 import roll_reference as RR
-import test_gpu_batch_costmap as TC
-import test_gpu_batch_fleet as TF
-import test_gpu_batch_obstacles as TO
-import test_gpu_batch_params as TP
+from batch_support import GRID, SHIFT
 from ccv_mppi_path_tracker_amd import BatchController, batch, capi, configs
+from costmap_support import derived, occ_map, same
 
 pytestmark = pytest.mark.gpu
-SHIFT, GRID = TC.SHIFT, TC.GRID
 u8p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
-same, derived, occ_map = TC.same, TC.derived, TC.occ_map
 ORIGIN0, RES = (-1.7, 0.3), 0.05
 FREE = CR.FREE_VALUE
 
@@ -172,7 +172,7 @@ def test_rolls_and_patches_back_to_back(small_handle, n_rolls):
 
 
 # 4. the same bits as a twin -----------------------------------------------------------------------------------------------------
-INFLATION = TC.INFLATION
+INFLATION = CS.INFLATION
 
 
 def rolled_twin_maps(geos, moves, seed=0):
@@ -181,8 +181,8 @@ def rolled_twin_maps(geos, moves, seed=0):
     occ, exposed, flt = [], [], []
     for m, (g, (dx, dy)) in enumerate(zip(geos, moves)):
         origin0 = (g.ox - dx * g.resolution, g.oy - dy * g.resolution)   # (so that the rolled window lies about where g does)
-        cells = TC.layer_like(g, seed + m)
-        strips = RR.strips_of(TC.layer_like(g, seed + 10 + m), dx, dy)
+        cells = CS.layer_like(g, seed + m)
+        strips = RR.strips_of(CS.layer_like(g, seed + 10 + m), dx, dy)
         new = RR.roll_layer(cells, dx, dy, strips=strips)
         occ.append((cells, origin0, g.resolution, float(g.outside), 128))
         exposed.append(strips)
@@ -198,22 +198,22 @@ MOVES = [(3, -2), (-5, 1)]
 def test_a_rolled_handle_gives_the_bits_of_a_twin(shift, discs):
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
     occ, exposed, flt = rolled_twin_maps(geos, MOVES)
-    d = TO.discs_for(p, inputs, ns=(32, 0, 3, 3, 32)) if discs != "none" else None
+    d = OC.discs_for(p, inputs, ns=(32, 0, 3, 3, 32)) if discs != "none" else None
     vels = [np.stack([0.3 * np.cos(np.arange(len(a)) + b), 0.2 * np.sin(np.arange(len(a)) - b)], axis=1).reshape(-1, 2)
             for b, a in enumerate(d)] if discs == "moving" else None
-    s0, rseeds = TP.start_poses(p, B)
+    s0, rseeds = BS.start_poses(p, B)
     rgeos = [GR.map_ahead(s0[b, :3], p.v_ref, p.dt, p.horizon, salt=b - 1, ahead=2.0) for b in (1, 2)]
     rocc, rexposed, rflt = rolled_twin_maps(rgeos, MOVES[::-1], seed=7)
     out = []
     for source in ("rolled", "grids"):
         bat = BatchController(p, B, min_shift=shift)
         if d is not None:
-            bat.set_obstacles(d, TO.W_OBS, velocities=vels)
+            bat.set_obstacles(d, OC.W_OBS, velocities=vels)
         if source == "rolled":
             bat.set_occupancy(occ, INFLATION, map_of, w)
             bat.set_nominal(nom)
@@ -225,40 +225,40 @@ def test_a_rolled_handle_gives_the_bits_of_a_twin(shift, discs):
             bat.set_grids(flt, map_of, w)
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        res = [TO.snapshot(bat, u, st), bat.last_kernel(), derived(bat, 0), derived(bat, 1)]
+        res = [BS.snapshot(bat, u, st), bat.last_kernel(), derived(bat, 0), derived(bat, 1)]
         # five resident ticks over maps placed from the start poses
         if source == "rolled":
             bat.set_occupancy(rocc, INFLATION, map_of, w)
             bat.roll_occupancy([1, 0], [m[0] for m in MOVES], [m[1] for m in MOVES], rexposed[::-1])
         else:
             bat.set_grids(rflt, map_of, w)
-        bat.resident_set_paths([TP.path_of(b) for b in range(B)])
+        bat.resident_set_paths([BS.path_of(b) for b in range(B)])
         bat.resident_set_poses(s0, rseeds)
         for it in range(5):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
-            res.append(TC.tick_bits(bat) + [r.tobytes() for r in bat.resident_read()[:2]] + [bat.resident_read_trace(b).tobytes() for b in range(B)])
+            res.append(CS.tick_bits(bat) + [r.tobytes() for r in bat.resident_read()[:2]] + [bat.resident_read_trace(b).tobytes() for b in range(B)])
         res.append(bat.last_kernel())
         bat.close()
         out.append(res)
     a, b = out
     assert a[1] == b[1] == a[-1] == b[-1] == capi.BATCH_KERNEL_FOUR_WAVE | GRID | (SHIFT if shift else 0)
     assert same(a[2], b[2]) and same(a[3], b[3]) and len(np.unique(a[2])) > 5
-    assert all(TO.same_bits(x, y) for x, y in zip(a[0], b[0]))
+    assert all(BS.same_bits(x, y) for x, y in zip(a[0], b[0]))
     for it in range(5):
         assert a[4 + it] == b[4 + it], it
 
 
 def test_a_rolled_handle_gives_the_bits_of_a_twin_beside_the_fleet_term():
-    p = TF.params("diff_drive", 1000, 15)
+    p = FS.params("diff_drive", 1000, 15)
     B = 5
-    s0, seeds, paths = TF.fleet_start(p, B)
+    s0, seeds, paths = FS.fleet_start(p, B)
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(s0[b, :3], p.v_ref, p.dt, p.horizon, salt=b - 1, ahead=2.0) for b in (1, 2)]
     occ, exposed, flt = rolled_twin_maps(geos, MOVES, seed=3)
-    static = [TF.far_discs(b % 3, b) for b in range(B)]
+    static = [FS.far_discs(b % 3, b) for b in range(B)]
     out = []
     for source in ("rolled", "grids"):
-        bat = TF.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
+        bat = FS.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
         bat.resident_set_fleet_prediction(True)
         if source == "rolled":
             bat.set_occupancy(occ, INFLATION, map_of, w)
@@ -268,7 +268,7 @@ def test_a_rolled_handle_gives_the_bits_of_a_twin_beside_the_fleet_term():
         res = []
         for it in range(5):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
-            res.append(TC.tick_bits(bat) + [bat.resident_read()[0].tobytes()])
+            res.append(CS.tick_bits(bat) + [bat.resident_read()[0].tobytes()])
         res.append(bat.last_kernel())
         bat.close()
         out.append(res)
@@ -298,8 +298,8 @@ def test_rolls_take_effect_in_stream_order():
     p = configs.diff_drive_defaults(128, 15)
     B, R = 2, 3
     profile, free = CR.distinct_profile(R) * np.float32(0.001), 0.0
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     geo = GR.map_ahead(s0[0, :3], p.v_ref, p.dt, p.horizon, ahead=0.5)
     nx, ny, res, origin0, outside = geo.nx, geo.ny, geo.resolution, (geo.ox, geo.oy), 0.5
     map_of, w = np.array([0, -1], dtype=np.int32), np.array([0.5, 0.0])
@@ -360,7 +360,7 @@ def test_rolls_take_effect_in_stream_order():
 def test_refusals_change_nothing_and_the_setters_keep_the_rolled_map():
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
@@ -379,7 +379,7 @@ def test_refusals_change_nothing_and_the_setters_keep_the_rolled_map():
     def tick():
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        return TO.snapshot(bat, u, st, states=False)
+        return BS.snapshot(bat, u, st, states=False)
 
     def state():
         return [bat.read_occupancy(m).tobytes() + derived(bat, m).tobytes() for m in range(2)] + [bat.get_occupancy(), bat.get_grids()[0][0][1]]
@@ -388,7 +388,7 @@ def test_refusals_change_nothing_and_the_setters_keep_the_rolled_map():
     before, bits = state(), tick()
     bat.roll_occupancy([0, 1], 0, 0)
     bat.roll_occupancy([1], 0, 0, [(None, None)])
-    assert state() == before and all(TO.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
+    assert state() == before and all(BS.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
     # one roll, then every refusal
     bat.roll_occupancy([0, 1], [m[0] for m in MOVES], [m[1] for m in MOVES], exposed)
     rolled = [(RR.roll_layer(occ[m][0], *MOVES[m], strips=exposed[m]), RR.rolled_origin(occ[m][1], MOVES[m], occ[m][2]), 128, R, profile,
@@ -407,18 +407,18 @@ def test_refusals_change_nothing_and_the_setters_keep_the_rolled_map():
     assert call(bat._h, 1, None, ip([1]), ip([0]), None, 0) == capi.ERR_INVALID_ARG
     assert call(bat._h, 1, ip([0]), None, ip([0]), None, 0) == capi.ERR_INVALID_ARG
     assert call(bat._h, 1, ip([0]), ip([1]), None, big.ctypes.data_as(u8p), 0) == capi.ERR_INVALID_ARG
-    assert state() == before and all(TO.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
+    assert state() == before and all(BS.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
     # the other setters keep the rolled map and its origin
-    discs = TO.discs_for(p, inputs, ns=(0, 3, 0, 3, 0))
+    discs = OC.discs_for(p, inputs, ns=(0, 3, 0, 3, 0))
     bat.set_params([p] * B)
     bat.set_params(None)
-    bat.set_obstacles(discs, TO.W_OBS, velocities=[np.zeros((len(a), 2)) for a in discs])
+    bat.set_obstacles(discs, OC.W_OBS, velocities=[np.zeros((len(a), 2)) for a in discs])
     bat.set_obstacle_velocities(None)
     bat.set_obstacles(None)
     bat.set_min_shift(True)
     bat.set_min_shift(False)
     holds(bat, rolled)
-    assert state() == before and all(TO.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
+    assert state() == before and all(BS.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
     # a patch addresses the rolled frame
     patch = np.full((3, 4), 255, dtype=np.uint8)
     bat.update_occupancy(0, 2, 1, patch)
@@ -480,7 +480,7 @@ def test_rolling_returns_all_device_memory():
     import torch
     p = configs.diff_drive_defaults(1000, 15)
     B = 16
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     map_of, w = np.array([b % 2 for b in range(B)], dtype=np.int32), np.full(B, 0.01)
     big = (np.ones((700, 900), dtype=np.uint8), (0.0, 0.0), 0.05, 0.0, 1)      # (0.6 MiB of layer, 2.4 MiB of cells, twice over)
     small = (np.ones((3, 5), dtype=np.uint8), (0.0, 0.0), 0.05, 0.0, 1)
@@ -508,10 +508,10 @@ def test_rolling_returns_all_device_memory():
 
     for _ in range(3):   # runtime pools settle
         cycle()
-    free0, rss0 = level(), TC._rss_kb()
+    free0, rss0 = level(), CS._rss_kb()
     for _ in range(40):
         cycle()
-    free1, rss1 = level(), TC._rss_kb()
+    free1, rss1 = level(), CS._rss_kb()
     assert free0 - free1 < 8 * 2**20, "device memory shrank by %.1f MiB over 40 cycles" % ((free0 - free1) / 2**20)
     assert rss1 - rss0 < 96 * 1024, "resident host memory grew by %d kB over 40 cycles" % (rss1 - rss0)
     # _set_grids and _set_occupancy(NULL) give the second allocation back with the first, while the handle lives

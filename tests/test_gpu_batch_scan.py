@@ -14,24 +14,23 @@ import sys
 import numpy as np
 import pytest
 
+import batch_support as BS
 import costmap_reference as CR
+import costmap_support as CS
+import fleet_support as FS
 import grid_reference as GR
+import obstacle_cases as OC
 import roll_reference as RR
 import scan_reference as SR
-import test_gpu_batch_costmap as TC
-import test_gpu_batch_fleet as TF
-import test_gpu_batch_obstacles as TO
-import test_gpu_batch_params as TP
-import test_scan_reference as TS
+from batch_support import GRID, SHIFT
 from ccv_mppi_path_tracker_amd import BatchController, batch, capi, configs
+from costmap_support import CLEAR_TICK, block_scans, derived, occ_map, same
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import costmap_door_cpu as CD  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SHIFT, GRID = TC.SHIFT, TC.GRID
 u8p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
-same, derived, occ_map = TC.same, TC.derived, TC.occ_map
 FREE = CR.FREE_VALUE
 CALL = "ccv_mppi_batch_scan_occupancy_enqueue"
 
@@ -192,7 +191,7 @@ def test_scans_patches_and_rolls_back_to_back(small_handle):
 
 
 # 4. the same bits as a twin -----------------------------------------------------------------------------------------------------
-INFLATION = TC.INFLATION
+INFLATION = CS.INFLATION
 
 
 def scanned_twin_maps(geos, seed=0):
@@ -201,7 +200,7 @@ def scanned_twin_maps(geos, seed=0):
     R, profile, free = INFLATION
     occ, scans, flt = [], [], []
     for m, g in enumerate(geos):
-        cells = TC.layer_like(g, seed + m)
+        cells = CS.layer_like(g, seed + m)
         s = (g.nx // 2 + m, g.ny // 3)
         ends, hits = SR.fan(s, 180, 0.4 * max(g.nx, g.ny), hit_every=5, phase=0.3 * m)
         new = SR.apply_scan(cells, s, ends, hits)
@@ -220,22 +219,22 @@ def scan_all(bat, scans, order):
 def test_a_scanned_handle_gives_the_bits_of_a_twin(shift, discs):
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
     occ, scans, flt = scanned_twin_maps(geos)
-    d = TO.discs_for(p, inputs, ns=(32, 0, 3, 3, 32)) if discs != "none" else None
+    d = OC.discs_for(p, inputs, ns=(32, 0, 3, 3, 32)) if discs != "none" else None
     vels = [np.stack([0.3 * np.cos(np.arange(len(a)) + b), 0.2 * np.sin(np.arange(len(a)) - b)], axis=1).reshape(-1, 2)
             for b, a in enumerate(d)] if discs == "moving" else None
-    s0, rseeds = TP.start_poses(p, B)
+    s0, rseeds = BS.start_poses(p, B)
     rgeos = [GR.map_ahead(s0[b, :3], p.v_ref, p.dt, p.horizon, salt=b - 1, ahead=2.0) for b in (1, 2)]
     rocc, rscans, rflt = scanned_twin_maps(rgeos, seed=7)
     out = []
     for source in ("scanned", "grids"):
         bat = BatchController(p, B, min_shift=shift)
         if d is not None:
-            bat.set_obstacles(d, TO.W_OBS, velocities=vels)
+            bat.set_obstacles(d, OC.W_OBS, velocities=vels)
         if source == "scanned":
             bat.set_occupancy(occ, INFLATION, map_of, w)
             bat.set_nominal(nom)
@@ -247,40 +246,40 @@ def test_a_scanned_handle_gives_the_bits_of_a_twin(shift, discs):
             bat.set_grids(flt, map_of, w)
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        res = [TO.snapshot(bat, u, st), bat.last_kernel(), derived(bat, 0), derived(bat, 1)]
+        res = [BS.snapshot(bat, u, st), bat.last_kernel(), derived(bat, 0), derived(bat, 1)]
         # five resident ticks over maps placed from the start poses
         if source == "scanned":
             bat.set_occupancy(rocc, INFLATION, map_of, w)
             scan_all(bat, rscans, [1, 0])
         else:
             bat.set_grids(rflt, map_of, w)
-        bat.resident_set_paths([TP.path_of(b) for b in range(B)])
+        bat.resident_set_paths([BS.path_of(b) for b in range(B)])
         bat.resident_set_poses(s0, rseeds)
         for it in range(5):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
-            res.append(TC.tick_bits(bat) + [r.tobytes() for r in bat.resident_read()[:2]] + [bat.resident_read_trace(b).tobytes() for b in range(B)])
+            res.append(CS.tick_bits(bat) + [r.tobytes() for r in bat.resident_read()[:2]] + [bat.resident_read_trace(b).tobytes() for b in range(B)])
         res.append(bat.last_kernel())
         bat.close()
         out.append(res)
     a, b = out
     assert a[1] == b[1] == a[-1] == b[-1] == capi.BATCH_KERNEL_FOUR_WAVE | GRID | (SHIFT if shift else 0)
     assert same(a[2], b[2]) and same(a[3], b[3]) and len(np.unique(a[2])) > 5
-    assert all(TO.same_bits(x, y) for x, y in zip(a[0], b[0]))
+    assert all(BS.same_bits(x, y) for x, y in zip(a[0], b[0]))
     for it in range(5):
         assert a[4 + it] == b[4 + it], it
 
 
 def test_a_scanned_handle_gives_the_bits_of_a_twin_beside_the_fleet_term():
-    p = TF.params("diff_drive", 1000, 15)
+    p = FS.params("diff_drive", 1000, 15)
     B = 5
-    s0, seeds, paths = TF.fleet_start(p, B)
+    s0, seeds, paths = FS.fleet_start(p, B)
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(s0[b, :3], p.v_ref, p.dt, p.horizon, salt=b - 1, ahead=2.0) for b in (1, 2)]
     occ, scans, flt = scanned_twin_maps(geos, seed=3)
-    static = [TF.far_discs(b % 3, b) for b in range(B)]
+    static = [FS.far_discs(b % 3, b) for b in range(B)]
     out = []
     for source in ("scanned", "grids"):
-        bat = TF.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
+        bat = FS.make(p, B, True, static, 50.0, paths, s0, seeds, fleet=(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0)))
         bat.resident_set_fleet_prediction(True)
         if source == "scanned":
             bat.set_occupancy(occ, INFLATION, map_of, w)
@@ -290,7 +289,7 @@ def test_a_scanned_handle_gives_the_bits_of_a_twin_beside_the_fleet_term():
         res = []
         for it in range(5):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
-            res.append(TC.tick_bits(bat) + [bat.resident_read()[0].tobytes()])
+            res.append(CS.tick_bits(bat) + [bat.resident_read()[0].tobytes()])
         res.append(bat.last_kernel())
         bat.close()
         out.append(res)
@@ -311,8 +310,8 @@ def test_scans_take_effect_in_stream_order():
     p = configs.diff_drive_defaults(128, 15)
     B, R = 2, 3
     profile, free = CR.distinct_profile(R) * np.float32(0.001), 0.0   # (1.000 .. 1.009: the ring costs about what a cell does)
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     geo = GR.map_ahead(s0[0, :3], p.v_ref, p.dt, p.horizon, ahead=3.0)
     map_of, w = np.array([0, -1], dtype=np.int32), np.array([0.5, 0.0])
     inv = 1.0 / geo.resolution
@@ -331,7 +330,7 @@ def test_scans_take_effect_in_stream_order():
     for it in range(T_STREAM):
         ref.set_grids([(cost, (geo.ox, geo.oy), geo.resolution, float(geo.outside))], map_of, w)
         ref.resident_step_enqueue(p.dt, it, advance=it > 0)
-        hit_cells = TC.cells_hit(geo, ref.read_candidates(0)[:, :GR.n_covered(p.model, p.horizon)])
+        hit_cells = CS.cells_hit(geo, ref.read_candidates(0)[:, :GR.n_covered(p.model, p.horizon)])
         if changed is not None:
             looked_at += bool(np.intersect1d(hit_cells, changed).size)
         assert hit_cells.size > 0, "the fan left the map"
@@ -371,9 +370,6 @@ def test_scans_take_effect_in_stream_order():
 
 
 # 6. an obstacle appears in a scan and leaves in a later one -------------------------------------------------------------------------
-CLEAR_TICK, block_scans = TS.CLEAR_TICK, TS.block_scans
-
-
 def test_an_obstacle_appears_in_a_scan_and_leaves_in_a_later_one():
     """The door's scene (tools/costmap_door_cpu.py; tests/test_costmap_door_cpu.py holds its CPU restatement): the block is marked by
     a scan right after tick PATCH_TICK.  never: no scan -- some trace poses lie in the block's cells; marked: none do; cleared_by_scan: a
@@ -416,7 +412,7 @@ def test_an_obstacle_appears_in_a_scan_and_leaves_in_a_later_one():
 def test_refusals_and_empty_calls_change_nothing_and_the_setters_keep_the_scanned_map():
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 1], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.0, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
@@ -433,7 +429,7 @@ def test_refusals_and_empty_calls_change_nothing_and_the_setters_keep_the_scanne
     def tick():
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        return TO.snapshot(bat, u, st, states=False)
+        return BS.snapshot(bat, u, st, states=False)
 
     def state():
         return [bat.read_occupancy(m).tobytes() + derived(bat, m).tobytes() for m in range(2)] + [bat.get_occupancy()]
@@ -469,12 +465,12 @@ def test_refusals_and_empty_calls_change_nothing_and_the_setters_keep_the_scanne
     assert call(bat._h, 1, ip([0]), ip([1, 1]), None, e.ctypes.data_as(i32p), h.ctypes.data_as(u8p), 0, 255) == capi.ERR_INVALID_ARG
     assert call(bat._h, 1, ip([0]), ip([1, 1]), ip([1]), None, h.ctypes.data_as(u8p), 0, 255) == capi.ERR_INVALID_ARG
     assert call(bat._h, 1, ip([0]), ip([1, 1]), ip([1]), e.ctypes.data_as(i32p), None, 0, 255) == capi.ERR_INVALID_ARG
-    assert state() == before and all(TO.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
+    assert state() == before and all(BS.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
     # the other setters keep the scanned map
-    discs = TO.discs_for(p, inputs, ns=(0, 3, 0, 3, 0))
+    discs = OC.discs_for(p, inputs, ns=(0, 3, 0, 3, 0))
     bat.set_params([p] * B)
     bat.set_params(None)
-    bat.set_obstacles(discs, TO.W_OBS, velocities=[np.zeros((len(a), 2)) for a in discs])
+    bat.set_obstacles(discs, OC.W_OBS, velocities=[np.zeros((len(a), 2)) for a in discs])
     bat.set_obstacle_velocities(None)
     bat.set_obstacles(None)
     bat.set_min_shift(True)
@@ -482,7 +478,7 @@ def test_refusals_and_empty_calls_change_nothing_and_the_setters_keep_the_scanne
     bat.resident_set_fleet(np.full(B, 0.25), 3.0, 4, np.full(B, 50.0))
     bat.resident_set_fleet(None)
     holds(bat, scanned)
-    assert state() == before and all(TO.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
+    assert state() == before and all(BS.same_bits(a, b, states=False) for a, b in zip(bits, tick()))
     # the float maps are a caller's again: no scan
     bat.set_grids(flt, map_of, w)
     raw_scan(bat, [0], [(1, 1)], *one_ray, expect=capi.ERR_STATE)
@@ -520,7 +516,7 @@ def test_the_slot_size_limit():
 def test_one_instances_scan_changes_no_bit_of_an_instance_on_another_map():
     p = configs.diff_drive_defaults(1000, 15)
     B, j = 5, 2   # (instance 2 alone is on map 1)
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     x0, dt, xr, yr, yaw0, seeds, nom = inputs
     map_of, w = np.array([-1, 0, 1, 0, 0], dtype=np.int32), np.array([0.0, 0.01, 0.01, 0.02, 0.025])
     geos = [GR.map_ahead(x0[b, :3], p.v_ref, dt[b], p.horizon, salt=m) for m, b in enumerate((1, 2))]
@@ -535,17 +531,17 @@ def test_one_instances_scan_changes_no_bit_of_an_instance_on_another_map():
             bat.scan_occupancy([1], [scans[1][0]], [ends], [hits])
         bat.set_nominal(nom)
         u, st = bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0)
-        snaps.append(TO.snapshot(bat, u, st))
+        snaps.append(BS.snapshot(bat, u, st))
         bat.close()
     assert not np.array_equal(snaps[0][j]["c"], snaps[1][j]["c"])
-    assert all(TO.same_bits(snaps[0][b], snaps[1][b]) for b in range(B) if b != j)
+    assert all(BS.same_bits(snaps[0][b], snaps[1][b]) for b in range(B) if b != j)
 
 
 def test_scanning_returns_all_device_and_pinned_memory():
     import torch
     p = configs.diff_drive_defaults(1000, 15)
     B = 16
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
     map_of, w = np.array([b % 2 for b in range(B)], dtype=np.int32), np.full(B, 0.01)
     big = (np.ones((700, 900), dtype=np.uint8), (0.0, 0.0), 0.05, 0.0, 1)
     small = (np.ones((3, 5), dtype=np.uint8), (0.0, 0.0), 0.05, 0.0, 1)
@@ -569,10 +565,10 @@ def test_scanning_returns_all_device_and_pinned_memory():
 
     for _ in range(3):   # runtime pools settle
         cycle()
-    free0, rss0 = level(), TC._rss_kb()
+    free0, rss0 = level(), CS._rss_kb()
     for _ in range(40):
         cycle()
-    free1, rss1 = level(), TC._rss_kb()
+    free1, rss1 = level(), CS._rss_kb()
     assert free0 - free1 < 8 * 2**20, "device memory shrank by %.1f MiB over 40 cycles" % ((free0 - free1) / 2**20)
     # the staging ring is 4 MiB of pinned, hence resident, host memory per handle: 40 rings left behind would be 160 MiB
     assert rss1 - rss0 < 96 * 1024, "resident host memory grew by %d kB over 40 cycles" % (rss1 - rss0)

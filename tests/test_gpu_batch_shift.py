@@ -24,24 +24,20 @@ of 1, and the sensitivity conditions on the inputs (drop >= 100 for every sample
 lambda comes from regime_lambda.  The plain family (exact shift, one exp) is held to the same E_SHIFT: it needs less.
 The observed maxima of err / bound are printed (-s); the assertion is the bound.
 """
-import math
-
 import numpy as np
 import pytest
 
+import batch_support as BS
 import ccv_mppi_path_tracker_amd as amd
 import helpers
+import update_checks as UC
 import update_reference as R
-import test_gpu_batch_params as TP
-import test_gpu_update as TU
+from batch_support import MODEL_DEFAULTS, SV
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIError
+from update_checks import check_shift
 
 pytestmark = pytest.mark.gpu
-LD = np.longdouble
-E_SHIFT = 2 * R.E_MAX + 1
-MODEL_DEFAULTS = TU.MODEL_DEFAULTS
-SV = capi.BATCH_KERNEL_SHIFT | capi.BATCH_KERNEL_VARIED
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -49,47 +45,11 @@ def _need_gpu(gpu_required):
     capi.load()
 
 
-def check_shift(what, costs, controls, lam, u_dev, sum_w=None, w_norm=None, stats=None, sens=True):
-    """Check 1 of the module docstring for one instance.  sum_w None (resident ticks return no statistics): the normalised
-    weights are held against w_ref / S_ref with the bound of S added to theirs, as test_gpu_update.check_update does."""
-    K, E = len(costs), E_SHIFT
-    shift = float(costs.min())
-    ref = R.reference(costs, controls, lam, shift)
-    if w_norm is not None:
-        w_norm = np.asarray(w_norm)
-        w_ref, x, _ = R.weight_errors(costs, lam, w_norm, shift)
-        if sum_w is not None:
-            allowed = np.maximum((2 * np.abs(x).astype(LD) + E + 2) * LD(R.U) * w_ref, LD(R.TINY) * (E + 1))
-            rw = float(np.max(np.abs((w_norm * sum_w).astype(LD) - w_ref) / allowed))
-        else:
-            wn_ref = (w_ref / ref.S).astype(np.float64)
-            allowed = np.maximum((2 * np.abs(x) + E + 2 + K + 1 + ref.xmax + E) * R.U * wn_ref, R.TINY * (E + 1))
-            rw = float(np.max(np.abs(w_norm - wn_ref) / allowed))
-        print("err/bound [batch shift] %s weights: %.3g" % (what, rw))
-        assert rw <= 1.0, (what, rw)
-        assert abs(math.fsum(w_norm) - 1.0) <= K * R.U
-    ratio = ref.err_over_bound(u_dev, E)
-    print("err/bound [batch shift] %s u*: %.3g" % (what, ratio))
-    assert ratio <= 1.0, (what, ratio)
-    if sum_w is not None:
-        assert sum_w >= 1.0
-        assert abs(LD(sum_w) - ref.S) <= ref.bound_S(E)
-    if stats is not None:
-        assert stats.min_cost == costs.min() and stats.max_cost == costs.max() and stats.nonfinite == 0
-        must, may = R.zero_count_range(costs, lam, E, shift)
-        assert must <= stats.n_zero_weight <= may, (what, must, stats.n_zero_weight, may)
-    if sens and K >= 64:
-        drop, swap = R.sensitivities(costs, controls, ref, E)
-        assert drop.min() >= 100.0, (what, drop.min())
-        assert np.mean(swap >= 100.0) >= 0.99, (what, np.mean(swap < 100.0))
-    return ref
-
-
 def check_batch_shift(what, bat, plist, kinds, noms, seeds, it, u, stats=None, only=None):
     for b, p in enumerate(plist):
         if only is not None and b not in only:
             continue
-        ctl = TU.host_controls(p, noms[b], seeds[b], it)
+        ctl = UC.host_controls(p, noms[b], seeds[b], it)
         check_shift("%s b=%d %s" % (what, b, kinds[b]), bat.read_costs(b), ctl, p.lam, u[b],
                     stats[b].sum_w if stats else None, bat.read_weights(b), stats[b] if stats else None,
                     sens=kinds[b] != "one")
@@ -99,12 +59,12 @@ def family_code(kernel, model, K, B):
     if kernel == "v1":
         return capi.BATCH_KERNEL_PLAIN
     nblk = B * (-(-K // 64))
-    return capi.BATCH_KERNEL_ONE_WAVE if nblk > (1 if model == "full_body" else 5) * TP._cus() else capi.BATCH_KERNEL_FOUR_WAVE
+    return capi.BATCH_KERNEL_ONE_WAVE if nblk > (1 if model == "full_body" else 5) * BS.cus() else capi.BATCH_KERNEL_FOUR_WAVE
 
 
 # 1. against the extended-precision reference ------------------------------------------------------------------------------
 # four-wave: dd tail (H = 15), dd no tail (H = 50), dd wide (dt = 0.41), sd tail / no tail, fb tail / no tail; one-wave: dd, sd
-# (13 x 100 workgroups: test_gpu_update.batch_inputs has poses for 14 instances), fb (3 x 157); plain: dd, sd, fb;
+# (13 x 100 workgroups: update_checks.batch_inputs has poses for 14 instances), fb (3 x 157); plain: dd, sd, fb;
 # K = 65 537: 1025 workgroups per instance, the smallest count that takes the update's second pass over the partial columns
 # (shift_scaled_sum2 and the statistics wave beyond 1024 columns), the last workgroup with one live sample
 CASES = [(None, "diff_drive", 1000, 15, 8, {}), (None, "diff_drive", 1000, 50, 3, {}), (None, "diff_drive", 1000, 50, 3, {"dt": 0.41}),
@@ -119,14 +79,14 @@ CASES = [(None, "diff_drive", 1000, 15, 8, {}), (None, "diff_drive", 1000, 50, 3
 @pytest.mark.parametrize("varied", [False, True], ids=["shared", "varied"])
 @pytest.mark.parametrize("kernel,model,K,H,B,over", CASES)
 def test_shifted_update_against_the_reference(monkeypatch, kernel, model, K, H, B, over, varied):
-    TU.set_kernel(monkeypatch, kernel)
+    UC.set_kernel(monkeypatch, kernel)
     p = MODEL_DEFAULTS[model](K, H)
     if over:
         p = p.with_(**over)
-    x0, xr, yr, yaw0, seeds = TU.batch_inputs(p, B)
+    x0, xr, yr, yaw0, seeds = UC.batch_inputs(p, B)
     probe = BatchController(p, B)
     probe.iterate(x0, p.dt, xr, yr, yaw0, seeds, 7, want_stats=False)
-    lk = TU.lambdas_for([probe.read_costs(b) for b in range(B)], varied)
+    lk = UC.lambdas_for([probe.read_costs(b) for b in range(B)], varied)
     probe.close()
     kinds = [k for k, _ in lk]
     plist = [p.with_(lam=l) for _, l in lk]
@@ -152,7 +112,7 @@ def test_single_winner():
     the zero-weight count is K - 1."""
     K, H, B = 1000, 15, 3
     p = configs.diff_drive_defaults(K, H)
-    x0, xr, yr, yaw0, seeds = TU.batch_inputs(p, B)
+    x0, xr, yr, yaw0, seeds = UC.batch_inputs(p, B)
     probe = BatchController(p, B)
     probe.iterate(x0, p.dt, xr, yr, yaw0, seeds, 7, want_stats=False)
     c0 = [probe.read_costs(b) for b in range(B)]
@@ -167,7 +127,7 @@ def test_single_winner():
     for b in range(B):
         c = bat.read_costs(b)
         np.testing.assert_array_equal(c, c0[b])
-        best = TU.host_controls(plist[b], np.zeros((H - 1, p.udim)), seeds[b], 7)[int(np.argmin(c))]
+        best = UC.host_controls(plist[b], np.zeros((H - 1, p.udim)), seeds[b], 7)[int(np.argmin(c))]
         assert np.all(np.abs(u[b] - best) <= 2 * np.spacing(np.abs(best)))
         assert st[b].sum_w == 1.0 and st[b].n_zero_weight == K - 1 and st[b].nonfinite == 0
         w = bat.read_weights(b)
@@ -181,7 +141,7 @@ def test_where_the_plain_weights_underflow(monkeypatch, kernel):
     """Odd instances start 40 m beside the path with path_weight 1e4 (the case of test_min_shift_where_plain_weights_underflow):
     in the graded regime their min cost / lambda is beyond 800 and every plain weight is 0; the even instances start on the
     path.  Shift off: the odd instances return NaN and sum_w == 0.  Shift on, same handle: every instance passes check 1."""
-    TU.set_kernel(monkeypatch, kernel)
+    UC.set_kernel(monkeypatch, kernel)
     B, K, H = 4, 1000, 20
     p = configs.workload("C2").params.with_(num_samples=K, horizon=H, path_weight=1e4)
     path = helpers.oracle_path("sinusoid")
@@ -190,7 +150,7 @@ def test_where_the_plain_weights_underflow(monkeypatch, kernel):
         x0[b] = (3.0, 40.0, 0.0) if b % 2 else (path[0][5 * b], path[1][5 * b] + 0.05, 0.0)
         xr[b], yr[b], yaw = helpers.oracle_window(p, path, x0[b])
         yaw0[b] = yaw[0]
-    seeds = np.array([(0x9E3779B97F4A7C15 * (b + 1)) & 0xFFFFFFFFFFFFFFFF for b in range(B)], dtype=np.uint64)
+    seeds = np.array([BS.instance_seed(b) for b in range(B)], dtype=np.uint64)
     probe = BatchController(p, B)
     probe.iterate(x0, p.dt, xr, yr, yaw0, seeds, 0, want_stats=False)
     c0 = [probe.read_costs(b) for b in range(B)]
@@ -219,15 +179,15 @@ def test_where_the_plain_weights_underflow(monkeypatch, kernel):
 
 # 3. bit-exact properties with shift on ---------------------------------------------------------------------------------
 def bits(bat, b, u, st):
-    return (u[b].tobytes(), TP.stats_tuple(st[b]), bat.read_costs(b).tobytes(), bat.read_weights(b).tobytes())
+    return (u[b].tobytes(), BS.stats_tuple(st[b]), bat.read_costs(b).tobytes(), bat.read_weights(b).tobytes())
 
 
 def test_instance_of_a_batch_equals_the_batch_of_one():
     p = configs.diff_drive_defaults(1000, 15)
     B = 6
     assert family_code(None, p.model, 1000, B) == family_code(None, p.model, 1000, 1) == capi.BATCH_KERNEL_FOUR_WAVE
-    seq = TP.varied(p, B)
-    x0, dt, xr, yr, yaw0, seeds, nom = TP.instance_inputs(p, B)
+    seq = BS.varied(p, B)
+    x0, dt, xr, yr, yaw0, seeds, nom = BS.instance_inputs(p, B)
     bat = BatchController(seq, B, min_shift=True)
     bat.set_nominal(nom)
     ones = [BatchController([seq[b]], 1, min_shift=True) for b in range(B)]
@@ -239,14 +199,14 @@ def test_instance_of_a_batch_equals_the_batch_of_one():
             u1, s1 = g.iterate(x0[b:b + 1], dt[b:b + 1], xr[b:b + 1], yr[b:b + 1], yaw0[b:b + 1], seeds[b:b + 1], it)
             assert bits(bat, b, u, st) == bits(g, 0, u1, s1)
     assert bat.last_kernel() == SV | capi.BATCH_KERNEL_FOUR_WAVE
-    TP.close_all(bat, ones)
+    BS.close_all(bat, ones)
 
 
 def test_one_instances_inputs_change_no_bit_of_another():
     p = configs.diff_drive_defaults(1000, 15)
     B, j = 6, 2
-    seq = TP.varied(p, B)
-    x0, dt, xr, yr, yaw0, seeds, nom = TP.instance_inputs(p, B)
+    seq = BS.varied(p, B)
+    x0, dt, xr, yr, yaw0, seeds, nom = BS.instance_inputs(p, B)
     x2, xr2, yr2, seeds2, seq2 = x0.copy(), xr.copy(), yr.copy(), seeds.copy(), list(seq)
     x2[j] += (0.3, -0.2, 0.05)
     xr2[j] += 0.1
@@ -263,7 +223,7 @@ def test_one_instances_inputs_change_no_bit_of_another():
     for i in range(B):
         if i != j:
             assert bits(a, i, ua, sa) == bits(b, i, ub, sb)
-    TP.close_all(a, b)
+    BS.close_all(a, b)
 
 
 def test_copies_of_the_configuration_null_and_switching_off():
@@ -271,7 +231,7 @@ def test_copies_of_the_configuration_null_and_switching_off():
     switching the mode off reproduces the shift-off bits of a fresh handle."""
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    x0, dt, xr, yr, yaw0, seeds, nom = TP.instance_inputs(p, B)
+    x0, dt, xr, yr, yaw0, seeds, nom = BS.instance_inputs(p, B)
     plain, copies, fresh = (BatchController(p, B, min_shift=True), BatchController([p] * B, B, min_shift=True),
                             BatchController(p, B))
     for h in (plain, copies, fresh):
@@ -299,7 +259,7 @@ def test_copies_of_the_configuration_null_and_switching_off():
         for b in range(B):
             assert bits(plain, b, ua, sa) == bits(fresh, b, uf, sf)
     assert plain.last_kernel() == fresh.last_kernel() == capi.BATCH_KERNEL_FOUR_WAVE
-    TP.close_all(plain, copies, fresh)
+    BS.close_all(plain, copies, fresh)
 
 
 # 4. the resident loop -------------------------------------------------------------------------------------------------
@@ -308,9 +268,9 @@ def test_resident_loop_with_shift_equals_the_host_prologue():
     (calc_ref_path, plant_step) driving ccv_mppi_batch_iterate on a batch in the same mode, bit for bit."""
     p = configs.diff_drive_defaults(1000, 15)
     B, ticks = 6, 56
-    seq = TP.varied(p, B)
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    seq = BS.varied(p, B)
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     host = BatchController(seq, B, min_shift=True)
     s, u, ref = s0.copy(), None, []
     for it in range(ticks):
@@ -359,7 +319,7 @@ def test_shift_resident_tick_pair(model, K, H, B, varied):
         i = 7 * b + 3
         s0[b, 0], s0[b, 1] = paths[b][0][i], paths[b][1][i] + 0.05
         s0[b, 2] = np.arctan2(paths[b][1][i + 1] - paths[b][1][i], paths[b][0][i + 1] - paths[b][0][i])
-    seeds = np.array([(0x9E3779B97F4A7C15 * (b + 1)) & 0xFFFFFFFFFFFFFFFF for b in range(B)], dtype=np.uint64)
+    seeds = np.array([BS.instance_seed(b) for b in range(B)], dtype=np.uint64)
 
     def make(params, shift=True):
         bat = BatchController(params, B, min_shift=shift)
@@ -370,7 +330,7 @@ def test_shift_resident_tick_pair(model, K, H, B, varied):
     probe = make(p, shift=False)
     probe.resident_step_enqueue(p.dt, 0, advance=False)
     probe.synchronize()
-    lk = TU.lambdas_for([probe.read_costs(b) for b in range(B)], varied)
+    lk = UC.lambdas_for([probe.read_costs(b) for b in range(B)], varied)
     probe.close()
     kinds = [k for k, _ in lk]
     plist = [p.with_(lam=l) for _, l in lk]
@@ -390,7 +350,7 @@ def test_shift_resident_tick_pair(model, K, H, B, varied):
     # the pose Y moved to is the plant's step with the command X's finalize stored
     want = np.array([amd.plant_step(p.model, s0[b], u0[b][0], p.dt) for b in range(B)])
     np.testing.assert_array_equal(Y.resident_read()[0], want)
-    TP.close_all(X, Y)
+    BS.close_all(X, Y)
 
 
 def test_resident_batch_stays_finite_where_lambda_underflows():
@@ -398,8 +358,8 @@ def test_resident_batch_stays_finite_where_lambda_underflows():
     pose and every trace row of a 40-tick resident run is finite, and u* too."""
     p = configs.diff_drive_defaults(1000, 15)
     B, ticks = 6, 40
-    s0, seeds = TP.start_poses(p, B)
-    paths = [TP.path_of(b) for b in range(B)]
+    s0, seeds = BS.start_poses(p, B)
+    paths = [BS.path_of(b) for b in range(B)]
     probe = BatchController(p, B)
     probe.resident_set_paths(paths)
     probe.resident_set_poses(s0, seeds)
@@ -429,13 +389,13 @@ def test_mode_switches_flush_a_pending_resident_update_and_mix_with_host_iterati
     resident steps: the same reads as the same sequence with a synchronisation after every step"""
     p = configs.diff_drive_defaults(1000, 15)
     B = 5
-    seq = TP.varied(p, B)
-    s0, seeds = TP.start_poses(p, B)
-    x0, dt, xr, yr, yaw0, hseeds, _ = TP.instance_inputs(p, B)
+    seq = BS.varied(p, B)
+    s0, seeds = BS.start_poses(p, B)
+    x0, dt, xr, yr, yaw0, hseeds, _ = BS.instance_inputs(p, B)
 
     def run(sync):
         bat = BatchController(seq, B)
-        bat.resident_set_paths([TP.path_of(b) for b in range(B)])
+        bat.resident_set_paths([BS.path_of(b) for b in range(B)])
         bat.resident_set_poses(s0, seeds)
         reads, kernels, it = [], [], 0
 
@@ -475,12 +435,12 @@ def test_mode_switches_flush_a_pending_resident_update_and_mix_with_host_iterati
 
 
 def test_plain_family_is_refused_by_a_resident_step(monkeypatch):
-    TU.set_kernel(monkeypatch, "v1")
+    UC.set_kernel(monkeypatch, "v1")
     p = configs.diff_drive_defaults(256, 15)
     B = 3
-    s0, seeds = TP.start_poses(p, B)
+    s0, seeds = BS.start_poses(p, B)
     bat = BatchController(p, B, min_shift=True)
-    bat.resident_set_paths([TP.path_of(b) for b in range(B)])
+    bat.resident_set_paths([BS.path_of(b) for b in range(B)])
     bat.resident_set_poses(s0, seeds)
     with pytest.raises(MPPIError) as e:
         bat.resident_step_enqueue(p.dt, 0, advance=False)
@@ -494,10 +454,10 @@ def test_plain_family_is_refused_by_a_resident_step(monkeypatch):
 @pytest.mark.parametrize("kernel", [None, "v1"])
 def test_shift_mode_returns_all_device_memory(monkeypatch, kernel):
     import torch
-    TU.set_kernel(monkeypatch, kernel)
+    UC.set_kernel(monkeypatch, kernel)
     p = configs.diff_drive_defaults(1000, 15)
     B = 16
-    inputs = TP.instance_inputs(p, B)
+    inputs = BS.instance_inputs(p, B)
 
     def cycle():
         bat = BatchController(p, B, min_shift=True)

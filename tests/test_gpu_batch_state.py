@@ -15,9 +15,9 @@ weight (the fleet's setter replaces it), so that the final state does not depend
 import numpy as np
 import pytest
 
+import batch_support as BS
+import fleet_support as FS
 import fleet_velocity_reference as FV
-import test_gpu_batch_fleet as TF
-import test_gpu_batch_params as TP
 from ccv_mppi_path_tracker_amd import BatchController, capi
 
 pytestmark = pytest.mark.gpu
@@ -37,12 +37,12 @@ def _need_gpu(gpu_required):
 def terms(p, at):
     """the final state's additions around the instances' positions at [B][>= 2]: (parameters, discs, velocities, maps' arguments)"""
     discs = [np.zeros((0, 3)), np.array([[at[1, 0] + 0.3, at[1, 1] + 0.1, 0.3]]),
-             np.concatenate([[[at[2, 0], at[2, 1] - 0.3, 0.25]], TF.far_discs(2)])]
+             np.concatenate([[[at[2, 0], at[2, 1] - 0.3, 0.25]], FS.far_discs(2)])]
     velocities = [np.zeros((0, 2)), np.array([[-0.1, 0.05]]), np.array([[0.08, 0.12], [0.3, -0.2], [-0.4, 0.6]])]
     cells = (0.25 + np.random.default_rng(7).random((24, 24))).astype(np.float32)
     maps = ([(cells, (at[0, 0] - 3.0, at[0, 1] - 3.0), 0.25, 0.5), (cells.T.copy(), (at[2, 0] - 3.0, at[2, 1] - 3.0), 0.25, 0.0)],
             [0, -1, 1], [0.01, 0.0, 0.025])
-    return TP.varied(p, B), discs, velocities, maps
+    return BS.varied(p, B), discs, velocities, maps
 
 
 def road_a(bat, seq, discs, velocities, maps, fleet):
@@ -77,18 +77,18 @@ def road_b(bat, seq, discs, velocities, maps, fleet):
 
 @pytest.mark.parametrize("model,K", SHAPES, ids=["dd", "fb"])
 def test_two_roads_to_one_state_with_the_fleet_term(model, K):
-    """6 resident ticks from the same poses and warm start: u*, poses, indices, windows and costs (TF.bits), the _read_fleet
+    """6 resident ticks from the same poses and warm start: u*, poses, indices, windows and costs (FS.bits), the _read_fleet
     counts and rows, the _read_fleet_velocities rows and last_kernel() are equal after every tick."""
-    p = TF.params(model, K, H)
-    assert TP.families(model, K, B)[1] == "r4"
-    s0, seeds, paths = TF.fleet_start(p, B)
+    p = FS.params(model, K, H)
+    assert BS.families(model, K, B)[1] == "r4"
+    s0, seeds, paths = FS.fleet_start(p, B)
     seq, discs, velocities, maps = terms(p, s0)
     nom = np.zeros((B, H - 1, p.udim))
     n_static = np.array([len(d) for d in discs])
     sv = FV.table(velocities)
     out = []
     for road in (road_a, road_b):
-        bat = TF.make(p, B, False, None, 0.0, paths, s0, seeds)
+        bat = FS.make(p, B, False, None, 0.0, paths, s0, seeds)
         road(bat, seq, discs, velocities, maps, True)
         bat.resident_set_poses(s0, seeds)
         bat.set_nominal(nom)
@@ -96,7 +96,7 @@ def test_two_roads_to_one_state_with_the_fleet_term(model, K):
         for it in range(TICKS):
             bat.resident_step_enqueue(p.dt, it, advance=it > 0)
             ns, nt, xyr = bat.resident_read_fleet()
-            ticks.append((TF.bits(bat), ns.tolist(), nt.tolist(), xyr.tobytes(), bat.resident_read_fleet_velocities(), bat.last_kernel()))
+            ticks.append((FS.bits(bat), ns.tolist(), nt.tolist(), xyr.tobytes(), bat.resident_read_fleet_velocities(), bat.last_kernel()))
         bat.close()
         out.append(ticks)
     a, b = out
@@ -117,9 +117,9 @@ def test_two_roads_to_one_state_with_the_fleet_term(model, K):
 @pytest.mark.parametrize("model,K", SHAPES, ids=["dd", "fb"])
 def test_two_roads_to_one_state_without_the_fleet_term(model, K):
     """one iterate from the same inputs: u* and every instance's costs are equal"""
-    p = TP.MODEL_DEFAULTS[model](K, H)
-    assert TP.families(model, K, B)[1] == "r4"
-    x0, dt, xr, yr, yaw0, seeds, nom = TP.instance_inputs(p, B)
+    p = BS.MODEL_DEFAULTS[model](K, H)
+    assert BS.families(model, K, B)[1] == "r4"
+    x0, dt, xr, yr, yaw0, seeds, nom = BS.instance_inputs(p, B)
     seq, discs, velocities, maps = terms(p, x0)
     out = []
     for road in (road_a, road_b):

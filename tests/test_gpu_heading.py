@@ -23,9 +23,8 @@ import numpy as np
 import pytest
 
 import helpers
+import resident_loops as RL
 import rollout_reference as RR
-import test_gpu_batch_resident as TBR
-import test_gpu_resident as TR
 import ccv_mppi_path_tracker_amd as amd
 from ccv_mppi_path_tracker_amd import BatchController, capi
 from ccv_mppi_path_tracker_amd.controller import MPPIController
@@ -186,7 +185,7 @@ def test_resident_loop_heading_west(yaw):
     s0 = np.array([px[0], py[0], yaw])
     s0[:2] += 0.05 * np.array([-math.sin(yaw), math.cos(yaw)])
     ticks, seed = 12, 77
-    poses, wins, us = TR.host_loop(p, px, py, s0, ticks, seed, p.num_samples)
+    poses, wins, us = RL.host_loop(p, px, py, s0, ticks, seed, p.num_samples)
     g = MPPIController(p)
     g.resident_set_path(px, py)
     g.resident_set_pose(s0)
@@ -213,8 +212,8 @@ def test_resident_batch_heading_west(yaw):
     s0 = np.array([[path[0][i], path[1][i], yaw + 0.05 * (b - 1)] for b, i in enumerate((0, 7, 15))])
     seeds = np.array([77, 78, 79], dtype=np.uint64)
     ticks = 12
-    ref = TBR.host_batch_loop(p, B, p.num_samples, s0, seeds, ticks, paths=[path] * B)
-    bat = TBR.resident_batch(p, B, p.num_samples, s0, seeds, paths=[path] * B)
+    ref = RL.host_batch_loop(p, B, p.num_samples, s0, seeds, ticks, paths=[path] * B)
+    bat = RL.resident_batch(p, B, p.num_samples, s0, seeds, paths=[path] * B)
     for it in range(ticks):
         bat.resident_step_enqueue(p.dt, it, advance=it > 0)
     st, idx, xr, yr, yaw0, steps = bat.resident_read()

@@ -12,13 +12,13 @@ One handle per shift in {off, on} walks up the rungs with the same warm start, s
 asserted at every rung:
   base, Varied   every instance against the oracle, with the shared and with its own parameters
                  (test_every_instance_matches_the_oracle_with_its_own_parameters: TOL_U, TOL_COST); NULL restores the base bits
-  Obst           TO.discs_for, TO.check_penalty; an instance without discs or without weight keeps every bit
-  Moving         TM.moving_discs_for, TM.check_moving (the static run of the same discs beside it); a velocity table of zeros
+  Obst           OC.discs_for, OC.check_penalty; an instance without discs or without weight keeps every bit
+  Moving         OC.moving_discs_for, OC.check_moving (the static run of the same discs beside it); a velocity table of zeros
                  runs the MOVING kernels and gives the static bits
-  Grid           on top of the moving discs: TG.check_identity, cost_on == fma(w, G, cost_off) in every bit.  Full body has no
+  Grid           on top of the moving discs: GC.check_identity, cost_on == fma(w, G, cost_off) in every bit.  Full body has no
                  one-wave GRID form (has_one_wave_form): in the one-wave family its grid rung reports the four-wave bits and the
                  identity is held within TOL_COST, as test_full_body_beyond_one_workgroup_per_cu_runs_the_four_wave_form
-  shift on       every rung's costs bit-equal to shift off; u*, sum_w and n_zero_weight through TS.check_shift with E_SHIFT
+  shift on       every rung's costs bit-equal to shift off; u*, sum_w and n_zero_weight through UC.check_shift with E_SHIFT
   down           every rung's kernel and bits restored, as test_gpu_batch_forms.py
 The one-wave family: the five instances repeated until the batch has more workgroups than the rule's threshold; the first five
 are read back and checked.  The plain family: CCV_MPPI_KERNEL=v1.
@@ -26,23 +26,20 @@ are read back and checked.  The plain family: CCV_MPPI_KERNEL=v1.
 import numpy as np
 import pytest
 
+import batch_support as BS
+import grid_cases as GC
 import grid_reference as GR
 import helpers
 import horizon_cases as HC
 import horizon_sweep_inputs as HI
-import test_gpu_batch_grid as TG
-import test_gpu_batch_moving as TM
-import test_gpu_batch_obstacles as TO
-import test_gpu_batch_params as TP
-import test_gpu_batch_shift as TS
+import obstacle_cases as OC
+import update_checks as UC
+from batch_support import GRID, MOV, OV, SHIFT
 from ccv_mppi_path_tracker_amd import BatchController, capi
 
 pytestmark = pytest.mark.gpu
 B = HI.B
-VARIED, SHIFT = capi.BATCH_KERNEL_VARIED, capi.BATCH_KERNEL_SHIFT
-OV = capi.BATCH_KERNEL_OBST | VARIED
-MOV = capi.BATCH_KERNEL_MOVING | OV
-GRID = capi.BATCH_KERNEL_GRID | MOV
+VARIED = capi.BATCH_KERNEL_VARIED
 FAMILY = {"r4": capi.BATCH_KERNEL_FOUR_WAVE, "solo": capi.BATCH_KERNEL_ONE_WAVE, "plain": capi.BATCH_KERNEL_PLAIN}
 
 
@@ -56,13 +53,13 @@ def repetitions(model, family):
     if family != "solo":
         return 1
     per_instance = -(-HI.K // 64)
-    threshold = (1 if model == "full_body" else 5) * TP._cus()
+    threshold = (1 if model == "full_body" else 5) * BS.cus()
     return -(-(threshold + 1) // (per_instance * B))
 
 
 def snapshot(bat, u, st):
-    """the first five instances' read-backs (the form TO.snapshot gives, with the statistics beside their tuple)"""
-    return [dict(u=u[b].copy(), st=TP.stats_tuple(st[b]), stats=st[b], c=bat.read_costs(b), w=bat.read_weights(b),
+    """the first five instances' read-backs (the form BS.snapshot gives, with the statistics beside their tuple)"""
+    return [dict(u=u[b].copy(), st=BS.stats_tuple(st[b]), stats=st[b], c=bat.read_costs(b), w=bat.read_weights(b),
                  xy=bat.read_candidates(b)) for b in range(B)]
 
 
@@ -71,7 +68,7 @@ def walk(model, H, family, shift, plain_costs):
     c = HI.batch_case(model, H)
     p, reps = c.p, repetitions(model, family)
     fam = FAMILY[family]
-    assert family == "plain" or TP.families(model, HI.K, B * reps)[1] == family
+    assert family == "plain" or BS.families(model, HI.K, B * reps)[1] == family
     x0, dt, xr, yr, yaw0, seeds, nom = [np.concatenate([a] * reps) for a in c.inputs]
     sh = SHIFT if shift else 0
     base_code = fam | ((SHIFT | VARIED) if shift else 0)
@@ -90,19 +87,19 @@ def walk(model, H, family, shift, plain_costs):
                 what = "%s %s b=%d" % (what0, rung, b)
                 assert snap[b]["c"].tobytes() == plain_costs[rung][b].tobytes(), what   # costs: the shift-off run's bits
                 q = params[b] if params else p
-                TS.check_shift(what, snap[b]["c"], HI.oracle_iteration(model, H, params is not None)[b]["ctl"], q.lam, snap[b]["u"],
+                UC.check_shift(what, snap[b]["c"], HI.oracle_iteration(model, H, params is not None)[b]["ctl"], q.lam, snap[b]["u"],
                                snap[b]["stats"].sum_w, snap[b]["w"], snap[b]["stats"], sens=False)
         return snap
 
     def against_oracle(rung, snap, varied):
         for b, ref in enumerate(HI.oracle_iteration(model, H, varied)):
             what = "%s %s b=%d" % (what0, rung, b)
-            assert np.max(np.abs(snap[b]["c"] - ref["c"]) / ref["c"]) < TP.TOL_COST, what
+            assert np.max(np.abs(snap[b]["c"] - ref["c"]) / ref["c"]) < BS.TOL_COST, what
             if not shift:   # (the oracle forms the reference's weights; the shifted update: check_shift, in run)
-                assert helpers.rel_err(snap[b]["u"], ref["u"]) < TP.TOL_U, what
+                assert helpers.rel_err(snap[b]["u"], ref["u"]) < BS.TOL_U, what
 
     def restored(rung, snap, want):
-        assert all(TO.same_bits(want[b], snap[b]) for b in range(B)), (what0, "down to " + rung)
+        assert all(BS.same_bits(want[b], snap[b]) for b in range(B)), (what0, "down to " + rung)
 
     # ---- base and Varied
     base = run("base", base_code)
@@ -118,9 +115,9 @@ def walk(model, H, family, shift, plain_costs):
     obst = run("obst", fam | OV | sh)
     for b in range(B):
         what = "%s obst b=%d n=%d" % (what0, b, len(c.discs[b]))
-        TO.check_penalty(what, p, c.inputs[0][b], c.discs[b], c.w_obs[b], base[b], obst[b])
+        OC.check_penalty(what, p, c.inputs[0][b], c.discs[b], c.w_obs[b], base[b], obst[b])
         if len(c.discs[b]) == 0 or c.w_obs[b] == 0.0:
-            assert TO.same_bits(base[b], obst[b]), what
+            assert BS.same_bits(base[b], obst[b]), what
         else:
             assert not np.array_equal(base[b]["c"], obst[b]["c"]), what
     # ---- Moving: the same discs standing, under a table of zeros, moving
@@ -132,12 +129,12 @@ def walk(model, H, family, shift, plain_costs):
     mov = run("moving", fam | MOV | sh)
     for b in range(B):
         what = "%s moving b=%d n=%d" % (what0, b, len(c.mdiscs[b]))
-        TM.check_moving(what, p, c.inputs[0][b], c.inputs[1][b], c.mdiscs[b], c.vels[b], c.w_obs[b], base[b], sta[b], mov[b])
+        OC.check_moving(what, p, c.inputs[0][b], c.inputs[1][b], c.mdiscs[b], c.vels[b], c.w_obs[b], base[b], sta[b], mov[b])
         if len(c.mdiscs[b]) == 0 or c.w_obs[b] == 0.0:
-            assert TO.same_bits(base[b], mov[b]), what
+            assert BS.same_bits(base[b], mov[b]), what
         else:
             assert not np.array_equal(sta[b]["c"], mov[b]["c"]), what
-        assert TO.same_bits(sta[b], zero[b]), what
+        assert BS.same_bits(sta[b], zero[b]), what
     # ---- Grid, on top of the moving discs
     one_wave_form = not (family == "solo" and model == "full_body")   # (has_one_wave_form, csrc/mppi_launch.h)
     grid_code = (fam if one_wave_form else capi.BATCH_KERNEL_FOUR_WAVE) | GRID | sh
@@ -147,23 +144,23 @@ def walk(model, H, family, shift, plain_costs):
         what = "%s grid b=%d map=%d w=%g" % (what0, b, c.map_of[b], c.w_grid[b])
         if one_wave_form:
             if c.map_of[b] < 0:
-                assert TO.same_bits(mov[b], grid[b]), what
+                assert BS.same_bits(mov[b], grid[b]), what
                 continue
-            TG.check_identity(what, p, c.maps[c.map_of[b]], c.w_grid[b], mov[b], grid[b])
+            GC.check_identity(what, p, c.maps[c.map_of[b]], c.w_grid[b], mov[b], grid[b])
             if c.w_grid[b] == 0.0:
-                assert TO.same_bits(mov[b], grid[b]), what
+                assert BS.same_bits(mov[b], grid[b]), what
             else:
                 assert not np.array_equal(mov[b]["c"], grid[b]["c"]), what
         elif c.map_of[b] < 0 or c.w_grid[b] == 0.0:   # (the term-off run is another kernel's: no term, the same costs within TOL_COST)
-            assert np.max(np.abs(grid[b]["c"] - mov[b]["c"]) / np.abs(mov[b]["c"])) < TP.TOL_COST, what
-            assert helpers.rel_err(grid[b]["u"], mov[b]["u"]) < TP.TOL_U, what
+            assert np.max(np.abs(grid[b]["c"] - mov[b]["c"]) / np.abs(mov[b]["c"])) < BS.TOL_COST, what
+            assert helpers.rel_err(grid[b]["u"], mov[b]["u"]) < BS.TOL_U, what
         else:   # (the identity within TOL_COST, G from the term-on states)
             g = c.maps[c.map_of[b]]
             P = grid[b]["xy"][:, :GR.n_covered(model, H)]
             share_in, share_out, cells = GR.coverage(g, P)
             assert share_in >= 0.25 and share_out >= 0.05 and cells >= 50, (what, share_in, share_out, cells)
             want = GR.cost_on(mov[b]["c"], c.w_grid[b], GR.grid_sum(g, P))
-            assert np.max(np.abs(grid[b]["c"] - want) / np.abs(want)) < TP.TOL_COST, what
+            assert np.max(np.abs(grid[b]["c"] - want) / np.abs(want)) < BS.TOL_COST, what
     # ---- down
     bat.set_grids(None)
     restored("moving", run("moving", fam | MOV | sh), mov)
@@ -208,6 +205,6 @@ def test_one_wave_batch_with_an_instance_on_the_reference_clamp():
         o = helpers.oracle_for(seq[b])
         o.set_nominal(nom[b])
         u_o = o.iterate(x0[b], dt[b], xr[b], yr[b], yaw0[b], seed=int(seeds[b]), rng="philox", iteration=HI.IT)
-        assert np.max(np.abs(bat.read_costs(b) - o.costs()) / o.costs()) < TP.TOL_COST, b
-        assert helpers.rel_err(u[b], u_o) < TP.TOL_U, b
+        assert np.max(np.abs(bat.read_costs(b) - o.costs()) / o.costs()) < BS.TOL_COST, b
+        assert helpers.rel_err(u[b], u_o) < BS.TOL_U, b
     bat.close()

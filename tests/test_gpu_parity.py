@@ -17,6 +17,7 @@ import helpers
 import ccv_mppi_path_tracker_amd as amd
 from ccv_mppi_path_tracker_amd import capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIController, MPPIError
+from resident_loops import start_state
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +30,6 @@ TOL_COST = 1e-9   # SURVEY.md 8c O->G
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu(gpu_required):
     capi.load()
-
-
-def start_state(p, path, lateral=0.0):
-    s = np.zeros(p.nstate)
-    s[0], s[1] = path[0][0], path[1][0] + lateral
-    return s
 
 
 # --------------------------------------------------------------------------------------------------------------

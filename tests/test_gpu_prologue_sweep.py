@@ -41,7 +41,7 @@ import ccv_mppi_path_tracker_amd as amd
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIController
 import prologue_reference as PR
-import test_gpu_resident as TR
+import resident_loops as RL
 
 pytestmark = pytest.mark.gpu
 
@@ -227,7 +227,7 @@ def check_moving(cfg, model, chunk, got, ticks, bad):
     else:
         (c,) = chunk
         p = params(model, c["H"], c["v_ref"])
-        wp, _, wu = TR.host_loop(p.with_(resolution=c["resolution"]), c["px"], c["py"], pose_of(c, p.nstate), ticks, 11, K)
+        wp, _, wu = RL.host_loop(p.with_(resolution=c["resolution"]), c["px"], c["py"], pose_of(c, p.nstate), ticks, 11, K)
         poses, us = [np.array(wp)], [wu[-1]]
     for b, c in enumerate(chunk):
         st, idx, xr, yr, yaw0, tr, u = got[b]

@@ -13,6 +13,7 @@ import helpers
 import ccv_mppi_path_tracker_amd as amd
 from ccv_mppi_path_tracker_amd import capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIController, MPPIError
+from resident_loops import host_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -28,23 +29,6 @@ def start(p, px, py, lateral=0.05):
     s = np.zeros(p.nstate)
     s[0], s[1], s[2] = px[0], py[0] + lateral, 0.02
     return s
-
-
-def host_loop(p, px, py, s0, ticks, seed, num_samples):
-    """The same closed loop with the prologue on the host: window -> iterate -> plant."""
-    g = MPPIController(p, num_samples=num_samples)
-    s = s0.copy()
-    poses, wins, us = [], [], []
-    u = None
-    for it in range(ticks):
-        if it > 0:
-            s = amd.plant_step(p.model, s, u[0], p.dt)
-        idx, xr, yr, yaw = amd.calc_ref_path(px, py, s[0], s[1], p.v_ref, p.dt, p.resolution, p.horizon)
-        u = g.iterate(s, p.dt, xr, yr, yaw[0], seed, it, want_stats=False)
-        poses.append(s.copy())
-        wins.append((idx, xr.copy(), yr.copy(), yaw[0]))
-        us.append(u.copy())
-    return poses, wins, us
 
 
 @pytest.mark.parametrize("model", ["diff_drive", "steering_diff_drive"])

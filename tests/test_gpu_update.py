@@ -34,8 +34,10 @@ import pytest
 import helpers
 import update_reference as R
 import ccv_mppi_path_tracker_amd as amd
+from batch_support import MODEL_DEFAULTS, instance_seed
 from ccv_mppi_path_tracker_amd import BatchController, capi, configs
 from ccv_mppi_path_tracker_amd.controller import MPPIController
+from update_checks import batch_inputs, check_handle, check_update, host_controls, lambdas_for, report, set_kernel
 
 pytestmark = pytest.mark.gpu
 LD = np.longdouble
@@ -62,67 +64,12 @@ def regimes_for(K):
     return ("flat", "graded") if K >= 64 else ("flat",)
 
 
-def report(group, what, ratio):
-    print("err/bound [%s] %s: %.3g" % (group, what, ratio))
-
-
-def check_update(group, what, costs, controls, lam, u_dev, sum_w=None, w_norm=None, stats=None, shift=0.0, sens=True):
-    """Everything the module docstring lists, from the device's own arrays.  Returns the reference.
-    sum_w None (enqueue-only paths return no statistics: exchange, resident ticks): E cannot be separated from the error of
-    the device's S there, so E is its cap E_MAX and the normalised weights are held against w_ref / S_ref with the bound of S,
-    (K + 1 + X + E) u, added to theirs."""
-    K = len(costs)
-    ref = R.reference(costs, controls, lam, shift)
-    E = R.E_MAX if sum_w is None else 1
-    if w_norm is not None:
-        w_norm = np.asarray(w_norm)
-        if sum_w is not None:
-            w_dev = w_norm * sum_w
-            E = R.measured_exp_ulps(costs, lam, w_dev, shift)
-            assert E <= R.E_MAX, "device exp off by %d ulp" % E
-            assert R.check_weights(costs, lam, w_dev, E, shift) <= 1.0
-        else:
-            w_ref, x, _ = R.weight_errors(costs, lam, w_norm, shift)
-            allowed = (np.abs(x) + 2 * E + 2 + K + 1 + ref.xmax + E) * R.U * (w_ref / ref.S).astype(np.float64)
-            assert np.all(np.abs(w_norm - (w_ref / ref.S).astype(np.float64)) <= np.maximum(allowed, R.TINY * (E + 1)))
-        assert abs(math.fsum(w_norm) - 1.0) <= K * R.U
-    ratio = ref.err_over_bound(u_dev, E)
-    report(group, what, ratio)
-    assert ratio <= 1.0, (what, ratio)
-    if sum_w is not None:
-        assert abs(LD(sum_w) - ref.S) <= ref.bound_S(E)
-    if stats is not None:
-        assert stats.min_cost == costs.min() and stats.max_cost == costs.max() and stats.nonfinite == 0
-        must, may = R.zero_count_range(costs, lam, E, shift)
-        assert must <= stats.n_zero_weight <= may
-        if w_norm is not None and sum_w <= 1.0:     # (w / S cannot underflow where w did not)
-            assert stats.n_zero_weight == int((w_norm == 0).sum())
-    if sens and K >= 64:
-        drop, swap = R.sensitivities(costs, controls, ref, E)
-        assert drop.min() >= 100.0, (what, drop.min())
-        assert np.mean(swap >= 100.0) >= 0.99, (what, np.mean(swap < 100.0))
-    return ref
-
-
-def check_handle(group, what, g, lam, u_dev, st, shift=False, sens=True):
-    c = g.read_costs()
-    return check_update(group, what, c, g.read_controls(), lam, u_dev, st.sum_w, g.read_weights(), st,
-                        shift=float(c.min()) if shift else 0.0, sens=sens)
-
-
 def probe_costs(p, state, xr, yr, yaw0, it, **kw):
     g = MPPIController(p.with_(lam=1.0), **kw)
     g.iterate(state, p.dt, xr, yr, yaw0, SEED, it, want_stats=False)
     c = g.read_costs()
     g.close()
     return c
-
-
-def set_kernel(monkeypatch, kernel):
-    if kernel:
-        monkeypatch.setenv("CCV_MPPI_KERNEL", kernel)
-    else:
-        monkeypatch.delenv("CCV_MPPI_KERNEL", raising=False)
 
 
 def fused_case(monkeypatch, group, kernel, wl, K, H, over=None, handle_kw=None, env=None):
@@ -354,39 +301,6 @@ def test_direct_exchange_two_ranks(wl, K, H, regime):
 
 
 # 6. batch handles ---------------------------------------------------------------------------------------------------------
-def batch_inputs(p, B):
-    x0, xr, yr, yaw0 = (np.zeros((B, p.nstate)), np.zeros((B, p.horizon)), np.zeros((B, p.horizon)), np.zeros(B))
-    paths = [helpers.oracle_path("sinusoid"), helpers.oracle_path("dkan")]
-    for b in range(B):
-        px, py = paths[b % 2]
-        i = 7 * b + 3
-        x0[b, 0], x0[b, 1] = px[i], py[i] + 0.05
-        x0[b, 2] = np.arctan2(py[i + 1] - py[i], px[i + 1] - px[i])
-        xr[b], yr[b], yaw = helpers.oracle_window(p, (px, py), x0[b])
-        yaw0[b] = yaw[0]
-    seeds = np.array([(0x9E3779B97F4A7C15 * (b + 1)) & 0xFFFFFFFFFFFFFFFF for b in range(B)], dtype=np.uint64)
-    return x0, xr, yr, yaw0, seeds
-
-
-def host_controls(p, nominal, seed, it):
-    """The batch binding reads no sample controls back: they are rebuilt on the host from the oracle's Philox restatement,
-    which is bit-exact with the device (test_noise_bit_exact, test_fused_iteration_matches_oracle_philox)."""
-    o = helpers.oracle_for(p)
-    o.set_nominal(nominal)
-    o.sampling(int(seed), rng="philox", iteration=it)
-    return o.get_controls()
-
-
-def lambdas_for(costs_per_instance, varied):
-    """varied: the instances alternate lambda = 1, flat, graded (a leak of one instance's partials into a neighbour's row then
-    shows in the flat neighbour); shared: flat for all"""
-    out = []
-    for b, c in enumerate(costs_per_instance):
-        kind = ("one", "flat", "graded")[b % 3] if varied else "flat"
-        out.append((kind, 1.0 if kind == "one" else R.regime_lambda(c, kind)))
-    return out
-
-
 def check_batch(group, what, bat, plist, kinds, noms, seeds, it, u, stats=None):
     for b, p in enumerate(plist):
         ctl = host_controls(p, noms[b], seeds[b], it)
@@ -398,8 +312,6 @@ def check_batch(group, what, bat, plist, kinds, noms, seeds, it, u, stats=None):
 BATCH = [(None, "diff_drive", 1000, 15, 8), (None, "diff_drive", 63, 17, 3), (None, "steering_diff_drive", 1000, 50, 3),
          (None, "diff_drive", 1000, 15, 1), (None, "full_body", 1000, 15, 3), (None, "full_body", 10000, 15, 3),
          ("v1", "diff_drive", 1000, 15, 3), ("v1", "full_body", 63, 9, 8), ("v1", "steering_diff_drive", 1000, 25, 1)]
-MODEL_DEFAULTS = {"diff_drive": configs.diff_drive_defaults, "steering_diff_drive": configs.steering_defaults,
-                  "full_body": configs.full_body_defaults}
 
 
 @pytest.mark.parametrize("varied", [False, True], ids=["shared", "varied"])
@@ -451,7 +363,7 @@ def test_batch_resident_tick_pair(model, K, H, B, varied):
         i = 7 * b + 3
         s0[b, 0], s0[b, 1] = paths[b][0][i], paths[b][1][i] + 0.05
         s0[b, 2] = np.arctan2(paths[b][1][i + 1] - paths[b][1][i], paths[b][0][i + 1] - paths[b][0][i])
-    seeds = np.array([(0x9E3779B97F4A7C15 * (b + 1)) & 0xFFFFFFFFFFFFFFFF for b in range(B)], dtype=np.uint64)
+    seeds = np.array([instance_seed(b) for b in range(B)], dtype=np.uint64)
 
     def make(params):
         bat = BatchController(params, B)

@@ -7,7 +7,10 @@ import math
 import numpy as np
 import pytest
 
+import batch_support as BS
+import grid_cases as GC
 import grid_reference as GR
+import obstacle_cases as OC
 
 NAN, INF = float("nan"), float("inf")
 
@@ -187,25 +190,22 @@ def test_a_wrong_version_differs_on_some_case(variant):
 # ---- the GPU tests' maps on the oracle's rollouts ---------------------------------------------------------------------------
 def test_the_gpu_tests_maps_meet_their_conditions_on_the_oracles_rollouts():
     """every instance with a map: >= 25 % of the covered states in bounds, >= 5 % out of bounds, >= 50 distinct cells hit"""
-    import test_gpu_batch_grid as TG
-    import test_gpu_batch_obstacles as TO
-    import test_gpu_batch_params as TP
     seen = set()
-    for model, K, H, B, over, fam in TG.CASES + [TG.PLAIN_CASE]:
+    for model, K, H, B, over, fam in GC.CASES + [GC.PLAIN_CASE]:
         K = min(K, 1000)   # (the one-wave case differs from the first in K alone: the fan is the same)
         if (model, K, H, tuple(over.items())) in seen:
             continue
         seen.add((model, K, H, tuple(over.items())))
-        p = TP.MODEL_DEFAULTS[model](K, H)
+        p = BS.MODEL_DEFAULTS[model](K, H)
         if over:
             p = p.with_(**over)
-        inputs = TG.grid_inputs(p, B)
-        maps, map_of, _ = TG.maps_for(p, inputs)
+        inputs = GC.grid_inputs(p, B)
+        maps, map_of, _ = GC.maps_for(p, inputs)
         x0, dt, xr, yr, yaw0, seeds, nom = inputs
         for b in range(B):
             if map_of[b] < 0:
                 continue
-            P = TO.oracle_states(p, x0[b], dt[b], nom[b], seeds[b], 0)
+            P = OC.oracle_states(p, x0[b], dt[b], nom[b], seeds[b], 0)
             share_in, share_out, cells = GR.coverage(maps[map_of[b]], P)
             print("%s K=%d H=%d %s b=%d: in %.2f out %.2f cells %d" % (model, K, H, over, b, share_in, share_out, cells))
             assert share_in >= 0.25 and share_out >= 0.05 and cells >= 50, (model, K, H, over, b, share_in, share_out, cells)

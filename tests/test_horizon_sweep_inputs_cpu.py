@@ -1,6 +1,6 @@
 """The conditions on the inputs of the batch horizon sweep, on the reference alone (no GPU): at every model and horizon of the
 sweep, at its K = 130, the oracle's rollouts give every instance with discs a non-zero reference penalty on 10 % .. 90 % of the
-samples -- static (TO.discs_for, obstacle_reference) and moving (TM.moving_discs_for, moving_obstacle_reference) -- and every
+samples -- static (OC.discs_for, obstacle_reference) and moving (OC.moving_discs_for, moving_obstacle_reference) -- and every
 instance with a map (GR.map_over) at least 25 % of its covered states in bounds, at least 5 % out of bounds and at least 50
 distinct cells hit.  The GPU tests assert the same on the device's own states; this one says the inputs were not tuned on them."""
 import numpy as np
@@ -24,8 +24,8 @@ def test_discs_and_maps_meet_their_conditions_at_every_horizon(model):
             what = (model, H, b)
             assert P.shape == (HI.K, HC.nstates(model, H), 2)
             if len(c.discs[b]):
-                tot, _ = OR.sample_penalty(P, x0[b, :2], c.discs[b], HI.TO.W_OBS)
-                mtot, _ = MR.sample_penalty(P, x0[b, :2], np.arange(P.shape[1]), dt[b], c.mdiscs[b], c.vels[b], HI.TO.W_OBS)
+                tot, _ = OR.sample_penalty(P, x0[b, :2], c.discs[b], HI.OC.W_OBS)
+                mtot, _ = MR.sample_penalty(P, x0[b, :2], np.arange(P.shape[1]), dt[b], c.mdiscs[b], c.vels[b], HI.OC.W_OBS)
                 for frac in (float(np.mean(tot > 0)), float(np.mean(mtot > 0))):
                     assert 0.10 <= frac <= 0.90, (what, frac)
                     worst["lo"], worst["hi"] = min(worst["lo"], frac), max(worst["hi"], frac)
@@ -44,14 +44,14 @@ def test_discs_and_maps_meet_their_conditions_at_every_horizon(model):
 def test_the_salted_case_is_the_one_that_needs_it():
     """steering H = 5 with the default salt: a moving-disc instance every sample of which is penalised (horizon_cases.BATCH_SALT)"""
     assert HC.BATCH_SALT == {("steering_diff_drive", 5): HC.batch_salt("steering_diff_drive", 5)}
-    p = HI.TP.MODEL_DEFAULTS["steering_diff_drive"](HI.K, 5)
-    inputs = HI.TP.instance_inputs(p, HI.B)
+    p = HI.BS.MODEL_DEFAULTS["steering_diff_drive"](HI.K, 5)
+    inputs = HI.BS.instance_inputs(p, HI.B)
     x0, dt, _, _, _, seeds, nom = inputs
-    mdiscs, vels = HI.TM.moving_discs_for(p, inputs, it=HI.IT)
+    mdiscs, vels = HI.OC.moving_discs_for(p, inputs, it=HI.IT)
     fracs = []
     for b in range(HI.B):
         if len(mdiscs[b]):
-            P = HI.TO.oracle_states(p, x0[b], dt[b], nom[b], seeds[b], HI.IT)
-            tot, _ = MR.sample_penalty(P, x0[b, :2], np.arange(P.shape[1]), dt[b], mdiscs[b], vels[b], HI.TO.W_OBS)
+            P = HI.OC.oracle_states(p, x0[b], dt[b], nom[b], seeds[b], HI.IT)
+            tot, _ = MR.sample_penalty(P, x0[b, :2], np.arange(P.shape[1]), dt[b], mdiscs[b], vels[b], HI.OC.W_OBS)
             fracs.append(float(np.mean(tot > 0)))
     assert max(fracs) > 0.90, fracs

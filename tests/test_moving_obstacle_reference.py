@@ -13,12 +13,12 @@ import numpy as np
 import pytest
 
 import moving_obstacle_reference as MR
+import obstacle_cases as OC
 import obstacle_reference as OR
-import test_obstacle_reference as TO
 from ccv_mppi_path_tracker_amd import BatchController, batch, build, capi
 
 LD = np.longdouble
-fma, fmin = TO.fma, TO.fmin
+fma, fmin = OC.fma, OC.fmin
 KTU = 8   # the kernels' block of states
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ccv_mppi.h")
@@ -83,7 +83,7 @@ def scene(n, seed, kmax=14, dt=0.1, still=False):
     for j in range(min(n, 3)):
         for k in (kmax, kmax // 2, 1):
             centre = discs[j, :2] + vel[j] * (k * dt)
-            P += [TO.ring(rng, centre, discs[j, 2], 4, 1e-9), TO.ring(rng, centre, 0.5 * discs[j, 2], 3, 0.1)]
+            P += [OC.ring(rng, centre, discs[j, 2], 4, 1e-9), OC.ring(rng, centre, 0.5 * discs[j, 2], 3, 0.1)]
             ks += [[k] * 4, [k] * 3]
     return x0, discs, vel, np.concatenate(P), np.concatenate(ks).astype(np.int64), dt
 
@@ -127,7 +127,7 @@ def test_zero_velocity_is_the_static_reference_exactly(n):
     assert same_ld(ta[0], tb[0])
     # ... and so is the spec: at = a, bt = b, ct = c exactly
     s_m, c_m = spec(P, ks, x0, dt, discs, vel, 3.0)
-    s_o, c_o = TO.spec(P, x0, discs, 3.0)
+    s_o, c_o = OC.spec(P, x0, discs, 3.0)
     assert s_m.tobytes() == s_o.tobytes() and c_m == c_o
 
 

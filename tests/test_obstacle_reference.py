@@ -2,76 +2,14 @@
 fp64 operation by operation with an exactly rounded fma, lies inside the reference's bounds -- at states within 1e-9 m of a
 disc's edge, 100 m away, for n in {0, 1, 3, 4, 32}, a NaN state and w_obs = 0 -- and seven wrong versions lie outside."""
 import math
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import obstacle_reference as OR
+from obstacle_cases import fma, ring, spec
 
 LD = np.longdouble
-
-
-def fma(a, b, c):
-    """fl(a b + c) with one rounding (Fraction -> float is correctly rounded); non-finite operands as IEEE."""
-    a, b, c = float(a), float(b), float(c)
-    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
-        with np.errstate(invalid="ignore"):
-            return float(np.float64(a) * np.float64(b) + np.float64(c))
-    return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def fmin(a, b):   # IEEE minNum: the number of a number and a NaN
-    return b if a != a else a if b != b else min(a, b)
-
-
-def spec(P, x0, discs, w, wrong=None):
-    """The device spec for states P [T][2] of one sample: (s [T], cost after the T fma's from 0.0)."""
-    discs = np.asarray(discs, dtype=np.float64).reshape(-1, 3)
-    n = discs.shape[0]
-    ab, cc = [], []
-    for ox, oy, r in discs:
-        dx, dy = (ox, oy) if wrong == "pose" else (ox - x0[0], oy - x0[1])
-        k = -1.0 if wrong == "factor2" else -2.0
-        ab.append((k * dx, k * dy))
-        cc.append(fma(dx, dx, dy * dy) - (r if wrong == "r" else r * r))
-    while len(ab) % 4:
-        ab.append((0.0, 0.0))
-        cc.append(0.0 if wrong == "pad0" else math.inf)
-    s_out, cost = [], 0.0
-    for X, Y in np.asarray(P, dtype=np.float64):
-        px, py = float(X - x0[0]), float(Y - x0[1])
-        p2 = fma(px, px, py * py)
-        f = [fma(a, px, fma(b, py, c)) for (a, b), c in zip(ab, cc)]
-        if n == 0:
-            s_out.append(math.inf if px == px and py == py else math.nan)
-            continue
-        if wrong == "sum":
-            g = 0.0
-            for fj in f[:n]:
-                sj = fj + p2
-                g += max(-sj, 0.0) if sj == sj else 0.0
-            s_out.append(math.nan)
-            cost = fma(w, g, cost)
-            continue
-        m = math.inf
-        for fj in f:
-            m = fmin(m, fj)
-        s = m + p2
-        s_out.append(s)
-        if wrong == "outside":
-            g = max(s, 0.0) if s == s and s < math.inf else 0.0
-        else:
-            g = max(-s, 0.0) if s == s else 0.0   # v_max_f64(-s, 0): NaN -> 0
-        cost = fma(w, g, cost)
-    return np.array(s_out), cost
-
-
-def ring(rng, centre, radius, count, eps):
-    """positions at distance radius + eps_i of the centre, eps_i spread over +-eps"""
-    th = rng.uniform(0, 2 * np.pi, count)
-    rr = radius + rng.uniform(-eps, eps, count)
-    return np.stack([centre[0] + rr * np.cos(th), centre[1] + rr * np.sin(th)], axis=1)
 
 
 def scene(n, seed, far=False):

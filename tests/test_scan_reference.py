@@ -237,23 +237,7 @@ def test_scan_cells_cuts_a_ray_beyond_the_reach_along_itself():
 # ---- the obstacle scene of tests/test_gpu_batch_scan.py, on the door's CPU restatement ------------------------------------------------
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import costmap_door_cpu as CD  # noqa: E402
-
-CLEAR_TICK = 20   # the clearing scan is enqueued right after this tick's step
-
-
-def block_scans():
-    """(sensor cell, the marking scan, the clearing scan) of the door's block (tools/costmap_door_cpu.py), seen from the start cell:
-    a hit on every cell of the block; then a miss through every cell of the block -- the ray to 2 c - s passes through c exactly,
-    (2 a_c 2 b_c + 2 a_c) div (4 a_c) = b_c.  The marked layer is the door's patched one, so its CPU restatement applies as it is;
-    the cleared one is the empty layer again."""
-    x0, y0, patch = CD.block_patch()
-    s = (int(np.floor((CD.START[0] - CD.ORIGIN[0]) / CD.RESOLUTION)), int(np.floor((CD.START[1] - CD.ORIGIN[1]) / CD.RESOLUTION)))
-    block = np.array([(x, y) for y in range(y0, y0 + patch.shape[0]) for x in range(x0, x0 + patch.shape[1])], dtype=np.int64)
-    through = 2 * block - np.array(s, dtype=np.int64)
-    marked = SR.apply_scan(CD.empty_layer(), s, block, np.ones(len(block), dtype=np.uint8))
-    assert same(marked, CR.apply_patch(CD.empty_layer(), x0, y0, patch))
-    assert same(SR.apply_scan(marked, s, through, np.zeros(len(block), dtype=np.uint8)), CD.empty_layer())
-    return s, (block, np.ones(len(block), dtype=np.uint8)), (through, np.zeros(len(block), dtype=np.uint8))
+from costmap_support import CLEAR_TICK, block_scans  # noqa: E402
 
 
 def test_the_obstacle_scene_on_the_doors_cpu_restatement():

@@ -38,7 +38,7 @@ for case in range(n_cases):
     p = w.params.with_(num_samples=K, horizon=H, control_noise=float(rng.choice([0.1, 0.5, 1.5])))
     path = helpers.oracle_path(w.path)
     state = np.array(path[0][:1].tolist() + path[1][:1].tolist() + [0.0]) if False else None
-    from test_gpu_parity import start_state  # noqa: E402
+    from resident_loops import start_state  # noqa: E402
     state = start_state(p, path)
     xr, yr, yaw = helpers.oracle_window(p, path, state)
     fb = wl == "C4"
