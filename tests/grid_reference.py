@@ -44,13 +44,42 @@ class Grid:
 
 
 # ---- numpy backend ---------------------------------------------------------------------------------------------------------
-def lookup(g, x, y):
-    """(v float32, in bool, flat cell index or -1) for arrays of states"""
+WRONG_LOOKUPS = ("le_nx", "noge0", "floor", "convfirst")
+
+
+def _wrap32(f):
+    """what a wrapping conversion to a 32-bit integer leaves of the whole number f (NaN, inf: 0)"""
+    with np.errstate(invalid="ignore"):
+        r = np.fmod(f, 2.0 ** 32)   # (exact)
+    i = np.where(np.isfinite(r), r, 0.0).astype(np.int64)
+    return (i + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+
+def lookup(g, x, y, wrong=None):
+    """(v float32, in bool, flat cell index or -1) for arrays of states.  wrong: one mistake, by name -- "le_nx" (f <= n at the
+    upper edge), "noge0" (no f >= 0 test), "floor" (the cell from floor(f) converted to a 32-bit integer, the range test made on
+    the integers), "convfirst" (the same with the truncating conversion: the conversion before the select).  A wrong index
+    stays an index (modulo the number of cells), and a conversion beyond the integers wraps."""
     x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
     with np.errstate(invalid="ignore", over="ignore"):
         fx = (x - g.ox) * g.inv
         fy = (y - g.oy) * g.inv
         inside = (fx >= 0.0) & (fx < float(g.nx)) & (fy >= 0.0) & (fy < float(g.ny))
+    if wrong is not None:
+        assert wrong in WRONG_LOOKUPS, wrong
+        with np.errstate(invalid="ignore", over="ignore"):
+            if wrong in ("floor", "convfirst"):
+                whole = np.floor if wrong == "floor" else np.trunc
+                ix, iy = _wrap32(whole(fx)), _wrap32(whole(fy))
+                inside = (ix >= 0) & (ix < g.nx) & (iy >= 0) & (iy < g.ny)
+            else:
+                lo = np.ones(fx.shape, dtype=bool) if wrong == "noge0" else (fx >= 0.0) & (fy >= 0.0)
+                hi = (fx <= float(g.nx)) & (fy <= float(g.ny)) if wrong == "le_nx" else (fx < float(g.nx)) & (fy < float(g.ny))
+                inside = lo & hi
+                ix, iy = _wrap32(np.trunc(np.where(inside, fx, 0.0))), _wrap32(np.trunc(np.where(inside, fy, 0.0)))
+        idx = (iy * g.nx + ix) % g.cells.size
+        v = np.where(inside, g.cells.reshape(-1)[idx], g.outside).astype(np.float32)
+        return v, inside, np.where(inside, idx, -1)
     ix = np.where(inside, fx, 0.0).astype(np.int64)   # (truncation; exact for 0 <= f < 32 768)
     iy = np.where(inside, fy, 0.0).astype(np.int64)
     idx = iy * g.nx + ix
@@ -58,10 +87,10 @@ def lookup(g, x, y):
     return v, inside, np.where(inside, idx, -1)
 
 
-def grid_sum(g, P):
+def grid_sum(g, P, wrong=None):
     """G [K] for states P [K][n][2] (already cut to the covered states), sequential in state order"""
     P = np.asarray(P, dtype=np.float64)
-    v, _, _ = lookup(g, P[..., 0], P[..., 1])
+    v, _, _ = lookup(g, P[..., 0], P[..., 1], wrong)
     G = np.zeros(P.shape[0], dtype=np.float64)
     for k in range(P.shape[1]):
         G = G + v[:, k].astype(np.float64)

@@ -52,9 +52,10 @@ their squares, the sum and r^2 one each: below 16 * 2^-64 of (|p| + |d| + |v| ta
     a sample's T states and the difference of two runs: obstacle_reference.sample_penalty's and bound_difference's reasoning,
     unchanged (the term adds the same T fma's to the running cost).
 
-They are derived, not tuned.  test_moving_obstacle_reference.py shows a numpy restatement of the spec inside them and seven
-wrong versions outside.
+They are derived, not tuned.  test_moving_obstacle_reference.py shows the numpy restatement of the spec (spec, below) inside
+them and seven wrong versions outside; tests/edge_probe.py holds the device against the same restatement bit for bit.
 """
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -168,6 +169,64 @@ def bound_penalty(P, x0, k, dt, discs, vel, w):
     """|w * device g - penalty| per state; 0 for a NaN position (the device's 0 is exact)."""
     b = float(w) * bound_s(P, x0, k, dt, discs, vel)
     return np.where(np.isnan(b), 0.0, b)
+
+
+KTU = 8   # the kernels' block of states
+
+
+def spec(P, ks, x0, dt, discs, vel, w, wrong=None, parts=False):
+    """The device spec for states P [T][2] of one sample at the global steps ks [T]: (s [T], cost after the T fma's from 0.0);
+    with `parts` (s [T], g [T], cost).  wrong: one mistake, by name -- "sign", "xonly", "cross1", "notau2", "nodt", "late" (tau of
+    k + 1), "early" (tau of k - 1), "local" (k inside the block of eight in place of the global step), "gpos" (g = max(s, 0)),
+    "nanmin" (a minimum that lets a NaN f through)."""
+    fma, fmin = OR.fma, OR.fmin
+    discs = np.asarray(discs, dtype=np.float64).reshape(-1, 3)
+    vel = np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+    n = discs.shape[0]
+    rows = []
+    for (ox, oy, r), (vx, vy) in zip(discs, vel):
+        if wrong == "sign":
+            vx, vy = -vx, -vy
+        if wrong == "xonly":
+            vy = 0.0
+        dx, dy = float(ox - x0[0]), float(oy - x0[1])
+        c = fma(dx, dx, dy * dy) - r * r
+        c1 = (1.0 if wrong == "cross1" else 2.0) * fma(dx, vx, dy * vy)
+        c2 = 0.0 if wrong == "notau2" else fma(vx, vx, vy * vy)
+        rows.append((-2.0 * dx, -2.0 * dy, c, -2.0 * vx, -2.0 * vy, c1, c2))
+    s_out, g_out, cost = [], [], 0.0
+    for (X, Y), k in zip(np.asarray(P, dtype=np.float64), ks):
+        k = int(k)
+        if wrong == "late":
+            k = k + 1
+        if wrong == "early":
+            k = k - 1
+        if wrong == "local":
+            k = k % KTU
+        tau = float(k) if wrong == "nodt" else float(k) * float(dt)
+        px, py = float(X - x0[0]), float(Y - x0[1])
+        p2 = fma(px, px, py * py)
+        if n == 0:
+            s_out.append(math.inf if px == px and py == py else math.nan)
+            g_out.append(0.0)
+            continue
+        m = math.inf
+        for a, b, c, va, vb, c1, c2 in rows:
+            at, bt = fma(va, tau, a), fma(vb, tau, b)
+            ct = fma(fma(c2, tau, c1), tau, c)
+            f = fma(at, px, fma(bt, py, ct))
+            m = OR.nanmin(m, f) if wrong == "nanmin" else fmin(m, f)
+        s = m + p2
+        s_out.append(s)
+        if wrong == "gpos":
+            g = max(s, 0.0) if s == s else 0.0
+        else:
+            g = max(-s, 0.0) if s == s else 0.0   # v_max_f64(-s, 0): NaN -> 0
+        g_out.append(g)
+        cost = fma(w, g, cost)
+    if parts:
+        return np.array(s_out), np.array(g_out), cost
+    return np.array(s_out), cost
 
 
 def sample_penalty(P, x0, k, dt, discs, vel, w, backend=None):

@@ -3,14 +3,15 @@
 The discs are chosen on the CPU from the oracle's Philox rollouts (discs_for, moving_discs_for) so that the conditions the GPU
 tests assert on their inputs hold; check_penalty and check_moving hold cost_on - cost_off of one handle against the penalty
 that tests/obstacle_reference.py and tests/moving_obstacle_reference.py give for the states the device stored.  The last
-part is the numpy restatement of the device spec of the static term (fma, fmin, spec, ring) that the two reference tests share.
+part is the numpy restatement of the device spec of the static term (spec, ring; fma and fmin live in obstacle_reference.py)
+that the two reference tests share and tests/edge_probe.py holds the device against bit for bit; the moving term's restatement
+is moving_obstacle_reference.spec.
 
 Used by tests/test_gpu_batch_obstacles.py and tests/test_gpu_batch_moving.py, which exercise the checkers, by the grid,
 costmap, roll, scan and horizon-sweep tests for their discs, and by tests/horizon_sweep_inputs.py, whose CPU test
 (tests/test_horizon_sweep_inputs_cpu.py) pins the conditions without a GPU.  tests/test_obstacle_reference.py pins spec.
 """
 import math
-from fractions import Fraction
 
 import numpy as np
 
@@ -153,7 +154,7 @@ def moving_discs_for(p, inputs, it=0, ns=NS):
     return discs, vels
 
 
-def check_moving(what, p, x0, dt, discs, vels, w, off, sta, mov):
+def check_moving(what, p, x0, dt, discs, vels, w, off, sta, mov, share=True):
     """states bit-equal; cost_moving - cost_off within the checker's bound of the reference penalty of the read-back states; the
     shares the docstring of tests/test_gpu_batch_moving.py states"""
     assert mov["xy"].tobytes() == off["xy"].tobytes() == sta["xy"].tobytes(), what
@@ -167,7 +168,7 @@ def check_moving(what, p, x0, dt, discs, vels, w, off, sta, mov):
     frac = float(np.mean(tot > 0))
     print("err/bound [moving] %s: %.3g  (share with a penalty %.2f, largest penalty %.3g)" % (what, ratio, frac, float(tot.max())))
     assert np.all(miss <= allowed), (what, ratio)
-    if len(discs) and w > 0:
+    if share and len(discs) and w > 0:
         assert 0.10 <= frac <= 0.90, (what, frac)
         stot, _ = OR.sample_penalty(P, x0[:2], discs, w)
         hit = tot > 0
@@ -178,21 +179,13 @@ def check_moving(what, p, x0, dt, discs, vels, w, off, sta, mov):
 
 # ---- the device spec of the static term, operation by operation -----------------------------------------------------------
 
-def fma(a, b, c):
-    """fl(a b + c) with one rounding (Fraction -> float is correctly rounded); non-finite operands as IEEE."""
-    a, b, c = float(a), float(b), float(c)
-    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
-        with np.errstate(invalid="ignore"):
-            return float(np.float64(a) * np.float64(b) + np.float64(c))
-    return float(Fraction(a) * Fraction(b) + Fraction(c))
+fma, fmin = OR.fma, OR.fmin   # (their home is obstacle_reference.py: the moving spec, which this module imports, needs them too)
 
 
-def fmin(a, b):   # IEEE minNum: the number of a number and a NaN
-    return b if a != a else a if b != b else min(a, b)
-
-
-def spec(P, x0, discs, w, wrong=None):
-    """The device spec for states P [T][2] of one sample: (s [T], cost after the T fma's from 0.0)."""
+def spec(P, x0, discs, w, wrong=None, parts=False):
+    """The device spec for states P [T][2] of one sample: (s [T], cost after the T fma's from 0.0); with `parts`
+    (s [T], g [T], cost).  wrong: one mistake, by name -- "pose", "factor2", "r", "pad0", "sum", "outside" (pinned by
+    tests/test_obstacle_reference.py), "gpos" (g = max(s, 0)), "nanmin" (a minimum that lets a NaN f through)."""
     discs = np.asarray(discs, dtype=np.float64).reshape(-1, 3)
     n = discs.shape[0]
     ab, cc = [], []
@@ -204,13 +197,14 @@ def spec(P, x0, discs, w, wrong=None):
     while len(ab) % 4:
         ab.append((0.0, 0.0))
         cc.append(0.0 if wrong == "pad0" else math.inf)
-    s_out, cost = [], 0.0
+    s_out, g_out, cost = [], [], 0.0
     for X, Y in np.asarray(P, dtype=np.float64):
         px, py = float(X - x0[0]), float(Y - x0[1])
         p2 = fma(px, px, py * py)
         f = [fma(a, px, fma(b, py, c)) for (a, b), c in zip(ab, cc)]
         if n == 0:
             s_out.append(math.inf if px == px and py == py else math.nan)
+            g_out.append(0.0)
             continue
         if wrong == "sum":
             g = 0.0
@@ -218,18 +212,24 @@ def spec(P, x0, discs, w, wrong=None):
                 sj = fj + p2
                 g += max(-sj, 0.0) if sj == sj else 0.0
             s_out.append(math.nan)
+            g_out.append(g)
             cost = fma(w, g, cost)
             continue
         m = math.inf
         for fj in f:
-            m = fmin(m, fj)
+            m = OR.nanmin(m, fj) if wrong == "nanmin" else fmin(m, fj)
         s = m + p2
         s_out.append(s)
         if wrong == "outside":
             g = max(s, 0.0) if s == s and s < math.inf else 0.0
+        elif wrong == "gpos":
+            g = max(s, 0.0) if s == s else 0.0
         else:
             g = max(-s, 0.0) if s == s else 0.0   # v_max_f64(-s, 0): NaN -> 0
+        g_out.append(g)
         cost = fma(w, g, cost)
+    if parts:
+        return np.array(s_out), np.array(g_out), cost
     return np.array(s_out), cost
 
 

@@ -50,6 +50,7 @@ differs from the real sum of its rounded terms by at most N u cost, and
 They are derived, not tuned.  test_obstacle_reference.py shows a numpy restatement of the spec inside them and seven wrong
 versions outside.
 """
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -65,6 +66,56 @@ REF_ULPS = 12   # longdouble: two differences, two squares, two sums, the subtra
 def _discs(discs):
     d = np.zeros((0, 3)) if discs is None else np.asarray(discs, dtype=np.float64)
     return d.reshape(-1, 3)
+
+
+# ---- the two operations the device specs of the disc terms are written in (obstacle_cases.spec, moving_obstacle_reference.spec)
+
+def fma_rational(a, b, c):
+    """fl(a b + c) with one rounding (Fraction -> float is correctly rounded); non-finite operands, and a sum beyond the
+    largest double, as IEEE.  An exact zero is +0.0."""
+    a, b, c = float(a), float(b), float(c)
+    if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return float(np.float64(a) * np.float64(b) + np.float64(c))
+    r = Fraction(a) * Fraction(b) + Fraction(c)
+    try:
+        return float(r)
+    except OverflowError:
+        return math.inf if r > 0 else -math.inf
+
+
+_SPLIT = 134217729.0   # 2^27 + 1 (Veltkamp)
+
+
+def fma(a, b, c):
+    """fma_rational's value, faster: the product as an unevaluated sum of two doubles (Dekker), then math.fsum, which rounds
+    the exact sum of its three terms once.  Factors far from 1 (the splitting could overflow or the product's low part
+    underflow) and non-finite operands go to fma_rational.  tests/test_edge_probe_cpu.py holds the two together."""
+    a, b, c = float(a), float(b), float(c)
+    if a == 0.0 or b == 0.0:
+        return c + 0.0 if math.isfinite(a) and math.isfinite(b) else fma_rational(a, b, c)
+    if not (1e-100 < abs(a) < 1e100 and 1e-100 < abs(b) < 1e100 and math.isfinite(c)):
+        return fma_rational(a, b, c)
+    p = a * b
+    t = _SPLIT * a
+    ah = t - (t - a)
+    al = a - ah
+    t = _SPLIT * b
+    bh = t - (t - b)
+    bl = b - bh
+    try:
+        r = math.fsum((p, ((ah * bh - p) + ah * bl + al * bh) + al * bl, c))
+    except OverflowError:
+        return fma_rational(a, b, c)
+    return r if r != 0.0 else 0.0
+
+
+def fmin(a, b):   # IEEE minNum: the number of a number and a NaN
+    return b if a != a else a if b != b else min(a, b)
+
+
+def nanmin(a, b):   # a wrong version's minimum: a NaN operand goes through
+    return math.nan if (a != a or b != b) else min(a, b)
 
 
 def power(P, discs, backend=None):

@@ -1,4 +1,4 @@
-"""Pins tests/moving_obstacle_reference.py: a numpy restatement of the device spec of the moving-disc term (DESIGN.md section
+"""Pins tests/moving_obstacle_reference.py: its numpy restatement of the device spec of the moving-disc term (DESIGN.md section
 10g), fp64 operation by operation with an exactly rounded fma, lies inside the reference's bounds -- at states within 1e-9 m of
 a moving disc's edge, tau at step 127, v = 0, n in {0, 1, 3, 4, 32}, a NaN state -- and seven wrong versions lie outside; with
 v = 0 the reference is obstacle_reference's, exactly.  And the CPU side of the interface: the new names declared, exported,
@@ -18,8 +18,7 @@ import obstacle_reference as OR
 from ccv_mppi_path_tracker_amd import BatchController, batch, build, capi
 
 LD = np.longdouble
-fma, fmin = OC.fma, OC.fmin
-KTU = 8   # the kernels' block of states
+spec = MR.spec
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ccv_mppi.h")
 MOVING = {"ccv_mppi_batch_set_obstacle_velocities", "ccv_mppi_batch_get_obstacle_velocities"}
@@ -27,47 +26,6 @@ MOVING = {"ccv_mppi_batch_set_obstacle_velocities", "ccv_mppi_batch_get_obstacle
 
 def same_ld(a, b):   # (the bytes of a longdouble include padding)
     return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
-
-
-def spec(P, ks, x0, dt, discs, vel, w, wrong=None):
-    """The device spec for states P [T][2] of one sample at the global steps ks [T]: (s [T], cost after the T fma's from 0.0)."""
-    discs = np.asarray(discs, dtype=np.float64).reshape(-1, 3)
-    vel = np.asarray(vel, dtype=np.float64).reshape(-1, 2)
-    n = discs.shape[0]
-    rows = []
-    for (ox, oy, r), (vx, vy) in zip(discs, vel):
-        if wrong == "sign":
-            vx, vy = -vx, -vy
-        if wrong == "xonly":
-            vy = 0.0
-        dx, dy = float(ox - x0[0]), float(oy - x0[1])
-        c = fma(dx, dx, dy * dy) - r * r
-        c1 = (1.0 if wrong == "cross1" else 2.0) * fma(dx, vx, dy * vy)
-        c2 = 0.0 if wrong == "notau2" else fma(vx, vx, vy * vy)
-        rows.append((-2.0 * dx, -2.0 * dy, c, -2.0 * vx, -2.0 * vy, c1, c2))
-    s_out, cost = [], 0.0
-    for (X, Y), k in zip(np.asarray(P, dtype=np.float64), ks):
-        k = int(k)
-        if wrong == "late":
-            k = k + 1
-        if wrong == "local":
-            k = k % KTU
-        tau = float(k) if wrong == "nodt" else float(k) * float(dt)
-        px, py = float(X - x0[0]), float(Y - x0[1])
-        p2 = fma(px, px, py * py)
-        if n == 0:
-            s_out.append(math.inf if px == px and py == py else math.nan)
-            continue
-        m = math.inf
-        for a, b, c, va, vb, c1, c2 in rows:
-            at, bt = fma(va, tau, a), fma(vb, tau, b)
-            ct = fma(fma(c2, tau, c1), tau, c)
-            m = fmin(m, fma(at, px, fma(bt, py, ct)))
-        s = m + p2
-        s_out.append(s)
-        g = max(-s, 0.0) if s == s else 0.0   # v_max_f64(-s, 0): NaN -> 0
-        cost = fma(w, g, cost)
-    return np.array(s_out), cost
 
 
 def scene(n, seed, kmax=14, dt=0.1, still=False):
