@@ -143,6 +143,17 @@ def scan_cells(geometry, sensor_xy, sensor_yaw, ranges, angle_min, angle_increme
     return (sx, sy), ends, np.ascontiguousarray(hits & ~far, dtype=np.uint8)
 
 
+def beam_fan(n, reach_cells, phase=0.0):
+    """The beam table of BatchController.resident_sense for a sensor that looks all round: int32 [n][2], beam k's end offset
+    (rint(reach_cells * cos(t)), rint(reach_cells * sin(t))) with t = phase + 2 pi k / n -- the rint of a circle's points, so no
+    component exceeds reach_cells in magnitude.  ValueError unless n >= 1 and 0 <= reach_cells <= capi.SCAN_MAX_REACH."""
+    n, reach = int(n), float(reach_cells)
+    if n < 1 or not 0.0 <= reach <= capi.SCAN_MAX_REACH:
+        raise ValueError("beam_fan: need n >= 1 and 0 <= reach_cells <= %d" % capi.SCAN_MAX_REACH)
+    t = float(phase) + 2.0 * np.pi * np.arange(n, dtype=np.float64) / n
+    return np.ascontiguousarray(np.stack([np.rint(reach * np.cos(t)), np.rint(reach * np.sin(t))], axis=1), dtype=np.int32)
+
+
 def inflation_profile(radius_m, resolution, kind="linear", lethal=1.0, inscribed=None, inscribed_m=0.0, free_value=0.0, scaling=10.0):
     """(R, profile float32 [R * R + 1], free_value) for BatchController.set_occupancy: the cost of a cell by the squared distance
     D2, in cells, from its centre to the centre of the nearest occupied cell, built on the host -- the device only looks it up.
@@ -467,6 +478,77 @@ class BatchController:
         out = np.empty((ny, nx), dtype=np.uint8)
         self._check(self.lib.ccv_mppi_batch_read_occupancy(self._h, int(map), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ---- range sensors simulated on the device (ccv_mppi_batch_set_world, _resident_sense_enqueue) ----
+    def set_world(self, cells, threshold=1, origin=(0.0, 0.0), resolution=1.0, anchors=None, max_beams=capi.SENSE_MAX_BEAMS):
+        """The ground-truth world the resident robots' beams are cast through: cells [ny][nx] uint8 (occupied: >= threshold),
+        or None: no world.  anchors [n_maps][2] int32: the world cell that coincided with each occupancy map's cell (0, 0) when
+        set_occupancy was called (the maps must have the world's resolution bit for bit).  max_beams: the most beams a
+        resident_sense call may carry.  Needs set_occupancy; a later set_occupancy or set_grids drops the world.  Flushes a
+        pending resident update."""
+        if cells is None:
+            self._check(self.lib.ccv_mppi_batch_set_world(self._h, None, None, 0))
+            return
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        if cells.ndim != 2:
+            raise ValueError("set_world: cells must be [ny][nx]")
+        anchors = np.ascontiguousarray(np.asarray(anchors, dtype=np.int32).reshape(-1, 2))
+        n_maps = len(self.get_occupancy())
+        if n_maps and len(anchors) != n_maps:
+            raise ValueError("set_world: expected %d anchors, got %d" % (n_maps, len(anchors)))
+        row = capi.Occupancy(float(origin[0]), float(origin[1]), float(resolution), 0.0, cells.shape[1], cells.shape[0], int(threshold),
+                             cells.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._check(self.lib.ccv_mppi_batch_set_world(self._h, C.byref(row), anchors.ctypes.data_as(C.POINTER(C.c_int32)), int(max_beams)))
+
+    def get_world(self):
+        """((origin_x, origin_y), resolution, nx, ny, threshold, anchors int32 [n_maps][2], max_beams) as the library holds
+        them; MPPIError (capi.ERR_STATE) while no world is set."""
+        row, mb = capi.Occupancy(), C.c_int32(0)
+        n_maps = len(self.get_occupancy())
+        anchors = np.zeros((n_maps, 2), dtype=np.int32)
+        self._check(self.lib.ccv_mppi_batch_get_world(self._h, C.byref(row), anchors.ctypes.data_as(C.POINTER(C.c_int32)), n_maps, C.byref(mb)))
+        return (row.origin_x, row.origin_y), row.resolution, row.nx, row.ny, row.threshold, anchors, mb.value
+
+    def read_world(self):
+        """cells [ny][nx] uint8 of the world, read back from the device; synchronises."""
+        row = capi.Occupancy()
+        self._check(self.lib.ccv_mppi_batch_get_world(self._h, C.byref(row), None, 0, None))
+        out = np.empty((row.ny, row.nx), dtype=np.uint8)
+        self._check(self.lib.ccv_mppi_batch_read_world(self._h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def update_world(self, x0, y0, patch2d):
+        """The world's cells [y0 : y0 + h, x0 : x0 + w] become patch2d [h][w] uint8, in stream order: a resident_sense enqueued
+        before this call reads the old world, every one enqueued after it the new one.  No synchronisation."""
+        patch = np.ascontiguousarray(patch2d, dtype=np.uint8)
+        if patch.ndim != 2:
+            raise ValueError("patch2d must be [h][w]")
+        self._check(self.lib.ccv_mppi_batch_update_world_enqueue(self._h, int(x0), int(y0), patch.shape[1], patch.shape[0],
+                                                                  patch.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def resident_sense(self, instances, beams, clear=0, mark=255):
+        """The instances `instances` (each at most once, each on a map of its own) sense, in stream order and in two launches for
+        all of them: from the world cell its resident pose lies in, each casts the beams `beams` int32 [n][2] (end offsets in
+        cells, world-aligned: beam_fan) through the world.  A beam clears its map's cells up to the first occupied world cell
+        and marks that cell, or clears up to its end cell and marks nothing; marks come after all clears; the float cells are
+        what set_occupancy of the new layer would derive.  A robot outside the world senses nothing.  No synchronisation; the
+        arguments may be reused when the call returns."""
+        inst = np.ascontiguousarray(np.atleast_1d(instances), dtype=np.int32)
+        beams = np.ascontiguousarray(np.asarray(beams, dtype=np.int32).reshape(-1, 2))
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ccv_mppi_batch_resident_sense_enqueue(self._h, len(inst), inst.ctypes.data_as(ip), len(beams), beams.ctypes.data_as(ip),
+                                                                    int(clear), int(mark)))
+
+    def resident_read_sense(self):
+        """(first int32 [B][max_beams], sensor_cell int32 [B][2]): per instance the blocked cell index of every beam of its last
+        sensing (-1: not blocked, or nothing sensed) and the world cell it sensed from ((-1, -1): nothing sensed); synchronises."""
+        mb = C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_get_world(self._h, None, None, 0, C.byref(mb)))
+        first = np.empty((self.B, mb.value), dtype=np.int32)
+        cell = np.empty((self.B, 2), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ccv_mppi_batch_resident_read_sense(self._h, first.ctypes.data_as(ip), cell.ctypes.data_as(ip)))
+        return first, cell
 
     # ---- warm starts [B][H-1][u_dim] ----
     def set_nominal(self, u):

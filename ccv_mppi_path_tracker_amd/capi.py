@@ -1,5 +1,5 @@
 """ctypes binding of libccv_mppi_hip.so -- exactly the symbols include/ccv_mppi.h and
-include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
+include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES) and include/ccv_mppi_sense.h (SENSE_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
 if the library is missing it is built with hipcc, and if that fails the import raises.
 """
 import ctypes as C
@@ -36,6 +36,8 @@ OCC_PATCH_MAX_CELLS = 1 << 20
 OCC_PATCH_SLOTS = 4
 SCAN_MAX_REACH = 4096
 SCAN_RAY_BYTES, SCAN_ENTRY_BYTES = 9, 128   # of a staging slot (OCC_PATCH_MAX_CELLS bytes) per ray, and per entry that has rays
+SENSE_MAX_BEAMS = 4096
+SENSE_BEAM_BYTES, SENSE_ENTRY_BYTES = 8, 112   # of a staging slot per beam of ccv_mppi_batch_resident_sense_enqueue, and per entry
 BEST_MAX = 1024
 BATCH_TRACE_ROWS = 1024
 
@@ -158,6 +160,10 @@ SIGNATURES = {
                                                         C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32, C.c_int32]),
     "ccv_mppi_batch_get_occupancy": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(Inflation), C.c_int32, C.POINTER(C.c_int32)]),
     "ccv_mppi_batch_read_occupancy": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint8)]),
+    "ccv_mppi_batch_set_world": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(C.c_int32), C.c_int32]),
+    "ccv_mppi_batch_get_world": (C.c_int, [_H, C.POINTER(Occupancy), C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "ccv_mppi_batch_read_world": (C.c_int, [_H, C.POINTER(C.c_uint8)]),
+    "ccv_mppi_batch_update_world_enqueue": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "ccv_mppi_batch_iterate": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64, _dp,
                                          C.POINTER(Stats)]),
     "ccv_mppi_batch_iterate_enqueue": (C.c_int, [_H, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64), C.c_uint64]),
@@ -211,6 +217,12 @@ FLEET_SIGNATURES = {
     "ccv_mppi_batch_resident_read_fleet": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
 }
 
+# include/ccv_mppi_sense.h: the simulated range sensor of the resident loop, a table of its own like its header
+SENSE_SIGNATURES = {
+    "ccv_mppi_batch_resident_sense_enqueue": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
+    "ccv_mppi_batch_resident_read_sense": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+}
+
 _lib = None
 
 
@@ -222,7 +234,7 @@ def load():
         if not os.path.exists(path):
             raise ImportError("libccv_mppi_hip.so is missing and could not be built; there is no CPU fallback")
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError = the .so does not export what the header declares
             fn.restype = res
             fn.argtypes = args

@@ -224,6 +224,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     bh->Discs::release();
     bh->Grids::release();
     bh->Costmap::release();
+    bh->World::release();
     bh->Fleet::release();
     delete bh;
     return CCV_MPPI_OK;

@@ -1,13 +1,15 @@
 // C ABI, batch handles: the maps of the grid term -- a caller's float cells (ccv_mppi_batch_set_grids) or costmaps derived on the
 // device from occupancy layers (_set_occupancy; mppi_costmap.h), and what changes those layers in stream order: patches, rolls
-// and range scans (struct ccv_mppi_batch and its parts Grids and Costmap: capi_internal.h).  Two shapes.  The setters have
+// and range scans, and the simulated range sensor with its world (struct ccv_mppi_batch and its parts Grids, Costmap and World:
+// capi_internal.h).  Two shapes.  The setters have
 // capi_batch_config.hip's: validate (every check before anything changes), quiesce, commit the host-side state, sync_tables.
-// The three *_enqueue calls: validate, take a slot of the staging ring, fill it, launch, seal it -- no flush of the deferred
+// The *_enqueue calls: validate, take a slot of the staging ring, fill it, launch, seal it -- no flush of the deferred
 // resident update (it reads no map), no allocation after the handle's first roll, no wait but for the launches that last read the slot.
 #include "capi_internal.h"
 #include "mppi_costmap_rects.h"
 #include "mppi_costmap_roll.h"
 #include "mppi_costmap_scan.h"
+#include "mppi_costmap_sense.h"
 
 namespace {
 
@@ -38,6 +40,7 @@ int maps_off(ccv_mppi_batch* bh) {
     if (bh->d_grid_cells) HIP_TRY(bh, hipFree(bh->d_grid_cells));
     bh->d_grid_cells = nullptr;
     bh->drop_layers();
+    bh->drop_world();   // (the anchors spoke of the old layers)
     bh->grid = false;
     bh->grid_maps.clear();
     bh->grid_offset.clear();
@@ -184,6 +187,7 @@ int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int3
     for (ccv_mppi_grid& g : geo) g.cells = nullptr;
     if (int rc = install_maps(bh, geo, cells, offset, map_of, weight)) return rc;
     bh->drop_layers();   // (the cells are the caller's now)
+    bh->drop_world();   // (the anchors spoke of the old layers)
     return sync_tables(bh);
 }
 
@@ -279,6 +283,7 @@ int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* bh, const ccv_mppi_occupancy* m
         return rc;
     }
     bh->drop_layers();
+    bh->drop_world();   // (the anchors spoke of the old layers)
     bh->d_occ = layers;
     bh->d_profile = profiles;
     bh->layers.swap(recs);
@@ -482,6 +487,193 @@ int ccv_mppi_batch_scan_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     launch_scan_trace(reinterpret_cast<const ScanEntry*>(slot.device), (int32_t)traced, bh->stream);
     launch_inflate_rects(reinterpret_cast<const InflateArgs*>(slot.device + entry_bytes), (int32_t)traced, max_tiles, bh->stream);
     return slot_seal(bh, slot, hipGetLastError());   // (after the second launch: both read the slot)
+}
+
+// ---- the simulated range sensor: a ground-truth world, and the resident robots' beams cast through it (mppi_costmap_sense.h) ----
+
+int ccv_mppi_batch_set_world(ccv_mppi_batch* bh, const ccv_mppi_occupancy* world, const int32_t* anchor_xy, int32_t max_beams) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "set_world: ";
+    if (!world) {
+        if (!bh->world) return CCV_MPPI_OK;
+        const DeviceGuard guard(bh->cfg.device);
+        if (int rc = quiesce(bh)) return rc;   // (a queued sensing may still read the world and write the read-back)
+        bh->drop_world();
+        return CCV_MPPI_OK;
+    }
+    // every check comes before anything changes
+    if (!bh->occ) return fail(bh, CCV_MPPI_ERR_STATE, "set_world: no occupancy is set (ccv_mppi_batch_set_occupancy)");
+    if (!world->cells || !anchor_xy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (const char* fault = geometry_fault(world->nx, world->ny, world->resolution, world->origin_x, world->origin_y, 0.0f)) return refuse(bh, who, fault);
+    if (world->threshold < 0 || world->threshold > 255) return refuse(bh, who, "a threshold outside [0, 255]");
+    if (max_beams < 1 || max_beams > CCV_MPPI_SENSE_MAX_BEAMS) return refuse(bh, who, "max_beams outside [1, CCV_MPPI_SENSE_MAX_BEAMS]");
+    const size_t n_maps = bh->grid_maps.size();
+    constexpr int32_t kMaxAnchor = 1 << 29;
+    for (size_t i = 0; i < 2 * n_maps; ++i)
+        if (anchor_xy[i] < -kMaxAnchor || anchor_xy[i] > kMaxAnchor) return refuse(bh, who, "an anchor beyond 2^29 cells");
+    const DeviceGuard guard(bh->cfg.device);
+    if (int rc = quiesce(bh)) return rc;
+    // the world, the read-back and the rectangle table: four allocations, filled before the old ones go
+    const size_t cells = (size_t)world->nx * (size_t)world->ny, first_bytes = (size_t)bh->B * (size_t)max_beams * sizeof(int32_t);
+    const size_t cell_bytes = (size_t)bh->B * 2 * sizeof(int32_t);
+    uint8_t* layer = nullptr;
+    int32_t *first = nullptr, *sensor = nullptr;
+    InflateArgs* rects = nullptr;
+    hipError_t e = hipMalloc(&layer, cells);
+    if (e == hipSuccess) e = hipMalloc(&first, first_bytes);
+    if (e == hipSuccess) e = hipMalloc(&sensor, cell_bytes);
+    if (e == hipSuccess) e = hipMalloc(&rects, (size_t)bh->B * sizeof(InflateArgs));
+    if (e == hipSuccess) e = hipMemcpy(layer, world->cells, cells, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(first, 0xFF, first_bytes, bh->stream);   // (-1: no beam blocked, nothing sensed)
+    if (e == hipSuccess) e = hipMemsetAsync(sensor, 0xFF, cell_bytes, bh->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(rects, 0, (size_t)bh->B * sizeof(InflateArgs), bh->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(bh->stream);
+    if (e != hipSuccess) {
+        free_device({layer, first, sensor, rects});
+        return fail(bh, CCV_MPPI_ERR_HIP, "set_world: allocating or copying the world", e);
+    }
+    bh->drop_world();
+    bh->d_world = layer;
+    bh->d_sense_first = first;
+    bh->d_sense_cell = sensor;
+    bh->d_sense_rects = rects;
+    bh->world_geo = *world;
+    bh->world_geo.cells = nullptr;
+    bh->world_anchor.assign(anchor_xy, anchor_xy + 2 * n_maps);
+    bh->world_max_beams = max_beams;
+    bh->world = true;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_get_world(ccv_mppi_batch* bh, ccv_mppi_occupancy* world, int32_t* anchor_xy, int32_t max_maps, int32_t* max_beams) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!bh->world) return fail(bh, CCV_MPPI_ERR_STATE, "get_world: no world is set (ccv_mppi_batch_set_world)");
+    if (anchor_xy && (max_maps < 0 || (size_t)max_maps < bh->grid_maps.size())) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_world: max_maps below the number of maps");
+    if (world) *world = bh->world_geo;
+    if (anchor_xy) std::memcpy(anchor_xy, bh->world_anchor.data(), bh->world_anchor.size() * sizeof(int32_t));
+    if (max_beams) *max_beams = bh->world_max_beams;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_read_world(ccv_mppi_batch* bh, uint8_t* out) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!out) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->world) return fail(bh, CCV_MPPI_ERR_STATE, "read_world: no world is set (ccv_mppi_batch_set_world)");
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (queued patch writers)
+    HIP_TRY(bh, hipMemcpy(out, bh->d_world, (size_t)bh->world_geo.nx * (size_t)bh->world_geo.ny, hipMemcpyDeviceToHost));
+    return CCV_MPPI_OK;
+}
+
+// One launch: the patch writer on the world layer.  Nothing is derived from the world; the next sensing reads the new cells.
+int ccv_mppi_batch_update_world_enqueue(ccv_mppi_batch* bh, int32_t x0, int32_t y0, int32_t w, int32_t h, const uint8_t* patch) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "update_world: ";
+    if (!bh->world) return fail(bh, CCV_MPPI_ERR_STATE, "update_world: no world is set (ccv_mppi_batch_set_world)");
+    if (!patch) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    const ccv_mppi_occupancy& g = bh->world_geo;
+    if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > g.nx - x0 || h > g.ny - y0) return refuse(bh, who, "the rectangle is not inside the world");
+    if ((int64_t)w * h > CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "more than CCV_MPPI_OCC_PATCH_MAX_CELLS cells");
+    Slot slot;
+    if (int rc = slot_take(bh, slot)) return rc;
+    std::memcpy(slot.host, patch, (size_t)w * (size_t)h);
+    launch_occupancy_patch(bh->d_world, g.nx, slot.device, x0, y0, w, h, bh->stream);
+    return slot_seal(bh, slot, hipGetLastError());
+}
+
+// Two launches however many robots sense: the beams (k_sense_trace, which also writes the rectangles into device memory) and
+// the inflation of those rectangles.  The poses are the device's: nothing here reads one.
+int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const int32_t* instance, int32_t n_beams, const int32_t* beam_xy,
+                                          int32_t clear_value, int32_t mark_value) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    static const char who[] = "resident_sense: ";
+    // every check comes first, then the next slot of the ring
+    if (!bh->world) return fail(bh, CCV_MPPI_ERR_STATE, "resident_sense: no world is set (ccv_mppi_batch_set_world)");
+    if (!bh->have_paths || !bh->have_poses) return fail(bh, CCV_MPPI_ERR_STATE, "resident_sense: ccv_mppi_batch_resident_set_paths and _set_poses first");
+    if (!instance || !beam_xy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (n < 1 || n > bh->B) return refuse(bh, who, "n outside [1, B]");
+    if (n_beams < 1 || n_beams > bh->world_max_beams) return refuse(bh, who, "n_beams outside [1, max_beams]");
+    if (clear_value < 0 || clear_value > 255 || mark_value < 0 || mark_value > 255) return refuse(bh, who, "clear_value or mark_value outside [0, 255]");
+    const size_t entry_bytes = (size_t)n * sizeof(SenseEntry), beam_bytes = (size_t)n_beams * 2 * sizeof(int32_t);
+    if (entry_bytes + beam_bytes > (size_t)CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "entries and beams above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
+    constexpr int64_t kMaxOffset = (int64_t)1 << 30;
+    std::vector<uint8_t> named_b((size_t)bh->B, 0), named_m(bh->grid_maps.size(), 0);
+    for (int i = 0; i < n; ++i) {
+        const int b = instance[i];
+        if (b < 0 || b >= bh->B) return refuse(bh, who, "instance out of range");
+        if (named_b[(size_t)b]) return refuse(bh, who, "an instance is named twice");
+        named_b[(size_t)b] = 1;
+        const int m = bh->grid_map_of[(size_t)b];
+        if (m < 0) return refuse(bh, who, "an instance without a map");
+        if (named_m[(size_t)m]) return refuse(bh, who, "two named instances on one map");
+        named_m[(size_t)m] = 1;
+        if (std::memcmp(&bh->grid_maps[(size_t)m].resolution, &bh->world_geo.resolution, sizeof(double)) != 0)
+            return refuse(bh, who, "a map's resolution differs from the world's");
+        const Costmap::Layer& l = bh->layers[(size_t)m];
+        const int64_t ox = bh->world_anchor[2 * (size_t)m] + l.cx, oy = bh->world_anchor[2 * (size_t)m + 1] + l.cy;
+        if (ox < -kMaxOffset || ox > kMaxOffset || oy < -kMaxOffset || oy > kMaxOffset) return refuse(bh, who, "a frame offset beyond 2^30 cells");
+    }
+    SenseArgs A{};
+    // (the extent of the beam table starts from the offset (0, 0): the box holds the sensor cell and every end cell)
+    for (int r = 0; r < n_beams; ++r) {
+        const int32_t dx = beam_xy[2 * (size_t)r], dy = beam_xy[2 * (size_t)r + 1];
+        if (dx < -CCV_MPPI_SCAN_MAX_REACH || dx > CCV_MPPI_SCAN_MAX_REACH || dy < -CCV_MPPI_SCAN_MAX_REACH || dy > CCV_MPPI_SCAN_MAX_REACH)
+            return refuse(bh, who, "a reach above CCV_MPPI_SCAN_MAX_REACH");
+        A.min_dx = std::min(A.min_dx, dx);
+        A.max_dx = std::max(A.max_dx, dx);
+        A.min_dy = std::min(A.min_dy, dy);
+        A.max_dy = std::max(A.max_dy, dy);
+    }
+    Slot slot;
+    if (int rc = slot_take(bh, slot)) return rc;
+    // the slot: the entries, the beams (the kernel reads both in place)
+    SenseEntry* entries = reinterpret_cast<SenseEntry*>(slot.host);
+    std::memcpy(slot.host + entry_bytes, beam_xy, beam_bytes);
+    const ccv_mppi_occupancy& w = bh->world_geo;
+    A.world = bh->d_world;
+    A.beam_xy = reinterpret_cast<const int32_t*>(slot.device + entry_bytes);
+    A.origin_x = w.origin_x;
+    A.origin_y = w.origin_y;
+    A.inv = 1.0 / w.resolution;
+    A.wnx = w.nx;
+    A.wny = w.ny;
+    A.threshold = w.threshold;
+    A.n_beams = n_beams;
+    A.clear_value = clear_value;
+    A.mark_value = mark_value;
+    const int32_t span_x = A.max_dx - A.min_dx + 1, span_y = A.max_dy - A.min_dy + 1;
+    int32_t max_tiles = 1;
+    for (int i = 0; i < n; ++i) {
+        const int b = instance[i], m = bh->grid_map_of[(size_t)b];
+        const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
+        const Costmap::Layer& l = bh->layers[(size_t)m];
+        SenseEntry& e = entries[i];
+        e.rect = inflate_args(bh, m, Rect{0, 0, 0, 0});
+        e.layer = layer_of(bh, m);
+        e.pose = bh->d_rframe[b].x0;   // (an address: the host reads no pose)
+        e.first = bh->d_sense_first + (size_t)b * (size_t)bh->world_max_beams;
+        e.sensor_cell = bh->d_sense_cell + 2 * (size_t)b;
+        e.off_x = (int32_t)(bh->world_anchor[2 * (size_t)m] + l.cx);
+        e.off_y = (int32_t)(bh->world_anchor[2 * (size_t)m + 1] + l.cy);
+        e.pad[0] = e.pad[1] = 0;
+        // the largest rectangle the device can form: the box clipped to the map, grown by R and clipped again
+        max_tiles = std::max(max_tiles, inflate_tiles(std::min(g.nx, span_x + 2 * l.radius), std::min(g.ny, span_y + 2 * l.radius)));
+    }
+    launch_sense_trace(reinterpret_cast<const SenseEntry*>(slot.device), bh->d_sense_rects, n, A, bh->stream);
+    launch_inflate_rects(bh->d_sense_rects, n, max_tiles, bh->stream);
+    return slot_seal(bh, slot, hipGetLastError());   // (after the second launch; only the first reads the slot)
+}
+
+int ccv_mppi_batch_resident_read_sense(ccv_mppi_batch* bh, int32_t* first, int32_t* sensor_cell) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!bh->world) return fail(bh, CCV_MPPI_ERR_STATE, "resident_read_sense: no world is set (ccv_mppi_batch_set_world)");
+    const DeviceGuard guard(bh->cfg.device);
+    HIP_TRY(bh, hipSetDevice(bh->cfg.device));
+    HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (queued sensings)
+    if (first) HIP_TRY(bh, hipMemcpy(first, bh->d_sense_first, (size_t)bh->B * (size_t)bh->world_max_beams * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sensor_cell) HIP_TRY(bh, hipMemcpy(sensor_cell, bh->d_sense_cell, (size_t)bh->B * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* bh, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps) {

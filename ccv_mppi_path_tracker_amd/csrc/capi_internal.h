@@ -311,6 +311,32 @@ struct Costmap {
     }
 };
 
+// the simulated range sensor (ccv_mppi_batch_set_world / _resident_sense_enqueue, mppi_costmap_sense.h): one ground-truth occupancy
+// map the resident robots' beams are cast through, the anchors that tie the occupancy layers' frames to it, and the read-back of
+// the last sensing per instance.  Lives from _set_world to _set_world(NULL), the next _set_occupancy or _set_grids (the anchors
+// speak of those layers) or destroy.
+struct InflateArgs;
+struct World {
+    bool world = false;
+    ccv_mppi_occupancy world_geo = {};       // the world's geometry and threshold (cells: null)
+    uint8_t* d_world = nullptr;              // [ny][nx]
+    int32_t* d_sense_first = nullptr;        // [B][world_max_beams]: the blocked cell of every beam, -1 without
+    int32_t* d_sense_cell = nullptr;         // [B][2]: the robots' world cells, (-1, -1) for one that sensed nothing
+    InflateArgs* d_sense_rects = nullptr;    // [B]: the rectangles k_sense_trace writes and k_inflate_rects reads
+    std::vector<int32_t> world_anchor;       // [n_maps][2]: the world cell of the map's cell (0, 0) at _set_occupancy
+    int32_t world_max_beams = 0;
+    void drop_world() {
+        free_device({d_world, d_sense_first, d_sense_cell, d_sense_rects});
+        d_world = nullptr;
+        d_sense_first = d_sense_cell = nullptr;
+        d_sense_rects = nullptr;
+        world_anchor.clear();
+        world_max_beams = 0;
+        world = false;
+    }
+    void release() { free_device({d_world, d_sense_first, d_sense_cell, d_sense_rects}); }
+};
+
 // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
 // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
 // the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance).
@@ -336,7 +362,7 @@ struct Fleet {
 // batch_view): the core of a single handle, whose K is the instance's and whose
 // pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
 // one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
-struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, Fleet {
+struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, World, Fleet {
     int B = 0, kpad = 0;
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)

@@ -496,6 +496,62 @@ int ccv_mppi_batch_scan_occupancy_enqueue(ccv_mppi_batch* b, int32_t n, const in
                                           int32_t clear_value, int32_t mark_value);
 int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* b, ccv_mppi_occupancy* maps, ccv_mppi_inflation* inflation, int32_t max_maps, int32_t* n_maps);
 int ccv_mppi_batch_read_occupancy(ccv_mppi_batch* b, int32_t map, uint8_t* out);
+/* Range sensors simulated on the device (NOT reference behaviour; off until called; batch handles and resident steps only).  The
+ * handle holds one ground-truth world map with the geometry of ccv_mppi_occupancy (origin, resolution, nx, ny, threshold, uint8
+ * cells; `outside` is not read): a world cell is occupied when cells >= threshold, a cell outside the world is not occupied.  The
+ * world is read by the sensor only and is never a cost term.  Every costmap that is sensed into must have the world's resolution
+ * bit for bit; per map the caller states an anchor (ax, ay), the world cell that coincided with the map's cell (0, 0) when
+ * _set_occupancy was called.  With (cx, cy) the cells the map has rolled since then, the map's cell (0, 0) is the world cell
+ * (ax + cx, ay + cy) at call time and local cell = world cell - that offset: no floating point enters the frame change, and the
+ * caller answers for the anchor being true (the grid term goes on using the map's own origin).
+ * _resident_sense_enqueue: the n named instances (instance [n], each at most once, no two on one map, 1 <= n <= B) sense.  The
+ * pose of instance b is its resident pose as the stream finds it -- the pose _resident_read would return at that point, which is
+ * the pose the last enqueued tick rolled out from.  Its world cell is the grid term's formula against the world:
+ *     inv = 1.0 / resolution                                  (rounded once, on the host)
+ *     fx  = (x - origin_x) * inv,  fy = (y - origin_y) * inv    (one subtraction, one multiplication, no FMA)
+ *     in  = fx >= 0 && fx < nx && fy >= 0 && fy < ny           (fp64 compares: false for NaN)
+ *     s   = ((int)fx, (int)fy)
+ * A robot that is not `in` (outside the world, or a NaN pose) senses nothing: no cell of its map changes and its rectangle is
+ * empty.  beam_xy [n_beams][2] holds the end offsets (dx, dy) of the beams in cells, |dx|, |dy| <= CCV_MPPI_SCAN_MAX_REACH,
+ * world-aligned and shared by all entries (1 <= n_beams <= max_beams).  Beam r of a robot at world cell s runs along
+ * _scan_occupancy_enqueue's line from s to e = s + (dx, dy); its cells are i = 0 .. a by the same closed form, cell a being the
+ * end cell.  Integers only:
+ *     f = min { i in [1, a] : cell i lies inside the world and is occupied }          (the sensor's own cell is not tested)
+ *     f exists:  the local cells of i in [0, f) = clear_value,  local cell f = mark_value     (after ALL clears of that map)
+ *     otherwise: the local cells of i in [0, a) = clear_value,  nothing is marked
+ * The cleared cells are a prefix of the beam's own line, not the line re-traced to cell f.  Local cells outside the map are
+ * skipped, never wrapped; the sensor's local cell may lie outside its map.  clear_value and mark_value are per call, each in
+ * [0, 255].  After the call the layer and the float cells of every sensed map are, in every bit, what a fresh _set_occupancy of
+ * the new layer would produce: per entry one rectangle is derived again -- the box s_local + [min dx, max dx] x [min dy, max dy]
+ * clipped to the map, grown by R and clipped again, min and max taken over the beam table and the offset (0, 0), so that the
+ * box holds the sensor cell and every end cell.  Stream-ordered like the three _occupancy_enqueue calls: no synchronisation,
+ * no allocation, no flush of a pending resident update; every array may be reused when the call returns; two kernel launches
+ * however many robots sense.  Beams and entry table share one slot of the patches' ring: 8 bytes per beam and 112 bytes per
+ * entry must not exceed CCV_MPPI_OCC_PATCH_MAX_CELLS bytes.  No world set, or no resident poses set: CCV_MPPI_ERR_STATE.  n or
+ * n_beams out of range, an instance out of range or named twice, an instance without a map, two named instances on one map
+ * (split the call: a later call's marks win over an earlier call's clears), a map whose resolution differs from the world's, an
+ * offset ax + cx or ay + cy beyond +-2^30, a reach above the limit, a value outside [0, 255], a call that does not fit a slot,
+ * NULL arrays: CCV_MPPI_ERR_INVALID_ARG.  Nothing changes either way.
+ * _resident_read_sense: the simulated scan itself.  first [B][max_beams] int32: f of beam r of instance b's last sensing, or -1
+ * where the beam was not blocked or the robot sensed nothing (-1 everywhere before an instance's first sensing and past the
+ * beams of its last call); sensor_cell [B][2]: the robot's world cell, or (-1, -1) where it sensed nothing.  Only the rows of
+ * instances named by a call are written.  Synchronises, as _read_occupancy does; either pointer may be NULL.
+ * _set_world: world (cells copied) and anchor_xy [n_maps][2] for the maps of _set_occupancy, max_beams in
+ * [1, CCV_MPPI_SENSE_MAX_BEAMS]; a setter like _set_occupancy: flushes a pending resident update and synchronises.  No occupancy
+ * set: CCV_MPPI_ERR_STATE.  A size out of range, a non-finite origin or resolution, a threshold outside [0, 255], max_beams out
+ * of range, NULL cells or anchors, an anchor beyond +-2^29: CCV_MPPI_ERR_INVALID_ARG.  world == NULL drops the world; so do a
+ * later _set_occupancy and _set_grids (the anchors speak of those layers) and destroy; the other setters keep it.
+ * _get_world: the geometry (cells NULL), anchor_xy [max_maps][2] and *max_beams; any may be NULL; CCV_MPPI_ERR_STATE while no
+ * world is set; max_maps below the number of maps with anchor_xy != NULL: CCV_MPPI_ERR_INVALID_ARG.
+ * _read_world: out [ny * nx], the world read back from the device; synchronises.
+ * _update_world_enqueue: the w x h rectangle at cell (x0, y0) of the world becomes `patch`, in stream order and in one launch,
+ * with the refusals of _update_occupancy_enqueue: the ground truth can change under a running fleet (a door closes). */
+#define CCV_MPPI_SENSE_MAX_BEAMS 4096     /* beams of one ccv_mppi_batch_resident_sense_enqueue */
+int ccv_mppi_batch_set_world(ccv_mppi_batch* b, const ccv_mppi_occupancy* world, const int32_t* anchor_xy /*[n_maps][2]*/, int32_t max_beams);
+int ccv_mppi_batch_get_world(ccv_mppi_batch* b, ccv_mppi_occupancy* world /*cells NULL*/, int32_t* anchor_xy, int32_t max_maps, int32_t* max_beams);
+int ccv_mppi_batch_read_world(ccv_mppi_batch* b, uint8_t* out);
+int ccv_mppi_batch_update_world_enqueue(ccv_mppi_batch* b, int32_t x0, int32_t y0, int32_t w, int32_t h, const uint8_t* patch);
+/* (ccv_mppi_batch_resident_sense_enqueue and ccv_mppi_batch_resident_read_sense are declared in ccv_mppi_sense.h, included below.) */
 /* x0 [B][5] (x, y, yaw[, roll, pitch]; unused entries ignored), dt [B], x_ref / y_ref [B][H], yaw_ref0 [B], seed [B];
  * u_opt_out [B][(H-1)][u_dim]; stats [B] or NULL.  Blocking: the result arrives through the pinned mailbox, B * (R + 4) slots. */
 int ccv_mppi_batch_iterate(ccv_mppi_batch* b, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
@@ -571,4 +627,5 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int3
 }
 #endif
 #include "ccv_mppi_fleet.h"
+#include "ccv_mppi_sense.h"
 #endif /* CCV_MPPI_H_ */
