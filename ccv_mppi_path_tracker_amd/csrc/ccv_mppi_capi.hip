@@ -752,7 +752,7 @@ int ccv_mppi_create(const ccv_mppi_config* cfg, ccv_mppi_handle** out) {
         const int v = std::atoi(pv);
         h->prio_rotate = v == 0 ? 0 : (((v >= 2 && v <= 5) || (v >= 16 && v < 16 + 256)) && h->stagewise == KernelFamily::FourWave) ? v : h->prio_rotate;
     }
-    // CCV_MPPI_PRUNE=0/1 forces the window pruning (experiments; results do not depend on it, tested)
+    // CCV_MPPI_PRUNE=0/1 forces the window pruning (experiments; results do not depend on it: tests/test_gpu_prune_edges.py)
     if (const char* pv = std::getenv("CCV_MPPI_PRUNE")) h->prune = std::strcmp(pv, "0") != 0;
     if (const char* pv = std::getenv("CCV_MPPI_FAST_CLAMP")) h->fast_clamp_allowed = std::strcmp(pv, "0") != 0;
 

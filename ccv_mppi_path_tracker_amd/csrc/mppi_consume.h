@@ -92,6 +92,8 @@ __device__ __forceinline__ void pc_prune_window(const RolloutArgs& A, const SH& 
         ok[k] = at != 0ull;
         const int r = ok[k] ? __builtin_ctzll(at) : 0;
         jr[k] = r + (int)((upper[k] >> r) & 1ull) * 64;
+        // (every valid lane NaN and the padding's +inf the minimum: jr = H, the padding -- for H a multiple of 4 below 64 the entry
+        //  after it, which stage_window does not write; such a window is beyond fp32's range, every d^2 ends at the gate: DESIGN 13)
         abr[k] = sh.ab[jr[k]];   // wave-uniform address: broadcast reads, all four in flight together
         cr[k] = sh.c[jr[k]];
     }
