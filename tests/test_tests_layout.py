@@ -1,8 +1,9 @@
 """CPU tests of the layout of tests/: what tests share lives in plain modules (batch_support.py, update_checks.py, ...), never in
 a test module.  No file of tests/ or tools/ imports a test_*.py module; no plain module of tests/ defines a test or a fixture
 (pytest would not collect the one nor find the other); the plain modules' imports of each other form no cycle, so any of them
-imports alone; and batch_support.instance_seed gives the values of the two spellings it replaced.  Sources are read as text and
-ASTs; nothing of the GPU side is touched."""
+imports alone; and batch_support.instance_seed gives the values of the two spellings it replaced.  The bench tools of tools/ are
+held the same way: none imports a *_bench module, what they share is tools/bench_support.py, which imports no other file of tools/
+and reaches torch only inside functions.  Sources are read as text and ASTs; nothing of the GPU side is touched."""
 import ast
 import glob
 import os
@@ -48,6 +49,22 @@ def test_no_file_imports_a_test_module():
     bad = [(os.path.relpath(f, ROOT), line, mod) for f in sorted(files) for mod, line in _imported(_tree(f))
            if mod.split(".")[-1].startswith("test_")]
     assert not bad, bad
+
+
+def test_no_tool_imports_a_bench_tool_and_bench_support_imports_no_tool():
+    tools = sorted(glob.glob(os.path.join(ROOT, "tools", "*.py")))
+    names = {os.path.basename(f)[:-3] for f in tools}
+    assert "bench_support" in names and len([n for n in names if n.endswith("_bench")]) == 13
+    bad = [(os.path.relpath(f, ROOT), line, mod) for f in tools for mod, line in _imported(_tree(f))
+           if mod.split(".")[-1].endswith("_bench")]
+    assert not bad, bad
+    support = _tree(os.path.join(ROOT, "tools", "bench_support.py"))
+    assert not [mod for mod, _ in _imported(support) if mod.split(".")[0] in names]
+    # (torch only inside functions: nothing that runs when the module is imported reaches it)
+    in_function = {id(n) for f in ast.walk(support) if isinstance(f, (ast.FunctionDef, ast.AsyncFunctionDef)) for n in ast.walk(f)}
+    torch_lines = [(line, id(n) in in_function) for n in ast.walk(support) if isinstance(n, (ast.Import, ast.ImportFrom))
+                   for mod, line in _imported(n) if mod.split(".")[0] == "torch"]
+    assert torch_lines and all(inside for _, inside in torch_lines), torch_lines
 
 
 def test_plain_modules_define_no_test_and_no_fixture():

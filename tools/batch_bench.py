@@ -11,50 +11,20 @@ For every configuration (model, K, H, B): B instances on poses along the model's
   mailbox_blocking_us / copy_blocking_us   the blocking call with the result forced through the pinned mailbox
                       (CCV_MPPI_BATCH_MAIL=1) or through one copy + stream synchronisation (CCV_MPPI_MAILBOX=0): the
                       batch handle takes the mailbox only up to a single handle's largest one
-Batch and singles alternate round by round (--rounds), so that both see the same clock and the same neighbours.  The C2-shaped
+Batch and singles alternate round by round (--rounds): the method of tools/bench_support.py.  The C2-shaped
 batch (B = 64 x K = 1 024, H = 50) is compared with the 65 536-sample single handle too (c2_single_kernel_us).  One JSON
 document goes to stdout (and --out)."""
-import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bench_support as bs  # noqa: E402  (puts the repository root on sys.path)
 import ccv_mppi_path_tracker_amd as amd  # noqa: E402
 from ccv_mppi_path_tracker_amd import configs  # noqa: E402
-
-PATH_OF = {"diff_drive": "sinusoid", "steering_diff_drive": "sinusoid", "full_body": "dkan"}
-
-
-def inputs(p, B):
-    px, py = amd.make_path(PATH_OF[p.model])
-    nx = p.nstate
-    x0, xr, yr = np.zeros((B, nx)), np.zeros((B, p.horizon)), np.zeros((B, p.horizon))
-    dt, yaw0 = np.zeros(B), np.zeros(B)
-    for b in range(B):
-        i = (13 * b) % (len(px) // 2)
-        x0[b, 0], x0[b, 1] = px[i], py[i] + 0.02 * ((b % 5) - 2)
-        x0[b, 2] = np.arctan2(py[i + 1] - py[i], px[i + 1] - px[i])
-        dt[b] = p.dt * (1.0 + 0.02 * (b % 3))
-        _, xr[b], yr[b], yaw = amd.calc_ref_path(px, py, x0[b, 0], x0[b, 1], p.v_ref, dt[b], p.resolution, p.horizon)
-        yaw0[b] = yaw[0]
-    seeds = np.arange(1, B + 1, dtype=np.uint64) * np.uint64(7919)
-    return x0, dt, xr, yr, yaw0, seeds
-
-
-def kernel_times(h, step, n):
-    """mean rollout-kernel and launch-sequence us over n timed iterations (h: a batch or a single handle)"""
-    h.timing_enable(True)
-    for i in range(n):
-        step(i)
-    roll, tot, cnt = h.timing_read()
-    h.timing_enable(False)
-    return roll / cnt, tot / cnt
 
 
 def blocking_with(env, p, B, ins, iters, warmup):
@@ -80,7 +50,7 @@ def blocking_with(env, p, B, ins, iters, warmup):
 
 
 def measure(p, B, iters, rounds, warmup):
-    x0, dt, xr, yr, yaw0, seeds = inputs(p, B)
+    x0, dt, xr, yr, yaw0, seeds = bs.inputs(p, B)
     bat = amd.BatchController(p, B)
     singles = [amd.MPPIController(p) for _ in range(B)]
     it = [0]
@@ -96,16 +66,16 @@ def measure(p, B, iters, rounds, warmup):
         bat.iterate(x0, dt, xr, yr, yaw0, seeds, 0, want_stats=False)
         for b, g in enumerate(singles):
             g.iterate(x0[b], dt[b], xr[b], yr[b], yaw0[b], int(seeds[b]), 0, want_stats=False)
-    res = {"model": p.model, "K": p.num_samples, "H": p.horizon, "B": B}
+    res = bs.shape(p, B)
     bk, bi, sk, bb, sb = [], [], [], [], []
     for _r in range(rounds):
-        k, t = kernel_times(bat, bstep, iters)
+        k, t = bs.launch_us(bat, bstep, iters)
         bk.append(k)
         bi.append(t)
         tk = 0.0
         n_single = max(8, iters // B)
         for b, g in enumerate(singles):
-            tk += kernel_times(g, sstep(g, b), n_single)[0]
+            tk += bs.launch_us(g, sstep(g, b), n_single)[0]
         sk.append(tk)
         t0 = time.perf_counter()
         for i in range(iters):
@@ -133,19 +103,12 @@ def measure(p, B, iters, rounds, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=256, help="timed launches per round (>= 256 for the kernel figure)")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import torch
-    props = torch.cuda.get_device_properties(0)
+    args = bs.parser(None, iters=256).parse_args()
     plan = [(configs.diff_drive_defaults(1000, 15), B) for B in (1, 8, 64, 256)] + \
            [(configs.steering_defaults(10000, 15), B) for B in (1, 4, 16)] + \
            [(configs.full_body_defaults(10000, 15), B) for B in (1, 4, 16)] + \
            [(configs.workload("C2").params.with_(num_samples=1024), 64)]
-    out = {"device": props.name, "cus": props.multi_processor_count, "configs": []}
+    out = {**bs.header(), "configs": []}
     for p, B in plan:
         r = measure(p, B, args.iters, args.rounds, args.warmup)
         out["configs"].append(r)
@@ -154,22 +117,17 @@ def main():
             r["singles_blocking_us"], r["mailbox_blocking_us"], r["copy_blocking_us"]), file=sys.stderr, flush=True)
     # the C2-shaped batch against the 65 536-sample single handle of C2
     p = configs.workload("C2").params
-    x0, dt, xr, yr, yaw0, seeds = inputs(p, 1)
+    x0, dt, xr, yr, yaw0, seeds = bs.inputs(p, 1)
     g = amd.MPPIController(p)
     for _ in range(args.warmup):
         g.iterate(x0[0], dt[0], xr[0], yr[0], yaw0[0], 1, 0, want_stats=False)
-    ks = [kernel_times(g, lambda i: g.iterate_enqueue(x0[0], dt[0], xr[0], yr[0], yaw0[0], 1, i), args.iters)[0]
+    ks = [bs.launch_us(g, lambda i: g.iterate_enqueue(x0[0], dt[0], xr[0], yr[0], yaw0[0], 1, i), args.iters)[0]
           for _ in range(args.rounds)]
     out["c2_single_kernel_us"] = float(np.median(ks))
     out["c2_single_kernel_us_per_round"] = ks
     g.close()
     print("C2 single handle K=65536: kernel %.2f us" % out["c2_single_kernel_us"], file=sys.stderr)
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    bs.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -16,34 +16,19 @@ Per B:
 `single_large`: one instance of K = 65 536 (one workgroup selects among all of them: the design point is many small instances),
 N = 100, after a host-record tick: `best_us`, `best_nopaths_us`, and `read_costs_us`, one read_costs of all K for scale.
 Every figure is recorded; none is asserted.  One JSON document goes to stdout (and --out)."""
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bench_support as bs  # noqa: E402  (puts the repository root on sys.path)
 import ccv_mppi_path_tracker_amd as amd  # noqa: E402
 from ccv_mppi_path_tracker_amd import configs  # noqa: E402
-from batch_obstacles_bench import fleet  # noqa: E402
 
 BATCHES = (1, 64, 1024)
 COUNTS = (1, 10, 100)
-
-
-def stats(v):
-    return {"median": float(np.median(v)), "rounds": [float(x) for x in v]}
-
-
-def timed(fn):
-    t0 = time.perf_counter()
-    out = fn()
-    return (time.perf_counter() - t0) * 1e6, out
 
 
 def parent_best(h, n):
@@ -70,9 +55,8 @@ def parent_paths(h, p, poses, dt):
 
 
 def one_batch(p, B, rounds, ticks, warmup):
-    import torch
-    paths, s0, seeds = fleet(p, B)
-    stream = torch.cuda.Stream()
+    paths, s0, seeds = bs.fleet(p, B)
+    stream = bs.new_stream()
     h = amd.BatchController(p, B)
     h.set_stream(stream.cuda_stream)
     h.resident_set_paths(paths)
@@ -84,24 +68,24 @@ def one_batch(p, B, rounds, ticks, warmup):
     for n in COUNTS:
         new, lean, old = [], [], []
         for _ in range(rounds):
-            t, got = timed(lambda: h.read_best_candidates(n))
+            t, got = bs.wall_us(lambda: h.read_best_candidates(n))
             new.append(t)
-            lean.append(timed(lambda: h.read_best_candidates(n, with_paths=False))[0])
-            t, want = timed(lambda: parent_best(h, n))
+            lean.append(bs.wall_us(lambda: h.read_best_candidates(n, with_paths=False))[0])
+            t, want = bs.wall_us(lambda: parent_best(h, n))
             old.append(t)
             assert all(a.tobytes() == b.tobytes() for a, b in zip(got, want))
-        out["counts"].append({"N": n, "best_us": stats(new), "best_nopaths_us": stats(lean), "parent_best_us": stats(old)})
+        out["counts"].append({"N": n, "best_us": bs.stats(new), "best_nopaths_us": bs.stats(lean), "parent_best_us": bs.stats(old)})
         print("B=%4d N=%3d: best %.1f us (no paths %.1f), parent's route %.1f us" % (B, n, np.median(new), np.median(lean), np.median(old)),
               file=sys.stderr, flush=True)
     poses = h.resident_read()[0]
     new, old = [], []
     for _ in range(rounds):
-        t, got = timed(h.read_optimal_paths)
+        t, got = bs.wall_us(h.read_optimal_paths)
         new.append(t)
-        t, want = timed(lambda: parent_paths(h, p, poses, p.dt))
+        t, want = bs.wall_us(lambda: parent_paths(h, p, poses, p.dt))
         old.append(t)
         assert got.tobytes() == want.tobytes()
-    out["paths_us"], out["parent_paths_us"] = stats(new), stats(old)
+    out["paths_us"], out["parent_paths_us"] = bs.stats(new), bs.stats(old)
     period = {False: [], True: []}
     for _ in range(rounds):
         for feed in (False, True):
@@ -109,16 +93,14 @@ def one_batch(p, B, rounds, ticks, warmup):
             for i in range(warmup):
                 h.resident_step_enqueue(p.dt, i, advance=i > 0)
             h.synchronize()
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record(stream)
-            for i in range(ticks):
+
+            def tick(i):
                 h.resident_step_enqueue(p.dt, warmup + i)
                 if feed:
                     h.read_best_candidates(10, with_paths=False)
-            stop.record(stream)
-            stop.synchronize()
-            period[feed].append(start.elapsed_time(stop) * 1e3 / ticks)
-    out["tick_us"], out["tick_best_us"] = stats(period[False]), stats(period[True])
+
+            period[feed].append(bs.tick_us(stream, ticks, tick))
+    out["tick_us"], out["tick_best_us"] = bs.stats(period[False]), bs.stats(period[True])
     print("B=%4d: optimal paths %.1f us, parent's route %.1f us; resident tick %.2f us, with best candidates every tick %.2f us"
           % (B, np.median(new), np.median(old), np.median(period[False]), np.median(period[True])), file=sys.stderr, flush=True)
     h.close()
@@ -136,33 +118,21 @@ def single_large(rounds):
     h.read_best_candidates(100)   # (warm-up: the scratch buffer)
     new, lean, costs = [], [], []
     for _ in range(rounds):
-        new.append(timed(lambda: h.read_best_candidates(100))[0])
-        lean.append(timed(lambda: h.read_best_candidates(100, with_paths=False))[0])
-        costs.append(timed(lambda: h.read_costs(0))[0])
+        new.append(bs.wall_us(lambda: h.read_best_candidates(100))[0])
+        lean.append(bs.wall_us(lambda: h.read_best_candidates(100, with_paths=False))[0])
+        costs.append(bs.wall_us(lambda: h.read_costs(0))[0])
     h.close()
     print("B=1 K=65536 N=100: best %.1f us (no paths %.1f), one read_costs of all K %.1f us" % (np.median(new), np.median(lean), np.median(costs)),
           file=sys.stderr, flush=True)
-    return {"B": 1, "K": 65536, "N": 100, "best_us": stats(new), "best_nopaths_us": stats(lean), "read_costs_us": stats(costs)}
+    return {"B": 1, "K": 65536, "N": 100, "best_us": bs.stats(new), "best_nopaths_us": bs.stats(lean), "read_costs_us": bs.stats(costs)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--ticks", type=int, default=256)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_feed_bench.json"))
-    args = ap.parse_args()
-    import torch
-    props = torch.cuda.get_device_properties(0)
+    args = bs.parser("batch_feed_bench.json", ticks=256, rounds=5).parse_args()
     p = configs.diff_drive_defaults(1000, 15)
-    out = {"device": props.name, "cus": props.multi_processor_count, "model": p.model, "K": p.num_samples, "H": p.horizon,
-           "rounds": args.rounds, "ticks": args.ticks, "batches": [one_batch(p, B, args.rounds, args.ticks, args.warmup) for B in BATCHES], "single_large": single_large(args.rounds)}
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    out = {**bs.header(), "model": p.model, "K": p.num_samples, "H": p.horizon, "rounds": args.rounds, "ticks": args.ticks,
+           "batches": [one_batch(p, B, args.rounds, args.ticks, args.warmup) for B in BATCHES], "single_large": single_large(args.rounds)}
+    bs.emit(out, args.out)
 
 
 if __name__ == "__main__":

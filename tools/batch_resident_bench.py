@@ -8,50 +8,24 @@ For every configuration (model, K, H, B), each instance on its own path (even b 
   host_prologue_us      (c) the batch with the prologue on the host: calc_ref_path + plant_step per instance, then one
                         blocking BatchController.iterate
 per tick, from device events on the stream every handle runs on, over --ticks (>= 256) ticks after --warmup ticks from the
-start poses; the three alternate round by round (--rounds), the median is reported.  host_nonfinite_ticks counts the host
+start poses; the three alternate round by round (--rounds), the median is reported (the method of tools/bench_support.py,
+the three legs in the place of one handle's modes).  host_nonfinite_ticks counts the host
 leg's instance-ticks whose command was not finite (the pose is then held: ccv_mppi_plant_step refuses it).  One JSON document
 goes to stdout (and --out, by default profiles/batch_resident_bench.json)."""
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bench_support as bs  # noqa: E402  (puts the repository root on sys.path)
 import ccv_mppi_path_tracker_amd as amd  # noqa: E402
 from ccv_mppi_path_tracker_amd import configs  # noqa: E402
 
 
-def paths_and_poses(p, B):
-    kinds = [amd.make_path("sinusoid", length=40.0), amd.make_path("dkan")]   # (a round's ticks stay on the path)
-    paths = [kinds[b % 2] for b in range(B)]
-    s0 = np.zeros((B, p.nstate))
-    for b in range(B):
-        px, py = paths[b]
-        i = (13 * b) % (len(px) // 4)
-        s0[b, 0], s0[b, 1] = px[i], py[i] + 0.02 * ((b % 5) - 2)
-        s0[b, 2] = np.arctan2(py[i + 1] - py[i], px[i + 1] - px[i])
-    seeds = np.arange(1, B + 1, dtype=np.uint64) * np.uint64(7919)
-    return paths, s0, seeds
-
-
-def timed(stream, ticks, tick):
-    """us per tick by device events around `ticks` calls of tick(i) on `stream`"""
-    import torch
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record(stream)
-    for i in range(ticks):
-        tick(i)
-    stop.record(stream)
-    stop.synchronize()
-    return start.elapsed_time(stop) * 1e3 / ticks
-
-
 def measure(p, B, ticks, rounds, warmup, stream):
-    paths, s0, seeds = paths_and_poses(p, B)
+    paths, s0, seeds = bs.fleet(p, B)
     sp = stream.cuda_stream
     # (a) the batched resident loop
     res = amd.BatchController(p, B)
@@ -117,9 +91,9 @@ def measure(p, B, ticks, rounds, warmup, stream):
             for i in range(warmup):   # (clocks up, code objects loaded, pools settled)
                 tick(i)
             stream.synchronize()
-            per_round[k].append(timed(stream, ticks, tick))
+            per_round[k].append(bs.tick_us(stream, ticks, tick))
             stream.synchronize()
-    out = {"model": p.model, "K": p.num_samples, "H": p.horizon, "B": B, "kernel": res.last_kernel(), "rounds": rounds,
+    out = {**bs.shape(p, B), "kernel": res.last_kernel(), "rounds": rounds,
            "ticks_per_round": ticks, "host_nonfinite_ticks": state["nonfinite"], "per_round": per_round}
     for k, v in per_round.items():
         out[k] = float(np.median(v))
@@ -131,31 +105,19 @@ def measure(p, B, ticks, rounds, warmup, stream):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--ticks", type=int, default=256, help="timed ticks per round and leg (>= 256)")
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_resident_bench.json"))
-    args = ap.parse_args()
-    import torch
-    props = torch.cuda.get_device_properties(0)
-    stream = torch.cuda.Stream()
+    args = bs.parser("batch_resident_bench.json", ticks=256).parse_args()
+    out = {**bs.header(), "configs": []}
+    stream = bs.new_stream()
     plan = [(configs.diff_drive_defaults(1000, 15), B) for B in (1, 8, 64, 256)] + \
            [(configs.steering_defaults(10000, 15), B) for B in (1, 4, 16)] + \
            [(configs.full_body_defaults(10000, 15), B) for B in (1, 4, 16)]
-    out = {"device": props.name, "cus": props.multi_processor_count, "configs": []}
     for p, B in plan:
         r = measure(p, B, args.ticks, args.rounds, args.warmup, stream)
         out["configs"].append(r)
         print("%-20s K=%6d H=%3d B=%4d  resident batch %8.2f us/tick  %d single resident handles %9.2f  host prologue %9.2f" % (
             p.model, p.num_samples, p.horizon, B, r["resident_batch_us"], B, r["resident_singles_us"], r["host_prologue_us"]),
             file=sys.stderr, flush=True)
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    bs.emit(out, args.out)
 
 
 if __name__ == "__main__":

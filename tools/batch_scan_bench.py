@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Scan tracing (ccv_mppi_batch_scan_occupancy_enqueue) against what a caller of the parent commit has to do
-with a range scan: `python tools/batch_scan_bench.py [--out FILE]` (default profiles/batch_scan_bench.json).  The method of
-tools/batch_roll_bench.py: medians of --rounds rounds beside the max - min of the baseline's rounds.
+with a range scan: `python tools/batch_scan_bench.py [--out FILE]` (default profiles/batch_scan_bench.json).  The method and the
+resident loop (its costmap form) are those of tools/bench_support.py.
 
 Resident tick, diff drive K = 1 000, H = 15, B = 64, one 200 x 200 map per robot, R = 6: `none`, no map change; `scan`, all 64
 maps scanned with 360 rays each from the map's centre after every tick, in one call (ends and hits prepared beforehand: what is
@@ -12,24 +12,17 @@ of the same loop; `scan_call_us`, the host time of one scan call of the 64 maps 
 One 4 000 x 3 000 map at R = 6 with 2 000 rays of reach about 600 in one entry -- one workgroup traces them all: `scan_ms`, the
 wall time of the call and a synchronisation, and `scan_kernels_us`, the two launches between two events.  One JSON document goes
 to stdout (and --out)."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import bench_support as bs  # noqa: E402  (puts the repository root on sys.path)
 import ccv_mppi_path_tracker_amd as amd  # noqa: E402
-from ccv_mppi_path_tracker_amd import batch, capi, configs  # noqa: E402
-from batch_costmap_bench import layer, stats  # noqa: E402
-from batch_obstacles_bench import fleet  # noqa: E402
+from ccv_mppi_path_tracker_amd import capi, configs  # noqa: E402
 
 RESOLUTION = 0.05
 W_GRID = 0.01
@@ -48,7 +41,9 @@ def scan_of(sensor, n, lo, hi, seed):
 
 
 def trace_host(cells, sensor, ends, hits, clear=0, mark=255):
-    """the call's spec with numpy, all rays of an entry at once, in place -> the bounding box (x0, y0, w, h) of what it touched"""
+    """the call's spec with numpy, all rays of an entry at once, in place -> the bounding box (x0, y0, w, h) of what it touched.
+    The closed form and the box are those of tests/scan_reference.py (ray_cells, scan_box), which takes one ray at a time: this
+    is the vectorised form a caller of the parent would write, and its cost is what mode `host_trace` charges."""
     ny, nx = cells.shape
     d = ends.astype(np.int64) - np.asarray(sensor, dtype=np.int64)
     ad = np.abs(d)
@@ -76,13 +71,10 @@ def raw_scan(h, maps, sensors, n_rays, end_xy, hit):
 
 
 def resident_tick(ticks, rounds, warmup):
-    import torch
-    p, B, n = configs.diff_drive_defaults(1000, 15), 64, TICK_N
-    paths, s0, seeds = fleet(p, B)
-    res = RESOLUTION
-    infl = batch.inflation_profile(TICK_R * res, res)
-    assert infl[0] == TICK_R
-    cells = [layer(n, n, seed=20 + b) for b in range(B)]
+    p, B, n, res = configs.diff_drive_defaults(1000, 15), 64, TICK_N, RESOLUTION
+    paths, s0, seeds = bs.fleet(p, B)
+    infl = bs.inflation(TICK_R, res)
+    cells = [bs.layer(n, n, seed=20 + b) for b in range(B)]
     occ = [(cells[b], (s0[b, 0] - 0.5 * n * res, s0[b, 1] - 0.5 * n * res), res, 0.0, 128) for b in range(B)]
     sensor = (n // 2, n // 2)
     per_map = [[scan_of(sensor, TICK_RAYS, 40, 99, 1000 * phase + b) for b in range(B)] for phase in range(16)]
@@ -91,52 +83,30 @@ def resident_tick(ticks, rounds, warmup):
     calls = [(maps, sensors, n_rays, np.ascontiguousarray(np.concatenate([e for e, _ in ph])), np.ascontiguousarray(np.concatenate([h for _, h in ph])))
              for ph in per_map]
     map_of = np.arange(B, dtype=np.int32)
-    stream = torch.cuda.Stream()
-    h = amd.BatchController([p] * B, B, min_shift=True)
-    h.set_stream(stream.cuda_stream)
-    h.resident_set_paths(paths)
-    times = {m: [] for m in TICK_MODES}
-    wall = {m: [] for m in TICK_MODES}
-    for _r in range(rounds):
-        for mode in TICK_MODES:
-            h.set_occupancy(occ, infl, map_of, W_GRID)
-            mirror = [c.copy() for c in cells]   # (the host's copy of the layers, which mode `host_trace` needs)
-            h.resident_set_poses(s0, seeds)   # (every round from the start poses)
-            for i in range(warmup):
-                h.resident_step_enqueue(p.dt, i, advance=i > 0)
-            h.synchronize()
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0 = time.perf_counter()
-            start.record(stream)
-            for i in range(ticks):
-                h.resident_step_enqueue(p.dt, warmup + i)
-                if mode == "scan":
-                    raw_scan(h, *calls[i % 16])
-                elif mode == "host_trace":
-                    for b in range(B):
-                        ends, hits = per_map[i % 16][b]
-                        x0, y0, bw, bh = trace_host(mirror[b], sensor, ends, hits)
-                        h.update_occupancy(b, x0, y0, mirror[b][y0:y0 + bh, x0:x0 + bw])
-            stop.record(stream)
-            stop.synchronize()
-            wall[mode].append((time.perf_counter() - t0) * 1e6 / ticks)
-            times[mode].append(start.elapsed_time(stop) * 1e3 / ticks)
-            assert h.last_kernel() & capi.BATCH_KERNEL_GRID
-    # the host time of the call itself: stream idle, slots free (fewer calls than slots between two synchronisations)
-    call = []
-    for _r in range(8 * rounds):
-        h.synchronize()
-        t0 = time.perf_counter()
-        for i in range(capi.OCC_PATCH_SLOTS - 1):
-            raw_scan(h, *calls[i])
-        call.append((time.perf_counter() - t0) * 1e6 / (capi.OCC_PATCH_SLOTS - 1))
+    stream = bs.new_stream()
+    h = bs.resident_handle([p] * B, B, stream, paths, min_shift=True)
+    mirror = []   # (the host's copy of the layers, which mode `host_trace` needs)
+
+    def set_mode(h, _mode):
+        h.set_occupancy(occ, infl, map_of, W_GRID)
+        mirror[:] = [c.copy() for c in cells]
+
+    def after_step(mode, i):
+        if mode == "scan":
+            raw_scan(h, *calls[i % 16])
+        elif mode == "host_trace":
+            for b in range(B):
+                ends, hits = per_map[i % 16][b]
+                x0, y0, bw, bh = trace_host(mirror[b], sensor, ends, hits)
+                h.update_occupancy(b, x0, y0, mirror[b][y0:y0 + bh, x0:x0 + bw])
+
+    times, wall, _kernel = bs.resident_modes(h, stream, s0, seeds, p.dt, TICK_MODES, set_mode, ticks, rounds, warmup,
+                                             after_step=after_step, costmap_form=True, check=bs.check_grid)
+    out = {**bs.shape(p, B), "maps": B, "map": [n, n], "R": TICK_R, "ticks": ticks,
+           "scan": "%d rays per map from the centre, ranges 40 .. 99 cells, 70 %% hits, one call for all maps" % TICK_RAYS,
+           "scan_call_us": bs.idle_call_us(h, lambda i: raw_scan(h, *calls[i]), rounds)}
     h.close()
-    out = {"model": p.model, "K": p.num_samples, "H": p.horizon, "B": B, "maps": B, "map": [n, n], "R": TICK_R, "ticks": ticks,
-           "scan": "%d rays per map from the centre, ranges 40 .. 99 cells, 70 %% hits, one call for all maps" % TICK_RAYS}
-    out["scan_call_us"] = stats(call[rounds:])
-    for mode in TICK_MODES:
-        out[mode + "_tick_us"] = stats(times[mode], mode == "none")
-        out[mode + "_wall_us"] = stats(wall[mode], mode == "none")
+    bs.tick_stats(out, times, wall)
     print("resident B=64 tick us (device events / wall): none %.2f / %.2f (spread %.2f)  scan %.2f / %.2f  host_trace %.2f / %.2f; "
           "one scan call of 64 maps %.2f us of host time"
           % (out["none_tick_us"]["median"], out["none_wall_us"]["median"], out["none_tick_us"]["spread"], out["scan_tick_us"]["median"],
@@ -146,55 +116,28 @@ def resident_tick(ticks, rounds, warmup):
 
 
 def big_map(rounds):
-    import torch
     nx, ny = BIG
     h = amd.BatchController(configs.diff_drive_defaults(128, 15), 1)
-    infl = batch.inflation_profile(BIG_R * RESOLUTION, RESOLUTION)
-    assert infl[0] == BIG_R
-    h.set_occupancy([(layer(nx, ny), (0.0, 0.0), RESOLUTION, 0.0, 128)], infl, [0], W_GRID)
-    stream = torch.cuda.Stream()
+    h.set_occupancy([(bs.layer(nx, ny), (0.0, 0.0), RESOLUTION, 0.0, 128)], bs.inflation(BIG_R, RESOLUTION), [0], W_GRID)
+    stream = bs.new_stream()
     h.set_stream(stream.cuda_stream)
     sensor = (nx // 2, ny // 2)
     ends, hits = scan_of(sensor, BIG_RAYS, BIG_REACH - 50, BIG_REACH + 50, 5)
     args = (np.zeros(1, dtype=np.int32), np.array([sensor], dtype=np.int32), np.full(1, BIG_RAYS, dtype=np.int32), ends, hits)
     raw_scan(h, *args)   # (warm-up)
     h.synchronize()
-    wall, kern = [], []
-    for _ in range(rounds):
-        t0 = time.perf_counter()
-        raw_scan(h, *args)
-        h.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e3)
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record(stream)
-        raw_scan(h, *args)
-        stop.record(stream)
-        stop.synchronize()
-        kern.append(start.elapsed_time(stop) * 1e3)
+    scan_ms, kernels_us = bs.one_call_ms_and_us(h, stream, rounds, lambda: raw_scan(h, *args))
     h.close()
-    out = {"nx": nx, "ny": ny, "R": BIG_R, "rays": BIG_RAYS, "reach": BIG_REACH, "scan_ms": stats(wall), "scan_kernels_us": stats(kern)}
+    out = {"nx": nx, "ny": ny, "R": BIG_R, "rays": BIG_RAYS, "reach": BIG_REACH, "scan_ms": scan_ms, "scan_kernels_us": kernels_us}
     print("4000 x 3000 R=6, one entry of 2000 rays of reach 600: call and synchronisation %.3f ms, kernels %.1f us"
           % (out["scan_ms"]["median"], out["scan_kernels_us"]["median"]), file=sys.stderr, flush=True)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--ticks", type=int, default=256)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_scan_bench.json"))
-    args = ap.parse_args()
-    import torch
-    props = torch.cuda.get_device_properties(0)
-    out = {"device": props.name, "cus": props.multi_processor_count, "resident": resident_tick(args.ticks, args.rounds, args.warmup),
-           "big_map": big_map(args.rounds)}
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    args = bs.parser("batch_scan_bench.json", ticks=256).parse_args()
+    out = {**bs.header(), "resident": resident_tick(args.ticks, args.rounds, args.warmup), "big_map": big_map(args.rounds)}
+    bs.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """The simulated range sensor (ccv_mppi_batch_resident_sense_enqueue) against what a caller of the parent
 commit has to do to give a resident fleet sensor data: `python tools/batch_sense_bench.py [--out FILE]` (default
-profiles/batch_sense_bench.json).  The method of tools/batch_scan_bench.py: medians of --rounds rounds beside the max - min of the
-baseline's rounds.
+profiles/batch_sense_bench.json).  The method and the resident loop (its costmap form) are those of tools/bench_support.py.
 
 Resident tick, diff drive K = 1 000, H = 15, B = 64, one 200 x 200 map per robot placed round its start pose, R = 6, one world
 under all of them (2 % occupied), 360 beams of reach 99: `none`, no sensing; `sense`, all 64 robots sense after every tick, in
@@ -15,25 +14,21 @@ from a map's centre to its edge, so every sensor cell stays inside its map (the 
 One robot with 4 096 beams of reach 600 in a 4 000 x 3 000 world (0.2 % occupied) and a map of its size at R = 6 -- one
 workgroup casts them all: `sense_ms`, the wall time of the call and a synchronisation, and `sense_kernels_us`, the two launches
 between two events.  One JSON document goes to stdout (and --out)."""
-import argparse
 import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bench_support as bs  # noqa: E402  (puts the repository root on sys.path)
+
+sys.path.insert(0, os.path.join(bs.ROOT, "tests"))
 
 import ccv_mppi_path_tracker_amd as amd  # noqa: E402
 from ccv_mppi_path_tracker_amd import batch, capi, configs  # noqa: E402
 import sense_reference as SN  # noqa: E402
-from batch_costmap_bench import layer, stats  # noqa: E402
-from batch_obstacles_bench import fleet  # noqa: E402
 
 RESOLUTION = 0.05
 W_GRID = 0.01
@@ -49,7 +44,9 @@ def raw_sense(h, inst, beams):
 
 
 def cast_host(world, threshold, s, beams):
-    """(ends int32 [n][2] in world cells, hits uint8 [n]) of one robot: the blocked cell of a blocked beam, else its end cell"""
+    """(ends int32 [n][2] in world cells, hits uint8 [n]) of one robot: the blocked cell of a blocked beam, else its end cell.
+    The cast is the reference's; the one cell per beam below is its closed form (tests/sense_reference.py, beam_cells, which
+    lists every cell of one beam) for all beams at once, as a caller of the parent would write it: mode `host_cast` charges it."""
     first = SN.sense_vectorised(world, threshold, s, beams)
     d = beams.astype(np.int64)
     ad = np.abs(d)
@@ -64,14 +61,13 @@ def cast_host(world, threshold, s, beams):
 
 
 def resident_tick(ticks, rounds, warmup):
-    import torch
     p, B, n, res = configs.diff_drive_defaults(1000, 15), 64, TICK_N, RESOLUTION
-    paths, s0, seeds = fleet(p, B)
-    infl = batch.inflation_profile(TICK_R * res, res)
-    assert infl[0] == TICK_R and (warmup + ticks) * p.v_ref * p.dt / res < n // 2
+    paths, s0, seeds = bs.fleet(p, B)
+    infl = bs.inflation(TICK_R, res)
+    assert (warmup + ticks) * p.v_ref * p.dt / res < n // 2
     origin = (float(np.floor(s0[:, 0].min()) - 12.0), float(np.floor(s0[:, 1].min()) - 12.0))
     wnx, wny = int((s0[:, 0].max() + 24.0 - origin[0]) / res), int((s0[:, 1].max() + 24.0 - origin[1]) / res)
-    world = layer(wnx, wny, seed=4)
+    world = bs.layer(wnx, wny, seed=4)
     cell0 = [SN.pose_cell(s0[b, 0], s0[b, 1], origin, res, wnx, wny) for b in range(B)]
     anchors = np.array([(c[0] - n // 2, c[1] - n // 2) for c in cell0], dtype=np.int32)
     occ = [(np.zeros((n, n), dtype=np.uint8), (origin[0] + anchors[b, 0] * res, origin[1] + anchors[b, 1] * res), res, 0.0, 128) for b in range(B)]
@@ -79,64 +75,44 @@ def resident_tick(ticks, rounds, warmup):
     inst = np.arange(B, dtype=np.int32)
     map_of = np.arange(B, dtype=np.int32)
     n_rays = np.full(B, TICK_BEAMS, dtype=np.int32)
-    stream = torch.cuda.Stream()
-    h = amd.BatchController([p] * B, B, min_shift=True)
-    h.set_stream(stream.cuda_stream)
-    h.resident_set_paths(paths)
-    times = {m: [] for m in TICK_MODES}
-    wall = {m: [] for m in TICK_MODES}
-    for _r in range(rounds):
-        for mode in TICK_MODES:
-            h.set_occupancy(occ, infl, map_of, W_GRID)
-            h.set_world(world, 128, origin, res, anchors, TICK_BEAMS)
-            h.resident_set_poses(s0, seeds)   # (every round from the start poses)
-            for i in range(warmup):
-                h.resident_step_enqueue(p.dt, i, advance=i > 0)
-            h.synchronize()
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0 = time.perf_counter()
-            start.record(stream)
-            for i in range(ticks):
-                h.resident_step_enqueue(p.dt, warmup + i)
-                if mode == "sense":
-                    raw_sense(h, inst, beams)
-                elif mode == "host_cast":
-                    pose = h.resident_read()[0]
-                    sensors, ends, hits = [], [], []
-                    for b in range(B):
-                        s = SN.pose_cell(pose[b, 0], pose[b, 1], origin, res, wnx, wny)
-                        e, hit = cast_host(world, 128, s, beams)
-                        sensors.append((s[0] - anchors[b, 0], s[1] - anchors[b, 1]))
-                        ends.append(e - anchors[b])
-                        hits.append(hit)
-                    sensors = np.ascontiguousarray(sensors, dtype=np.int32)
-                    end_xy = np.ascontiguousarray(np.concatenate(ends), dtype=np.int32)
-                    hit = np.ascontiguousarray(np.concatenate(hits))
-                    rc = h.lib.ccv_mppi_batch_scan_occupancy_enqueue(h._h, B, map_of.ctypes.data_as(i32p), sensors.ctypes.data_as(i32p), n_rays.ctypes.data_as(i32p),
-                                                                     end_xy.ctypes.data_as(i32p), hit.ctypes.data_as(u8p), 0, 255)
-                    assert rc == capi.OK, rc
-            stop.record(stream)
-            stop.synchronize()
-            wall[mode].append((time.perf_counter() - t0) * 1e6 / ticks)
-            times[mode].append(start.elapsed_time(stop) * 1e3 / ticks)
-            assert h.last_kernel() & capi.BATCH_KERNEL_GRID
-            if mode != "none":
-                assert max(int(h.read_occupancy(b).max()) for b in (0, B - 1)) == 255, "nothing was marked"
-    # the host time of the call itself: stream idle, slots free (fewer calls than slots between two synchronisations)
-    call = []
-    for _r in range(8 * rounds):
-        h.synchronize()
-        t0 = time.perf_counter()
-        for i in range(capi.OCC_PATCH_SLOTS - 1):
+    stream = bs.new_stream()
+    h = bs.resident_handle([p] * B, B, stream, paths, min_shift=True)
+
+    def set_mode(h, _mode):
+        h.set_occupancy(occ, infl, map_of, W_GRID)
+        h.set_world(world, 128, origin, res, anchors, TICK_BEAMS)
+
+    def after_step(mode, _i):
+        if mode == "sense":
             raw_sense(h, inst, beams)
-        call.append((time.perf_counter() - t0) * 1e6 / (capi.OCC_PATCH_SLOTS - 1))
+        elif mode == "host_cast":
+            pose = h.resident_read()[0]
+            sensors, ends, hits = [], [], []
+            for b in range(B):
+                s = SN.pose_cell(pose[b, 0], pose[b, 1], origin, res, wnx, wny)
+                e, hit = cast_host(world, 128, s, beams)
+                sensors.append((s[0] - anchors[b, 0], s[1] - anchors[b, 1]))
+                ends.append(e - anchors[b])
+                hits.append(hit)
+            sensors = np.ascontiguousarray(sensors, dtype=np.int32)
+            end_xy = np.ascontiguousarray(np.concatenate(ends), dtype=np.int32)
+            hit = np.ascontiguousarray(np.concatenate(hits))
+            rc = h.lib.ccv_mppi_batch_scan_occupancy_enqueue(h._h, B, map_of.ctypes.data_as(i32p), sensors.ctypes.data_as(i32p), n_rays.ctypes.data_as(i32p),
+                                                             end_xy.ctypes.data_as(i32p), hit.ctypes.data_as(u8p), 0, 255)
+            assert rc == capi.OK, rc
+
+    def check(mode, kernel):
+        bs.check_grid(mode, kernel)
+        if mode != "none":
+            assert max(int(h.read_occupancy(b).max()) for b in (0, B - 1)) == 255, "nothing was marked"
+
+    times, wall, _kernel = bs.resident_modes(h, stream, s0, seeds, p.dt, TICK_MODES, set_mode, ticks, rounds, warmup,
+                                             after_step=after_step, costmap_form=True, check=check)
+    out = {**bs.shape(p, B), "maps": B, "map": [n, n], "R": TICK_R, "ticks": ticks, "warmup": warmup, "world": [wnx, wny],
+           "sense": "%d beams of reach %d per robot, one call for all robots" % (TICK_BEAMS, TICK_REACH),
+           "sense_call_us": bs.idle_call_us(h, lambda _i: raw_sense(h, inst, beams), rounds)}
     h.close()
-    out = {"model": p.model, "K": p.num_samples, "H": p.horizon, "B": B, "maps": B, "map": [n, n], "R": TICK_R, "ticks": ticks, "warmup": warmup,
-           "world": [wnx, wny], "sense": "%d beams of reach %d per robot, one call for all robots" % (TICK_BEAMS, TICK_REACH)}
-    out["sense_call_us"] = stats(call[rounds:])
-    for mode in TICK_MODES:
-        out[mode + "_tick_us"] = stats(times[mode], mode == "none")
-        out[mode + "_wall_us"] = stats(wall[mode], mode == "none")
+    bs.tick_stats(out, times, wall)
     print("resident B=64 tick us (device events / wall): none %.2f / %.2f (spread %.2f)  sense %.2f / %.2f  host_cast %.2f / %.2f; "
           "one sense call of 64 robots %.2f us of host time"
           % (out["none_tick_us"]["median"], out["none_wall_us"]["median"], out["none_tick_us"]["spread"], out["sense_tick_us"]["median"],
@@ -146,60 +122,33 @@ def resident_tick(ticks, rounds, warmup):
 
 
 def big_world(rounds):
-    import torch
     nx, ny = BIG
     p = configs.diff_drive_defaults(128, 15)
     h = amd.BatchController(p, 1)
-    infl = batch.inflation_profile(BIG_R * RESOLUTION, RESOLUTION)
-    assert infl[0] == BIG_R
-    h.set_occupancy([(np.zeros((ny, nx), dtype=np.uint8), (0.0, 0.0), RESOLUTION, 0.0, 128)], infl, [0], W_GRID)
+    h.set_occupancy([(np.zeros((ny, nx), dtype=np.uint8), (0.0, 0.0), RESOLUTION, 0.0, 128)], bs.inflation(BIG_R, RESOLUTION), [0], W_GRID)
     world = np.where(np.random.default_rng(6).random((ny, nx)) < 0.002, 255, 0).astype(np.uint8)
     h.set_world(world, 128, (0.0, 0.0), RESOLUTION, [(0, 0)], BIG_BEAMS)
     h.resident_set_paths(amd.make_path("dkan"))
     h.resident_set_poses(np.array([[(nx // 2 + 0.5) * RESOLUTION, (ny // 2 + 0.5) * RESOLUTION, 0.0]]), 1)
-    stream = torch.cuda.Stream()
+    stream = bs.new_stream()
     h.set_stream(stream.cuda_stream)
     inst, beams = np.zeros(1, dtype=np.int32), batch.beam_fan(BIG_BEAMS, BIG_REACH)
     raw_sense(h, inst, beams)   # (warm-up)
     h.synchronize()
     first = h.resident_read_sense()[0][0]
-    wall, kern = [], []
-    for _ in range(rounds):
-        t0 = time.perf_counter()
-        raw_sense(h, inst, beams)
-        h.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e3)
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record(stream)
-        raw_sense(h, inst, beams)
-        stop.record(stream)
-        stop.synchronize()
-        kern.append(start.elapsed_time(stop) * 1e3)
+    sense_ms, kernels_us = bs.one_call_ms_and_us(h, stream, rounds, lambda: raw_sense(h, inst, beams))
     h.close()
     out = {"nx": nx, "ny": ny, "R": BIG_R, "beams": BIG_BEAMS, "reach": BIG_REACH, "blocked": int((first >= 0).sum()),
-           "mean_cells_searched": float(np.where(first >= 0, first, BIG_REACH).mean()), "sense_ms": stats(wall), "sense_kernels_us": stats(kern)}
+           "mean_cells_searched": float(np.where(first >= 0, first, BIG_REACH).mean()), "sense_ms": sense_ms, "sense_kernels_us": kernels_us}
     print("4000 x 3000 R=6, one robot, 4096 beams of reach 600 (%d blocked): call and synchronisation %.3f ms, kernels %.1f us"
           % (out["blocked"], out["sense_ms"]["median"], out["sense_kernels_us"]["median"]), file=sys.stderr, flush=True)
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--ticks", type=int, default=40)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_sense_bench.json"))
-    args = ap.parse_args()
-    import torch
-    props = torch.cuda.get_device_properties(0)
-    out = {"device": props.name, "cus": props.multi_processor_count, "resident": resident_tick(args.ticks, args.rounds, args.warmup),
-           "big_world": big_world(args.rounds)}
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    args = bs.parser("batch_sense_bench.json", ticks=40, warmup=10).parse_args()
+    out = {**bs.header(), "resident": resident_tick(args.ticks, args.rounds, args.warmup), "big_world": big_world(args.rounds)}
+    bs.emit(out, args.out)
 
 
 if __name__ == "__main__":
