@@ -20,7 +20,7 @@ CAPI_UNITS = ["ccv_mppi_capi.hip", "capi_exchange.hip", "capi_resident.hip", "ca
 SOURCES = KERNEL_UNITS + ["mppi_launch.hip"] + CAPI_UNITS + ["ccv_mppi_host.cpp", os.path.join("host", "mppi_node.cpp")]
 HEADERS = ["capi_internal.h", "mppi_diag.h", "mppi_kernels.h", "mppi_device_util.h", "mppi_cost_terms.h", "mppi_handoff.h", "mppi_produce.h", "mppi_consume.h",
            "mppi_epilogue.h", "mppi_update.h", "mppi_launch.h", "mppi_rollout_plain.h", "mppi_rollout_pc.h", "mppi_rollout_r3.h", "mppi_rollout_r4.h",
-           "mppi_rollout_solo.h", "k_batch_form.h", "mppi_resident.h", "mppi_update_device.h", "mppi_fleet.h", "mppi_fleet_device.h", "mppi_costmap.h", "mppi_costmap_device.h", "mppi_costmap_rects.h", "mppi_costmap_roll.h", "mppi_costmap_scan.h", "mppi_costmap_sense.h", "mppi_select.h", "mppi_feed.h", "fast_trig.h", "noise_spec.h",
+           "mppi_rollout_solo.h", "k_batch_form.h", "mppi_resident.h", "mppi_update_device.h", "mppi_fleet.h", "mppi_fleet_device.h", "mppi_costmap.h", "mppi_costmap_device.h", "mppi_costmap_rects.h", "mppi_costmap_roll.h", "mppi_costmap_scan.h", "mppi_costmap_sense.h", "mppi_select.h", "mppi_top_weights.h", "mppi_feed.h", "fast_trig.h", "noise_spec.h",
            os.path.join("..", "..", "include", "ccv_mppi.h"), os.path.join("..", "..", "include", "ccv_mppi_host.h"),
            os.path.join("..", "..", "include", "ccv_mppi_fleet.h"), os.path.join("..", "..", "include", "ccv_mppi_sense.h"),
            os.path.join("..", "..", "include", "ccv_mppi_node.hpp")]

@@ -1,8 +1,7 @@
 // C ABI, one stage at a time (sampling / rollout / weights / update, as the reference's member functions), the read-back
 // calls and the timing of the fused iteration.
-#include <algorithm>
-
 #include "capi_internal.h"
+#include "mppi_top_weights.h"
 
 extern "C" {
 
@@ -131,19 +130,13 @@ int ccv_mppi_read_top_candidates(ccv_mppi_handle* h, int32_t count, int32_t* sam
     HIP_TRY(h, hipMemcpyAsync(idx.data(), d_idx, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(wsel.data(), d_wsel, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    // descending weight (NaN first), ties by sample index
-    std::vector<int> order(count);
-    for (int i = 0; i < count; ++i) order[i] = i;
-    auto key = [&](int i) { return (unsigned long long)*reinterpret_cast<const long long*>(&wsel[i]); };
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return key(a) != key(b) ? key(a) > key(b) : idx[a] < idx[b]; });
-    std::vector<int> sorted_idx(count);
+    top_order_pairs(count, idx.data(), wsel.data());   // NaN weights first, then descending weight; ties by sample index
     for (int i = 0; i < count; ++i) {
-        sorted_idx[i] = idx[order[i]];
-        sample_out[i] = sorted_idx[i];
-        if (weight_out) weight_out[i] = wsel[order[i]];
+        sample_out[i] = idx[i];
+        if (weight_out) weight_out[i] = wsel[i];
     }
     if (xy_out) {
-        HIP_TRY(h, hipMemcpyAsync(d_idx, sorted_idx.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(d_idx, idx.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, h->stream));
         hipLaunchKernelGGL(k_gather_xy_list, dim3((count * h->H + kBlock - 1) / kBlock), dim3(kBlock), 0, h->stream, h->d_xs, h->d_ys,
                            h->pitch, h->H, d_idx, count, d_xy);
         HIP_TRY(h, hipGetLastError());

@@ -5,6 +5,7 @@
 // kernels' translation units (k_*.hip) include mppi_launch.h and their family's header (mppi_rollout_*.h), not this one.
 #pragma once
 #include "mppi_kernels.h"
+#include "mppi_top_weights.h"
 
 namespace ccv {
 
@@ -93,8 +94,8 @@ __global__ void k_reweight_batch(const double* cost, const double* cmin, const B
 // ---- read-back helpers -----------------------------------------------------------------------------------------
 // out[c][t][2] = (xs[t][first + c*stride], ys[t][...])
 __global__ void k_gather_xy(const double* xs, const double* ys, int pitch, int H, int first, int count, int stride, double* out);
-// top-N candidates by weight: one workgroup of kTopBlock; the host sorts the N pairs
-constexpr int kTopBlock = 1024;
+// top-N candidates by weight: one workgroup of kTopBlock running top_weights(); top_order_pairs() sorts the N pairs on the
+// host (both, the key and kTopBlock: mppi_top_weights.h)
 __global__ void k_top_weights(const double* w, int K, int N, int* idx_out, double* w_out);
 // gather of listed samples: out[c][t] = (x, y) of sample idx[c] at step t
 __global__ void k_gather_xy_list(const double* xs, const double* ys, int pitch, int H, const int* idx, int count, double* out);
