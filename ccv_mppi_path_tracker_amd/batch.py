@@ -154,6 +154,21 @@ def beam_fan(n, reach_cells, phase=0.0):
     return np.ascontiguousarray(np.stack([np.rint(reach * np.cos(t)), np.rint(reach * np.sin(t))], axis=1), dtype=np.int32)
 
 
+def goal_cells(geometry, xy):
+    """Goal cells for BatchController.resident_plan: int32 [n][2], the cell of each point xy [n][2] of a map with
+    geometry = ((origin_x, origin_y), resolution, nx, ny) by the grid term's formula -- f = (p - origin) * (1 / resolution), one
+    subtraction and one multiplication, truncated -- clamped to the map: a point outside it gets the nearest border cell (a NaN
+    coordinate cell 0)."""
+    (ox, oy), resolution, nx, ny = geometry
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    inv = 1.0 / float(resolution)
+    out = np.empty(xy.shape, dtype=np.int32)
+    for k, (o, n) in enumerate(((float(ox), int(nx)), (float(oy), int(ny)))):
+        f = (xy[:, k] - o) * inv
+        out[:, k] = np.trunc(np.clip(np.where(np.isnan(f), 0.0, f), 0.0, n - 1)).astype(np.int32)
+    return np.ascontiguousarray(out)
+
+
 def inflation_profile(radius_m, resolution, kind="linear", lethal=1.0, inscribed=None, inscribed_m=0.0, free_value=0.0, scaling=10.0):
     """(R, profile float32 [R * R + 1], free_value) for BatchController.set_occupancy: the cost of a cell by the squared distance
     D2, in cells, from its centre to the centre of the nearest occupied cell, built on the host -- the device only looks it up.
@@ -688,6 +703,71 @@ class BatchController:
         n = C.c_int32()
         self._check(self.lib.ccv_mppi_batch_resident_read_trace(self._h, int(instance), max_rows, capi.dptr(rows), C.byref(n)))
         return rows[:n.value].copy()
+
+    # ---- paths planned on the device (ccv_mppi_batch_resident_set_plan, _plan_enqueue; include/ccv_mppi_plan.h) ----
+    def resident_set_plan(self, capacity, keep_fields=False):
+        """capacity: one value or [B], the most poses a planned path of the instance may have (0: the instance does not plan, at
+        most capi.PLAN_MAX_POSES), or None: planning off, the paths stay as they are.  keep_fields: every planning instance's
+        distance field is kept for resident_read_plan_field.  After resident_set_paths, which also turns planning off; every
+        path keeps its bits.  Flushes a pending resident update and synchronises."""
+        if capacity is None:
+            self._check(self.lib.ccv_mppi_batch_resident_set_plan(self._h, None, 0))
+            return
+        cap = np.ascontiguousarray(np.broadcast_to(np.asarray(capacity, dtype=np.int32), (self.B,)))
+        self._check(self.lib.ccv_mppi_batch_resident_set_plan(self._h, cap.ctypes.data_as(C.POINTER(C.c_int32)), 1 if keep_fields else 0))
+
+    def resident_get_plan(self):
+        """(capacity int32 [B], keep_fields) as the library holds them; MPPIError (capi.ERR_STATE) while planning is off."""
+        cap, keep = np.zeros(self.B, dtype=np.int32), C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_resident_get_plan(self._h, cap.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(keep)))
+        return cap, bool(keep.value)
+
+    def resident_plan(self, instances, goals, lethal, max_sweeps=None):
+        """The instances `instances` (each at most once) plan, in stream order and in one launch for all of them: from the cell
+        of its own map its resident pose lies in, each gets the path of cell centres that descends the map's distance field to
+        its goal cell goals [n][2] (goal_cells), over the cells whose value is <= lethal, 8-connected without corner cutting.
+        max_sweeps: the most relaxation sweeps (default: the largest nx * ny + 1 of the named instances' maps, which is always
+        enough).  The outcome: resident_read_plan.  No synchronisation; the arguments may be reused when the call returns."""
+        inst = np.ascontiguousarray(np.atleast_1d(instances), dtype=np.int32)
+        goals = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 2))
+        if len(goals) != len(inst):
+            raise ValueError("resident_plan: expected %d goals, got %d" % (len(inst), len(goals)))
+        if max_sweeps is None:
+            n = C.c_int32(0)
+            mo = np.zeros(self.B, dtype=np.int32)
+            self._check(self.lib.ccv_mppi_batch_get_grids(self._h, None, 0, C.byref(n), mo.ctypes.data_as(C.POINTER(C.c_int32)), None))
+            rows = (capi.Grid * max(n.value, 1))()
+            self._check(self.lib.ccv_mppi_batch_get_grids(self._h, rows, n.value, None, None, None))
+            named = [mo[b] for b in inst if 0 <= b < self.B and mo[b] >= 0]
+            max_sweeps = min(max([rows[m].nx * rows[m].ny + 1 for m in named] or [1]), capi.PLAN_MAX_FIELD)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ccv_mppi_batch_resident_plan_enqueue(self._h, len(inst), inst.ctypes.data_as(ip), goals.ctypes.data_as(ip),
+                                                                   float(lethal), int(max_sweeps)))
+
+    def resident_read_plan(self):
+        """(status [B], poses [B], start_cell [B][2], start_dist [B], sweeps [B]), int32, of every instance's last plan: status a
+        capi.PLAN_* value (0: never planned), poses the cells the descent visited (0 without one), start_cell the cell the pose
+        lay in ((-1, -1): in none), start_dist the field's value there (-1: no converged field); synchronises."""
+        out = [np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32), np.zeros((self.B, 2), dtype=np.int32),
+               np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)]
+        self._check(self.lib.ccv_mppi_batch_resident_read_plan(self._h, *[a.ctypes.data_as(C.POINTER(C.c_int32)) for a in out]))
+        return tuple(out)
+
+    def resident_read_plan_field(self, instance, shape):
+        """uint16 [ny][nx] (shape = (ny, nx) of the instance's map): the distance field of the instance's last plan -- 65535 on
+        blocked cells, 0 on the goal, 65533 where the goal is not reached within 65532; synchronises.  MPPIError
+        (capi.ERR_STATE) without keep_fields or while the last plan's status is not OK, TRUNCATED or UNREACHABLE."""
+        out = np.empty((int(shape[0]), int(shape[1])), dtype=np.uint16)
+        self._check(self.lib.ccv_mppi_batch_resident_read_plan_field(self._h, int(instance), out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out
+
+    def resident_read_path(self, instance):
+        """(path_x, path_y) of the instance as the device holds it now, planned or set; synchronises."""
+        n = C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_resident_read_path(self._h, int(instance), 0, None, None, C.byref(n)))
+        x, y = np.empty(n.value), np.empty(n.value)
+        self._check(self.lib.ccv_mppi_batch_resident_read_path(self._h, int(instance), n.value, capi.dptr(x), capi.dptr(y), C.byref(n)))
+        return x[:n.value], y[:n.value]
 
     # ---- fleet term: the robots of the batch keep clear of each other (ccv_mppi_batch_resident_set_fleet) ----
     def resident_set_fleet(self, radius, range=0.0, max_neighbours=0, weight=0.0):

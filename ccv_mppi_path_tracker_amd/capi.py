@@ -1,5 +1,5 @@
 """ctypes binding of libccv_mppi_hip.so -- exactly the symbols include/ccv_mppi.h and
-include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES) and include/ccv_mppi_sense.h (SENSE_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
+include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES), include/ccv_mppi_sense.h (SENSE_SIGNATURES) and include/ccv_mppi_plan.h (PLAN_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
 if the library is missing it is built with hipcc, and if that fails the import raises.
 """
 import ctypes as C
@@ -38,6 +38,8 @@ SCAN_MAX_REACH = 4096
 SCAN_RAY_BYTES, SCAN_ENTRY_BYTES = 9, 128   # of a staging slot (OCC_PATCH_MAX_CELLS bytes) per ray, and per entry that has rays
 SENSE_MAX_BEAMS = 4096
 SENSE_BEAM_BYTES, SENSE_ENTRY_BYTES = 8, 112   # of a staging slot per beam of ccv_mppi_batch_resident_sense_enqueue, and per entry
+PLAN_MAX_FIELD, PLAN_MAX_POSES = 81920, 16384
+PLAN_OK, PLAN_TRUNCATED, PLAN_NO_START, PLAN_START_BLOCKED, PLAN_GOAL_BLOCKED, PLAN_UNREACHABLE, PLAN_NOT_CONVERGED = 1, 2, 3, 4, 5, 6, 7
 BEST_MAX = 1024
 BATCH_TRACE_ROWS = 1024
 
@@ -223,6 +225,17 @@ SENSE_SIGNATURES = {
     "ccv_mppi_batch_resident_read_sense": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
+# include/ccv_mppi_plan.h: paths planned on the device for the resident loop, a table of its own like its header
+_i32p = C.POINTER(C.c_int32)
+PLAN_SIGNATURES = {
+    "ccv_mppi_batch_resident_set_plan": (C.c_int, [_H, _i32p, C.c_int32]),
+    "ccv_mppi_batch_resident_get_plan": (C.c_int, [_H, _i32p, _i32p]),
+    "ccv_mppi_batch_resident_plan_enqueue": (C.c_int, [_H, C.c_int32, _i32p, _i32p, C.c_float, C.c_int32]),
+    "ccv_mppi_batch_resident_read_plan": (C.c_int, [_H, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "ccv_mppi_batch_resident_read_plan_field": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint16)]),
+    "ccv_mppi_batch_resident_read_path": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _i32p]),
+}
+
 _lib = None
 
 
@@ -234,7 +247,7 @@ def load():
         if not os.path.exists(path):
             raise ImportError("libccv_mppi_hip.so is missing and could not be built; there is no CPU fallback")
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()) + list(PLAN_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError = the .so does not export what the header declares
             fn.restype = res
             fn.argtypes = args

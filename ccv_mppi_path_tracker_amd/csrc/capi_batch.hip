@@ -225,6 +225,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     bh->Grids::release();
     bh->Costmap::release();
     bh->World::release();
+    bh->Plan::release();
     bh->Fleet::release();
     delete bh;
     return CCV_MPPI_OK;
@@ -357,6 +358,7 @@ int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* bh, const double* path_x, 
     }
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued prologue may still read the old paths)
+    bh->drop_plan();   // (the paths are the caller's again: ccv_mppi_batch_resident_set_plan comes after this call)
     if (total > bh->n_total || !bh->d_rpath) {
         if (bh->d_rpath) HIP_TRY(bh, hipFree(bh->d_rpath));
         bh->d_rpath = nullptr;
@@ -398,7 +400,10 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));
     HIP_TRY(bh, hipMemcpy2D(bh->d_rframe, sizeof(ResidentFrame), heads.data(), sizeof(FrameHead), sizeof(FrameHead), (size_t)B,
                            hipMemcpyHostToDevice));
-    HIP_TRY(bh, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    if (bh->plan)   // (the device's n_path is the truth while planning is set: the noise keys alone go up)
+        HIP_TRY(bh, hipMemcpy2D(&bh->d_inst->seed_lo, sizeof(BatchInstance), &bh->inst[0].seed_lo, sizeof(BatchInstance), 2 * sizeof(uint32_t),
+                               (size_t)B, hipMemcpyHostToDevice));
+    else HIP_TRY(bh, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
     if (bh->fleet) {
         std::vector<double> xy((size_t)B * 2);
         for (int b = 0; b < B; ++b) std::memcpy(&xy[(size_t)b * 2], heads[b].x0, 2 * sizeof(double));

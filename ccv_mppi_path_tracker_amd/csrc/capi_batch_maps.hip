@@ -11,6 +11,42 @@
 #include "mppi_costmap_scan.h"
 #include "mppi_costmap_sense.h"
 
+namespace ccv {
+
+float* cells_of(const ccv_mppi_batch* bh, const int m, const bool back) {
+    const bool second = bh->occ && ((bh->layers[(size_t)m].front != 0) != back);
+    return (second ? bh->d_cells_roll : bh->d_grid_cells) + bh->grid_offset[(size_t)m];
+}
+
+// ---- the staging ring of the *_enqueue calls (Costmap, capi_internal.h): the kernels read a slot in place --------------------
+// at the first _set_occupancy or _resident_set_plan (kept until destroy)
+int ring_create(ccv_mppi_batch* bh) {
+    if (bh->h_patch) return CCV_MPPI_OK;
+    HIP_TRY(bh, hipHostMalloc(&bh->h_patch, (size_t)Costmap::kPatchSlots * CCV_MPPI_OCC_PATCH_MAX_CELLS, hipHostMallocDefault));
+    HIP_TRY(bh, hipHostGetDevicePointer(reinterpret_cast<void**>(&bh->d_patch), bh->h_patch, 0));
+    for (hipEvent_t& e : bh->patch_ev) HIP_TRY(bh, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return CCV_MPPI_OK;
+}
+
+// the next slot, free to be filled: the call's only wait
+int slot_take(ccv_mppi_batch* bh, Slot& s) {
+    const int i = bh->patch_next;
+    bh->patch_next = (i + 1) % Costmap::kPatchSlots;
+    if (bh->patch_used[i]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[i]));
+    s = Slot{i, bh->h_patch + (size_t)i * CCV_MPPI_OCC_PATCH_MAX_CELLS, bh->d_patch + (size_t)i * CCV_MPPI_OCC_PATCH_MAX_CELLS};
+    return CCV_MPPI_OK;
+}
+
+// after the last launch that reads the slot (launched: hipGetLastError() after it)
+int slot_seal(ccv_mppi_batch* bh, const Slot& s, const hipError_t launched) {
+    bh->patch_used[s.index] = true;
+    HIP_TRY(bh, launched);
+    HIP_TRY(bh, hipEventRecord(bh->patch_ev[s.index], bh->stream));
+    return CCV_MPPI_OK;
+}
+
+}  // namespace ccv
+
 namespace {
 
 // what is wrong with a map's geometry (the checks _set_grids and _set_occupancy share, in this order), or null
@@ -89,10 +125,6 @@ int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, float* cel
 uint8_t* layer_of(const ccv_mppi_batch* bh, const int m, const bool back = false) {
     return ((bh->layers[(size_t)m].front != 0) != back ? bh->d_occ_roll : bh->d_occ) + bh->grid_offset[(size_t)m];
 }
-float* cells_of(const ccv_mppi_batch* bh, const int m, const bool back = false) {
-    const bool second = bh->occ && ((bh->layers[(size_t)m].front != 0) != back);
-    return (second ? bh->d_cells_roll : bh->d_grid_cells) + bh->grid_offset[(size_t)m];
-}
 
 // one inflation of the rectangle r inside map m: the float cells from the layer, both the front ones or both the back ones
 InflateArgs inflate_args(const ccv_mppi_batch* bh, const int m, const Rect& r, const bool back = false) {
@@ -105,35 +137,6 @@ InflateArgs inflate_args(const ccv_mppi_batch* bh, const int m, const Rect& r, c
 // ... of the float cells that changed layer cells in [x0, x1) x [y0, y1) of map m can move (grown_rect over the map's R)
 InflateArgs grown_args(const ccv_mppi_batch* bh, const int m, const int64_t x0, const int64_t y0, const int64_t x1, const int64_t y1) {
     return inflate_args(bh, m, grown_rect(x0, y0, x1, y1, bh->layers[(size_t)m].radius, bh->grid_maps[(size_t)m].nx, bh->grid_maps[(size_t)m].ny));
-}
-
-// ---- the staging ring of the *_enqueue calls (Costmap, capi_internal.h): the kernels read a slot in place --------------------
-struct Slot { int index; uint8_t* host; const uint8_t* device; };   // (device: the same bytes as the kernels address them)
-
-// at the first _set_occupancy (kept until destroy)
-int ring_create(ccv_mppi_batch* bh) {
-    if (bh->h_patch) return CCV_MPPI_OK;
-    HIP_TRY(bh, hipHostMalloc(&bh->h_patch, (size_t)Costmap::kPatchSlots * CCV_MPPI_OCC_PATCH_MAX_CELLS, hipHostMallocDefault));
-    HIP_TRY(bh, hipHostGetDevicePointer(reinterpret_cast<void**>(&bh->d_patch), bh->h_patch, 0));
-    for (hipEvent_t& e : bh->patch_ev) HIP_TRY(bh, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return CCV_MPPI_OK;
-}
-
-// the next slot, free to be filled: the call's only wait
-int slot_take(ccv_mppi_batch* bh, Slot& s) {
-    const int i = bh->patch_next;
-    bh->patch_next = (i + 1) % Costmap::kPatchSlots;
-    if (bh->patch_used[i]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[i]));
-    s = Slot{i, bh->h_patch + (size_t)i * CCV_MPPI_OCC_PATCH_MAX_CELLS, bh->d_patch + (size_t)i * CCV_MPPI_OCC_PATCH_MAX_CELLS};
-    return CCV_MPPI_OK;
-}
-
-// after the last launch that reads the slot (launched: hipGetLastError() after it)
-int slot_seal(ccv_mppi_batch* bh, const Slot& s, const hipError_t launched) {
-    bh->patch_used[s.index] = true;
-    HIP_TRY(bh, launched);
-    HIP_TRY(bh, hipEventRecord(bh->patch_ev[s.index], bh->stream));
-    return CCV_MPPI_OK;
 }
 
 static_assert(kRollBands == kRollMaxRects, "a roll's bands and the rectangles its slot has room for");

@@ -8,6 +8,7 @@
 //   capi_batch_maps.hip  batch handles: the maps of the grid term, a caller's cells or costmaps derived on the device, and the
 //                        stream-ordered patches, rolls and scans of those
 //   capi_batch_feed.hip  batch handles: best candidates and optimal paths of every instance (mppi_feed.h)
+//   capi_batch_plan.hip  batch handles: paths planned on the device from the maps to goal cells (mppi_plan.h)
 // A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".
@@ -337,6 +338,29 @@ struct World {
     void release() { free_device({d_world, d_sense_first, d_sense_cell, d_sense_rects}); }
 };
 
+// paths planned on the device (ccv_mppi_batch_resident_set_plan / _plan_enqueue, mppi_plan.h; capi_batch_plan.hip): while `plan`,
+// BatchResident::d_rpath has room for max(n_path, capacity) poses per instance and the device's BatchInstance::n_path is the
+// truth -- the host copy's n_path is what the last setter saw.  Lives from _set_plan to _set_plan(NULL), the next
+// _resident_set_paths or destroy.
+struct Plan {
+    bool plan = false, plan_keep = false;
+    std::vector<int32_t> plan_capacity;      // [B] poses a plan may write, 0: the instance does not plan
+    std::vector<int32_t> plan_field_of;      // [B] the instance's field in d_plan_fields, -1 without
+    std::vector<int32_t> plan_dims;          // [B][2]: nx, ny of the map of the instance's last plan call
+    int32_t* d_plan_result = nullptr;        // [B][6]: status, poses, start cell, D(start), sweeps of every instance's last plan
+    uint16_t* d_plan_fields = nullptr;       // [instances with capacity][CCV_MPPI_PLAN_MAX_FIELD], with keep_fields
+    void drop_plan() {
+        free_device({d_plan_result, d_plan_fields});
+        d_plan_result = nullptr;
+        d_plan_fields = nullptr;
+        plan_capacity.clear();
+        plan_field_of.clear();
+        plan_dims.clear();
+        plan = plan_keep = false;
+    }
+    void release() { free_device({d_plan_result, d_plan_fields}); }
+};
+
 // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
 // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
 // the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance).
@@ -362,7 +386,7 @@ struct Fleet {
 // batch_view): the core of a single handle, whose K is the instance's and whose
 // pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
 // one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
-struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, World, Fleet {
+struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, World, Plan, Fleet {
     int B = 0, kpad = 0;
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
@@ -518,5 +542,13 @@ inline bool valid_weight(const double w) { return w >= 0.0 && std::isfinite(w); 
 // the fleet's snapshots start over (the caller has quiesced): both halves of the position table from xy [B][2] (null: as they are)
 // and, under prediction, both halves of the velocity snapshot zero -- no robot has moved yet
 int fleet_restart(ccv_mppi_batch* bh, const double* xy);
+
+// ---- batch handles: the staging ring of the *_enqueue calls (Costmap; capi_batch_maps.hip), for the units that enqueue through it ---
+struct Slot { int index; uint8_t* host; const uint8_t* device; };   // (device: the same bytes as the kernels address them)
+int ring_create(ccv_mppi_batch* bh);                                // at the first _set_occupancy or _resident_set_plan; idempotent
+int slot_take(ccv_mppi_batch* bh, Slot& s);                         // the next slot, free to be filled: the call's only wait
+int slot_seal(ccv_mppi_batch* bh, const Slot& s, hipError_t launched);   // after the last launch that reads the slot
+// the float cells that hold map m now: the second allocation after an odd number of rolls (Costmap::Layer::front)
+float* cells_of(const ccv_mppi_batch* bh, int m, bool back = false);
 
 }  // namespace ccv

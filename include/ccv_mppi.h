@@ -622,10 +622,59 @@ int ccv_mppi_batch_resident_read(ccv_mppi_batch* b, double* state, int32_t* curr
 int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int32_t max_rows, double* rows, int32_t* n_rows);
 /* The fleet term of the resident loop -- the robots of one batch keep clear of each other,
  * ccv_mppi_batch_resident_set_fleet / _get_fleet / _read_fleet -- is declared in ccv_mppi_fleet.h, included below. */
+/* Paths planned on the device (NOT reference behaviour; off until called; batch handles and resident steps only): the six calls
+ * ccv_mppi_batch_resident_set_plan / _get_plan / _plan_enqueue / _read_plan / _read_plan_field / _read_path are declared in
+ * ccv_mppi_plan.h, included below.  What they promise.  Instance b plans on its own map (of _set_grids or _set_occupancy, in the
+ * current, rolled frame; nx x ny float cells) from the cell its resident pose lies in to a goal cell.  Integers only, but for one
+ * pose-to-cell step and one cell-to-pose step:
+ *     blocked(c) = !(cell(c) <= lethal)    an fp32 compare: a NaN cell is blocked, a cell equal to lethal is free; everything
+ *                                          outside the map is blocked
+ *     moves      (x, y) -> (x + dx, y + dy), dx, dy in {-1, 0, 1}, not both zero; a straight move has weight 5, a diagonal move
+ *                weight 7; a move is allowed iff the target is not blocked, and a diagonal move also needs (x + dx, y) and
+ *                (x, y + dy) both not blocked (no corner cutting; the rule is symmetric)
+ *     field      D uint16: 65535 on blocked cells, D(goal) = 0, elsewhere min(65533, least total weight of an allowed path to
+ *                the goal); 65533 means both "not reached" and "farther than 65532".  D is the one fixpoint of
+ *                D(c) = min(D(c), min(65533, D(n) + w)), whatever order the device relaxes in
+ *     start      fx = (x - origin_x) * inv, fy likewise (the grid term's formula against the map's own origin as rolled: one
+ *                subtraction, one multiplication, no FMA); in = fx >= 0 && fx < nx && fy >= 0 && fy < ny; s = ((int)fx, (int)fy);
+ *                the pose is the resident pose as the stream finds it, as for the sensor: the host reads no pose
+ *     descent    from c = s until D(c) == 0: the first allowed neighbour in the order E, N, W, S, NE, NW, SW, SE with
+ *                D(n) + w == D(c).  L = the cells visited, start and goal included
+ *     pose i     the centre of cell i: x = origin_x + ((double)ix + 0.5) * resolution (one multiplication, one addition, no FMA),
+ *                y likewise; pose 0 is the start cell.  Diagonal poses are sqrt(2) * resolution apart, straight ones
+ *                resolution: the window stride of the prologue counts poses, so a planned window is up to sqrt(2) longer.
+ * Status per instance, the first that applies: CCV_MPPI_PLAN_NO_START (not `in`, or a NaN pose), _START_BLOCKED, _GOAL_BLOCKED,
+ * _NOT_CONVERGED (no sweep without a change within max_sweeps), _UNREACHABLE (D(s) == 65533), _TRUNCATED (L > capacity[b]), _OK;
+ * 0: the instance has never planned.  On _OK and _TRUNCATED the first min(L, capacity[b]) poses replace the instance's path and
+ * n_path becomes that count; on every other status no bit of the path, n_path or the next tick changes.  A sweep relaxes every
+ * free cell at least once against values at least as new as the end of the previous sweep; the call converges whenever
+ * max_sweeps >= J, the sweeps of a Jacobi iteration including its last one that changes nothing (nx * ny + 1 is always enough);
+ * below J the outcome is the device's own.  (nx + 2)(ny + 2) <= CCV_MPPI_PLAN_MAX_FIELD: the field lives in one CU's LDS.  The
+ * instance's path resolution must equal its map's resolution bit for bit, so the stride check of _resident_step_enqueue stays
+ * true whether or not a plan succeeds.
+ * _set_plan: capacity [B], each in [0, CCV_MPPI_PLAN_MAX_POSES] (0: the instance does not plan); a setter: flushes a pending
+ * resident update and synchronises.  Comes after _resident_set_paths (CCV_MPPI_ERR_STATE before).  The paths are laid out again
+ * with room for max(n_path[b], capacity[b]) poses per instance and the present paths copied: no bit of any tick changes.  With
+ * keep_fields one field of CCV_MPPI_PLAN_MAX_FIELD uint16 is kept per instance that has capacity.  capacity == NULL turns
+ * planning off (the paths stay as they are); so does a later _resident_set_paths; destroy frees everything.  While planning is
+ * set, _resident_set_poses keeps every instance's path, planned or not.
+ * _plan_enqueue: the n named instances (instance [n], each at most once, 1 <= n <= B; two may share a map, which is only read)
+ * plan to goal_xy [n][2], in stream order and in one kernel launch: no synchronisation, no allocation, no flush of a pending
+ * resident update, no copy; every array may be reused when the call returns.  It may come between steps, patches, rolls, scans
+ * and sensings; the next tick's prologue finds the new path.  Planning not set, or no resident poses: CCV_MPPI_ERR_STATE.  n out
+ * of range, an instance out of range or named twice, an instance without a map or with capacity 0, a goal outside the map, a
+ * map above the size limit, a resolution mismatch, a NaN lethal, max_sweeps outside [1, CCV_MPPI_PLAN_MAX_FIELD], NULL arrays:
+ * CCV_MPPI_ERR_INVALID_ARG.  Nothing changes either way.
+ * _read_plan: per instance the status, poses (L, or 0 without a descent), start_cell [B][2] ((-1, -1) for _NO_START and before
+ * the first plan), start_dist (D(s), or -1 where the field did not converge or was not built) and the sweeps taken, of its last
+ * plan; synchronises; any pointer may be NULL.  _read_plan_field: out [ny][nx], instance's field of its last plan; synchronises;
+ * CCV_MPPI_ERR_STATE without keep_fields or while the instance's last status is not 1, 2 or 6.  _read_path: the instance's current
+ * path, planned or set: *n_path and the first min(n_path, max_poses) poses; synchronises. */
 
 #ifdef __cplusplus
 }
 #endif
 #include "ccv_mppi_fleet.h"
 #include "ccv_mppi_sense.h"
+#include "ccv_mppi_plan.h"
 #endif /* CCV_MPPI_H_ */
