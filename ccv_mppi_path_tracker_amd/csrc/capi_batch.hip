@@ -40,10 +40,9 @@ int batch_trig(const ccv_mppi_batch* bh, const int b, const RolloutArgs& A, cons
 int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const double* x_ref, const double* y_ref,
                   const double* yaw_ref0, const uint64_t* seed, uint64_t iter) {
     const int B = bh->B, H = bh->H, nx = bh->cfg.model == CCV_MPPI_FULL_BODY ? 5 : 3;
-    const int slot = bh->rec_next;
-    bh->rec_next = (slot + 1) % ccv_mppi_batch::kRecSlots;
-    if (bh->rec_used[slot]) HIP_TRY(bh, hipEventSynchronize(bh->rec_ev[slot]));
-    double* rec = bh->h_rec[slot];
+    Slot slot;
+    HIP_TRY(bh, bh->rec_ring.take(slot));
+    double* rec = reinterpret_cast<double*>(slot.host);
     std::memset(rec, 0, (size_t)B * bh->rec_doubles * sizeof(double));
     RolloutArgs A;
     fill_args(bh, A, x0, dt[0], yaw_ref0[0], seed[0], iter);
@@ -69,9 +68,8 @@ int batch_enqueue(ccv_mppi_batch* bh, const double* x0, const double* dt, const 
             trig = batch_trig(bh, b, A, trig);
         }
     }
-    HIP_TRY(bh, hipMemcpyAsync(bh->d_rec, rec, (size_t)B * bh->rec_doubles * sizeof(double), hipMemcpyHostToDevice, bh->stream));
-    HIP_TRY(bh, hipEventRecord(bh->rec_ev[slot], bh->stream));
-    bh->rec_used[slot] = true;
+    HIP_TRY(bh, bh->rec_ring.seal(slot, hipMemcpyAsync(bh->d_rec, rec, (size_t)B * bh->rec_doubles * sizeof(double), hipMemcpyHostToDevice, bh->stream),
+                                  bh->stream));
     return batch_launch(bh, A, trig, false);
 }
 
@@ -81,7 +79,7 @@ int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool 
     const int B = bh->B;
     const RolloutPlan plan = make_plan(*bh, bh->cfg.model, MODE_FUSED, trig, B, batch_form(bh), bh->min_shift);
     const bool plain = plan.family == KernelFamily::Plain;
-    A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
+    A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec.get());
     A.nparts = B * bh->nblocks;   // (partials [(R+1)][B * nblocks]: column = workgroup)
     A.fuse_update = plain ? 0 : 1;
     A.store_u = 1;
@@ -99,7 +97,7 @@ int batch_launch(ccv_mppi_batch* bh, RolloutArgs& A, const int trig, const bool 
     const bool shift = plan.shift && !plain;   // (the update over block-relative partials)
     if (plain) {   // the plain kernel stores w and the controls: the single handle's unfused reduction, instance by instance
         if (plan.shift) {   // ... over weights re-formed around every instance's exact minimum cost (the single handle's MIN_SHIFT)
-            if (!bh->d_cmin) HIP_TRY(bh, hipMalloc(&bh->d_cmin, (size_t)B * sizeof(double)));
+            if (!bh->d_cmin) HIP_TRY(bh, bh->d_cmin.alloc((size_t)B));
             hipLaunchKernelGGL(k_min_cost_batch, dim3(B), dim3(1024), 0, bh->stream, bh->d_cost, bh->K, bh->kpad, bh->d_cmin);
             hipLaunchKernelGGL(k_reweight_batch, dim3((bh->K + kBlock - 1) / kBlock, B), dim3(kBlock), 0, bh->stream, bh->d_cost,
                                bh->d_cmin, bh->d_params, bh->K, bh->kpad, bh->d_w);
@@ -202,11 +200,8 @@ int ccv_mppi_batch_create(const ccv_mppi_config* cfg, int32_t batch, ccv_mppi_ba
     if (int rc = create_buffers(bh, BufferCounts{nparts_max, /*nominal=*/B * R + pad, /*vec=*/B * (R + 1), /*stats=*/B * 4, &bh->d_rec,
                                                 B * bh->rec_doubles, /*pin_doubles=*/B * (R + 4) * 2, /*mail_slots=*/B * (R + 4)}))
         return bail(rc);
-    for (int s = 0; s < ccv_mppi_batch::kRecSlots; ++s) {
-        if ((e = hipEventCreateWithFlags(&bh->rec_ev[s], hipEventDisableTiming)) != hipSuccess) return bail(fail(bh, CCV_MPPI_ERR_HIP, "hipEventCreate", e));
-        if ((e = hipHostMalloc(&bh->h_rec[s], B * bh->rec_doubles * sizeof(double), hipHostMallocDefault)) != hipSuccess)
-            return bail(fail(bh, CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e));
-    }
+    if ((e = bh->rec_ring.create(ccv_mppi_batch::kRecSlots, B * bh->rec_doubles * sizeof(double), /*mapped=*/false)) != hipSuccess)
+        return bail(fail(bh, CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e));
     if (const char* mv = std::getenv("CCV_MPPI_BATCH_MAIL")) bh->mail_any_size = std::strcmp(mv, "1") == 0;
     *out = bh;
     return CCV_MPPI_OK;
@@ -217,16 +212,7 @@ int ccv_mppi_batch_destroy(ccv_mppi_batch* bh) {
     const DeviceGuard guard(bh->cfg.device);
     (void)hipSetDevice(bh->cfg.device);
     if (bh->stream) (void)batch_flush(bh);
-    release_buffers(bh);
-    bh->BatchRecords::release();
-    bh->BatchResident::release();
-    bh->ParamTable::release();
-    bh->Discs::release();
-    bh->Grids::release();
-    bh->Costmap::release();
-    bh->World::release();
-    bh->Plan::release();
-    bh->Fleet::release();
+    wait_for_streams(bh);
     delete bh;
     return CCV_MPPI_OK;
 }
@@ -358,25 +344,36 @@ int ccv_mppi_batch_resident_set_paths(ccv_mppi_batch* bh, const double* path_x, 
     }
     if (int rc = batch_flush(bh)) return rc;
     HIP_TRY(bh, hipStreamSynchronize(bh->stream));   // (a queued prologue may still read the old paths)
+    // every allocation comes before anything is dropped: a longer set gets a new path array (a shorter one reuses the present
+    // one), the first call the frames, the instances and the traces
+    DeviceArray<double> path, trace;
+    DeviceArray<ResidentFrame> frames;
+    DeviceArray<BatchInstance> rows;
+    const bool grow = total > bh->n_total || !bh->d_rpath, first = !bh->d_rframe;
+    if (grow) HIP_TRY(bh, path.alloc((size_t)2 * total));
+    const size_t trace_doubles = (size_t)B * CCV_MPPI_BATCH_TRACE_ROWS * 6;
+    if (first) {
+        HIP_TRY(bh, frames.alloc((size_t)B));
+        HIP_TRY(bh, rows.alloc((size_t)B));
+        HIP_TRY(bh, trace.alloc(trace_doubles));
+    }
+    double* const to = grow ? path.get() : bh->d_rpath.get();
+    HIP_TRY(bh, hipMemcpy(to, path_x, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(bh, hipMemcpy(to + total, path_y, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
+    if (first) {
+        HIP_TRY(bh, hipMemset(frames, 0, (size_t)B * sizeof(ResidentFrame)));
+        HIP_TRY(bh, hipMemset(trace, 0, trace_doubles * sizeof(double)));
+    }
+    HIP_TRY(bh, hipMemcpy(first ? rows.get() : bh->d_inst.get(), inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    // commit: nothing below fails
     bh->drop_plan();   // (the paths are the caller's again: ccv_mppi_batch_resident_set_plan comes after this call)
-    if (total > bh->n_total || !bh->d_rpath) {
-        if (bh->d_rpath) HIP_TRY(bh, hipFree(bh->d_rpath));
-        bh->d_rpath = nullptr;
-        bh->have_paths = false;
-        HIP_TRY(bh, hipMalloc(&bh->d_rpath, (size_t)2 * total * sizeof(double)));
+    if (grow) bh->d_rpath = std::move(path);
+    if (first) {
+        bh->d_rframe = std::move(frames);
+        bh->d_inst = std::move(rows);
+        bh->d_rtrace = std::move(trace);
     }
-    bh->n_total = total;   // (the y half starts at n_total; a shorter set reuses the array, a longer one reallocates it)
-    HIP_TRY(bh, hipMemcpy(bh->d_rpath, path_x, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(bh, hipMemcpy(bh->d_rpath + total, path_y, (size_t)total * sizeof(double), hipMemcpyHostToDevice));
-    if (!bh->d_rframe) {
-        const size_t trace_bytes = (size_t)B * CCV_MPPI_BATCH_TRACE_ROWS * 6 * sizeof(double);
-        HIP_TRY(bh, hipMalloc(&bh->d_rframe, (size_t)B * sizeof(ResidentFrame)));
-        HIP_TRY(bh, hipMemset(bh->d_rframe, 0, (size_t)B * sizeof(ResidentFrame)));
-        HIP_TRY(bh, hipMalloc(&bh->d_inst, (size_t)B * sizeof(BatchInstance)));
-        HIP_TRY(bh, hipMalloc(&bh->d_rtrace, trace_bytes));
-        HIP_TRY(bh, hipMemset(bh->d_rtrace, 0, trace_bytes));
-    }
-    HIP_TRY(bh, hipMemcpy(bh->d_inst, inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
+    bh->n_total = total;   // (the y half starts at n_total)
     bh->inst.swap(inst);
     bh->have_paths = true;
     return CCV_MPPI_OK;
@@ -401,7 +398,7 @@ int ccv_mppi_batch_resident_set_poses(ccv_mppi_batch* bh, const double* state, c
     HIP_TRY(bh, hipMemcpy2D(bh->d_rframe, sizeof(ResidentFrame), heads.data(), sizeof(FrameHead), sizeof(FrameHead), (size_t)B,
                            hipMemcpyHostToDevice));
     if (bh->plan)   // (the device's n_path is the truth while planning is set: the noise keys alone go up)
-        HIP_TRY(bh, hipMemcpy2D(&bh->d_inst->seed_lo, sizeof(BatchInstance), &bh->inst[0].seed_lo, sizeof(BatchInstance), 2 * sizeof(uint32_t),
+        HIP_TRY(bh, hipMemcpy2D(&bh->d_inst.get()->seed_lo, sizeof(BatchInstance), &bh->inst[0].seed_lo, sizeof(BatchInstance), 2 * sizeof(uint32_t),
                                (size_t)B, hipMemcpyHostToDevice));
     else HIP_TRY(bh, hipMemcpy(bh->d_inst, bh->inst.data(), (size_t)B * sizeof(BatchInstance), hipMemcpyHostToDevice));
     if (bh->fleet) {
@@ -496,7 +493,7 @@ int ccv_mppi_batch_resident_step_enqueue(ccv_mppi_batch* bh, double dt, uint64_t
     bh->res_steps += 1;
     bh->res_angle_abs.swap(nb);
     // the rollout reads every instance's record (batch_view): pose, window, dt, noise key, warm start
-    A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec);
+    A.frame = reinterpret_cast<const ResidentFrame*>(bh->d_rec.get());
     return batch_launch(bh, A, trig, true);
 }
 

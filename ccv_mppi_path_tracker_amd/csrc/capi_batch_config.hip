@@ -23,7 +23,7 @@ bool velocities_on(const ccv_mppi_batch* bh) { return moving_on(bh) || (bh->grid
 // the instances' present disc counts, BatchParams::n_obst as the last prologue left it (the static counts after a setter)
 int read_disc_counts(ccv_mppi_batch* bh, std::vector<int32_t>& total) {
     total.resize((size_t)bh->B);
-    HIP_TRY(bh, hipMemcpy2D(total.data(), sizeof(int32_t), reinterpret_cast<const char*>(bh->d_params) + offsetof(BatchParams, n_obst),
+    HIP_TRY(bh, hipMemcpy2D(total.data(), sizeof(int32_t), reinterpret_cast<const char*>(bh->d_params.get()) + offsetof(BatchParams, n_obst),
                            sizeof(BatchParams), sizeof(int32_t), (size_t)bh->B, hipMemcpyDeviceToHost));
     return CCV_MPPI_OK;
 }
@@ -58,7 +58,7 @@ int sync_tables(ccv_mppi_batch* bh) {
     if (velocities_on(bh)) {
         const size_t count = (size_t)B * M * 2;
         const std::vector<double> zeros(bh->moving ? 0 : count, 0.0);
-        if (!bh->d_obst_v) HIP_TRY(bh, hipMalloc(&bh->d_obst_v, count * sizeof(double)));
+        if (!bh->d_obst_v) HIP_TRY(bh, bh->d_obst_v.alloc(count));
         HIP_TRY(bh, hipMemcpy(bh->d_obst_v, bh->moving ? bh->obst_vxy.data() : zeros.data(), count * sizeof(double), hipMemcpyHostToDevice));
     }
     // the static counts, for the fleet's prologue
@@ -97,7 +97,7 @@ int sync_tables(ccv_mppi_batch* bh) {
         // (without discs a GRID kernel sees n_obst = 0 and reads neither table)
         if (bh->grid && bh->grid_map_of[(size_t)b] >= 0) P.grid = bh->d_grid_rows + b;
     }
-    if (!bh->d_params) HIP_TRY(bh, hipMalloc(&bh->d_params, (size_t)B * sizeof(BatchParams)));
+    if (!bh->d_params) HIP_TRY(bh, bh->d_params.alloc((size_t)B));
     HIP_TRY(bh, hipMemcpy(bh->d_params, rows.data(), (size_t)B * sizeof(BatchParams), hipMemcpyHostToDevice));
     return CCV_MPPI_OK;
 }
@@ -107,7 +107,7 @@ int fleet_restart(ccv_mppi_batch* bh, const double* xy) {
     const size_t half = (size_t)bh->B * 2;
     for (int h = 0; h < 2 && xy; ++h) HIP_TRY(bh, hipMemcpy(bh->d_fleet_xy + h * half, xy, half * sizeof(double), hipMemcpyHostToDevice));
     if (!bh->fleet_pred) return CCV_MPPI_OK;
-    if (!bh->d_fleet_v) HIP_TRY(bh, hipMalloc(&bh->d_fleet_v, 2 * half * sizeof(double)));
+    if (!bh->d_fleet_v) HIP_TRY(bh, bh->d_fleet_v.alloc(2 * half));
     HIP_TRY(bh, hipMemset(bh->d_fleet_v, 0, 2 * half * sizeof(double)));
     return CCV_MPPI_OK;
 }
@@ -213,7 +213,7 @@ int ccv_mppi_batch_set_obstacles(ccv_mppi_batch* bh, const double* xyr, const in
     std::vector<double> rows((size_t)B * M * 3, 0.0);
     for (int b = 0; b < B && !off; ++b)
         for (int j = 0; j < n[b]; ++j) std::memcpy(&rows[((size_t)b * M + j) * 3], xyr + ((size_t)b * max_n + j) * 3, 3 * sizeof(double));
-    if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, rows.size() * sizeof(double)));
+    if (!bh->d_obst) HIP_TRY(bh, bh->d_obst.alloc(rows.size()));
     HIP_TRY(bh, hipMemcpy(bh->d_obst, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
     bh->obst_xyr.swap(rows);
     if (off) bh->obst_n.assign((size_t)B, 0);
@@ -325,16 +325,21 @@ int ccv_mppi_batch_resident_set_fleet(ccv_mppi_batch* bh, const double* radius, 
         }
         return sync_tables(bh);   // (the static counts again)
     }
-    if (!bh->d_obst) HIP_TRY(bh, hipMalloc(&bh->d_obst, (size_t)B * M * 3 * sizeof(double)));
+    if (!bh->d_obst) HIP_TRY(bh, bh->d_obst.alloc((size_t)B * M * 3));
     if (!obst_on(bh)) {   // no static discs: empty lists
         bh->obst_xyr.assign((size_t)B * M * 3, 0.0);
         bh->obst_n.assign((size_t)B, 0);
         HIP_TRY(bh, hipMemcpy(bh->d_obst, bh->obst_xyr.data(), bh->obst_xyr.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     if (!bh->d_fleet_xy) {
-        HIP_TRY(bh, hipMalloc(&bh->d_fleet_xy, (size_t)B * 4 * sizeof(double)));
-        HIP_TRY(bh, hipMalloc(&bh->d_fleet_radius, (size_t)B * sizeof(double)));
-        HIP_TRY(bh, hipMalloc(&bh->d_fleet_nstatic, (size_t)B * sizeof(int32_t)));
+        DeviceArray<double> table, radii;   // (all three or none: the test above looks at the first alone)
+        DeviceArray<int32_t> counts;
+        HIP_TRY(bh, table.alloc((size_t)B * 4));
+        HIP_TRY(bh, radii.alloc((size_t)B));
+        HIP_TRY(bh, counts.alloc((size_t)B));
+        bh->d_fleet_xy = std::move(table);
+        bh->d_fleet_radius = std::move(radii);
+        bh->d_fleet_nstatic = std::move(counts);
     }
     HIP_TRY(bh, hipMemcpy(bh->d_fleet_radius, radius, (size_t)B * sizeof(double), hipMemcpyHostToDevice));
     // the position table from the current frames (zeros before the first _set_poses, which writes it again)

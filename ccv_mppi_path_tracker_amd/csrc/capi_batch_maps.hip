@@ -3,7 +3,7 @@
 // and range scans, and the simulated range sensor with its world (struct ccv_mppi_batch and its parts Grids, Costmap and World:
 // capi_internal.h).  Two shapes.  The setters have
 // capi_batch_config.hip's: validate (every check before anything changes), quiesce, commit the host-side state, sync_tables.
-// The *_enqueue calls: validate, take a slot of the staging ring, fill it, launch, seal it -- no flush of the deferred
+// The *_enqueue calls: validate, take a slot of the staging ring (Staging), fill it, launch, seal it -- no flush of the deferred
 // resident update (it reads no map), no allocation after the handle's first roll, no wait but for the launches that last read the slot.
 #include "capi_internal.h"
 #include "mppi_costmap_rects.h"
@@ -16,33 +16,6 @@ namespace ccv {
 float* cells_of(const ccv_mppi_batch* bh, const int m, const bool back) {
     const bool second = bh->occ && ((bh->layers[(size_t)m].front != 0) != back);
     return (second ? bh->d_cells_roll : bh->d_grid_cells) + bh->grid_offset[(size_t)m];
-}
-
-// ---- the staging ring of the *_enqueue calls (Costmap, capi_internal.h): the kernels read a slot in place --------------------
-// at the first _set_occupancy or _resident_set_plan (kept until destroy)
-int ring_create(ccv_mppi_batch* bh) {
-    if (bh->h_patch) return CCV_MPPI_OK;
-    HIP_TRY(bh, hipHostMalloc(&bh->h_patch, (size_t)Costmap::kPatchSlots * CCV_MPPI_OCC_PATCH_MAX_CELLS, hipHostMallocDefault));
-    HIP_TRY(bh, hipHostGetDevicePointer(reinterpret_cast<void**>(&bh->d_patch), bh->h_patch, 0));
-    for (hipEvent_t& e : bh->patch_ev) HIP_TRY(bh, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return CCV_MPPI_OK;
-}
-
-// the next slot, free to be filled: the call's only wait
-int slot_take(ccv_mppi_batch* bh, Slot& s) {
-    const int i = bh->patch_next;
-    bh->patch_next = (i + 1) % Costmap::kPatchSlots;
-    if (bh->patch_used[i]) HIP_TRY(bh, hipEventSynchronize(bh->patch_ev[i]));
-    s = Slot{i, bh->h_patch + (size_t)i * CCV_MPPI_OCC_PATCH_MAX_CELLS, bh->d_patch + (size_t)i * CCV_MPPI_OCC_PATCH_MAX_CELLS};
-    return CCV_MPPI_OK;
-}
-
-// after the last launch that reads the slot (launched: hipGetLastError() after it)
-int slot_seal(ccv_mppi_batch* bh, const Slot& s, const hipError_t launched) {
-    bh->patch_used[s.index] = true;
-    HIP_TRY(bh, launched);
-    HIP_TRY(bh, hipEventRecord(bh->patch_ev[s.index], bh->stream));
-    return CCV_MPPI_OK;
 }
 
 }  // namespace ccv
@@ -73,8 +46,7 @@ int check_map_roles(ccv_mppi_batch* bh, const char* who, const int32_t n_maps, c
 
 // the grid term off (the caller has quiesced): cells, layers and host copies go, null in every row of the table
 int maps_off(ccv_mppi_batch* bh) {
-    if (bh->d_grid_cells) HIP_TRY(bh, hipFree(bh->d_grid_cells));
-    bh->d_grid_cells = nullptr;
+    bh->d_grid_cells.reset();
     bh->drop_layers();
     bh->drop_world();   // (the anchors spoke of the old layers)
     bh->grid = false;
@@ -85,9 +57,10 @@ int maps_off(ccv_mppi_batch* bh) {
     return sync_tables(bh);
 }
 
-// A new set of maps takes the place of the old one (the caller has quiesced and filled `cells`, which the handle owns from here
-// on, at `offset`): the grid rows, the host copies, the old cells freed.  geo: the maps' geometry, cells null.
-int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, float* cells, std::vector<size_t>& offset, const int32_t* map_of,
+// A new set of maps takes the place of the old one (the caller has quiesced and filled `cells` at `offset`): the grid rows, the
+// host copies, the old cells freed.  `cells` is taken on success and only then; on a failure it stays the caller's, whose local
+// frees it.  geo: the maps' geometry, cells null.
+int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, DeviceArray<float>&& cells, std::vector<size_t>& offset, const int32_t* map_of,
                  const double* weight) {
     const int B = bh->B;
     std::vector<GridRow> rows((size_t)B);
@@ -105,14 +78,10 @@ int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, float* cel
         r.ny = g.ny;
         r.outside = g.outside;
     }
-    hipError_t e = bh->d_grid_rows ? hipSuccess : hipMalloc(&bh->d_grid_rows, (size_t)B * sizeof(GridRow));
+    hipError_t e = bh->d_grid_rows ? hipSuccess : bh->d_grid_rows.alloc((size_t)B);
     if (e == hipSuccess) e = hipMemcpy(bh->d_grid_rows, rows.data(), rows.size() * sizeof(GridRow), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(cells);
-        return fail(bh, CCV_MPPI_ERR_HIP, "the grid rows", e);
-    }
-    if (bh->d_grid_cells) (void)hipFree(bh->d_grid_cells);
-    bh->d_grid_cells = cells;
+    if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "the grid rows", e);
+    bh->d_grid_cells = std::move(cells);
     bh->grid_maps.swap(geo);
     bh->grid_offset.swap(offset);
     bh->grid_map_of.assign(map_of, map_of + B);
@@ -140,6 +109,10 @@ InflateArgs grown_args(const ccv_mppi_batch* bh, const int m, const int64_t x0, 
 }
 
 static_assert(kRollBands == kRollMaxRects, "a roll's bands and the rectangles its slot has room for");
+// a slot holds an entry table and, directly after it, a table of another type: the second starts aligned whatever the count
+static_assert(sizeof(RollEntry) % alignof(InflateArgs) == 0, "a roll's rectangles follow its entries");
+static_assert(sizeof(ScanEntry) % alignof(InflateArgs) == 0, "a scan's rectangles follow its entries");
+static_assert(sizeof(SenseEntry) % alignof(int32_t) == 0, "a sensing's beams follow its entries");
 
 }  // namespace
 
@@ -172,23 +145,20 @@ int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int3
     if (int rc = quiesce(bh)) return rc;   // (a queued rollout may still read the old table, rows and cells)
     if (off) return maps_off(bh);
     // the cells of all maps are one allocation, sized by the maps: a new set is a new one, the old one goes when that is filled
-    float* cells = nullptr;
-    HIP_TRY(bh, hipMalloc(&cells, total * sizeof(float)));
+    DeviceArray<float> cells;
+    HIP_TRY(bh, cells.alloc(total));
     std::vector<size_t> offset((size_t)n_maps);
     size_t at = 0;
     for (int m = 0; m < n_maps; ++m) {
         const size_t n = (size_t)maps[m].nx * (size_t)maps[m].ny;
         const hipError_t e = hipMemcpy(cells + at, maps[m].cells, n * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(cells);
-            return fail(bh, CCV_MPPI_ERR_HIP, "set_grids: copying the cells", e);
-        }
+        if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "set_grids: copying the cells", e);
         offset[(size_t)m] = at;
         at += n;
     }
     std::vector<ccv_mppi_grid> geo(maps, maps + n_maps);
     for (ccv_mppi_grid& g : geo) g.cells = nullptr;
-    if (int rc = install_maps(bh, geo, cells, offset, map_of, weight)) return rc;
+    if (int rc = install_maps(bh, geo, std::move(cells), offset, map_of, weight)) return rc;
     bh->drop_layers();   // (the cells are the caller's now)
     bh->drop_world();   // (the anchors spoke of the old layers)
     return sync_tables(bh);
@@ -254,15 +224,15 @@ int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* bh, const ccv_mppi_occupancy* m
     const DeviceGuard guard(bh->cfg.device);
     if (int rc = quiesce(bh)) return rc;   // (a queued rollout may still read the old table, rows and cells)
     if (off) return maps_off(bh);
-    if (int rc = ring_create(bh)) return rc;
+    HIP_TRY(bh, staging_create(bh));
     // cells, layers and profile tables of all maps: three allocations sized by the maps, filled before the old ones go
-    float *cells = nullptr, *profiles = nullptr;
-    uint8_t* layers = nullptr;
+    DeviceArray<float> cells, profiles;
+    DeviceArray<uint8_t> layers;
     std::vector<size_t> offset((size_t)n_maps);
     std::vector<Costmap::Layer> recs((size_t)n_maps);
-    hipError_t e = hipMalloc(&cells, total * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&layers, total);
-    if (e == hipSuccess) e = hipMalloc(&profiles, n_profile * sizeof(float));
+    hipError_t e = cells.alloc(total);
+    if (e == hipSuccess) e = layers.alloc(total);
+    if (e == hipSuccess) e = profiles.alloc(n_profile);
     size_t at = 0, pat = 0;
     for (int m = 0; m < n_maps && e == hipSuccess; ++m) {
         const size_t n = (size_t)maps[m].nx * (size_t)maps[m].ny, np = (size_t)inflation[m].radius * (size_t)inflation[m].radius + 1;
@@ -274,21 +244,15 @@ int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* bh, const ccv_mppi_occupancy* m
         at += n;
         pat += np;
     }
-    if (e != hipSuccess) {
-        free_device({cells, layers, profiles});
-        return fail(bh, CCV_MPPI_ERR_HIP, "set_occupancy: allocating or copying the layers", e);
-    }
+    if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "set_occupancy: allocating or copying the layers", e);
     std::vector<ccv_mppi_grid> geo((size_t)n_maps);
     for (int m = 0; m < n_maps; ++m)
         geo[(size_t)m] = ccv_mppi_grid{maps[m].origin_x, maps[m].origin_y, maps[m].resolution, maps[m].outside, maps[m].nx, maps[m].ny, nullptr};
-    if (int rc = install_maps(bh, geo, cells, offset, map_of, weight)) {
-        free_device({layers, profiles});
-        return rc;
-    }
+    if (int rc = install_maps(bh, geo, std::move(cells), offset, map_of, weight)) return rc;
     bh->drop_layers();
     bh->drop_world();   // (the anchors spoke of the old layers)
-    bh->d_occ = layers;
-    bh->d_profile = profiles;
+    bh->d_occ = std::move(layers);
+    bh->d_profile = std::move(profiles);
     bh->layers.swap(recs);
     bh->occ = true;
     // one full inflation per map; the stream is idle again before the tables point at the cells
@@ -309,10 +273,10 @@ int ccv_mppi_batch_update_occupancy_enqueue(ccv_mppi_batch* bh, int32_t map, int
     if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > g.nx - x0 || h > g.ny - y0) return refuse(bh, who, "the rectangle is not inside the map");
     if ((int64_t)w * h > CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "more than CCV_MPPI_OCC_PATCH_MAX_CELLS cells");
     Slot slot;
-    if (int rc = slot_take(bh, slot)) return rc;
+    HIP_TRY(bh, bh->ring.take(slot));
     std::memcpy(slot.host, patch, (size_t)w * (size_t)h);
     launch_occupancy_patch(layer_of(bh, map), g.nx, slot.device, x0, y0, w, h, bh->stream);
-    if (int rc = slot_seal(bh, slot, hipGetLastError())) return rc;
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));
     launch_inflate(grown_args(bh, map, x0, y0, (int64_t)x0 + w, (int64_t)y0 + h), bh->stream);
     HIP_TRY(bh, hipGetLastError());
     return CCV_MPPI_OK;
@@ -362,20 +326,17 @@ int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
         if (int rc = quiesce(bh)) return rc;
         const ccv_mppi_grid& last = bh->grid_maps.back();
         const size_t total = bh->grid_offset.back() + (size_t)last.nx * (size_t)last.ny;
-        uint8_t* layers = nullptr;
-        float* cells = nullptr;
-        hipError_t e = hipMalloc(&layers, total);
-        if (e == hipSuccess) e = hipMalloc(&cells, total * sizeof(float));
-        if (e != hipSuccess) {
-            free_device({layers, cells});
-            return fail(bh, CCV_MPPI_ERR_HIP, "roll_occupancy: allocating the second set of layers and cells", e);
-        }
-        bh->d_occ_roll = layers;
-        bh->d_cells_roll = cells;
+        DeviceArray<uint8_t> layers;
+        DeviceArray<float> cells;
+        hipError_t e = layers.alloc(total);
+        if (e == hipSuccess) e = cells.alloc(total);
+        if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "roll_occupancy: allocating the second set of layers and cells", e);
+        bh->d_occ_roll = std::move(layers);
+        bh->d_cells_roll = std::move(cells);
     }
     if (moved == 0) return CCV_MPPI_OK;   // (nothing moves: no launch, no bit changes)
     Slot slot;
-    if (int rc = slot_take(bh, slot)) return rc;
+    HIP_TRY(bh, bh->ring.take(slot));
     // the slot: the entries, the rectangles, the strips (the kernels read all three in place)
     RollEntry* entries = reinterpret_cast<RollEntry*>(slot.host);
     InflateArgs* rects = reinterpret_cast<InflateArgs*>(slot.host + entry_bytes);
@@ -410,7 +371,8 @@ int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     }
     launch_roll_shift(reinterpret_cast<const RollEntry*>(slot.device), (int32_t)n_entries, max_cells, bh->d_grid_rows, bh->B, bh->stream);
     launch_inflate_rects(reinterpret_cast<const InflateArgs*>(slot.device + entry_bytes), (int32_t)n_rects, max_tiles, bh->stream);
-    return slot_seal(bh, slot, hipGetLastError());   // (after the second launch: both read the slot)
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));   // (after the second launch: both read the slot)
+    return CCV_MPPI_OK;
 }
 
 // Two launches however many maps are scanned; the front buffers are written in place (Layer::front, the grid rows: untouched).
@@ -462,7 +424,7 @@ int ccv_mppi_batch_scan_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     }
     if (traced == 0) return CCV_MPPI_OK;   // (nothing is traced: no launch, no bit changes)
     Slot slot;
-    if (int rc = slot_take(bh, slot)) return rc;
+    HIP_TRY(bh, bh->ring.take(slot));
     // the slot: the entries, the rectangles, the end cells, the hit bytes (the kernels read all four in place)
     const size_t end_at = entry_bytes + rect_bytes, hit_at = end_at + (size_t)total * 2 * sizeof(int32_t);
     ScanEntry* entries = reinterpret_cast<ScanEntry*>(slot.host);
@@ -489,7 +451,8 @@ int ccv_mppi_batch_scan_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     }
     launch_scan_trace(reinterpret_cast<const ScanEntry*>(slot.device), (int32_t)traced, bh->stream);
     launch_inflate_rects(reinterpret_cast<const InflateArgs*>(slot.device + entry_bytes), (int32_t)traced, max_tiles, bh->stream);
-    return slot_seal(bh, slot, hipGetLastError());   // (after the second launch: both read the slot)
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));   // (after the second launch: both read the slot)
+    return CCV_MPPI_OK;
 }
 
 // ---- the simulated range sensor: a ground-truth world, and the resident robots' beams cast through it (mppi_costmap_sense.h) ----
@@ -519,27 +482,24 @@ int ccv_mppi_batch_set_world(ccv_mppi_batch* bh, const ccv_mppi_occupancy* world
     // the world, the read-back and the rectangle table: four allocations, filled before the old ones go
     const size_t cells = (size_t)world->nx * (size_t)world->ny, first_bytes = (size_t)bh->B * (size_t)max_beams * sizeof(int32_t);
     const size_t cell_bytes = (size_t)bh->B * 2 * sizeof(int32_t);
-    uint8_t* layer = nullptr;
-    int32_t *first = nullptr, *sensor = nullptr;
-    InflateArgs* rects = nullptr;
-    hipError_t e = hipMalloc(&layer, cells);
-    if (e == hipSuccess) e = hipMalloc(&first, first_bytes);
-    if (e == hipSuccess) e = hipMalloc(&sensor, cell_bytes);
-    if (e == hipSuccess) e = hipMalloc(&rects, (size_t)bh->B * sizeof(InflateArgs));
+    DeviceArray<uint8_t> layer;
+    DeviceArray<int32_t> first, sensor;
+    DeviceArray<InflateArgs> rects;
+    hipError_t e = layer.alloc(cells);
+    if (e == hipSuccess) e = first.alloc(first_bytes / sizeof(int32_t));
+    if (e == hipSuccess) e = sensor.alloc(cell_bytes / sizeof(int32_t));
+    if (e == hipSuccess) e = rects.alloc((size_t)bh->B);
     if (e == hipSuccess) e = hipMemcpy(layer, world->cells, cells, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemsetAsync(first, 0xFF, first_bytes, bh->stream);   // (-1: no beam blocked, nothing sensed)
     if (e == hipSuccess) e = hipMemsetAsync(sensor, 0xFF, cell_bytes, bh->stream);
     if (e == hipSuccess) e = hipMemsetAsync(rects, 0, (size_t)bh->B * sizeof(InflateArgs), bh->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(bh->stream);
-    if (e != hipSuccess) {
-        free_device({layer, first, sensor, rects});
-        return fail(bh, CCV_MPPI_ERR_HIP, "set_world: allocating or copying the world", e);
-    }
+    if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "set_world: allocating or copying the world", e);
     bh->drop_world();
-    bh->d_world = layer;
-    bh->d_sense_first = first;
-    bh->d_sense_cell = sensor;
-    bh->d_sense_rects = rects;
+    bh->d_world = std::move(layer);
+    bh->d_sense_first = std::move(first);
+    bh->d_sense_cell = std::move(sensor);
+    bh->d_sense_rects = std::move(rects);
     bh->world_geo = *world;
     bh->world_geo.cells = nullptr;
     bh->world_anchor.assign(anchor_xy, anchor_xy + 2 * n_maps);
@@ -579,10 +539,11 @@ int ccv_mppi_batch_update_world_enqueue(ccv_mppi_batch* bh, int32_t x0, int32_t 
     if (w < 1 || h < 1 || x0 < 0 || y0 < 0 || w > g.nx - x0 || h > g.ny - y0) return refuse(bh, who, "the rectangle is not inside the world");
     if ((int64_t)w * h > CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "more than CCV_MPPI_OCC_PATCH_MAX_CELLS cells");
     Slot slot;
-    if (int rc = slot_take(bh, slot)) return rc;
+    HIP_TRY(bh, bh->ring.take(slot));
     std::memcpy(slot.host, patch, (size_t)w * (size_t)h);
     launch_occupancy_patch(bh->d_world, g.nx, slot.device, x0, y0, w, h, bh->stream);
-    return slot_seal(bh, slot, hipGetLastError());
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));
+    return CCV_MPPI_OK;
 }
 
 // Two launches however many robots sense: the beams (k_sense_trace, which also writes the rectangles into device memory) and
@@ -629,7 +590,7 @@ int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const i
         A.max_dy = std::max(A.max_dy, dy);
     }
     Slot slot;
-    if (int rc = slot_take(bh, slot)) return rc;
+    HIP_TRY(bh, bh->ring.take(slot));
     // the slot: the entries, the beams (the kernel reads both in place)
     SenseEntry* entries = reinterpret_cast<SenseEntry*>(slot.host);
     std::memcpy(slot.host + entry_bytes, beam_xy, beam_bytes);
@@ -665,7 +626,8 @@ int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     }
     launch_sense_trace(reinterpret_cast<const SenseEntry*>(slot.device), bh->d_sense_rects, n, A, bh->stream);
     launch_inflate_rects(bh->d_sense_rects, n, max_tiles, bh->stream);
-    return slot_seal(bh, slot, hipGetLastError());   // (after the second launch; only the first reads the slot)
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));   // (after the second launch; only the first reads the slot)
+    return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_resident_read_sense(ccv_mppi_batch* bh, int32_t* first, int32_t* sensor_cell) {

@@ -1,6 +1,6 @@
 // C ABI, batch handles: paths planned on the device (include/ccv_mppi_plan.h; mppi_plan.h; struct ccv_mppi_batch's part Plan:
 // capi_internal.h).  _set_plan has the setters' shape: validate (every check before anything changes), quiesce, allocate, commit.
-// _plan_enqueue has the *_enqueue calls' (capi_batch_maps.hip): validate, take a slot of the staging ring, fill it, launch, seal it --
+// _plan_enqueue has the *_enqueue calls' (capi_batch_maps.hip): validate, take a slot of the staging ring (Staging: capi_internal.h), fill it, launch, seal it --
 // no flush of the deferred resident update (it writes u*, which no plan reads), no allocation, no wait but for the launch that
 // last read the slot.  The host reads no pose: an entry carries the address of the instance's resident pose.
 #include "capi_internal.h"
@@ -44,7 +44,7 @@ int ccv_mppi_batch_resident_set_plan(ccv_mppi_batch* bh, const int32_t* capacity
         bh->drop_plan();
         return CCV_MPPI_OK;
     }
-    if (int rc = ring_create(bh)) return rc;
+    HIP_TRY(bh, staging_create(bh));
     // the paths laid out again with room for max(n_path, capacity) poses per instance; the present paths copied
     std::vector<int64_t> off(B);
     int64_t total = 0;
@@ -58,12 +58,12 @@ int ccv_mppi_batch_resident_set_plan(ccv_mppi_batch* bh, const int32_t* capacity
         const int32_t never[kPlanResultInts] = {0, 0, -1, -1, -1, 0};
         std::memcpy(&rows[b * kPlanResultInts], never, sizeof(never));
     }
-    double* path = nullptr;
-    int32_t* result = nullptr;
-    uint16_t* fields = nullptr;
-    hipError_t e = hipMalloc(&path, (size_t)2 * (size_t)total * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&result, rows.size() * sizeof(int32_t));
-    if (e == hipSuccess && n_fields) e = hipMalloc(&fields, n_fields * (size_t)CCV_MPPI_PLAN_MAX_FIELD * sizeof(uint16_t));
+    DeviceArray<double> path;
+    DeviceArray<int32_t> result;
+    DeviceArray<uint16_t> fields;
+    hipError_t e = path.alloc((size_t)2 * (size_t)total);
+    if (e == hipSuccess) e = result.alloc(rows.size());
+    if (e == hipSuccess && n_fields) e = fields.alloc(n_fields * (size_t)CCV_MPPI_PLAN_MAX_FIELD);
     if (e == hipSuccess) e = hipMemset(path, 0, (size_t)2 * (size_t)total * sizeof(double));
     if (e == hipSuccess) e = hipMemcpy(result, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     for (size_t b = 0; b < B && e == hipSuccess; ++b) {
@@ -74,25 +74,22 @@ int ccv_mppi_batch_resident_set_plan(ccv_mppi_batch* bh, const int32_t* capacity
     for (size_t b = 0; b < B; ++b) inst[b].path_off = off[b];
     if (e == hipSuccess) e = hipMemcpy(bh->d_inst, inst.data(), B * sizeof(BatchInstance), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        // (d_inst is only written after every other step went well: on a failure the old layout stands)
-        free_device({path, result, fields});
-        return fail(bh, CCV_MPPI_ERR_HIP, "resident_set_plan: allocating or copying the paths", e);
-    }
-    (void)hipFree(bh->d_rpath);
+    // (d_inst is only written after every other step went well: on a failure the old layout stands)
+    if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "resident_set_plan: allocating or copying the paths", e);
+    const bool keep = (bool)fields;
     bh->drop_plan();
-    bh->d_rpath = path;
+    bh->d_rpath = std::move(path);
     bh->n_total = total;
     bh->inst.swap(inst);
-    bh->d_plan_result = result;
-    bh->d_plan_fields = fields;
+    bh->d_plan_result = std::move(result);
+    bh->d_plan_fields = std::move(fields);
     bh->plan_capacity.assign(capacity, capacity + B);
     bh->plan_field_of.assign(B, -1);
     bh->plan_dims.assign(2 * B, 0);
     int32_t at = 0;
-    for (size_t b = 0; b < B && fields; ++b)
+    for (size_t b = 0; b < B && keep; ++b)
         if (capacity[b] > 0) bh->plan_field_of[b] = at++;
-    bh->plan_keep = fields != nullptr;
+    bh->plan_keep = keep;
     bh->plan = true;
     return CCV_MPPI_OK;
 }
@@ -135,7 +132,7 @@ int ccv_mppi_batch_resident_plan_enqueue(ccv_mppi_batch* bh, int32_t n, const in
             return refuse(bh, who, "a path's resolution differs from its map's");
     }
     Slot slot;
-    if (int rc = slot_take(bh, slot)) return rc;
+    HIP_TRY(bh, bh->ring.take(slot));
     PlanEntry* entries = reinterpret_cast<PlanEntry*>(slot.host);
     for (int i = 0; i < n; ++i) {
         const size_t b = (size_t)instance[i];
@@ -163,7 +160,8 @@ int ccv_mppi_batch_resident_plan_enqueue(ccv_mppi_batch* bh, int32_t n, const in
         bh->plan_dims[2 * b + 1] = g.ny;
     }
     launch_plan_field(reinterpret_cast<const PlanEntry*>(slot.device), n, lethal, max_sweeps, bh->stream);
-    return slot_seal(bh, slot, hipGetLastError());
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));
+    return CCV_MPPI_OK;
 }
 
 int ccv_mppi_batch_resident_read_plan(ccv_mppi_batch* bh, int32_t* status, int32_t* poses, int32_t* start_cell, int32_t* start_dist, int32_t* sweeps) {

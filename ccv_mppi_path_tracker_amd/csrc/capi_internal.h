@@ -9,7 +9,8 @@
 //                        stream-ordered patches, rolls and scans of those
 //   capi_batch_feed.hip  batch handles: best candidates and optimal paths of every instance (mppi_feed.h)
 //   capi_batch_plan.hip  batch handles: paths planned on the device from the maps to goal cells (mppi_plan.h)
-// A handle is made of named parts (below).  Core is what a single handle and a batch handle both have; the shared functions
+// A handle is made of named parts (below).  A part owns what it allocates, by type (capi_owned.h): device arrays, pinned staging
+// and events go with the part, nothing is freed by a list; a raw pointer in a part is a view into an array declared beside it.  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
 // Everything here is C++ with internal names (namespace ccv): only the ccv_mppi_* entry points are extern "C".
 #pragma once
@@ -22,10 +23,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <string>
 #include <vector>
 
+#include "capi_owned.h"
 #include "fast_trig.h"
 #include "mppi_kernels.h"
 #include "mppi_launch.h"
@@ -53,24 +54,24 @@ struct KernelChoice {
 };
 
 struct DeviceBuffers {
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    double* d_nominal = nullptr;
-    double* d_u = nullptr;
-    void* d_arena = nullptr;           // one allocation behind u, z, xs, ys, cost, w, partial (2 MB-aligned pieces)
-    float* d_z = nullptr;              // the fused iteration stores the normals in place of the controls (mppi_kernels.h)
-    double* d_nom_used = nullptr;      // ... and the warm start they were drawn around
+    Stream own_stream;                 // (first: the stream outlives every array and event of the handle)
+    hipStream_t stream = nullptr;      // own_stream, or the caller's (set_stream)
+    DeviceArray<double> d_nominal;
+    DeviceArray<char> d_arena;         // one allocation behind u, z, xs, ys, cost, w, partial (2 MB-aligned pieces)
+    double* d_u = nullptr;             // a view into d_arena
+    float* d_z = nullptr;              // a view into d_arena; the fused iteration stores the normals in place of the controls (mppi_kernels.h)
+    DeviceArray<double> d_nom_used;    // ... and the warm start they were drawn around
     bool controls_in_z = false;        // d_u is stale: the controls of the last iteration are (d_z, d_nom_used)
-    double* d_xs = nullptr;
+    double* d_xs = nullptr;            // views into d_arena, these five
     double* d_ys = nullptr;
     double* d_cost = nullptr;
     double* d_w = nullptr;
     double* d_partial = nullptr;
-    double* d_statpart = nullptr;
-    double* d_vec = nullptr;
-    double* d_stats = nullptr;
-    unsigned long long* d_dbg = nullptr;   // -DCCV_DIAG builds only (mppi_diag.h): the kernels' stamp buffer
-    double* d_scratch = nullptr;           // read-back staging (ensure_scratch)
+    DeviceArray<double> d_statpart;
+    DeviceArray<double> d_vec;
+    DeviceArray<double> d_stats;
+    DeviceArray<unsigned long long> d_dbg;   // -DCCV_DIAG builds only (mppi_diag.h): the kernels' stamp buffer
+    DeviceArray<double> d_scratch;           // read-back staging (ensure_scratch)
     size_t scratch_bytes = 0;
     int nparts_last = 0;   // number of partial columns the last cost evaluation produced (fused: workgroups, else: chunks)
     double inj_absmax[CCV_MPPI_MAX_UDIM] = {0, 0, 0, 0, 0};   // largest |control| per dimension in the buffer (sampled: clamp bound)
@@ -80,10 +81,10 @@ struct DeviceBuffers {
 // result mailbox of the blocking calls (FinalizeArgs::mail): pinned host-mapped memory the update kernel writes; and the pinned
 // host staging the result is decoded or copied into
 struct Mailbox {
-    double* h_pin = nullptr;
+    PinnedArray<double> h_pin;
     size_t pin_doubles = 0;
-    unsigned long long* h_mail = nullptr;
-    unsigned long long* d_mail = nullptr;   // its device address
+    PinnedArray<unsigned long long> h_mail;
+    unsigned long long* d_mail = nullptr;   // a view: h_mail as the device addresses it
     uint32_t mail_seq = 0;
     bool want_mail = false;      // the next plain update launch posts its result (set by the blocking entry points)
     bool mail_pending = false;   // ... and that launch is in flight: read_mail() polls the mailbox
@@ -95,7 +96,7 @@ struct Mailbox {
 // kThrottleEvery-th enqueue records an event and waits for the one recorded kThrottleSlots marks earlier
 struct Throttle {
     static constexpr int kThrottleEvery = 16, kThrottleSlots = 3;
-    hipEvent_t throttle_ev[kThrottleSlots] = {nullptr, nullptr, nullptr};
+    Event throttle_ev[kThrottleSlots];   // (its own rotation rule: the slot comes from the count)
     bool throttle_used[kThrottleSlots] = {false, false, false};
     uint64_t enqueued = 0;
     bool throttle = true;   // CCV_MPPI_THROTTLE=0 disables (experiments)
@@ -105,7 +106,7 @@ struct Timing {
     bool timing = false;
     int timing_every = 1;     // record events on every n-th iteration only
     int64_t timing_count = 0;
-    std::vector<hipEvent_t> ev;  // triples: rollout kernel begin, rollout kernel end, end of the launch sequence
+    std::vector<Event> ev;       // triples: rollout kernel begin, rollout kernel end, end of the launch sequence
     bool timed_now = false;      // the launch being enqueued is timed (timing_begin .. timing_end): its triple is
     size_t ev_slot = 0;          // ev[ev_slot .. ev_slot + 2]
     size_t ev_used = 0;
@@ -131,6 +132,8 @@ struct DeferredUpdate {
     UpdatePlan fin{};
 };
 
+// (the order of the bases matters: DeviceBuffers, whose first member is the stream, comes before every base that holds an event
+// or pinned memory, so the stream is destroyed after all of them)
 struct Core : Shape, KernelChoice, DeviceBuffers, Mailbox, Throttle, Timing, DeferredUpdate {
     std::string err;
 };
@@ -140,14 +143,14 @@ struct StageState {
     bool have_controls = false, have_rollout = false, have_weights = false;
     double st_x0[5] = {0, 0, 0, 0, 0};
     double st_dt = 0.1;
-    double* d_cmin = nullptr;   // CCV_MPPI_FLAG_MIN_SHIFT: the global minimum cost
+    DeviceArray<double> d_cmin;   // CCV_MPPI_FLAG_MIN_SHIFT: the global minimum cost
 };
 
 // device-resident closed loop (mppi_resident.h)
 struct ResidentLoop {
-    ResidentFrame* d_frame = nullptr;
-    double* d_path = nullptr;    // [2][n_path]: x then y
-    double* d_trace = nullptr;   // [kTraceRows][6]
+    DeviceArray<ResidentFrame> d_frame;
+    DeviceArray<double> d_path;    // [2][n_path]: x then y
+    DeviceArray<double> d_trace;   // [kTraceRows][6]
     static constexpr int kTraceRows = 8192;
     int n_path = 0;
     double path_resolution = 0.0;
@@ -178,6 +181,7 @@ struct Exchange {
 
 using namespace ccv;
 
+// (Core first: its stream outlives the arrays of the parts after it; Exchange is released by hand before the delete)
 struct ccv_mppi_handle : Core, StageState, ResidentLoop, Exchange {
     // deferred division: u* = pending_vec[1..] / pending_vec[0] (ccv_mppi_apply_partials_enqueue, the exchange); the next fused
     // rollout divides while it stages the warm start, any other reader gets k_apply_partials first (flush_division)
@@ -187,42 +191,25 @@ struct ccv_mppi_handle : Core, StageState, ResidentLoop, Exchange {
 // ---- a batch handle only (ccv_mppi_batch_*) -----------------------------------------------------------------------------
 namespace ccv {
 
-// a part's release(): its device allocations go (a null pointer: one it never made)
-inline void free_device(std::initializer_list<void*> ptrs) {
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-}
-
 // the instances' records: per call, poses, dt, windows and noise keys go to the device as one block
 struct BatchRecords {
     int rec_doubles = 0;
-    double* d_rec = nullptr;                        // [B][rec_doubles]: BatchHead + window a[H], b[H], c[H] per instance
-    static constexpr int kRecSlots = 4;             // pinned staging of the records, in rotation: a slot is refilled only
-    double* h_rec[kRecSlots] = {nullptr, nullptr, nullptr, nullptr};   // after the copy that read it has run
-    hipEvent_t rec_ev[kRecSlots] = {nullptr, nullptr, nullptr, nullptr};
-    bool rec_used[kRecSlots] = {false, false, false, false};
-    int rec_next = 0;
-    void release() {
-        for (hipEvent_t e : rec_ev)
-            if (e) (void)hipEventDestroy(e);
-        for (double* h : h_rec)
-            if (h) (void)hipHostFree(h);
-        free_device({d_rec});
-    }
+    DeviceArray<double> d_rec;                      // [B][rec_doubles]: BatchHead + window a[H], b[H], c[H] per instance
+    static constexpr int kRecSlots = 4;             // pinned staging of the records: kRecSlots slots of B * rec_doubles doubles,
+    StagingRing rec_ring;                           // not mapped -- the reader of a slot is batch_enqueue's hipMemcpyAsync
 };
 
 // device-resident closed loop of every instance (ccv_mppi_batch_resident_*, mppi_resident.h)
 struct BatchResident {
-    ResidentFrame* d_rframe = nullptr;      // [B]
-    BatchInstance* d_inst = nullptr;        // [B]
-    double* d_rpath = nullptr;              // [2][n_total]
-    double* d_rtrace = nullptr;             // [B][CCV_MPPI_BATCH_TRACE_ROWS][6]
+    DeviceArray<ResidentFrame> d_rframe;    // [B]
+    DeviceArray<BatchInstance> d_inst;      // [B]
+    DeviceArray<double> d_rpath;            // [2][n_total]
+    DeviceArray<double> d_rtrace;           // [B][CCV_MPPI_BATCH_TRACE_ROWS][6]
     int64_t n_total = 0;
     std::vector<BatchInstance> inst;        // host copy of d_inst
     std::vector<double> res_angle_abs;      // [B][3]: bounds on |yaw|, |roll|, |pitch| of every resident pose
     bool have_paths = false, have_poses = false;
     int64_t res_steps = 0;                  // resident ticks since the poses were set (every instance's step count)
-    void release() { free_device({d_rframe, d_inst, d_rpath, d_rtrace}); }
 };
 
 // per-instance parameters (ccv_mppi_batch_set_params): the VARIED kernels read instance b's row of d_params through the
@@ -232,11 +219,10 @@ struct BatchResident {
 struct ParamTable {
     bool varied = false;
     std::vector<ccv_mppi_config> cfgs;      // [B] the instances' configurations while varied
-    BatchParams* d_params = nullptr;        // [B], allocated when a form from Varied up first needs it (sync_tables), freed at destroy
+    DeviceArray<BatchParams> d_params;      // [B], allocated when a form from Varied up first needs it (sync_tables), kept until destroy
     bool min_shift = false;
-    double* d_cmin = nullptr;               // [B]: the plain family's exact instance minima (k_min_cost_batch)
+    DeviceArray<double> d_cmin;             // [B]: the plain family's exact instance minima (k_min_cost_batch)
     bool shift_result = false;              // the last launch left block-relative weights in d_w (ccv_mppi_batch_read_weights)
-    void release() { free_device({d_params, d_cmin}); }
 };
 
 // disc obstacles (ccv_mppi_batch_set_obstacles): the OBST rollout kernels, always over the parameter table too; the rows of
@@ -245,42 +231,39 @@ struct ParamTable {
 // the caller gave a velocity (a neighbour's disc under fleet prediction: what the prologue wrote this tick).
 struct Discs {
     bool obst = false;
-    double* d_obst = nullptr;               // [B][CCV_MPPI_MAX_OBSTACLES][3], allocated at the first _set_obstacles, freed at destroy
+    DeviceArray<double> d_obst;             // [B][CCV_MPPI_MAX_OBSTACLES][3], allocated at the first _set_obstacles, kept until destroy
     std::vector<double> obst_xyr;           // [B][CCV_MPPI_MAX_OBSTACLES][3] host copy while obst
     std::vector<int32_t> obst_n;            // [B]
     std::vector<double> obst_w;             // [B]
     bool moving = false;
-    double* d_obst_v = nullptr;             // [B][CCV_MPPI_MAX_OBSTACLES][2], allocated when first needed (sync_tables), freed at destroy
+    DeviceArray<double> d_obst_v;           // [B][CCV_MPPI_MAX_OBSTACLES][2], allocated when first needed (sync_tables), kept until destroy
     std::vector<double> obst_vxy;           // [B][CCV_MPPI_MAX_OBSTACLES][2] host copy while moving
-    void release() { free_device({d_obst, d_obst_v}); }
 };
 
 // occupancy grids (ccv_mppi_batch_set_grids): the GRID rollout kernels while `grid`.  A grid plan is a moving plan: without
 // discs the kernels see n_obst = 0 and read neither disc nor velocity rows; with discs and no velocities, d_obst_v is zero.
 struct Grids {
     bool grid = false;
-    GridRow* d_grid_rows = nullptr;         // [B], a row per instance (BatchParams::grid points at it, or is null)
-    float* d_grid_cells = nullptr;          // the cells of all maps, one allocation
+    DeviceArray<GridRow> d_grid_rows;       // [B], a row per instance (BatchParams::grid points at it, or is null)
+    DeviceArray<float> d_grid_cells;        // the cells of all maps, one allocation
     std::vector<ccv_mppi_grid> grid_maps;   // host copy of the maps' geometry (cells: null)
     std::vector<size_t> grid_offset;        // [n_maps] first cell of map m in d_grid_cells
     std::vector<int32_t> grid_map_of;       // [B]
     std::vector<double> grid_w;             // [B]
-    void release() { free_device({d_grid_rows, d_grid_cells}); }
 };
 
 // occupancy layers (ccv_mppi_batch_set_occupancy, mppi_costmap.h): while `occ`, the cells of Grids are not a caller's but derived
 // on the device from a uint8 layer per map (same geometry, same offsets: layer m starts at d_occ + grid_offset[m]) and the map's
 // inflation; patches of a layer, rolls of the maps' windows and range scans traced into the layers are enqueued on the stream
-// (ccv_mppi_batch_update_ / _roll_ / _scan_occupancy_enqueue) through the staging ring, which is allocated at the first
-// _set_occupancy and kept until destroy (capi_batch_maps.hip: ring_create, slot_take, slot_seal).
+// (ccv_mppi_batch_update_ / _roll_ / _scan_occupancy_enqueue) through the staging ring (Staging, below).
 struct Costmap {
     bool occ = false;
-    uint8_t* d_occ = nullptr;                // the layers of all maps, one allocation
-    float* d_profile = nullptr;              // the profile tables of all maps, one allocation
+    DeviceArray<uint8_t> d_occ;              // the layers of all maps, one allocation
+    DeviceArray<float> d_profile;            // the profile tables of all maps, one allocation
     // rolling maps (mppi_costmap_roll.h): a second allocation of the layers and of the float cells, same sizes and offsets, made at
-    // the first roll and freed with the layers.  A roll writes the one that does not hold the map and flips Layer::front.
-    uint8_t* d_occ_roll = nullptr;
-    float* d_cells_roll = nullptr;
+    // the first roll and dropped with the layers.  A roll writes the one that does not hold the map and flips Layer::front.
+    DeviceArray<uint8_t> d_occ_roll;
+    DeviceArray<float> d_cells_roll;
     struct Layer {
         size_t profile_offset;               // first entry of the map's table in d_profile
         int32_t threshold, radius;           // radius: R, in cells
@@ -290,26 +273,15 @@ struct Costmap {
         double ox0, oy0;                     // ... and the origin it was given
     };
     std::vector<Layer> layers;               // [n_maps]
-    static constexpr int kPatchSlots = CCV_MPPI_OCC_PATCH_SLOTS;   // pinned staging of the patches, in rotation: a slot is refilled
-    uint8_t* h_patch = nullptr;              // only after the writer that read it has run; [kPatchSlots][CCV_MPPI_OCC_PATCH_MAX_CELLS]
-    uint8_t* d_patch = nullptr;              // its device address (the patch writer reads the slots in place)
-    hipEvent_t patch_ev[kPatchSlots] = {};
-    bool patch_used[kPatchSlots] = {};
-    int patch_next = 0;
-    // the layers and tables go (the maps become a caller's, or none); the ring stays
-    void drop_layers() {
-        free_device({d_occ, d_profile, d_occ_roll, d_cells_roll});
-        d_occ = d_occ_roll = nullptr;
-        d_profile = d_cells_roll = nullptr;
-        layers.clear();
-        occ = false;
-    }
-    void release() {
-        for (hipEvent_t e : patch_ev)
-            if (e) (void)hipEventDestroy(e);
-        if (h_patch) (void)hipHostFree(h_patch);
-        free_device({d_occ, d_profile, d_occ_roll, d_cells_roll});
-    }
+    // the layers and tables go (the maps become a caller's, or none)
+    void drop_layers() { *this = Costmap{}; }
+};
+
+// the staging ring of the *_enqueue calls: CCV_MPPI_OCC_PATCH_SLOTS mapped slots of CCV_MPPI_OCC_PATCH_MAX_CELLS bytes the kernels
+// read in place.  Occupancy patches, rolls, scans, the world's patches, sensings and plans enqueue through it.  Made at the first
+// _set_occupancy or _resident_set_plan (staging_create) and kept until destroy, whatever becomes of the layers, the world or the plan.
+struct Staging {
+    StagingRing ring;
 };
 
 // the simulated range sensor (ccv_mppi_batch_set_world / _resident_sense_enqueue, mppi_costmap_sense.h): one ground-truth occupancy
@@ -320,22 +292,13 @@ struct InflateArgs;
 struct World {
     bool world = false;
     ccv_mppi_occupancy world_geo = {};       // the world's geometry and threshold (cells: null)
-    uint8_t* d_world = nullptr;              // [ny][nx]
-    int32_t* d_sense_first = nullptr;        // [B][world_max_beams]: the blocked cell of every beam, -1 without
-    int32_t* d_sense_cell = nullptr;         // [B][2]: the robots' world cells, (-1, -1) for one that sensed nothing
-    InflateArgs* d_sense_rects = nullptr;    // [B]: the rectangles k_sense_trace writes and k_inflate_rects reads
+    DeviceArray<uint8_t> d_world;            // [ny][nx]
+    DeviceArray<int32_t> d_sense_first;      // [B][world_max_beams]: the blocked cell of every beam, -1 without
+    DeviceArray<int32_t> d_sense_cell;       // [B][2]: the robots' world cells, (-1, -1) for one that sensed nothing
+    DeviceArray<InflateArgs> d_sense_rects;  // [B]: the rectangles k_sense_trace writes and k_inflate_rects reads
     std::vector<int32_t> world_anchor;       // [n_maps][2]: the world cell of the map's cell (0, 0) at _set_occupancy
     int32_t world_max_beams = 0;
-    void drop_world() {
-        free_device({d_world, d_sense_first, d_sense_cell, d_sense_rects});
-        d_world = nullptr;
-        d_sense_first = d_sense_cell = nullptr;
-        d_sense_rects = nullptr;
-        world_anchor.clear();
-        world_max_beams = 0;
-        world = false;
-    }
-    void release() { free_device({d_world, d_sense_first, d_sense_cell, d_sense_rects}); }
+    void drop_world() { *this = World{}; }
 };
 
 // paths planned on the device (ccv_mppi_batch_resident_set_plan / _plan_enqueue, mppi_plan.h; capi_batch_plan.hip): while `plan`,
@@ -347,18 +310,9 @@ struct Plan {
     std::vector<int32_t> plan_capacity;      // [B] poses a plan may write, 0: the instance does not plan
     std::vector<int32_t> plan_field_of;      // [B] the instance's field in d_plan_fields, -1 without
     std::vector<int32_t> plan_dims;          // [B][2]: nx, ny of the map of the instance's last plan call
-    int32_t* d_plan_result = nullptr;        // [B][6]: status, poses, start cell, D(start), sweeps of every instance's last plan
-    uint16_t* d_plan_fields = nullptr;       // [instances with capacity][CCV_MPPI_PLAN_MAX_FIELD], with keep_fields
-    void drop_plan() {
-        free_device({d_plan_result, d_plan_fields});
-        d_plan_result = nullptr;
-        d_plan_fields = nullptr;
-        plan_capacity.clear();
-        plan_field_of.clear();
-        plan_dims.clear();
-        plan = plan_keep = false;
-    }
-    void release() { free_device({d_plan_result, d_plan_fields}); }
+    DeviceArray<int32_t> d_plan_result;      // [B][6]: status, poses, start cell, D(start), sweeps of every instance's last plan
+    DeviceArray<uint16_t> d_plan_fields;     // [instances with capacity][CCV_MPPI_PLAN_MAX_FIELD], with keep_fields
+    void drop_plan() { *this = Plan{}; }
 };
 
 // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
@@ -369,15 +323,14 @@ struct Plan {
 // zero without ccv_mppi_batch_set_obstacle_velocities; the fleet's rows written by the prologue every tick)
 struct Fleet {
     bool fleet = false;
-    double* d_fleet_xy = nullptr;           // [2][B][2]: tick n reads half n & 1 and writes the other (n = res_steps)
-    double* d_fleet_radius = nullptr;       // [B]
-    int32_t* d_fleet_nstatic = nullptr;     // [B]: obst_n on the device, for the prologue (sync_tables)
+    DeviceArray<double> d_fleet_xy;         // [2][B][2]: tick n reads half n & 1 and writes the other (n = res_steps)
+    DeviceArray<double> d_fleet_radius;     // [B]
+    DeviceArray<int32_t> d_fleet_nstatic;   // [B]: obst_n on the device, for the prologue (sync_tables)
     std::vector<double> fleet_radius;       // [B]
     double fleet_range = 0.0;
     int32_t fleet_maxn = 0;
     bool fleet_pred = false;
-    double* d_fleet_v = nullptr;            // [2][B][2]: tick n reads half n & 1 and writes the other, like d_fleet_xy
-    void release() { free_device({d_fleet_xy, d_fleet_radius, d_fleet_nstatic, d_fleet_v}); }
+    DeviceArray<double> d_fleet_v;          // [2][B][2]: tick n reads half n & 1 and writes the other, like d_fleet_xy
 };
 
 }  // namespace ccv
@@ -386,7 +339,8 @@ struct Fleet {
 // batch_view): the core of a single handle, whose K is the instance's and whose
 // pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
 // one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
-struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, World, Plan, Fleet {
+// (Core first: its stream outlives the arrays, rings and events of the parts after it)
+struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, Staging, World, Plan, Fleet {
     int B = 0, kpad = 0;
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
@@ -435,12 +389,12 @@ void select_kernels(KernelChoice& k, const Shape& s, int64_t workgroups, bool ba
 struct BufferCounts {
     size_t nparts_max;   // partial columns (workgroups or chunks, whichever is more)
     size_t nominal, vec, stats;
-    double** extra;      // one more zeroed array of doubles: d_cmin of a single handle, d_rec of a batch
+    DeviceArray<double>* extra;   // one more zeroed array of doubles: d_cmin of a single handle, d_rec of a batch
     size_t n_extra;
     size_t pin_doubles, mail_slots;
 };
 int create_buffers(Core* h, const BufferCounts& n);
-void release_buffers(Core* h);
+void wait_for_streams(Core* h);   // before a handle is deleted: its stream and, under a caller's stream, its own are idle
 int set_stream(Core* h, void* hip_stream);
 hipError_t ensure_scratch(DeviceBuffers& d, size_t bytes);
 
@@ -543,11 +497,10 @@ inline bool valid_weight(const double w) { return w >= 0.0 && std::isfinite(w); 
 // and, under prediction, both halves of the velocity snapshot zero -- no robot has moved yet
 int fleet_restart(ccv_mppi_batch* bh, const double* xy);
 
-// ---- batch handles: the staging ring of the *_enqueue calls (Costmap; capi_batch_maps.hip), for the units that enqueue through it ---
-struct Slot { int index; uint8_t* host; const uint8_t* device; };   // (device: the same bytes as the kernels address them)
-int ring_create(ccv_mppi_batch* bh);                                // at the first _set_occupancy or _resident_set_plan; idempotent
-int slot_take(ccv_mppi_batch* bh, Slot& s);                         // the next slot, free to be filled: the call's only wait
-int slot_seal(ccv_mppi_batch* bh, const Slot& s, hipError_t launched);   // after the last launch that reads the slot
+// ---- batch handles: the staging ring of the *_enqueue calls (Staging; StagingRing: capi_owned.h), for the units that enqueue through it ---
+inline hipError_t staging_create(ccv_mppi_batch* bh) {   // at the first _set_occupancy or _resident_set_plan; idempotent
+    return bh->ring.create(CCV_MPPI_OCC_PATCH_SLOTS, CCV_MPPI_OCC_PATCH_MAX_CELLS, /*mapped=*/true);
+}
 // the float cells that hold map m now: the second allocation after an odd number of rolls (Costmap::Layer::front)
 float* cells_of(const ccv_mppi_batch* bh, int m, bool back = false);
 

@@ -56,18 +56,20 @@ int ccv_mppi_resident_set_path(ccv_mppi_handle* h, const double* path_x, const d
     if (!h) return CCV_MPPI_ERR_INVALID_ARG;
     if (!path_x || !path_y || n_path < 1 || !(resolution > 0.0)) return fail(h, CCV_MPPI_ERR_INVALID_ARG, "path: null, empty or resolution <= 0");
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a queued k_advance may still read the old path)
-    if (h->d_path) HIP_TRY(h, hipFree(h->d_path));
-    h->d_path = nullptr;
-    h->n_path = 0;
-    HIP_TRY(h, hipMalloc(&h->d_path, (size_t)2 * n_path * sizeof(double)));
-    HIP_TRY(h, hipMemcpy(h->d_path, path_x, (size_t)n_path * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_path + n_path, path_y, (size_t)n_path * sizeof(double), hipMemcpyHostToDevice));
+    // the new path is built beside the old one, which goes when the new one is in place; the frame and the trace at the first call
+    DeviceArray<double> path, trace;
+    DeviceArray<ResidentFrame> frame;
+    const size_t trace_doubles = (size_t)ccv_mppi_handle::kTraceRows * 6;
+    HIP_TRY(h, path.alloc((size_t)2 * n_path));
+    HIP_TRY(h, hipMemcpy(path, path_x, (size_t)n_path * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(path + n_path, path_y, (size_t)n_path * sizeof(double), hipMemcpyHostToDevice));
     if (!h->d_frame) {
-        HIP_TRY(h, hipMalloc(&h->d_frame, sizeof(ResidentFrame)));
-        HIP_TRY(h, hipMemset(h->d_frame, 0, sizeof(ResidentFrame)));
-        HIP_TRY(h, hipMalloc(&h->d_trace, (size_t)ccv_mppi_handle::kTraceRows * 6 * sizeof(double)));
-        HIP_TRY(h, hipMemset(h->d_trace, 0, (size_t)ccv_mppi_handle::kTraceRows * 6 * sizeof(double)));
+        HIP_TRY(h, frame.alloc_zeroed(1));
+        HIP_TRY(h, trace.alloc_zeroed(trace_doubles));
+        h->d_frame = std::move(frame);
+        h->d_trace = std::move(trace);
     }
+    h->d_path = std::move(path);
     h->n_path = n_path;
     h->path_resolution = resolution;
     return CCV_MPPI_OK;

@@ -120,7 +120,7 @@ int ccv_mppi_read_top_candidates(ccv_mppi_handle* h, int32_t count, int32_t* sam
     // scratch: [count] indices (as 8-byte slots) | [count] weights | [count][H][2] states
     const size_t n_xy = xy_out ? (size_t)count * h->H * 2 : 0;
     HIP_TRY(h, ensure_scratch(*h, ((size_t)count * 2 + n_xy) * sizeof(double)));
-    int* d_idx = reinterpret_cast<int*>(h->d_scratch);
+    int* d_idx = reinterpret_cast<int*>(h->d_scratch.get());
     double* d_wsel = h->d_scratch + count;
     double* d_xy = h->d_scratch + 2 * (size_t)count;
     hipLaunchKernelGGL(k_top_weights, dim3(1), dim3(kTopBlock), 0, h->stream, h->d_w, h->K, count, d_idx, d_wsel);

@@ -12,12 +12,9 @@ namespace ccv {
 
 hipError_t ensure_scratch(DeviceBuffers& d, size_t bytes) {
     if (bytes <= d.scratch_bytes) return hipSuccess;
-    if (d.d_scratch) {
-        if (hipError_t e = hipFree(d.d_scratch)) return e;
-    }
-    d.d_scratch = nullptr;
+    d.d_scratch.reset();
     d.scratch_bytes = 0;
-    if (hipError_t e = hipMalloc(&d.d_scratch, bytes)) return e;
+    if (hipError_t e = d.d_scratch.alloc((bytes + sizeof(double) - 1) / sizeof(double))) return e;
     d.scratch_bytes = bytes;
     return hipSuccess;
 }
@@ -356,9 +353,9 @@ hipError_t timing_begin(Timing& t) {
     const size_t slot = t.ev_slot = t.ev_used;
     if (t.ev.size() < slot + 3) {
         for (int i = 0; i < 3; ++i) {
-            hipEvent_t e;
-            if (hipError_t err = hipEventCreate(&e)) return err;
-            t.ev.push_back(e);
+            Event e;
+            if (hipError_t err = e.create(/*timing=*/true)) return err;
+            t.ev.push_back(std::move(e));
         }
     }
     t.ev_used += 3;
@@ -629,10 +626,10 @@ void set_shape(Shape& s, const ccv_mppi_config& cfg, const int pitch, const int 
 }
 
 // The handle's stream, device buffers, throttle events, pinned staging and mailbox, on the current device.  On an error the
-// message is in h->err and whatever exists by then is left to release_buffers().
+// message is in h->err and whatever exists by then goes with the handle.
 int create_buffers(Core* h, const BufferCounts& n) {
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipStreamCreate", e);
+    if ((e = h->own_stream.create()) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipStreamCreate", e);
     h->stream = h->own_stream;
     const size_t P = (size_t)h->pitch;
     // The large arrays are pieces of ONE allocation, each starting on a 2 MB boundary: one mapping, one set of large page
@@ -649,16 +646,15 @@ int create_buffers(Core* h, const BufferCounts& n) {
     constexpr size_t kPieceAlign = (size_t)2 << 20;
     size_t arena_bytes = 0;
     for (const Piece& pc : pieces) arena_bytes += (pc.bytes + kPieceAlign - 1) / kPieceAlign * kPieceAlign;
-    if ((e = hipMalloc(&h->d_arena, arena_bytes)) != hipSuccess) return fail(h, CCV_MPPI_ERR_ALLOC, "hipMalloc", e);
-    if ((e = hipMemset(h->d_arena, 0, arena_bytes)) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipMemset", e);
+    if ((e = h->d_arena.alloc_zeroed(arena_bytes)) != hipSuccess) return fail(h, CCV_MPPI_ERR_ALLOC, "hipMalloc", e);
     {
         size_t at = 0;
         for (const Piece& pc : pieces) {
-            *pc.p = static_cast<char*>(h->d_arena) + at;
+            *pc.p = h->d_arena + at;
             at += (pc.bytes + kPieceAlign - 1) / kPieceAlign * kPieceAlign;
         }
     }
-    struct { double** p; size_t n; } allocs[] = {
+    struct { DeviceArray<double>* p; size_t n; } allocs[] = {
         {&h->d_nominal, n.nominal},
         {&h->d_nom_used, (size_t)(CCV_MPPI_MAX_HORIZON + 8) * CCV_MPPI_MAX_UDIM},   // padded: read 4 at a time
         {&h->d_statpart, n.nparts_max * 3},
@@ -666,41 +662,26 @@ int create_buffers(Core* h, const BufferCounts& n) {
         {&h->d_stats, n.stats},
         {n.extra, n.n_extra},
     };
-    for (auto& a : allocs) {
-        if ((e = hipMalloc(a.p, a.n * sizeof(double))) != hipSuccess) return fail(h, CCV_MPPI_ERR_ALLOC, "hipMalloc", e);
-        if ((e = hipMemset(*a.p, 0, a.n * sizeof(double))) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipMemset", e);
-    }
+    for (auto& a : allocs)
+        if ((e = a.p->alloc_zeroed(a.n)) != hipSuccess) return fail(h, CCV_MPPI_ERR_ALLOC, "hipMalloc", e);
     if (const char* tv = std::getenv("CCV_MPPI_THROTTLE")) h->throttle = std::strcmp(tv, "0") != 0;
-    for (hipEvent_t& te : h->throttle_ev)
-        if ((e = hipEventCreateWithFlags(&te, hipEventDisableTiming)) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipEventCreate", e);
+    for (Event& te : h->throttle_ev)
+        if ((e = te.create()) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "creating an event", e);
     h->pin_doubles = n.pin_doubles;
-    if ((e = hipHostMalloc(&h->h_pin, h->pin_doubles * sizeof(double), hipHostMallocDefault)) != hipSuccess)
-        return fail(h, CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e);
-    const size_t mail_bytes = n.mail_slots * 2 * sizeof(unsigned long long);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->h_mail), mail_bytes, hipHostMallocMapped)) != hipSuccess)
-        return fail(h, CCV_MPPI_ERR_ALLOC, "hipHostMalloc(mailbox)", e);
-    std::memset(h->h_mail, 0, mail_bytes);   // (sequence numbers start at 1: nothing in a fresh box is taken for a packet)
-    if ((e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_mail), h->h_mail, 0)) != hipSuccess)
-        return fail(h, CCV_MPPI_ERR_HIP, "hipHostGetDevicePointer(mailbox)", e);
+    if ((e = h->h_pin.alloc(h->pin_doubles, hipHostMallocDefault)) != hipSuccess) return fail(h, CCV_MPPI_ERR_ALLOC, "hipHostMalloc", e);
+    if ((e = h->h_mail.alloc(n.mail_slots * 2, hipHostMallocMapped)) != hipSuccess) return fail(h, CCV_MPPI_ERR_ALLOC, "hipHostMalloc of the mailbox", e);
+    // (sequence numbers start at 1: nothing in a fresh box is taken for a packet)
+    std::memset(h->h_mail, 0, n.mail_slots * 2 * sizeof(unsigned long long));
+    if ((e = h->h_mail.device(&h->d_mail)) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipHostGetDevicePointer(mailbox)", e);
     if (const char* mv = std::getenv("CCV_MPPI_MAILBOX")) h->use_mail = std::strcmp(mv, "0") != 0;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(h, CCV_MPPI_ERR_HIP, "hipDeviceSynchronize", e);
     return CCV_MPPI_OK;
 }
 
-// waits for the handle's work, then gives back what create_buffers() made (and the scratch and timing events made since)
-void release_buffers(Core* h) {
+// waits for the handle's work: what the handle owns goes with the delete that follows
+void wait_for_streams(Core* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->own_stream && h->own_stream != h->stream) (void)hipStreamSynchronize(h->own_stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->throttle_ev)
-        if (e) (void)hipEventDestroy(e);
-    void* bufs[] = {h->d_arena, h->d_nominal, h->d_nom_used, h->d_statpart, h->d_vec, h->d_stats,
-                    h->d_scratch, h->d_dbg};   // (u, z, xs, ys, cost, w, partial: the arena)
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->h_pin) (void)hipHostFree(h->h_pin);
-    if (h->h_mail) (void)hipHostFree(h->h_mail);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
 }
 
 // (the caller has launched whatever was deferred)
@@ -773,8 +754,7 @@ int ccv_mppi_create(const ccv_mppi_config* cfg, ccv_mppi_handle** out) {
 #if defined(CCV_DIAG)
     {
         const size_t dbg_bytes = (size_t)(kDiagHeader + kDiagSlots * kDiagBlocks) * sizeof(unsigned long long);
-        if ((e = hipMalloc(&h->d_dbg, dbg_bytes)) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_ALLOC, "hipMalloc", e));
-        if ((e = hipMemset(h->d_dbg, 0, dbg_bytes)) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_HIP, "hipMemset", e));
+        if ((e = h->d_dbg.alloc_zeroed(dbg_bytes / sizeof(unsigned long long))) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_ALLOC, "hipMalloc", e));
         if ((e = hipDeviceSynchronize()) != hipSuccess) return bail(fail(h, CCV_MPPI_ERR_HIP, "hipDeviceSynchronize", e));
     }
 #endif
@@ -787,11 +767,8 @@ int ccv_mppi_destroy(ccv_mppi_handle* h) {
     // everything below belongs to the handle's device; the caller's current device is put back afterwards
     const DeviceGuard guard(h->cfg.device);
     (void)hipSetDevice(h->cfg.device);
-    release_buffers(h);
+    wait_for_streams(h);
     exchange_release(h);
-    void* bufs[] = {h->d_cmin, h->d_frame, h->d_path, h->d_trace};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     delete h;
     return CCV_MPPI_OK;
 }

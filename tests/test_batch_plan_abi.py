@@ -115,8 +115,11 @@ def test_the_python_side_offers_the_calls_and_the_build_has_the_units():
     for name in ("k_plan.hip", "mppi_plan.h", "capi_batch_plan.hip"):
         assert os.path.exists(os.path.join(build.CSRC, name)), name
     # the staging ring is declared where every enqueueing unit sees it, and defined once
-    internal = open(os.path.join(build.CSRC, "capi_internal.h")).read()
-    for name in ("struct Slot", "int ring_create(", "int slot_take(", "int slot_seal("):
-        assert name in internal, name
-    defined = [u for u in build.CAPI_UNITS if re.search(r"^int slot_take\(.*\{$", open(os.path.join(build.CSRC, u)).read(), re.M)]
-    assert defined == ["capi_batch_maps.hip"]
+    # (StagingRing, csrc/capi_owned.h, which capi_internal.h includes; the handle's part Staging holds the one the calls share)
+    internal, owned = (open(os.path.join(build.CSRC, name)).read() for name in ("capi_internal.h", "capi_owned.h"))
+    assert '#include "capi_owned.h"' in internal and "struct Staging" in internal and "hipError_t staging_create(" in internal
+    for name in ("struct Slot", "class StagingRing", "hipError_t create(", "hipError_t take(", "hipError_t seal("):
+        assert name in owned, name
+    sources = [f for f in sorted(os.listdir(build.CSRC)) if f.endswith((".h", ".hip"))]
+    defined = [f for f in sources if re.search(r"^\s*hipError_t take\(Slot& .*\{$", open(os.path.join(build.CSRC, f)).read(), re.M)]
+    assert defined == ["capi_owned.h"]
