@@ -169,6 +169,23 @@ def goal_cells(geometry, xy):
     return np.ascontiguousarray(out)
 
 
+def follow_shift(geometry, pose_xy, margin, max_step):
+    """The decision of BatchController.resident_follow in numpy, for callers who drive the host prologue and therefore know the
+    pose (they roll with roll_occupancy): int32 [n][2], the cells (dx, dy) the window of a map with geometry = ((origin_x,
+    origin_y), resolution, nx, ny) moves for each pose pose_xy [n][2].  Per axis e = floor((p - origin) * (1 / resolution)) -
+    n // 2 and d = 0 where |e| <= margin, else e clamped to [-max_step, max_step]; (0, 0) for a pose that is not finite or
+    2^30 cells or more from the origin.  (The limit of 2^30 accumulated cells is the roll's own check.)"""
+    (ox, oy), resolution, nx, ny = geometry
+    xy = np.asarray(pose_xy, dtype=np.float64).reshape(-1, 2)
+    inv = 1.0 / float(resolution)
+    f = np.stack([(xy[:, 0] - float(ox)) * inv, (xy[:, 1] - float(oy)) * inv], axis=1)
+    with np.errstate(invalid="ignore"):
+        ok = np.all(np.abs(f) < 2.0 ** 30, axis=1)
+    e = np.floor(np.where(ok[:, None], f, 0.0)).astype(np.int64) - np.array([int(nx) // 2, int(ny) // 2], dtype=np.int64)
+    d = np.where(np.abs(e) <= int(margin), 0, np.clip(e, -int(max_step), int(max_step)))
+    return np.ascontiguousarray(np.where(ok[:, None], d, 0), dtype=np.int32)
+
+
 def inflation_profile(radius_m, resolution, kind="linear", lethal=1.0, inscribed=None, inscribed_m=0.0, free_value=0.0, scaling=10.0):
     """(R, profile float32 [R * R + 1], free_value) for BatchController.set_occupancy: the cost of a cell by the squared distance
     D2, in cells, from its centre to the centre of the nearest occupied cell, built on the host -- the device only looks it up.
@@ -221,6 +238,7 @@ class BatchController:
         self.udim = params.udim
         self.nstate = params.nstate
         self.device = int(device)
+        self._plan_dims = None   # (nx, ny) per map for _default_sweeps; set_grids / set_occupancy forget it
         self.no_state_store = bool(no_state_store)
         self._h = capi._H()
         cfg = make_config(params, device, 0, False, no_state_store, self.K)
@@ -352,6 +370,7 @@ class BatchController:
         state the path term covers reads the cell it lies in (cells[int(fy)][int(fx)], f = (p - origin) * (1 / resolution);
         `outside` where there is none) and the cost gains weight_b * their sum.  Flushes a pending resident update; warm
         starts, paths, poses, per-instance parameters and discs stay."""
+        self._plan_dims = None
         if maps is None or len(maps) == 0:
             self._check(self.lib.ccv_mppi_batch_set_grids(self._h, None, 0, None, None))
             return
@@ -393,6 +412,7 @@ class BatchController:
         (cells >= threshold) is at squared distance D2 <= R * R costs profile[D2], every other cell free_value.  Takes the place
         of set_grids' maps (and a later set_grids takes the place of these); get_grids returns the derived cells.  Flushes a
         pending resident update."""
+        self._plan_dims = None
         if maps is None or len(maps) == 0:
             self._check(self.lib.ccv_mppi_batch_set_occupancy(self._h, None, None, 0, None, None))
             return
@@ -733,16 +753,22 @@ class BatchController:
         if len(goals) != len(inst):
             raise ValueError("resident_plan: expected %d goals, got %d" % (len(inst), len(goals)))
         if max_sweeps is None:
-            n = C.c_int32(0)
-            mo = np.zeros(self.B, dtype=np.int32)
-            self._check(self.lib.ccv_mppi_batch_get_grids(self._h, None, 0, C.byref(n), mo.ctypes.data_as(C.POINTER(C.c_int32)), None))
-            rows = (capi.Grid * max(n.value, 1))()
-            self._check(self.lib.ccv_mppi_batch_get_grids(self._h, rows, n.value, None, None, None))
-            named = [mo[b] for b in inst if 0 <= b < self.B and mo[b] >= 0]
-            max_sweeps = min(max([rows[m].nx * rows[m].ny + 1 for m in named] or [1]), capi.PLAN_MAX_FIELD)
+            max_sweeps = self._default_sweeps(inst)
         ip = C.POINTER(C.c_int32)
         self._check(self.lib.ccv_mppi_batch_resident_plan_enqueue(self._h, len(inst), inst.ctypes.data_as(ip), goals.ctypes.data_as(ip),
                                                                    float(lethal), int(max_sweeps)))
+
+    def _default_sweeps(self, inst):
+        """the largest nx * ny + 1 of the named instances' maps (the sizes never change, so no synchronisation is needed)"""
+        n = C.c_int32(0)
+        mo = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.ccv_mppi_batch_get_grids(self._h, None, 0, C.byref(n), mo.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        if self._plan_dims is None or len(self._plan_dims) != n.value:
+            rows = (capi.Grid * max(n.value, 1))()
+            self._check(self.lib.ccv_mppi_batch_get_grids(self._h, rows, n.value, None, None, None))
+            self._plan_dims = [(rows[m].nx, rows[m].ny) for m in range(n.value)]
+        named = [mo[b] for b in inst if 0 <= b < self.B and mo[b] >= 0]
+        return min(max([self._plan_dims[m][0] * self._plan_dims[m][1] + 1 for m in named] or [1]), capi.PLAN_MAX_FIELD)
 
     def resident_read_plan(self):
         """(status [B], poses [B], start_cell [B][2], start_dist [B], sweeps [B]), int32, of every instance's last plan: status a
@@ -768,6 +794,57 @@ class BatchController:
         x, y = np.empty(n.value), np.empty(n.value)
         self._check(self.lib.ccv_mppi_batch_resident_read_path(self._h, int(instance), n.value, capi.dptr(x), capi.dptr(y), C.byref(n)))
         return x[:n.value], y[:n.value]
+
+    # ---- costmaps that follow their robots (ccv_mppi_batch_resident_set_follow, _follow_enqueue; include/ccv_mppi_follow.h) ----
+    def resident_set_follow(self, on=True):
+        """The occupancy maps follow their robots from now on (resident_follow), or no longer.  While on, the device holds every
+        map's frame: roll_occupancy is refused (capi.ERR_STATE), resident_sense and resident_plan work in the frame as the
+        device has it, get_grids / get_occupancy synchronise to show it.  Needs set_occupancy; a later set_occupancy or
+        set_grids turns it off.  Flushes a pending resident update and synchronises."""
+        self._check(self.lib.ccv_mppi_batch_resident_set_follow(self._h, 1 if on else 0))
+
+    def resident_get_follow(self):
+        on = C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_resident_get_follow(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def resident_follow(self, instances, margin, max_step, fill=0):
+        """The maps of the instances `instances` (each at most once, each on a map of its own) are re-centred on their robots'
+        resident poses, in stream order and in two launches for all of them, decided on the device (follow_shift is the same
+        decision in numpy): per axis the window moves by d = 0 while the robot's cell is within `margin` cells of the centre
+        cell, else by the distance to it clamped to `max_step`; exposed cells become `fill`, the float cells are what
+        set_occupancy of the new layer would derive.  The outcome: resident_read_follow.  No synchronisation; the arguments
+        may be reused when the call returns."""
+        inst = np.ascontiguousarray(np.atleast_1d(instances), dtype=np.int32)
+        self._check(self.lib.ccv_mppi_batch_resident_follow_enqueue(self._h, len(inst), inst.ctypes.data_as(C.POINTER(C.c_int32)), int(margin),
+                                                                     int(max_step), int(fill)))
+
+    def resident_read_follow(self):
+        """(status int32 [n_maps], shift int32 [n_maps][2], offset int64 [n_maps][2], origin [n_maps][2]): per map the
+        capi.FOLLOW_* status (0: never followed) and the cells moved by its last resident_follow, the cells moved since
+        set_occupancy and the origin now; synchronises."""
+        n = C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_get_occupancy(self._h, None, None, 0, C.byref(n)))
+        m = max(n.value, 1)
+        status, shift = np.zeros(m, dtype=np.int32), np.zeros((m, 2), dtype=np.int32)
+        offset, origin = np.zeros((m, 2), dtype=np.int64), np.zeros((m, 2))
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.ccv_mppi_batch_resident_read_follow(self._h, status.ctypes.data_as(ip), shift.ctypes.data_as(ip),
+                                                                  offset.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(origin)))
+        return status[:n.value], shift[:n.value], offset[:n.value], origin[:n.value]
+
+    def resident_plan_goals(self, instances, goals_xy, lethal, max_sweeps=None):
+        """resident_plan with world goals goals_xy [n][2] (metres): the device turns each into a cell of the instance's map as
+        rolled (goal_cells' arithmetic, clamped to the map) -- for a caller whose maps follow their robots and who therefore
+        cannot name a goal cell.  MPPIError (capi.ERR_STATE) while following is not set: goal_cells and resident_plan serve there."""
+        inst = np.ascontiguousarray(np.atleast_1d(instances), dtype=np.int32)
+        goals = capi.as_f64(np.asarray(goals_xy, dtype=np.float64).reshape(-1, 2))
+        if len(goals) != len(inst):
+            raise ValueError("resident_plan_goals: expected %d goals, got %d" % (len(inst), len(goals)))
+        if max_sweeps is None:
+            max_sweeps = self._default_sweeps(inst)
+        self._check(self.lib.ccv_mppi_batch_resident_plan_goals_enqueue(self._h, len(inst), inst.ctypes.data_as(C.POINTER(C.c_int32)), capi.dptr(goals),
+                                                                         float(lethal), int(max_sweeps)))
 
     # ---- fleet term: the robots of the batch keep clear of each other (ccv_mppi_batch_resident_set_fleet) ----
     def resident_set_fleet(self, radius, range=0.0, max_neighbours=0, weight=0.0):

@@ -236,6 +236,16 @@ PLAN_SIGNATURES = {
     "ccv_mppi_batch_resident_read_path": (C.c_int, [_H, C.c_int32, C.c_int32, _dp, _dp, _i32p]),
 }
 
+# include/ccv_mppi_follow.h: costmaps that follow their robots in the resident loop, a table of its own like its header
+FOLLOW_SIGNATURES = {
+    "ccv_mppi_batch_resident_set_follow": (C.c_int, [_H, C.c_int32]),
+    "ccv_mppi_batch_resident_get_follow": (C.c_int, [_H, _i32p]),
+    "ccv_mppi_batch_resident_follow_enqueue": (C.c_int, [_H, C.c_int32, _i32p, C.c_int32, C.c_int32, C.c_int32]),
+    "ccv_mppi_batch_resident_read_follow": (C.c_int, [_H, _i32p, _i32p, C.POINTER(C.c_int64), _dp]),
+    "ccv_mppi_batch_resident_plan_goals_enqueue": (C.c_int, [_H, C.c_int32, _i32p, _dp, C.c_float, C.c_int32]),
+}
+FOLLOW_MOVED, FOLLOW_HELD, FOLLOW_NO_POSE, FOLLOW_LIMIT = 1, 2, 3, 4
+
 _lib = None
 
 
@@ -247,7 +257,7 @@ def load():
         if not os.path.exists(path):
             raise ImportError("libccv_mppi_hip.so is missing and could not be built; there is no CPU fallback")
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()) + list(PLAN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()) + list(PLAN_SIGNATURES.items()) + list(FOLLOW_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError = the .so does not export what the header declares
             fn.restype = res
             fn.argtypes = args

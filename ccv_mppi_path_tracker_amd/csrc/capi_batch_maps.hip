@@ -10,12 +10,35 @@
 #include "mppi_costmap_roll.h"
 #include "mppi_costmap_scan.h"
 #include "mppi_costmap_sense.h"
+#include "mppi_costmap_follow.h"
 
 namespace ccv {
 
 float* cells_of(const ccv_mppi_batch* bh, const int m, const bool back) {
     const bool second = bh->occ && ((bh->layers[(size_t)m].front != 0) != back);
     return (second ? bh->d_cells_roll : bh->d_grid_cells) + bh->grid_offset[(size_t)m];
+}
+
+uint8_t* layer_of(const ccv_mppi_batch* bh, const int m, const bool back) {
+    return ((bh->layers[(size_t)m].front != 0) != back ? bh->d_occ_roll : bh->d_occ) + bh->grid_offset[(size_t)m];
+}
+
+// (every cell of the second set that is read later is written first: a shift writes every layer cell, and the shift and the bands
+// every float cell)
+int ensure_roll_buffers(ccv_mppi_batch* bh) {
+    if (bh->d_occ_roll) return CCV_MPPI_OK;
+    const DeviceGuard guard(bh->cfg.device);
+    if (int rc = quiesce(bh)) return rc;
+    const ccv_mppi_grid& last = bh->grid_maps.back();
+    const size_t total = bh->grid_offset.back() + (size_t)last.nx * (size_t)last.ny;
+    DeviceArray<uint8_t> layers;
+    DeviceArray<float> cells;
+    hipError_t e = layers.alloc(total);
+    if (e == hipSuccess) e = cells.alloc(total);
+    if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "roll_occupancy: allocating the second set of layers and cells", e);
+    bh->d_occ_roll = std::move(layers);
+    bh->d_cells_roll = std::move(cells);
+    return CCV_MPPI_OK;
 }
 
 }  // namespace ccv
@@ -48,6 +71,7 @@ int check_map_roles(ccv_mppi_batch* bh, const char* who, const int32_t n_maps, c
 int maps_off(ccv_mppi_batch* bh) {
     bh->d_grid_cells.reset();
     bh->drop_layers();
+    bh->drop_follow();   // (the frames spoke of the old layers too)
     bh->drop_world();   // (the anchors spoke of the old layers)
     bh->grid = false;
     bh->grid_maps.clear();
@@ -88,11 +112,6 @@ int install_maps(ccv_mppi_batch* bh, std::vector<ccv_mppi_grid>& geo, DeviceArra
     bh->grid_w.assign(weight, weight + B);
     bh->grid = true;
     return CCV_MPPI_OK;
-}
-
-// the layer and the float cells that hold map m now: the second allocation after an odd number of rolls (Costmap::Layer::front)
-uint8_t* layer_of(const ccv_mppi_batch* bh, const int m, const bool back = false) {
-    return ((bh->layers[(size_t)m].front != 0) != back ? bh->d_occ_roll : bh->d_occ) + bh->grid_offset[(size_t)m];
 }
 
 // one inflation of the rectangle r inside map m: the float cells from the layer, both the front ones or both the back ones
@@ -160,6 +179,7 @@ int ccv_mppi_batch_set_grids(ccv_mppi_batch* bh, const ccv_mppi_grid* maps, int3
     for (ccv_mppi_grid& g : geo) g.cells = nullptr;
     if (int rc = install_maps(bh, geo, std::move(cells), offset, map_of, weight)) return rc;
     bh->drop_layers();   // (the cells are the caller's now)
+    bh->drop_follow();
     bh->drop_world();   // (the anchors spoke of the old layers)
     return sync_tables(bh);
 }
@@ -168,6 +188,8 @@ int ccv_mppi_batch_get_grids(ccv_mppi_batch* bh, ccv_mppi_grid* maps, int32_t ma
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     const int n = bh->grid ? (int)bh->grid_maps.size() : 0;
     if (maps && (max_maps < 0 || max_maps < n)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_grids: max_maps below the number of maps");
+    if (bh->follow && maps)
+        if (int rc = follow_refresh(bh)) return rc;   // (the origins are the device's)
     if (n_maps) *n_maps = n;
     for (int m = 0; m < n && maps; ++m) maps[m] = bh->grid_maps[(size_t)m];
     for (int b = 0; b < bh->B; ++b) {
@@ -250,6 +272,7 @@ int ccv_mppi_batch_set_occupancy(ccv_mppi_batch* bh, const ccv_mppi_occupancy* m
         geo[(size_t)m] = ccv_mppi_grid{maps[m].origin_x, maps[m].origin_y, maps[m].resolution, maps[m].outside, maps[m].nx, maps[m].ny, nullptr};
     if (int rc = install_maps(bh, geo, std::move(cells), offset, map_of, weight)) return rc;
     bh->drop_layers();
+    bh->drop_follow();
     bh->drop_world();   // (the anchors spoke of the old layers)
     bh->d_occ = std::move(layers);
     bh->d_profile = std::move(profiles);
@@ -289,6 +312,7 @@ int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     static const char who[] = "roll_occupancy: ";
     // every check comes before anything changes
     if (!bh->occ) return fail(bh, CCV_MPPI_ERR_STATE, "roll_occupancy: no occupancy is set (ccv_mppi_batch_set_occupancy)");
+    if (bh->follow) return fail(bh, CCV_MPPI_ERR_STATE, "roll_occupancy: the maps follow their robots (ccv_mppi_batch_resident_set_follow): the windows are the device's to move");
     if (!map || !dx || !dy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
     const int n_maps = (int)bh->grid_maps.size();
     if (n < 1 || n > n_maps) return refuse(bh, who, "n outside [1, the number of maps]");
@@ -319,21 +343,8 @@ int ccv_mppi_batch_roll_occupancy_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     const size_t entry_bytes = moved * sizeof(RollEntry), rect_bytes = moved * kRollMaxRects * sizeof(InflateArgs);
     if (entry_bytes + rect_bytes + strip_bytes > (size_t)CCV_MPPI_OCC_PATCH_MAX_CELLS)
         return refuse(bh, who, "tables and strips above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
-    // the second set of layers and cells, at the handle's first roll since the layers were set (every cell of it that is read
-    // later is written first: the shift writes every layer cell, and the shift and the bands every float cell)
-    if (!bh->d_occ_roll) {
-        const DeviceGuard guard(bh->cfg.device);
-        if (int rc = quiesce(bh)) return rc;
-        const ccv_mppi_grid& last = bh->grid_maps.back();
-        const size_t total = bh->grid_offset.back() + (size_t)last.nx * (size_t)last.ny;
-        DeviceArray<uint8_t> layers;
-        DeviceArray<float> cells;
-        hipError_t e = layers.alloc(total);
-        if (e == hipSuccess) e = cells.alloc(total);
-        if (e != hipSuccess) return fail(bh, CCV_MPPI_ERR_HIP, "roll_occupancy: allocating the second set of layers and cells", e);
-        bh->d_occ_roll = std::move(layers);
-        bh->d_cells_roll = std::move(cells);
-    }
+    // the second set of layers and cells, at the handle's first roll since the layers were set
+    if (int rc = ensure_roll_buffers(bh)) return rc;
     if (moved == 0) return CCV_MPPI_OK;   // (nothing moves: no launch, no bit changes)
     Slot slot;
     HIP_TRY(bh, bh->ring.take(slot));
@@ -559,7 +570,7 @@ int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     if (n < 1 || n > bh->B) return refuse(bh, who, "n outside [1, B]");
     if (n_beams < 1 || n_beams > bh->world_max_beams) return refuse(bh, who, "n_beams outside [1, max_beams]");
     if (clear_value < 0 || clear_value > 255 || mark_value < 0 || mark_value > 255) return refuse(bh, who, "clear_value or mark_value outside [0, 255]");
-    const size_t entry_bytes = (size_t)n * sizeof(SenseEntry), beam_bytes = (size_t)n_beams * 2 * sizeof(int32_t);
+    const size_t entry_bytes = (size_t)n * (bh->follow ? sizeof(SenseFollowEntry) : sizeof(SenseEntry)), beam_bytes = (size_t)n_beams * 2 * sizeof(int32_t);
     if (entry_bytes + beam_bytes > (size_t)CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "entries and beams above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
     constexpr int64_t kMaxOffset = (int64_t)1 << 30;
     std::vector<uint8_t> named_b((size_t)bh->B, 0), named_m(bh->grid_maps.size(), 0);
@@ -574,6 +585,7 @@ int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const i
         named_m[(size_t)m] = 1;
         if (std::memcmp(&bh->grid_maps[(size_t)m].resolution, &bh->world_geo.resolution, sizeof(double)) != 0)
             return refuse(bh, who, "a map's resolution differs from the world's");
+        if (bh->follow) continue;   // (the rolled count is the device's: at most 2^30 there, and the anchor at most 2^29)
         const Costmap::Layer& l = bh->layers[(size_t)m];
         const int64_t ox = bh->world_anchor[2 * (size_t)m] + l.cx, oy = bh->world_anchor[2 * (size_t)m + 1] + l.cy;
         if (ox < -kMaxOffset || ox > kMaxOffset || oy < -kMaxOffset || oy > kMaxOffset) return refuse(bh, who, "a frame offset beyond 2^30 cells");
@@ -591,8 +603,10 @@ int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const i
     }
     Slot slot;
     HIP_TRY(bh, bh->ring.take(slot));
-    // the slot: the entries, the beams (the kernel reads both in place)
+    // the slot: the entries, the beams (the kernel reads both in place).  While the maps follow, the entries carry the anchor and
+    // the address of the map's frame, and one small launch completes them in device memory (mppi_costmap_follow.h)
     SenseEntry* entries = reinterpret_cast<SenseEntry*>(slot.host);
+    SenseFollowEntry* followed = reinterpret_cast<SenseFollowEntry*>(slot.host);
     std::memcpy(slot.host + entry_bytes, beam_xy, beam_bytes);
     const ccv_mppi_occupancy& w = bh->world_geo;
     A.world = bh->d_world;
@@ -612,21 +626,34 @@ int ccv_mppi_batch_resident_sense_enqueue(ccv_mppi_batch* bh, int32_t n, const i
         const int b = instance[i], m = bh->grid_map_of[(size_t)b];
         const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
         const Costmap::Layer& l = bh->layers[(size_t)m];
-        SenseEntry& e = entries[i];
+        SenseEntry& e = bh->follow ? followed[i].entry : entries[i];
         e.rect = inflate_args(bh, m, Rect{0, 0, 0, 0});
         e.layer = layer_of(bh, m);
         e.pose = bh->d_rframe[b].x0;   // (an address: the host reads no pose)
         e.first = bh->d_sense_first + (size_t)b * (size_t)bh->world_max_beams;
         e.sensor_cell = bh->d_sense_cell + 2 * (size_t)b;
-        e.off_x = (int32_t)(bh->world_anchor[2 * (size_t)m] + l.cx);
-        e.off_y = (int32_t)(bh->world_anchor[2 * (size_t)m + 1] + l.cy);
         e.pad[0] = e.pad[1] = 0;
+        if (bh->follow) {   // (the anchor alone: the device adds the cells the map has rolled)
+            e.off_x = bh->world_anchor[2 * (size_t)m];
+            e.off_y = bh->world_anchor[2 * (size_t)m + 1];
+            followed[i].frame = bh->d_follow_frames + 2 * (size_t)m + bh->follow_slot[(size_t)m];
+            followed[i].pad = 0;
+        } else {
+            e.off_x = (int32_t)(bh->world_anchor[2 * (size_t)m] + l.cx);
+            e.off_y = (int32_t)(bh->world_anchor[2 * (size_t)m + 1] + l.cy);
+        }
         // the largest rectangle the device can form: the box clipped to the map, grown by R and clipped again
         max_tiles = std::max(max_tiles, inflate_tiles(std::min(g.nx, span_x + 2 * l.radius), std::min(g.ny, span_y + 2 * l.radius)));
     }
-    launch_sense_trace(reinterpret_cast<const SenseEntry*>(slot.device), bh->d_sense_rects, n, A, bh->stream);
+    if (bh->follow) {
+        launch_follow_resolve_sense(reinterpret_cast<const SenseFollowEntry*>(slot.device), bh->d_follow_sense, n, bh->stream);
+        launch_sense_trace(bh->d_follow_sense, bh->d_sense_rects, n, A, bh->stream);
+    } else {
+        launch_sense_trace(reinterpret_cast<const SenseEntry*>(slot.device), bh->d_sense_rects, n, A, bh->stream);
+    }
     launch_inflate_rects(bh->d_sense_rects, n, max_tiles, bh->stream);
-    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));   // (after the second launch; only the first reads the slot)
+    // (after the last launch; the beam kernel reads the slot, and while the maps follow the launch ahead of it does too)
+    HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));
     return CCV_MPPI_OK;
 }
 
@@ -645,6 +672,8 @@ int ccv_mppi_batch_get_occupancy(ccv_mppi_batch* bh, ccv_mppi_occupancy* maps, c
     if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
     const int n = bh->occ ? (int)bh->grid_maps.size() : 0;
     if ((maps || inflation) && (max_maps < 0 || max_maps < n)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "get_occupancy: max_maps below the number of maps");
+    if (bh->follow && maps)
+        if (int rc = follow_refresh(bh)) return rc;   // (the origins are the device's)
     if (n_maps) *n_maps = n;
     for (int m = 0; m < n; ++m) {
         const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];

@@ -5,6 +5,7 @@
 // last read the slot.  The host reads no pose: an entry carries the address of the instance's resident pose.
 #include "capi_internal.h"
 #include "mppi_plan.h"
+#include "mppi_costmap_follow.h"
 
 namespace {
 
@@ -102,19 +103,26 @@ int ccv_mppi_batch_resident_get_plan(ccv_mppi_batch* bh, int32_t* capacity, int3
     return CCV_MPPI_OK;
 }
 
-// One launch however many instances plan (k_plan_field).  The poses are the device's: nothing here reads one.
-int ccv_mppi_batch_resident_plan_enqueue(ccv_mppi_batch* bh, int32_t n, const int32_t* instance, const int32_t* goal_xy, float lethal,
-                                         int32_t max_sweeps) {
-    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
-    static const char who[] = "resident_plan: ";
+}  // extern "C"
+
+namespace {
+
+// _plan_enqueue (goal_xy: cells) and _plan_goals_enqueue (world_xy: world points; goal_xy null; while the maps follow only).  One launch however many
+// instances plan (k_plan_field), and while the maps follow one small launch ahead of it that completes the entries from the maps'
+// frames (mppi_costmap_follow.h).  The poses are the device's: nothing here reads one.
+int plan_enqueue(ccv_mppi_batch* bh, const char* who, int32_t n, const int32_t* instance, const int32_t* goal_xy, const double* world_xy, float lethal,
+                 int32_t max_sweeps) {
     // every check comes first, then the next slot of the ring
     if (!bh->plan) return fail(bh, CCV_MPPI_ERR_STATE, kNoPlan);
-    if (!bh->have_paths || !bh->have_poses) return fail(bh, CCV_MPPI_ERR_STATE, "resident_plan: ccv_mppi_batch_resident_set_poses first");
-    if (!instance || !goal_xy) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
+    if (!bh->have_paths || !bh->have_poses) return fail(bh, CCV_MPPI_ERR_STATE, (std::string(who) + "ccv_mppi_batch_resident_set_poses first").c_str());
+    // (a world goal is for the caller who cannot know the frame; one who can has batch.goal_cells and _plan_enqueue)
+    if (world_xy && !bh->follow) return fail(bh, CCV_MPPI_ERR_STATE, (std::string(who) + "following is not set (ccv_mppi_batch_resident_set_follow)").c_str());
+    if (!instance || (!goal_xy && !world_xy)) return fail(bh, CCV_MPPI_ERR_INVALID_ARG, "null pointer argument");
     if (n < 1 || n > bh->B) return refuse(bh, who, "n outside [1, B]");
+    const bool followed = bh->follow;
     if (lethal != lethal) return refuse(bh, who, "lethal is NaN");
     if (max_sweeps < 1 || max_sweeps > CCV_MPPI_PLAN_MAX_FIELD) return refuse(bh, who, "max_sweeps outside [1, CCV_MPPI_PLAN_MAX_FIELD]");
-    if ((size_t)n * sizeof(PlanEntry) > (size_t)CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "entries above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
+    if ((size_t)n * (followed ? sizeof(PlanFollowEntry) : sizeof(PlanEntry)) > (size_t)CCV_MPPI_OCC_PATCH_MAX_CELLS) return refuse(bh, who, "entries above a staging slot (CCV_MPPI_OCC_PATCH_MAX_CELLS bytes)");
     std::vector<uint8_t> named((size_t)bh->B, 0);
     for (int i = 0; i < n; ++i) {
         const int b = instance[i];
@@ -126,19 +134,24 @@ int ccv_mppi_batch_resident_plan_enqueue(ccv_mppi_batch* bh, int32_t n, const in
         if (bh->plan_capacity[(size_t)b] < 1) return refuse(bh, who, "an instance with capacity 0");
         const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
         if (((int64_t)g.nx + 2) * ((int64_t)g.ny + 2) > CCV_MPPI_PLAN_MAX_FIELD) return refuse(bh, who, "a map above CCV_MPPI_PLAN_MAX_FIELD: (nx + 2)(ny + 2)");
-        const int32_t gx = goal_xy[2 * (size_t)i], gy = goal_xy[2 * (size_t)i + 1];
-        if (gx < 0 || gx >= g.nx || gy < 0 || gy >= g.ny) return refuse(bh, who, "a goal outside the map");
+        if (world_xy) {
+            if (!std::isfinite(world_xy[2 * (size_t)i]) || !std::isfinite(world_xy[2 * (size_t)i + 1])) return refuse(bh, who, "a goal is not finite");
+        } else {
+            const int32_t gx = goal_xy[2 * (size_t)i], gy = goal_xy[2 * (size_t)i + 1];
+            if (gx < 0 || gx >= g.nx || gy < 0 || gy >= g.ny) return refuse(bh, who, "a goal outside the map");
+        }
         if (std::memcmp(&g.resolution, &bh->inst[(size_t)b].resolution, sizeof(double)) != 0)
             return refuse(bh, who, "a path's resolution differs from its map's");
     }
     Slot slot;
     HIP_TRY(bh, bh->ring.take(slot));
     PlanEntry* entries = reinterpret_cast<PlanEntry*>(slot.host);
+    PlanFollowEntry* wide = reinterpret_cast<PlanFollowEntry*>(slot.host);
     for (int i = 0; i < n; ++i) {
         const size_t b = (size_t)instance[i];
         const int m = bh->grid_map_of[b];
         const ccv_mppi_grid& g = bh->grid_maps[(size_t)m];
-        PlanEntry& e = entries[i];
+        PlanEntry& e = followed ? wide[i].entry : entries[i];
         e.cells = cells_of(bh, m);
         e.pose = bh->d_rframe[b].x0;   // (an address: the host reads no pose)
         e.path_x = bh->d_rpath + bh->inst[b].path_off;
@@ -152,16 +165,46 @@ int ccv_mppi_batch_resident_plan_enqueue(ccv_mppi_batch* bh, int32_t n, const in
         e.resolution = g.resolution;
         e.nx = g.nx;
         e.ny = g.ny;
-        e.goal_x = goal_xy[2 * (size_t)i];
-        e.goal_y = goal_xy[2 * (size_t)i + 1];
+        // (while the maps follow, the origin and a world goal's cell are the device's to form)
+        e.goal_x = goal_xy ? goal_xy[2 * (size_t)i] : 0;
+        e.goal_y = goal_xy ? goal_xy[2 * (size_t)i + 1] : 0;
+        if (followed) {
+            wide[i].frame = bh->d_follow_frames + 2 * (size_t)m + bh->follow_slot[(size_t)m];
+            wide[i].goal_wx = world_xy ? world_xy[2 * (size_t)i] : 0.0;
+            wide[i].goal_wy = world_xy ? world_xy[2 * (size_t)i + 1] : 0.0;
+            wide[i].world_goal = world_xy ? 1 : 0;
+            wide[i].pad = 0;
+        }
         e.capacity = bh->plan_capacity[b];
         e.pad[0] = e.pad[1] = e.pad[2] = 0;
         bh->plan_dims[2 * b] = g.nx;
         bh->plan_dims[2 * b + 1] = g.ny;
     }
-    launch_plan_field(reinterpret_cast<const PlanEntry*>(slot.device), n, lethal, max_sweeps, bh->stream);
+    if (followed) {
+        launch_follow_resolve_plan(reinterpret_cast<const PlanFollowEntry*>(slot.device), bh->d_follow_plan, n, bh->stream);
+        launch_plan_field(bh->d_follow_plan, n, lethal, max_sweeps, bh->stream);
+    } else {
+        launch_plan_field(reinterpret_cast<const PlanEntry*>(slot.device), n, lethal, max_sweeps, bh->stream);
+    }
     HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));
     return CCV_MPPI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccv_mppi_batch_resident_plan_enqueue(ccv_mppi_batch* bh, int32_t n, const int32_t* instance, const int32_t* goal_xy, float lethal,
+                                         int32_t max_sweeps) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    return plan_enqueue(bh, "resident_plan: ", n, instance, goal_xy, nullptr, lethal, max_sweeps);
+}
+
+// (declared in ccv_mppi_follow.h: the call a caller needs who cannot know the frame)
+int ccv_mppi_batch_resident_plan_goals_enqueue(ccv_mppi_batch* bh, int32_t n, const int32_t* instance, const double* goal_xy, float lethal,
+                                               int32_t max_sweeps) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    return plan_enqueue(bh, "resident_plan_goals: ", n, instance, nullptr, goal_xy, lethal, max_sweeps);
 }
 
 int ccv_mppi_batch_resident_read_plan(ccv_mppi_batch* bh, int32_t* status, int32_t* poses, int32_t* start_cell, int32_t* start_dist, int32_t* sweeps) {

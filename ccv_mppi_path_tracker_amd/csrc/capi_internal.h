@@ -9,6 +9,7 @@
 //                        stream-ordered patches, rolls and scans of those
 //   capi_batch_feed.hip  batch handles: best candidates and optimal paths of every instance (mppi_feed.h)
 //   capi_batch_plan.hip  batch handles: paths planned on the device from the maps to goal cells (mppi_plan.h)
+//   capi_batch_follow.hip  batch handles: costmaps that follow their robots, decided on the device (mppi_costmap_follow.h)
 // A handle is made of named parts (below).  A part owns what it allocates, by type (capi_owned.h): device arrays, pinned staging
 // and events go with the part, nothing is freed by a list; a raw pointer in a part is a view into an array declared beside it.  Core is what a single handle and a batch handle both have; the shared functions
 // take the core, or the one part they work on where they need no more (those return the HIP error, the caller reports it).
@@ -315,6 +316,24 @@ struct Plan {
     void drop_plan() { *this = Plan{}; }
 };
 
+// costmaps that follow their robots (ccv_mppi_batch_resident_set_follow / _follow_enqueue, mppi_costmap_follow.h): while `follow`
+// the device's frame table is the truth of every map's rolled offset and origin -- Costmap::Layer::cx, cy and the origins of
+// Grids::grid_maps are what the last call that synchronised saw (follow_refresh) -- and Layer::front stays the host's: a named
+// map changes buffers at every call.  Lives from _set_follow(1) to _set_follow(0), the next _set_occupancy or _set_grids or destroy.
+struct FollowFrame;
+struct SenseEntry;
+struct PlanEntry;
+struct Follow {
+    bool follow = false;
+    DeviceArray<FollowFrame> d_follow_frames;   // [n_maps][2]: the slot follow_slot[m] is map m's current frame
+    DeviceArray<int32_t> d_follow_result;       // [n_maps][4]: status, dx, dy, 0 of every map's last call
+    DeviceArray<InflateArgs> d_follow_rects;    // [n_maps][4]: the bands k_follow_shift writes and k_inflate_rects reads
+    DeviceArray<SenseEntry> d_follow_sense;     // [B]: a sensing's entries, completed on the device
+    DeviceArray<PlanEntry> d_follow_plan;       // [B]: a plan's
+    std::vector<uint8_t> follow_slot;           // [n_maps]: the parity of the map's follow count
+    void drop_follow() { *this = Follow{}; }
+};
+
 // fleet term (ccv_mppi_batch_resident_set_fleet, mppi_fleet.h): the resident prologue appends discs for the nearest other
 // robots to every instance's list.  While it is on the obstacle kernels run whether or not `obst` is set, over d_obst and
 // the three obst_* vectors (obst_n: the static counts, all 0 without static discs; obst_w: the one weight per instance).
@@ -340,7 +359,7 @@ struct Fleet {
 // pitch is the batch's.  Per call, the instances' poses, dt, windows and noise keys go to the device as one block of records;
 // one rollout launch, one update launch (k_finalize_batch), one mailbox of B * (R + 4) slots under one sequence number.
 // (Core first: its stream outlives the arrays, rings and events of the parts after it)
-struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, Staging, World, Plan, Fleet {
+struct ccv_mppi_batch : Core, BatchRecords, BatchResident, ParamTable, Discs, Grids, Costmap, Staging, World, Plan, Follow, Fleet {
     int B = 0, kpad = 0;
     int last_kernel = -1;   // CCV_MPPI_BATCH_KERNEL_* of the last launch, -1 before the first
     bool mail_any_size = false;   // CCV_MPPI_BATCH_MAIL=1: the mailbox however many slots (measurement)
@@ -503,5 +522,11 @@ inline hipError_t staging_create(ccv_mppi_batch* bh) {   // at the first _set_oc
 }
 // the float cells that hold map m now: the second allocation after an odd number of rolls (Costmap::Layer::front)
 float* cells_of(const ccv_mppi_batch* bh, int m, bool back = false);
+// ... and the layer
+uint8_t* layer_of(const ccv_mppi_batch* bh, int m, bool back = false);
+// the second set of layers and float cells (Costmap::d_occ_roll, d_cells_roll), made once: quiesces like a setter if it allocates
+int ensure_roll_buffers(ccv_mppi_batch* bh);
+// while the maps follow (Follow): the stream idle and the host's copies of every map's offset and origin as the device has them
+int follow_refresh(ccv_mppi_batch* bh);
 
 }  // namespace ccv

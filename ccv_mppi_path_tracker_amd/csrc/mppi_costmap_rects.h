@@ -7,6 +7,13 @@
 #include <cstdlib>
 #include <vector>
 
+// (roll_bands also runs in k_costmap_follow.hip: one statement for the host's rolls and the device's)
+#ifdef __HIPCC__
+#define CCV_RECTS_HD __host__ __device__
+#else
+#define CCV_RECTS_HD
+#endif
+
 namespace ccv {
 
 struct Rect { int32_t x0, y0, w, h; };
@@ -29,7 +36,7 @@ inline size_t roll_exposed_cells(const int32_t nx, const int32_t ny, const int64
 // wide) or of a cell that left the map (the trailing band, R wide), per axis; every other float cell is the shift's copy.  The
 // bands in y keep to the columns the bands in x leave: no cell is written twice.  Returns how many of the four are not empty.
 constexpr int kRollBands = 4;
-inline int roll_bands(const int nx, const int ny, const int ex, const int ey, const int R, Rect out[kRollBands]) {
+CCV_RECTS_HD inline int roll_bands(const int nx, const int ny, const int ex, const int ey, const int R, Rect out[kRollBands]) {
     const int lx = ex ? std::min(std::abs(ex) + R, nx) : 0, tx = ex ? std::min(R, nx - lx) : 0;
     const int ly = ey ? std::min(std::abs(ey) + R, ny) : 0, ty = ey ? std::min(R, ny - ly) : 0;
     const int xa = ex > 0 ? tx : lx, xb = ex > 0 ? nx - lx : nx - tx;   // the columns between the bands in x

@@ -670,6 +670,48 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int3
  * plan; synchronises; any pointer may be NULL.  _read_plan_field: out [ny][nx], instance's field of its last plan; synchronises;
  * CCV_MPPI_ERR_STATE without keep_fields or while the instance's last status is not 1, 2 or 6.  _read_path: the instance's current
  * path, planned or set: *n_path and the first min(n_path, max_poses) poses; synchronises. */
+/* Costmaps that follow their robots (NOT reference behaviour; off until called; batch handles and resident steps only): the five
+ * calls ccv_mppi_batch_resident_set_follow / _get_follow / _follow_enqueue / _read_follow / _plan_goals_enqueue are declared in
+ * ccv_mppi_follow.h, included below.  What they promise.  The window of a device-inflated costmap (_set_occupancy) is re-centred
+ * on the resident pose of its robot in stream order, decided on the device: the host reads no pose.  For a named instance b with
+ * map m = map_of[b], the map's frame as the stream finds it (cx, cy, origin_x, origin_y) and the resident pose (x, y):
+ *     fx = (x - origin_x) * inv,  fy likewise     (the grid term's formula: inv = RN(1 / resolution), the host's; one subtraction,
+ *                                                  one multiplication, no FMA)
+ *     ok = fabs(fx) < 2^30 && fabs(fy) < 2^30     (false for a NaN or infinite pose)
+ *     px = (int64)floor(fx), py likewise          (floor, not truncation: the pose may lie left of or below the map)
+ *     ex = px - nx / 2,  ey = py - ny / 2         (C integer division: the centre cell)
+ *     dx = |ex| <= margin ? 0 : clamp(ex, -max_step, max_step),  dy likewise, each axis on its own
+ *     cx' = cx + dx, cy' = cy + dy;  |cx'| > 2^30 or |cy'| > 2^30, or a rolled origin not finite: nothing moves
+ *     origin' = origin0 + (double)cx' * resolution    (one multiplication, one addition, no FMA: the host roll's formula)
+ *     status: CCV_MPPI_FOLLOW_MOVED, _HELD (dx = dy = 0), _NO_POSE (not ok), _LIMIT; 0: the map has never been followed
+ * On _MOVED the map is rolled by (dx, dy) with every exposed cell set to `fill`: the layer, the float cells, the instances' grid
+ * rows and the origin equal in every bit what ccv_mppi_batch_roll_occupancy_enqueue(m, dx, dy, exposed = NULL, fill) leaves, by
+ * that call's own promise a fresh _set_occupancy of the rolled layer.  On every other status no bit of the layer, the float cells,
+ * the origin or any tick changes.  Whatever the status, a named map changes to its second set of buffers (a copy where nothing
+ * moves): the host cannot know which maps moved.
+ * While following is set, the device's frame is the truth.  _resident_sense_enqueue keeps its meaning (the anchor plus the cells
+ * the map has rolled) and _resident_plan_enqueue its own (goal cells in the rolled frame, the same refusals; start cell and poses
+ * from the origin as rolled), each with one small launch more that completes its table on the device; _update_occupancy_enqueue
+ * and _scan_occupancy_enqueue address the rolled frame as the device has it; _roll_occupancy_enqueue returns CCV_MPPI_ERR_STATE
+ * (the windows are the device's to move); _get_grids, _get_occupancy and _read_follow synchronise and show the device's frame;
+ * _set_occupancy, _set_grids and destroy drop following.  A sensing does not check the frame offset against 2^30 on the host: the
+ * device holds |cx| <= 2^30 and the anchor is at most 2^29.
+ * _set_follow: a setter: flushes a pending resident update and synchronises.  Needs occupancy (CCV_MPPI_ERR_STATE otherwise).
+ * on != 0 allocates the second set of layers and cells if no roll has yet, the frame table seeded from the host's (cx, cy,
+ * origin) and the result rows; on = 0 reads the frames back into the host's layers and frees the part: host rolls work again
+ * and no bit of any tick changes.  _get_follow: *on = whether following is set.
+ * _follow_enqueue: the n named instances (instance [n], each at most once, 1 <= n <= B, each on a map of its own) follow, in
+ * stream order and in two kernel launches however many: no synchronisation, no allocation, no flush of a pending resident update,
+ * no copy; the array may be reused when the call returns.  n outside [1, B], an instance out of range or named twice, an instance
+ * without a map, two named instances on one map, margin outside [0, CCV_MPPI_GRID_MAX_DIM], max_step outside
+ * [1, CCV_MPPI_GRID_MAX_DIM], fill outside [0, 255], tables above one staging slot, NULL arrays: CCV_MPPI_ERR_INVALID_ARG.
+ * Following not set, or no resident poses: CCV_MPPI_ERR_STATE.  Nothing changes either way.
+ * _read_follow: per map the status and shift [n_maps][2] = (dx, dy) of its last call ((0, 0) unless _MOVED), and the current
+ * frame: offset [n_maps][2] = (cx, cy), origin [n_maps][2]; synchronises; any pointer may be NULL.
+ * _plan_goals_enqueue: _plan_enqueue with world goals goal_xy [n][2] as doubles, for a caller who cannot know the frame: the
+ * device turns each into a cell against the origin as rolled, f = (p - origin) * inv clamped to the map (f < 0 -> 0,
+ * f >= n -> n - 1, else (int)f); a goal that is not finite: CCV_MPPI_ERR_INVALID_ARG.  Everything else is _plan_enqueue's.
+ * Following not set: CCV_MPPI_ERR_STATE (a caller who knows the frame has _plan_enqueue). */
 
 #ifdef __cplusplus
 }
@@ -677,4 +719,5 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int3
 #include "ccv_mppi_fleet.h"
 #include "ccv_mppi_sense.h"
 #include "ccv_mppi_plan.h"
+#include "ccv_mppi_follow.h"
 #endif /* CCV_MPPI_H_ */
