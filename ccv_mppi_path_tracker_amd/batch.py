@@ -169,6 +169,20 @@ def goal_cells(geometry, xy):
     return np.ascontiguousarray(out)
 
 
+def plan_multiplier(cells, gain, max_penalty):
+    """The multipliers of BatchController.resident_set_plan_penalty in numpy: int32, the shape of `cells`, m = 1 + q with
+    t = float32(cell) * float32(gain) (one fp32 multiplication) and q = 0 where not t > 0 (zero, negative, NaN), max_penalty where
+    t >= max_penalty, else t truncated.  A step of a weighted plan out of cell c costs 5 * m(c) straight and 7 * m(c) diagonal."""
+    max_penalty = int(max_penalty)
+    if not 0 <= max_penalty <= capi.PLAN_MAX_PENALTY:
+        raise ValueError("plan_multiplier: max_penalty outside [0, %d]" % capi.PLAN_MAX_PENALTY)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        t = np.asarray(cells, dtype=np.float32) * np.float32(gain)
+        positive = t > 0
+    q = np.trunc(np.minimum(np.where(positive, t, np.float32(0)), np.float32(max_penalty)))
+    return np.ascontiguousarray(1 + q.astype(np.int32))
+
+
 def follow_shift(geometry, pose_xy, margin, max_step):
     """The decision of BatchController.resident_follow in numpy, for callers who drive the host prologue and therefore know the
     pose (they roll with roll_occupancy): int32 [n][2], the cells (dx, dy) the window of a map with geometry = ((origin_x,
@@ -794,6 +808,20 @@ class BatchController:
         x, y = np.empty(n.value), np.empty(n.value)
         self._check(self.lib.ccv_mppi_batch_resident_read_path(self._h, int(instance), n.value, capi.dptr(x), capi.dptr(y), C.byref(n)))
         return x[:n.value], y[:n.value]
+
+    # ---- traversal weights of the planned paths (ccv_mppi_batch_resident_set_plan_penalty; include/ccv_mppi_plan_cost.h) ----
+    def resident_set_plan_penalty(self, gain, max_penalty):
+        """Every later resident_plan / resident_plan_goals charges a step out of cell c 5 * m(c) straight and 7 * m(c) diagonal,
+        m = plan_multiplier(cell, gain, max_penalty): paths keep clear of costly cells where a detour is cheaper.  gain finite and
+        >= 0, max_penalty in [0, capi.PLAN_MAX_PENALTY]; (0, 0), which every resident_set_plan starts with: the unweighted plan.
+        After resident_set_plan (MPPIError, capi.ERR_STATE, before); host state only, no synchronisation."""
+        self._check(self.lib.ccv_mppi_batch_resident_set_plan_penalty(self._h, float(np.float32(gain)), int(max_penalty)))
+
+    def resident_get_plan_penalty(self):
+        """(gain, max_penalty) as the library holds them; MPPIError (capi.ERR_STATE) while planning is off."""
+        gain, max_penalty = C.c_float(0.0), C.c_int32(0)
+        self._check(self.lib.ccv_mppi_batch_resident_get_plan_penalty(self._h, C.byref(gain), C.byref(max_penalty)))
+        return gain.value, max_penalty.value
 
     # ---- costmaps that follow their robots (ccv_mppi_batch_resident_set_follow, _follow_enqueue; include/ccv_mppi_follow.h) ----
     def resident_set_follow(self, on=True):

@@ -15,15 +15,16 @@ LIB = os.path.join(LIBDIR, "libccv_mppi_hip.so")
 # C ABI (csrc/capi_internal.h) + the host prologue + the node mirror: they compile side by side
 # (mppi_launch.hip: the switch from a launch's plan to its unit, host code only)
 KERNEL_UNITS = ["k_r4_fb.hip", "k_batch.hip", "k_batch_varied.hip", "k_batch_shift.hip", "k_batch_obst.hip", "k_batch_obst_shift.hip", "k_batch_moving.hip", "k_batch_moving_shift.hip", "k_batch_grid.hip", "k_batch_grid_shift.hip", "k_r4.hip", "k_r3.hip", "k_pc.hip", "k_pc_fb.hip",
-                "k_solo.hip", "k_solo_fb.hip", "k_plain.hip", "k_update.hip", "k_fleet.hip", "k_fleet_pred.hip", "k_costmap.hip", "k_costmap_roll.hip", "k_costmap_scan.hip", "k_costmap_sense.hip", "k_costmap_follow.hip", "k_plan.hip", "k_feed.hip"]
+                "k_solo.hip", "k_solo_fb.hip", "k_plain.hip", "k_update.hip", "k_fleet.hip", "k_fleet_pred.hip", "k_costmap.hip", "k_costmap_roll.hip", "k_costmap_scan.hip", "k_costmap_sense.hip", "k_costmap_follow.hip", "k_plan.hip", "k_plan_cost.hip", "k_feed.hip"]
 CAPI_UNITS = ["ccv_mppi_capi.hip", "capi_exchange.hip", "capi_resident.hip", "capi_stage.hip", "capi_batch.hip", "capi_batch_config.hip", "capi_batch_maps.hip", "capi_batch_feed.hip", "capi_batch_plan.hip", "capi_batch_follow.hip"]
 SOURCES = KERNEL_UNITS + ["mppi_launch.hip"] + CAPI_UNITS + ["ccv_mppi_host.cpp", os.path.join("host", "mppi_node.cpp")]
 HEADERS = ["capi_internal.h", "capi_owned.h", "mppi_diag.h", "mppi_kernels.h", "mppi_device_util.h", "mppi_cost_terms.h", "mppi_handoff.h", "mppi_produce.h", "mppi_consume.h",
            "mppi_epilogue.h", "mppi_update.h", "mppi_launch.h", "mppi_rollout_plain.h", "mppi_rollout_pc.h", "mppi_rollout_r3.h", "mppi_rollout_r4.h",
-           "mppi_rollout_solo.h", "k_batch_form.h", "mppi_resident.h", "mppi_update_device.h", "mppi_fleet.h", "mppi_fleet_device.h", "mppi_costmap.h", "mppi_costmap_device.h", "mppi_costmap_rects.h", "mppi_costmap_roll.h", "mppi_costmap_scan.h", "mppi_costmap_sense.h", "mppi_costmap_follow.h", "mppi_costmap_follow_decide.h", "mppi_select.h", "mppi_top_weights.h", "mppi_feed.h", "mppi_plan.h", "fast_trig.h", "noise_spec.h",
+           "mppi_rollout_solo.h", "k_batch_form.h", "mppi_resident.h", "mppi_update_device.h", "mppi_fleet.h", "mppi_fleet_device.h", "mppi_costmap.h", "mppi_costmap_device.h", "mppi_costmap_rects.h", "mppi_costmap_roll.h", "mppi_costmap_scan.h", "mppi_costmap_sense.h", "mppi_costmap_follow.h", "mppi_costmap_follow_decide.h", "mppi_select.h", "mppi_top_weights.h", "mppi_feed.h", "mppi_plan.h", "mppi_plan_cost.h", "mppi_plan_penalty.h", "fast_trig.h", "noise_spec.h",
            os.path.join("..", "..", "include", "ccv_mppi.h"), os.path.join("..", "..", "include", "ccv_mppi_host.h"),
            os.path.join("..", "..", "include", "ccv_mppi_fleet.h"), os.path.join("..", "..", "include", "ccv_mppi_sense.h"),
            os.path.join("..", "..", "include", "ccv_mppi_plan.h"), os.path.join("..", "..", "include", "ccv_mppi_follow.h"),
+           os.path.join("..", "..", "include", "ccv_mppi_plan_cost.h"),
            os.path.join("..", "..", "include", "ccv_mppi_node.hpp")]
 DEPS = SOURCES + HEADERS
 

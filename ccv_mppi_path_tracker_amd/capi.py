@@ -1,5 +1,5 @@
 """ctypes binding of libccv_mppi_hip.so -- exactly the symbols include/ccv_mppi.h and
-include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES), include/ccv_mppi_sense.h (SENSE_SIGNATURES) and include/ccv_mppi_plan.h (PLAN_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
+include/ccv_mppi_host.h declare (SIGNATURES) and those of include/ccv_mppi_fleet.h (FLEET_SIGNATURES), include/ccv_mppi_sense.h (SENSE_SIGNATURES) include/ccv_mppi_plan.h (PLAN_SIGNATURES), include/ccv_mppi_follow.h (FOLLOW_SIGNATURES) and include/ccv_mppi_plan_cost.h (PLAN_COST_SIGNATURES).  No torch types cross this boundary; there is no CPU fallback:
 if the library is missing it is built with hipcc, and if that fails the import raises.
 """
 import ctypes as C
@@ -246,6 +246,13 @@ FOLLOW_SIGNATURES = {
 }
 FOLLOW_MOVED, FOLLOW_HELD, FOLLOW_NO_POSE, FOLLOW_LIMIT = 1, 2, 3, 4
 
+# include/ccv_mppi_plan_cost.h: traversal weights of the paths planned on the device, a table of its own like its header
+PLAN_COST_SIGNATURES = {
+    "ccv_mppi_batch_resident_set_plan_penalty": (C.c_int, [_H, C.c_float, C.c_int32]),
+    "ccv_mppi_batch_resident_get_plan_penalty": (C.c_int, [_H, C.POINTER(C.c_float), _i32p]),
+}
+PLAN_MAX_PENALTY = 15
+
 _lib = None
 
 
@@ -257,7 +264,7 @@ def load():
         if not os.path.exists(path):
             raise ImportError("libccv_mppi_hip.so is missing and could not be built; there is no CPU fallback")
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()) + list(PLAN_SIGNATURES.items()) + list(FOLLOW_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(FLEET_SIGNATURES.items()) + list(SENSE_SIGNATURES.items()) + list(PLAN_SIGNATURES.items()) + list(FOLLOW_SIGNATURES.items()) + list(PLAN_COST_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError = the .so does not export what the header declares
             fn.restype = res
             fn.argtypes = args

@@ -5,6 +5,7 @@
 // last read the slot.  The host reads no pose: an entry carries the address of the instance's resident pose.
 #include "capi_internal.h"
 #include "mppi_plan.h"
+#include "mppi_plan_cost.h"
 #include "mppi_costmap_follow.h"
 
 namespace {
@@ -18,6 +19,14 @@ static_assert(kPlanOk == CCV_MPPI_PLAN_OK && kPlanTruncated == CCV_MPPI_PLAN_TRU
                   kPlanStartBlocked == CCV_MPPI_PLAN_START_BLOCKED && kPlanGoalBlocked == CCV_MPPI_PLAN_GOAL_BLOCKED &&
                   kPlanUnreachable == CCV_MPPI_PLAN_UNREACHABLE && kPlanNotConverged == CCV_MPPI_PLAN_NOT_CONVERGED,
               "the header's status values");
+static_assert(kPlanMaxPenalty == CCV_MPPI_PLAN_MAX_PENALTY, "the header's limit");
+
+// the kernel of a plan call: k_plan_field while every multiplier is 1 -- the plan is then section 10q's in every bit, from the
+// kernel that section describes -- else k_plan_field_cost
+void launch_plan(const ccv_mppi_batch* bh, const PlanEntry* entries, int32_t n, float lethal, int32_t max_sweeps) {
+    if (bh->plan_max_penalty == 0 || bh->plan_gain == 0.0f) launch_plan_field(entries, n, lethal, max_sweeps, bh->stream);
+    else launch_plan_field_cost(entries, n, lethal, max_sweeps, bh->plan_gain, bh->plan_max_penalty, bh->stream);
+}
 
 }  // namespace
 
@@ -103,6 +112,25 @@ int ccv_mppi_batch_resident_get_plan(ccv_mppi_batch* bh, int32_t* capacity, int3
     return CCV_MPPI_OK;
 }
 
+// (declared in ccv_mppi_plan_cost.h) host state only: the value every later _plan_enqueue and _plan_goals_enqueue launches with
+int ccv_mppi_batch_resident_set_plan_penalty(ccv_mppi_batch* bh, float gain, int32_t max_penalty) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!bh->plan) return fail(bh, CCV_MPPI_ERR_STATE, kNoPlan);
+    if (!std::isfinite(gain) || gain < 0.0f) return refuse(bh, "resident_set_plan_penalty: ", "gain is NaN, infinite or negative");
+    if (max_penalty < 0 || max_penalty > CCV_MPPI_PLAN_MAX_PENALTY) return refuse(bh, "resident_set_plan_penalty: ", "max_penalty outside [0, CCV_MPPI_PLAN_MAX_PENALTY]");
+    bh->plan_gain = gain;
+    bh->plan_max_penalty = max_penalty;
+    return CCV_MPPI_OK;
+}
+
+int ccv_mppi_batch_resident_get_plan_penalty(ccv_mppi_batch* bh, float* gain, int32_t* max_penalty) {
+    if (!bh) return CCV_MPPI_ERR_INVALID_ARG;
+    if (!bh->plan) return fail(bh, CCV_MPPI_ERR_STATE, kNoPlan);
+    if (gain) *gain = bh->plan_gain;
+    if (max_penalty) *max_penalty = bh->plan_max_penalty;
+    return CCV_MPPI_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -182,9 +210,9 @@ int plan_enqueue(ccv_mppi_batch* bh, const char* who, int32_t n, const int32_t* 
     }
     if (followed) {
         launch_follow_resolve_plan(reinterpret_cast<const PlanFollowEntry*>(slot.device), bh->d_follow_plan, n, bh->stream);
-        launch_plan_field(bh->d_follow_plan, n, lethal, max_sweeps, bh->stream);
+        launch_plan(bh, bh->d_follow_plan, n, lethal, max_sweeps);
     } else {
-        launch_plan_field(reinterpret_cast<const PlanEntry*>(slot.device), n, lethal, max_sweeps, bh->stream);
+        launch_plan(bh, reinterpret_cast<const PlanEntry*>(slot.device), n, lethal, max_sweeps);
     }
     HIP_TRY(bh, bh->ring.seal(slot, hipGetLastError(), bh->stream));
     return CCV_MPPI_OK;

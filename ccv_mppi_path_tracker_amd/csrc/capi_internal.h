@@ -313,6 +313,9 @@ struct Plan {
     std::vector<int32_t> plan_dims;          // [B][2]: nx, ny of the map of the instance's last plan call
     DeviceArray<int32_t> d_plan_result;      // [B][6]: status, poses, start cell, D(start), sweeps of every instance's last plan
     DeviceArray<uint16_t> d_plan_fields;     // [instances with capacity][CCV_MPPI_PLAN_MAX_FIELD], with keep_fields
+    // traversal weights (_resident_set_plan_penalty, mppi_plan_cost.h): host state only; (0, 0) after every _set_plan
+    float plan_gain = 0.0f;
+    int32_t plan_max_penalty = 0;
     void drop_plan() { *this = Plan{}; }
 };
 

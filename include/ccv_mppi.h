@@ -670,6 +670,29 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int3
  * plan; synchronises; any pointer may be NULL.  _read_plan_field: out [ny][nx], instance's field of its last plan; synchronises;
  * CCV_MPPI_ERR_STATE without keep_fields or while the instance's last status is not 1, 2 or 6.  _read_path: the instance's current
  * path, planned or set: *n_path and the first min(n_path, max_poses) poses; synchronises. */
+/* Paths planned on the device: traversal weights (NOT reference behaviour; off until called; batch handles and resident steps
+ * only): the two calls ccv_mppi_batch_resident_set_plan_penalty / _get_plan_penalty are declared in ccv_mppi_plan_cost.h,
+ * included below.  What they promise.  Everything above stands -- blocked, the eight moves, no corner cutting, the uint16 field
+ * with 65535 and 65533, the start cell, the status order, the pose formula -- and two handle-wide values, gain and max_penalty,
+ * give every free cell a multiplier from its own float value:
+ *     t = cell(c) * gain                    one fp32 multiplication, round to nearest, no FMA
+ *     q(c) = !(t > 0) ? 0 : (t >= (float)max_penalty ? max_penalty : (int)t)      truncation; a NaN t gives 0
+ *     m(c) = 1 + q(c)                       1..16
+ *     step(c -> n) = w(c, n) * m(c)         w = 5 straight, 7 diagonal: the cell that is left is charged, not the cell entered
+ *     field      the one fixpoint of D(c) = min(D(c), min(65533, D(n) + step(c -> n))) over allowed moves, D(goal) = 0: the
+ *                least total charge of a path from c to the goal, every cell on it but the goal charged, the start included;
+ *                the move rule is no longer symmetric: D is the charge to the goal, not from it
+ *     descent    the first allowed neighbour in the order E, N, W, S, NE, NW, SW, SE with D(n) + step(c -> n) == D(c)
+ * Any relaxation order reaches the same integers, and the call converges whenever max_sweeps >= J, the sweeps of the weighted
+ * Jacobi iteration; D still falls by at least 5 a step, so CCV_MPPI_PLAN_MAX_POSES holds every path.  With max_penalty == 0 or
+ * gain == 0 every multiplier is 1: the plan is the unweighted one in every bit, from the same kernel as before.
+ * _set_plan_penalty: gain finite and >= 0, max_penalty in [0, CCV_MPPI_PLAN_MAX_PENALTY]; a NaN, infinite or negative gain or a
+ * max_penalty outside the range: CCV_MPPI_ERR_INVALID_ARG, and nothing changes.  Needs _resident_set_plan
+ * (CCV_MPPI_ERR_STATE otherwise).  Host state only: no synchronisation, no allocation, no launch; it holds for every later
+ * _plan_enqueue and _plan_goals_enqueue, which stay one kernel launch (two while the maps follow).  A fresh _set_plan starts at
+ * (0, 0); the setting is dropped with planning: _set_plan(NULL), _resident_set_paths, destroy.  _read_plan, _read_plan_field,
+ * _read_path, keep_fields and the status values are what they were and report the weighted plan.
+ * _get_plan_penalty: the values as the library holds them; either pointer may be NULL. */
 /* Costmaps that follow their robots (NOT reference behaviour; off until called; batch handles and resident steps only): the five
  * calls ccv_mppi_batch_resident_set_follow / _get_follow / _follow_enqueue / _read_follow / _plan_goals_enqueue are declared in
  * ccv_mppi_follow.h, included below.  What they promise.  The window of a device-inflated costmap (_set_occupancy) is re-centred
@@ -720,4 +743,5 @@ int ccv_mppi_batch_resident_read_trace(ccv_mppi_batch* b, int32_t instance, int3
 #include "ccv_mppi_sense.h"
 #include "ccv_mppi_plan.h"
 #include "ccv_mppi_follow.h"
+#include "ccv_mppi_plan_cost.h"
 #endif /* CCV_MPPI_H_ */
