@@ -13,13 +13,19 @@ namespace ccv {
 //   fails); the candidates in (d2, j) order, the first M_y = min(max_neighbours, 32 - n_static[y]) of them become rows
 //   (q_j[0], q_j[1], radius[y] + radius[j]) n_static[y] .. of the instance's list, and n_obst = n_static[y] + their number.
 // A candidate's row index is its rank, the number of candidates before it in that order, counted in a loop over LDS: no
-// atomics, no sort, and no dependence on the workgroup's width.  The LDS first holds the positions, then the keys: d2_j for a
-// candidate, NaN otherwise (a NaN key is before nothing and after nothing).
+// atomics and no sort.  The workgroup's width is fixed: thread t holds robots t, t + kBlock, ... in kPer = kFleetMaxBatch / kBlock
+// registers, so every robot has a thread only when the workgroup has exactly kBlock threads -- which the fused forms have by
+// their launch and the prologue kernels of their own because kBatchAdvanceThreads == kBlock (asserted beside kPer).  Which
+// thread or wave holds a robot changes no result: ties go by j, and the count is the sum of all kBlock / 64 wave totals.  The
+// LDS first holds the positions, then the keys: d2_j for a candidate, NaN otherwise (a NaN key is before nothing and after
+// nothing).
 // PRED (fleet prediction): a selected neighbour's velocity, formed by that robot's own prologue block one
 // tick ago (fleet_publish), goes into the velocity row that belongs to the disc row; the selection itself does not change.
 template <bool PRED = false>
 __device__ __forceinline__ void fleet_step(const FleetArgs& L, BatchParams* P, const int y, const FleetPredArgs* V = nullptr) {
     constexpr int kPer = kFleetMaxBatch / kBlock;   // candidates per thread: j = threadIdx.x + i * kBlock
+    static_assert(kPer * kBlock == kFleetMaxBatch && kBatchAdvanceThreads == kBlock && kBlock % 64 == 0,
+                  "fleet_step: kBlock threads, whichever kernel it is in, cover kFleetMaxBatch robots in kPer strides");
     __shared__ double s_key[2 * kFleetMaxBatch];    // [B][2] positions; then [B] keys
     __shared__ int s_cnt[kBlock / 64];
     const int B = L.B < kFleetMaxBatch ? L.B : kFleetMaxBatch;   // (the host refuses larger batches)

@@ -31,14 +31,15 @@ def lists(q, radius, n_static, max_neighbours, rng):
     radius = np.asarray(radius, dtype=np.float64)
     B = q.shape[0]
     M = room(n_static, max_neighbours)
-    range2 = np.float64(rng) * np.float64(rng)
+    with np.errstate(over="ignore"):   # (a range whose square overflows: +inf, as the host's product)
+        range2 = np.float64(rng) * np.float64(rng)
     j_all = np.arange(B)
     n_total, rows = np.zeros(B, dtype=np.int32), []
     for y in range(B):
-        dx = q[:, 0] - q[y, 0]
-        dy = q[:, 1] - q[y, 1]
-        d2 = dx * dx + dy * dy
-        with np.errstate(invalid="ignore"):
+        with np.errstate(over="ignore", invalid="ignore"):   # (positions that are not finite: IEEE's results, no warning)
+            dx = q[:, 0] - q[y, 0]
+            dy = q[:, 1] - q[y, 1]
+            d2 = dx * dx + dy * dy
             cand = (d2 <= range2) & (j_all != y)
         idx = np.flatnonzero(cand)
         take = idx[np.lexsort((idx, d2[idx]))][:M[y]]
@@ -61,13 +62,28 @@ def lists_exact(q, radius, n_static, max_neighbours, rng):
     M = room(n_static, max_neighbours)
     range2 = _rd(Fraction(float(rng)) * Fraction(float(rng)))
     n_total, rows = np.zeros(B, dtype=np.int32), []
+    # every operation is done once per pair of operands (a lattice of a thousand robots has few distinct differences); a rounded
+    # result is a double, and the comparisons below compare those doubles: the same order as the rationals'
+    Qf = q.tolist()
+    range2 = float(range2)
+    diff, key = {}, {}
+
+    def sub(a, b, k):
+        if k not in diff:
+            r = _rd(a - b)
+            diff[k] = (r, float(r))
+        return diff[k]
+
     for y in range(B):
         cands = []
         for j in range(B):
             if j == y:
                 continue
-            dx, dy = _rd(Q[j][0] - Q[y][0]), _rd(Q[j][1] - Q[y][1])
-            d2 = _rd(_rd(dx * dx) + _rd(dy * dy))
+            dx, dxf = sub(Q[j][0], Q[y][0], (Qf[j][0], Qf[y][0]))
+            dy, dyf = sub(Q[j][1], Q[y][1], (Qf[j][1], Qf[y][1]))
+            if (dxf, dyf) not in key:
+                key[(dxf, dyf)] = float(_rd(_rd(dx * dx) + _rd(dy * dy)))
+            d2 = key[(dxf, dyf)]
             if d2 <= range2:
                 cands.append((d2, j))
         cands.sort()

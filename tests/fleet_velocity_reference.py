@@ -63,16 +63,17 @@ def lists(q, radius, n_static, max_neighbours, rng):
     q = np.asarray(q, dtype=np.float64)
     B = q.shape[0]
     M = FR.room(n_static, max_neighbours)
-    range2 = np.float64(rng) * np.float64(rng)
+    with np.errstate(over="ignore"):
+        range2 = np.float64(rng) * np.float64(rng)
     n_total, rows = FR.lists(q, radius, n_static, max_neighbours, rng)
     taken = []
     for y in range(B):
-        dx, dy = q[:, 0] - q[y, 0], q[:, 1] - q[y, 1]
-        d2 = dx * dx + dy * dy
-        with np.errstate(invalid="ignore"):
+        with np.errstate(over="ignore", invalid="ignore"):
+            dx, dy = q[:, 0] - q[y, 0], q[:, 1] - q[y, 1]
+            d2 = dx * dx + dy * dy
             idx = np.flatnonzero((d2 <= range2) & (np.arange(B) != y))
         taken.append(idx[np.lexsort((idx, d2[idx]))][:M[y]])
-        assert np.array_equal(q[taken[-1]], rows[y][:, :2])
+        assert q[taken[-1]].tobytes() == rows[y][:, :2].tobytes()
     return n_total, rows, taken
 
 
