@@ -39,6 +39,9 @@ __device__ __forceinline__ double clampd(double v, double lo, double hi) { retur
 // comparisons are false), min / max would replace it by a bound: the kernels use this form only where the host has checked
 // sigma and the bounds and the kernel itself has found no NaN in the warm start (RolloutArgs::fast_clamp; a control is
 // double(z) * sigma + u* with a finite z).  (-0 against a bound of +0 comes out as +0 here and -0 there: equal values.)
+// Where the other form lives: the one-wave kernel chooses per block; the four-wave kernel (mppi_rollout_r4.h) has, for diff
+// drive and steering, one loop over the time blocks per form and chooses the loop -- the compare-and-select form costs a launch
+// that does not need it no register and no instruction; full body keeps the choice in its loop.
 __device__ __forceinline__ double clampd_fast(double v, double lo, double hi) { return __builtin_fmin(__builtin_fmax(v, lo), hi); }
 template <bool FAST>
 __device__ __forceinline__ double clampd_as(double v, double lo, double hi) {

@@ -197,21 +197,50 @@ __device__ __forceinline__ bool r4_stage_commit(const RolloutArgs& A, SH& sh, co
 
 // The per-lane sample indices, made afresh where a role (or the epilogue) needs them: five values that are live from the
 // first instruction to the last would otherwise be spilled at 128 registers (the asm statement keeps the compiler from
-// merging the copies back into one).
+// merging the copies back into one).  FRESH: the statement is on the lane count's INPUT, so that every caller counts for
+// itself.  On the count's result (the earlier form, !FRESH) it forces a copy only: the count itself, one value for all callers,
+// stays live through the whole kernel and was parked in scratch around the dynamics loop -- and reloaded in it.
 struct R4Lane {
     int lane, k, kk;
     bool live;
     uint32_t kg;
 };
+template <bool FRESH>
 __device__ __forceinline__ R4Lane r4_lane(const RolloutArgs& A) {
     R4Lane L;
-    L.lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // (all 64 lanes are active here)
-    asm volatile("" : "+v"(L.lane));
+    if constexpr (FRESH) {
+        uint32_t none = 0u;
+        asm volatile("" : "+v"(none));
+        L.lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, none));   // (all 64 lanes are active here)
+    } else {
+        L.lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(L.lane));
+    }
     L.k = (int)blockIdx.x * kPcSamples + L.lane;
     L.live = L.k < A.K;
     L.kk = L.live ? L.k : A.K - 1;
     L.kg = (uint32_t)(A.k_offset + L.kk);
     return L;
+}
+
+// The clamp form of the dynamics wave's blocks as a value: std::true_type / std::false_type where the loop exists once per form and
+// the choice is made around it, R4ClampInLoop where one loop holds both forms and chooses per block.  f(form) with the form as
+// an integral constant either way.
+struct R4ClampInLoop {
+    bool fast;
+};
+template <class C, class F>
+__device__ __forceinline__ void r4_with_clamp(const C c, F&& f) {
+    if constexpr (std::is_same<C, R4ClampInLoop>::value) {
+        if (c.fast) f(std::true_type{});
+        else f(std::false_type{});
+    } else {
+        f(c);
+    }
+}
+template <class B>
+constexpr unsigned r4_clamp_flag(B) {
+    return B::value ? kFastClamp : 0u;
 }
 
 // WIDE (diff drive, fused iteration): full-range sin / cos of every heading, for |w|max dt > pi/4 (pc_produce_batched)
@@ -242,6 +271,8 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     constexpr bool FB = MODEL == CCV_MPPI_FULL_BODY;
     constexpr bool COST = MODE != MODE_ROLLOUT;
     constexpr int UD = udim_of(MODEL);
+    // (R4Lane.  The stage-wise cost kernels park 16 B more in scratch with the fresh count than with the copied one: they keep it.)
+    constexpr bool kFreshLane = MODE == MODE_FUSED;
     static_assert(!WIDE || (MODEL == CCV_MPPI_DIFF_DRIVE && MODE == MODE_FUSED), "the wide-turn form exists for the fused diff-drive iteration");
     static_assert(!TAIL || MODE == MODE_FUSED, "the stage-wise modes carry the masked producer anyway");
     static_assert(!BATCH || MODE == MODE_FUSED, "batch handles run the fused iteration only");
@@ -288,7 +319,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         r4_stage_issue<MODEL, kR4Waves * 64, BATCH>(A, Wk, (int)threadIdx.x, staged);
         if (nfull > 0) {
             constexpr int NCALL = kTU * UD / 4;
-            const R4Lane L = r4_lane(A);
+            const R4Lane L = r4_lane<kFreshLane>(A);
             for (int c = wv; c < NCALL; c += kR4Waves) r4_noise_call<MODEL>(A, sh, 0, c, L.lane, L.kg);
         }
         if (wv == 0) CCV_DIAG_STAMP(A, 3);
@@ -303,7 +334,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         }
         // a NaN in the warm start: every wave says what its threads saw, every wave reads all four words after the barrier
         const bool wave_bad = __builtin_amdgcn_ballot_w64(bad_nominal) != 0ull;
-        if (r4_lane(A).lane == 0) sh.nan_seen[wv] = wave_bad ? 1 : 0;
+        if (r4_lane<kFreshLane>(A).lane == 0) sh.nan_seen[wv] = wave_bad ? 1 : 0;
     } else {
         if constexpr (COST) stage_window(A, Wk, sh, kR4Waves * 64);
         if (wv == 1) pc_initial_state<MODEL>(A, S);
@@ -335,14 +366,14 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         if constexpr (MODE == MODE_FUSED) {   // (stage-wise cost call: fp64 controls, 120 registers -- fetched after the barrier)
             if (rows.n > 0 && nb_early > 0) {   // (nb_early == 0: every wave reads its rows after the barrier)
                 pc_wait_for(seq_stored, nb_early);   // the rows are in HBM / L2
-                r4_fetch0(A, upd, rows, r4_lane(A).kk);
+                r4_fetch0(A, upd, rows, r4_lane<kFreshLane>(A).kk);
             }
         }
     };
     if (wv == 0) {
         // ---------------- noise wave
         if constexpr (MODE == MODE_FUSED) {
-            const R4Lane L = r4_lane(A);
+            const R4Lane L = r4_lane<kFreshLane>(A);
             const int lane = L.lane;
             const uint32_t kg = L.kg;
             for (int b = 1; b < nfull; ++b) {   // (block 0: above, beside the staging)
@@ -356,57 +387,102 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
             }
             CCV_DIAG_STAMP(A, 15);
         }
-        if constexpr (COST) sh.cost[0][r4_lane(A).lane] = 0.0;
+        if constexpr (COST) sh.cost[0][r4_lane<kFreshLane>(A).lane] = 0.0;
         if (A.prio_rotate) __builtin_amdgcn_s_setprio(0);
         early_fetch();
     } else if (wv == 1) {
         // ---------------- dynamics wave: all time blocks, state in registers
-        const R4Lane L = r4_lane(A);
-        const int lane = L.lane, k = L.k, kk = L.kk;
-        const bool live = L.live;
-        const uint32_t kg = L.kg;
+        R4Lane L;
+        if constexpr (MODE != MODE_FUSED) L = r4_lane<kFreshLane>(A);
         double cost = 0.0;
         cost += pc_initial_cost<MODEL, MODE>(A);
-        constexpr unsigned LDSZ = kNormalsInLds | (WIDE ? kWideTurn : 0u);   // (the noise wave's blocks: every form below has these)
-        for (int b = 0; b < nblocks; ++b) {
-            r4_rotate_priority(A, b, 1);
-            if (b >= 2) {   // the buffers of block b last held block b-2: both readers must have taken it
-                pc_wait_for(seq_dist, b - 1);
-                pc_wait_for(seq_store, b - 1);
-            }
-            const int nctl = min(kTU, H - 1 - b * kTU);   // steps of this block that carry controls
-            if (b < nfull) {
-                pc_wait_for(seq_noise, b + 1);
-                if (b == 0) CCV_DIAG_STAMP(A, 4);
-                // (two instantiations each: a NaN in the warm start is rare, but its results are to be the other kernels' bits too)
-                if (!TAIL || nctl == kTU) {
-                    if (fast_clamp)
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kFastClamp>(A, sh, S, cost, b, lane, k, kk, live, kg);
-                    else
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ>(A, sh, S, cost, b, lane, k, kk, live, kg);
-                } else if constexpr (TAIL) {
-                    // (six steps -- the reference's default horizon, H = 15 -- as an instantiation of their own: the masked batch
-                    //  computes all eight and drops two; same box, kernel: full body K = 10 000 17.8 -> 17.3 us, steering
-                    //  K = 1 000 14.3 -> 13.9 us per iteration, diff drive unchanged)
-                    if (fast_clamp && nctl == 6)
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kPartialBlock | kFastClamp, 6>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
-                    else if (fast_clamp)
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kPartialBlock | kFastClamp>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
-                    else
-                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | kPartialBlock>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
+        // Diff drive and steering: the loop exists once per clamp form, and the form is chosen here, once -- it is wave-uniform and
+        // known since the prologue's barrier.  A healthy launch's loop is ONE straight-line block per time block that holds the
+        // two-instruction form alone; the compare-and-select form (a NaN in the warm start is rare, but its results are to be the
+        // other kernels' bits too: the same batched producer, not pc_produce, whose sin / cos of the whole heading round
+        // differently) has a loop of its own that a healthy launch never enters.  With both forms in one loop -- and with the
+        // masked TAIL forms and the tail's sample indices live through it -- every fused instantiation of these two models parked
+        // 21 to 72 vector registers in scratch (80 to 212 B a lane), some of them in the healthy loop; now 59 of the 60 have no
+        // scratch segment, and the steering TAIL kernel of the grid batch form with shifted weights parks 2 (12 B; it had 35, 96 B)
+        // (profiles/r4_clamp_route_isa_meta.txt).
+        auto blocks = [&](auto CLAMP_) {
+            constexpr unsigned LDSZ = kNormalsInLds | (WIDE ? kWideTurn : 0u);   // (the noise wave's blocks: every form below has these)
+            auto opened = [&](const int b) {
+                r4_rotate_priority(A, b, 1);
+                if (b >= 2) {   // the buffers of block b last held block b-2: both readers must have taken it
+                    pc_wait_for(seq_dist, b - 1);
+                    pc_wait_for(seq_store, b - 1);
                 }
-            } else if (MODE != MODE_FUSED && nctl == kTU) {
-                pc_produce_batched<MODEL, MODE>(A, sh, S, cost, b, lane, k, kk, live, kg);
-            } else if (MODE != MODE_FUSED && nctl >= kPartialMin) {
-                pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, kPartialBlock>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
-            } else {
-                pc_produce<MODEL, MODE, false>(A, sh, S, cost, b, lane, k, kk, live, kg);   // (a short tail, or the final state only)
+                return min(kTU, H - 1 - b * kTU);   // steps of this block that carry controls
+            };
+            auto closed = [&](const int b) {
+                pc_publish(seq_ready, b + 1);
+                if (b == 0) CCV_DIAG_STAMP(A, 5);
+            };
+            // The blocks whose normals the noise wave has made (MODE_FUSED; none otherwise).  On this kernel's staging layout
+            // (kNormalsInLds, R4Shared::kStage) the batched producer reads none of k, kk, live and kg: the lane is all these blocks keep of
+            // the sample's indices; the others are the step-by-step tail's, made afresh below (R4Lane).
+            if constexpr (MODE == MODE_FUSED) {
+                const int lane = r4_lane<kFreshLane>(A).lane;
+                auto noise_fed = [&](const int b) {
+                    const int nctl = opened(b);
+                    pc_wait_for(seq_noise, b + 1);
+                    if (b == 0) CCV_DIAG_STAMP(A, 4);
+                    return nctl;
+                };
+                // TAIL: the masked batch is the horizon's last noise-fed block and nothing else -- it stands after the loop, which holds
+                // the full form alone in every instantiation
+                const int nwhole = (TAIL && nfull > 0 && H - 1 - (nfull - 1) * kTU < kTU) ? nfull - 1 : nfull;
+                for (int b = 0; b < nwhole; ++b) {
+                    noise_fed(b);
+                    r4_with_clamp(CLAMP_, [&](auto FAST_) {
+                        pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LDSZ | r4_clamp_flag(FAST_)>(A, sh, S, cost, b, lane, 0, 0, false, 0u);
+                    });
+                    closed(b);
+                }
+                if constexpr (TAIL) {
+                    if (nwhole < nfull) {
+                        const int b = nwhole, nctl = noise_fed(b);
+                        // (six steps -- the reference's default horizon, H = 15 -- as an instantiation of their own: the masked batch
+                        //  computes all eight and drops two; same box, kernel: full body K = 10 000 17.8 -> 17.3 us, steering
+                        //  K = 1 000 14.3 -> 13.9 us per iteration, diff drive unchanged)
+                        r4_with_clamp(CLAMP_, [&](auto FAST_) {
+                            constexpr unsigned LP = LDSZ | kPartialBlock | r4_clamp_flag(FAST_);
+                            if (decltype(FAST_)::value && nctl == 6)
+                                pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LP, 6>(A, sh, S, cost, b, lane, 0, 0, false, 0u, kNoNormalsAhead, nctl);
+                            else
+                                pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, LP>(A, sh, S, cost, b, lane, 0, 0, false, 0u, kNoNormalsAhead, nctl);
+                        });
+                        closed(b);
+                    }
+                }
             }
-            pc_publish(seq_ready, b + 1);
-            if (b == 0) CCV_DIAG_STAMP(A, 5);
+            if constexpr (MODE == MODE_FUSED) L = r4_lane<kFreshLane>(A);
+            const int lane = L.lane, k = L.k, kk = L.kk;
+            const bool live = L.live;
+            const uint32_t kg = L.kg;
+            for (int b = nfull; b < nblocks; ++b) {
+                const int nctl = opened(b);
+                if (MODE != MODE_FUSED && nctl == kTU) {
+                    pc_produce_batched<MODEL, MODE>(A, sh, S, cost, b, lane, k, kk, live, kg);
+                } else if (MODE != MODE_FUSED && nctl >= kPartialMin) {
+                    pc_produce_batched<MODEL, MODE, R4Shared<MODEL>, kPartialBlock>(A, sh, S, cost, b, lane, k, kk, live, kg, kNoNormalsAhead, nctl);
+                } else {
+                    pc_produce<MODEL, MODE, false>(A, sh, S, cost, b, lane, k, kk, live, kg);   // (a short tail, or the final state only)
+                }
+                closed(b);
+            }
+        };
+        if constexpr (MODE == MODE_FUSED && !FB) {
+            if (fast_clamp) blocks(std::true_type{});
+            else blocks(std::false_type{});
+        } else {
+            // (full body, alone on its SIMD with 512 registers, has no scratch either way and 22 to 45 more scalar registers parked
+            //  in vector lanes with two loops: it keeps the choice in the loop.  The stage-wise modes read their controls.)
+            blocks(R4ClampInLoop{fast_clamp});
         }
         CCV_DIAG_STAMP(A, 6);
-        if constexpr (COST) sh.cost[1][lane] = cost;
+        if constexpr (COST) sh.cost[1][L.lane] = cost;
         if (A.prio_rotate) __builtin_amdgcn_s_setprio(0);
         early_fetch();
     } else if (wv == 2) {
@@ -414,7 +490,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         // (round 3 tried handing every second one of the last blocks to the noise wave, which is idle from two thirds of the
         //  kernel on: +1.5 us -- the loop is priced by the instructions all four waves of a SIMD issue, not by this wave's share)
         int prune_on = 1;
-        const int lane = r4_lane(A).lane;
+        const int lane = r4_lane<kFreshLane>(A).lane;
         double cost = 0.0;
         for (int b = 0; b < nblocks; ++b) {
             r4_rotate_priority(A, b, 2);
@@ -434,7 +510,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
         // ---------------- store wave: normals (MODE_FUSED) and states (not in MODE_COST) of block b, LDS -> registers ->
         // HBM.  Everything is read from LDS first and the buffer handed back before the first store issues.
         const size_t pitch = (size_t)A.pitch;
-        const R4Lane L = r4_lane(A);
+        const R4Lane L = r4_lane<kFreshLane>(A);
         const int lane = L.lane;
         const uint32_t koff4 = (uint32_t)L.k * 4u, koff8 = (uint32_t)L.k * 8u;
         GridAcc grid_acc{};
@@ -512,7 +588,7 @@ __global__ __launch_bounds__(kR4Waves * 64, MODEL == CCV_MPPI_FULL_BODY ? 1 : 4)
     if constexpr (COST) {
         const int R = (H - 1) * UD;
         const int mcount = rows.n;
-        const R4Lane L = r4_lane(A);
+        const R4Lane L = r4_lane<kFreshLane>(A);
         const int lane = L.lane, k = L.k, kk = L.kk;
         const bool live = L.live;
         // the one barrier of the kernel: every wave is through its loop (the store wave with all its stores acknowledged),
